@@ -4,6 +4,12 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  With N > 1 and no launcher around it
 (WORLD_SIZE unset) the script re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`.
 
+A plain run measures the headline only: set-up, warm-up, the K timed decode steps and the JSON line (metric, value, unit,
+ms_per_step, the decode roofline of the timed region).  `--full` adds every other leg listed below (per-kernel decode, batched
+decode, profile_consistency, prefill, dropin, the BASELINE.json configs, cpu_baseline); their --no-* options still apply under it.
+`--dump-outputs DIR` writes what the last timed step computed, one float32 DIR/<launch kind>.npy per kind ([launches, N]: qkv, o,
+gate_up, down), so two builds can be compared output for output on the same seeded weights and activations.
+
   step      = one decode pass of the hot path: the 160 WQLinear GEMV calls (32 layers x
               {qkv 4096->6144, o 4096->4096, gate 4096->14336, up 4096->14336, down 14336->4096})
               of one Llama-3-8B token, M = 1, every layer with its OWN packed weights (3.7 GB total,
@@ -95,6 +101,27 @@ def launcher_command(n_gpus, argv, port=None):
             "--master-port", str(int(port)), os.path.abspath(__file__), *argv]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, kinds, outs):
+    """outs[i] = the output of launch i, of launch kind kinds[i]: one float32 <kind>.npy per kind, [launches of that kind, elements per launch].
+    Past DUMP_MAX_BYTES in all, every kind keeps the same fixed, seeded sample of its flattened elements (the same share of each)."""
+    import numpy as np
+    arrays = {}
+    for kind, t in zip(kinds, outs):
+        arrays.setdefault(kind, []).append(t.detach().float().reshape(-1).cpu().numpy())
+    arrays = {k: np.stack(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            flat = a.reshape(-1)
+            pick = np.random.default_rng(0).choice(flat.size, flat.size * DUMP_MAX_BYTES // total, replace=False)
+            a = flat[np.sort(pick)]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def algo_bytes(M, K, N, esz=2, group=128):
     """packed int4 + scales + scaled_zeros + x + out."""
     return N * K // 2 + 2 * (K // group) * N * esz + M * K * esz + M * N * esz
@@ -126,6 +153,8 @@ def main():
                     help="gate/up: one launch on the 8+8 row-interleaved stack QuantLlamaMLP builds (default), one launch on the plain [gate; up] stack, or two launches + F.silu * mul left out (160 launches per token)")
     ap.add_argument("--sz", default="half", choices=["half", "packed"], help="decode side buffer: sz_half (f16-mantissa dequant) or the T-typed sz_packed")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"], help="activation / scale dtype: bf16 is BASELINE.json's configuration (default); f16 is the reference's default WQLinear dtype (single-GPU leg only)")
+    ap.add_argument("--full", action="store_true", help="run every leg beside the headline decode steps (per-kernel, batched decode, prefill, dropin, other configs, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as float32 DIR/<launch kind>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -147,6 +176,8 @@ def main():
     dist = None
     force_tp = os.environ.get("AWQ_BENCH_FORCE_TP") == "1"  # exercise the tensor-parallel leg on one GPU (world size 1)
     if world > 1 or force_tp:
+        if args.dump_outputs:
+            ap.error("--dump-outputs covers the single-GPU leg only")
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if force_tp and "WORLD_SIZE" not in os.environ:  # (no launcher around a world-1 run: the env:// rendezvous still wants its variables)
@@ -202,7 +233,7 @@ def main():
                 nat.append(native(name, 4096, 14336, ws[name]["qweight"], ws[name]["scales"], ws[name]["scaled_zeros"], 0))
         nat.append(native("down", 14336, 4096, ws["down"]["qweight"], ws["down"]["scales"], ws["down"]["scaled_zeros"], 0))
         del ws, g, u
-    if args.no_dropin and args.layout != "v2":
+    if (args.no_dropin or not args.full) and args.layout != "v2":
         raw = []
     torch.cuda.synchronize()
 
@@ -267,15 +298,16 @@ def main():
     side = torch.cuda.Stream(device=dev)
 
     def timed_decode(run_pass, steps, warmup, use_graph=True, M=1):
+        """-> (wall ms, event ms, graphed, the outputs of the last timed step)"""
         xs1 = make_x(M)
-        graph = None
+        graph = keep = None
         with torch.cuda.stream(side):
             run_pass(xs1)  # lazy init / cache builds outside capture
             torch.cuda.synchronize()
             if use_graph:
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, stream=side):
-                    keep = run_pass(xs1)  # noqa: F841
+                    keep = run_pass(xs1)  # the graph's output buffers: every replay rewrites them
             step = (lambda: graph.replay()) if graph is not None else (lambda: run_pass(xs1))
             # clock ramp: a token is ~1 ms of GPU time, and the driver's --warmup 5 ends before the chip has left its idle clocks (--steps 5 --warmup 2 reads
             # 860 tok/s where --steps 50 --warmup 10 reads 1030 on the same box).  Untimed replays up to CLOCK_RAMP_STEPS in total come first; the W warmup
@@ -289,12 +321,12 @@ def main():
             t0 = time.perf_counter()
             e0.record(side)
             for _ in range(steps):
-                step()
+                last = step()
             e1.record(side)
             torch.cuda.synchronize()
             wall_ms = (time.perf_counter() - t0) * 1e3
             ev_ms = e0.elapsed_time(e1)
-        return wall_ms, ev_ms, graph is not None
+        return wall_ms, ev_ms, graph is not None, (keep if graph is not None else last)
 
     def timed_prefill(run_pass, M, n_lin):
         """two untimed passes (lazy init, clock ramp: the first timed leg of a run used to read 3 % slow), then --prefill-iters passes each
@@ -367,8 +399,11 @@ def main():
     native_leg = args.layout == "cdna4"
     run_main = run_native if native_leg else run_dropin
     # ---------------- decode leg: K timed steps ----------------
-    wall_ms, ev_ms, graphed = timed_decode(run_main, args.steps, args.warmup, not args.no_graph)
+    wall_ms, ev_ms, graphed, last_outs = timed_decode(run_main, args.steps, args.warmup, not args.no_graph)
     ms_per_step = wall_ms / args.steps
+    if args.dump_outputs:
+        kinds = [t[0] for t in (nat if native_leg else raw)]
+        dump_outputs(args.dump_outputs, kinds * (len(last_outs) // len(kinds)), last_outs)
     launches = len(nat) * args.repeat_layers if native_leg else len(raw)
     bytes_step = bytes_native(1) * args.repeat_layers if native_leg else sum(algo_bytes(1, K, N) for (_n, K, N, *_r) in raw)
     avg_launch_us = ev_ms * 1e3 / (args.steps * launches)
@@ -380,7 +415,7 @@ def main():
                 "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                 "avg_launch_us": round(avg_launch_us, 3), "algorithmic_bytes_per_launch": bytes_step // launches,
                 "launches_per_step": launches, "timing": "hip events on the launch stream over the timed region"}
-    if native_leg and graphed and not probe_streams and args.repeat_layers == 1:
+    if args.full and native_leg and graphed and not probe_streams and args.repeat_layers == 1:
         roofline["per_kernel"] = per_kernel_decode(max(5, args.steps // 2), max(2, args.warmup // 2))
     tok_s = 1e3 / ms_per_step * (L * args.repeat_layers / LAYERS)  # tokens/s of a full 32-layer model
 
@@ -397,13 +432,16 @@ def main():
                       "prefill_mlp": "SiLU*mul fused into the gate/up GEMM epilogue" if (native_leg and args.mlp == "interleaved") else "separate",
                       "mlp": args.mlp if native_leg else "unfused (two gemv_forward_cuda_new calls, as tinychat issues them)",
                       "decode_side_buffer": ("sz_half" if args.sz == "half" else "sz_packed") if native_leg else "engine cache",
-                      "launches_per_token": launches, "parallelism": "tp1", **({"tune": args.tune} if args.tune else {})},
+                      "launches_per_token": launches, "parallelism": "tp1", "full": args.full, **({"tune": args.tune} if args.tune else {})},
            "roofline": roofline, "device": torch.cuda.get_device_name(dev)}
+    if not args.full:
+        print(json.dumps(out))
+        return
 
     # ---------------- batched decode (the reference GEMV serves 1..7 rows, gemv_cuda.cu:291-329): same launches, M = 4 and 7 ----------------
     if native_leg and not args.no_batched_decode:
         for Mb in (4, 7):
-            b_wall, b_ev, _g = timed_decode(run_main, max(5, args.steps // 2), max(2, args.warmup // 2), not args.no_graph, M=Mb)
+            b_wall, b_ev, _g, _o = timed_decode(run_main, max(5, args.steps // 2), max(2, args.warmup // 2), not args.no_graph, M=Mb)
             b_steps = max(5, args.steps // 2)
             b_bytes = bytes_native(Mb) * args.repeat_layers
             b_gbs = b_bytes * b_steps / (b_ev * 1e-3) / 1e9
@@ -435,7 +473,7 @@ def main():
     # ---------------- the same work through the reference's entry points on raw v2 buffers ----------------
     if native_leg and raw:
         def dropin_leg(with_prefill):
-            d_wall, d_ev, _g = timed_decode(run_dropin, args.steps, args.warmup, not args.no_graph)
+            d_wall, d_ev, _g, _o = timed_decode(run_dropin, args.steps, args.warmup, not args.no_graph)
             d_bytes = sum(algo_bytes(1, K, N) for (_n, K, N, *_r) in raw)
             d_gbs = d_bytes * args.steps / (d_ev * 1e-3) / 1e9
             d = {"launches_per_token": len(raw), "decode_tok_s": round(1e3 / (d_wall / args.steps) * (L / LAYERS), 2),

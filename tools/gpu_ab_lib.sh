@@ -8,7 +8,7 @@ cp $LIB /tmp/lib_a.so; cp $2 /tmp/lib_b.so
 for rep in 1 2 3; do
   for v in a b; do
     cp /tmp/lib_$v.so $LIB
-    ( timeout 300 python bench.py --no-cpu-baseline --no-dropin --prefill-m2 0 --prefill-m3 0 2>&1 | tail -1 ) > $O/bench_${v}_$rep.json
+    ( timeout 300 python bench.py --full --no-cpu-baseline --no-dropin --prefill-m2 0 --prefill-m3 0 2>&1 | tail -1 ) > $O/bench_${v}_$rep.json
     python - "$O/bench_${v}_$rep.json" "$v$rep" <<'PY'
 import json, sys
 try:

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-.}"
 O=${1:-gpurun_out/dg}; mkdir -p $O
 export TMPDIR=/tmp
-( timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof -o dec -- python bench.py --steps 40 --warmup 5 --no-prefill --no-batched-decode --no-dropin --no-extra-configs --no-cpu-baseline 2>$O/bench_graph.err | grep '"metric"' | tail -1 ) > $O/bench_graph.json
+( timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof -o dec -- python bench.py --full --steps 40 --warmup 5 --no-prefill --no-batched-decode --no-dropin --no-extra-configs --no-cpu-baseline 2>$O/bench_graph.err | grep '"metric"' | tail -1 ) > $O/bench_graph.json
 python tools/rocpd_stats.py $O/prof/dec_results.db $O/decode_graph_kernel_stats.csv > $O/decode_graph_kernel_stats.txt
 python - "$O" <<'PY'
 import csv, json, sys

@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 tail -3 $O/pytest_gpu_seed0.log
 ( timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 ) > $O/smoke.log
 tail -1 $O/smoke.log
-( timeout 400 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1 ) > $O/bench.json
+( timeout 400 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1 ) > $O/bench.json
 cut -c1-400 $O/bench.json
 bash tools/gpu_decode_graph_profile.sh $O/dg | cut -c1-300
-PF="--no-cpu-baseline --no-dropin --no-batched-decode --no-graph --no-extra-configs --prefill-iters 1"
+PF="--full --no-cpu-baseline --no-dropin --no-batched-decode --no-graph --no-extra-configs --prefill-iters 1"
 ( timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o bench -- python bench.py --steps 20 --warmup 3 $PF 2>&1 | tail -3 ) > $O/rocprof_bench.log
 python tools/rocpd_stats.py $O/prof_bench/bench_results.db $O/bench_kernel_stats.csv > $O/bench_kernel_stats.txt
 head -24 $O/bench_kernel_stats.txt | cut -c1-220

@@ -14,7 +14,7 @@ with torch.cuda.stream(s):
     r = bench_extra.moe_mixtral(eng, dev, s, 3)
 print(r["block"])
 PY
-DENSE="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-dropin --no-batched-decode --no-graph --no-extra-configs --prefill-iters 1 --prefill-small 0 --prefill-m 4096 --prefill-m2 0 --prefill-m3 0"
+DENSE="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-dropin --no-batched-decode --no-graph --no-extra-configs --prefill-iters 1 --prefill-small 0 --prefill-m 4096 --prefill-m2 0 --prefill-m3 0"
 i=0
 for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum TCC_EA_RDREQ_sum TCC_EA_RDREQ_32B_sum" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM_RD SQ_INSTS_SALU SQ_WAVES"; do
   i=$((i+1))
