@@ -172,7 +172,8 @@ size_t awq_w4a16_forward_cdna4_workspace_bytes(int m, int n, int k);
  * gemm_cuda.cu:1155-1206, :546-619.  Its K split across blocks keeps the fp32 parts in the caller's workspace and the ticket words in a library-owned,
  * zero-initialised per-device array in which a word belongs to ONE launch at a time: eager launches use the lane of their stream, a launch recorded
  * during a stream capture gets words of its own that are never handed out again (so graphs may be replayed on any streams); no lane / region left, or
- * no workspace: the call runs unsplit.  awq_midm_init allocates that array for the current device ahead of the first call (optional; the first
+ * no workspace: the call runs unsplit.  hipStreamPerThread (a different stream in every thread under one handle value) never gets a lane: its calls
+ * run unsplit, so threads that share that handle never share ticket words.  awq_midm_init allocates that array for the current device ahead of the first call (optional; the first
  * split launch outside a capture does it otherwise).  Returns AWQ_OK or AWQ_ERR_LAUNCH. */
 int awq_midm_init(void);
 /* host-side query (no GPU work): the tiles the prefill GEMM launches for an [m, n] output of a 3- or 4-bit matrix.  *mode: 0 = 256 x 256

@@ -195,9 +195,13 @@ __device__ __forceinline__ u32x4 ldg_nt_u32x4(const u32* p) {
 // outputs by one ulp of T against an exact silu, which is also how far torch's own GPU silu sits from its CPU one); libm's expf and
 // an IEEE division cost ~40 instructions = +9 % on the gate/up GEMM at M = 2048.  The decode epilogues use the same form (silu_f32).
 // The ONE fp32 silu of the library (decode and prefill epilogues alike, so a row's QuantLlamaMLP output does not depend on how many
-// rows were batched with it): x * rcp(1 + exp2(-x log2 e)) on the hardware transcendentals.
+// rows were batched with it): x * rcp(1 + exp2(-x log2 e)) on the hardware transcendentals.  Below x = -64 the reciprocal of 1 + e^-x (~1e-38 at
+// x = -87.5) falls under the smallest normal fp32 number and the hardware returns 0, while torch's x / (1 + e^-x) keeps silu ~ -9e-37, a normal
+// bf16 value: there the denominator is scaled by 2^-64 before the reciprocal and the product by 2^-64 after it -- exact power-of-two scalings,
+// so every other input gives the same bits as the unscaled form.
 __device__ __forceinline__ float silu_f32(float x) {
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+  const float k = x < -64.0f ? 0x1p-64f : 1.0f;
+  return x * __builtin_amdgcn_rcpf((1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)) * k) * k;
 }
 template <typename DT>
 __device__ __forceinline__ u32 silu_mul_pair(u32 gate2, u32 up2) {

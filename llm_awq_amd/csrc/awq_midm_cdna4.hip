@@ -404,6 +404,7 @@ __global__ __launch_bounds__(64 * WAVES) void midm_kernel(const uint16_t* __rest
 namespace {
 // ---- ticket words of the K split.  A word belongs to ONE slab group of ONE launch at a time:
 //   * eager launches take the lane of their STREAM (launches of a stream are ordered; a lane is zero outside a launch that uses it);
+//     hipStreamPerThread names a different stream in every thread and gets no lane (those launches run unsplit);
 //   * a launch recorded during a stream capture gets words of its own from a bump region that is never handed out twice: two graphs -- or a graph and
 //     the eager work of the stream it was captured on -- never share a word, whatever streams they are replayed on (a graph never runs concurrently
 //     with itself).  When the region is exhausted, or no lane is free, the launch runs unsplit.
@@ -423,6 +424,9 @@ TicketPool g_pools[64];
 
 unsigned* splitk_ticket_words(hipStream_t st, int groups) {
   int dev = 0;
+  // hipStreamPerThread is one handle value for a different real stream in every thread: a lane keyed on it would be shared by launches that are
+  // not ordered with each other (the reducer could add another thread's partials), so its launches get no lane and run unsplit
+  if (st == hipStreamPerThread) return nullptr;
   if (groups > kLaneWords || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (st != nullptr && hipStreamIsCapturing(st, &cs) != hipSuccess) return nullptr;  // (the null stream cannot be captured; the query errors on it while another stream is)

@@ -7,6 +7,7 @@ CPU `randn` runs vectorised math whose last bits depend on the host's SIMD level
 Bounds.  Hard criteria are always elementwise / norm-wise error bounds.  "How many elements are bit-identical" is a
 STATISTICAL criterion: the expected number of flipped roundings is modelled (or stated by the caller) and the observed count
 must stay inside a Poisson tail (lambda + 6 sqrt(lambda) + 3: false-failure probability below 1e-6 per assertion)."""
+import contextlib
 import json
 import math
 import os
@@ -317,3 +318,147 @@ def check_fused_tail(y: torch.Tensor, gate: torch.Tensor, up: torch.Tensor, rel_
     record_rel(what, rel, rel_max)
     assert rel <= rel_max, f"{what}: norm-wise {rel:.3e} > {rel_max:.3e}"
     return rel
+
+
+# ---------------- integer lattice: inputs on which every correct kernel has ONE exact answer ----------------
+# q, z integers, scales s = m * 2^e (m in {1, 3, 5, 7}, e in {e0, e0 + 1}), x small integers: every weight (q - z) * s, every product x * w and every
+# partial sum of products -- in ANY order -- is an integer multiple of 2^e0 below 2^24 * 2^e0 in magnitude, so exact in fp32.  A correct kernel then
+# returns the single RNE rounding of the exact sum (bias added as the reference does: T(T(acc) + b)) and the tests demand bit equality, no tolerance.
+LATTICE_MANT = (1, 3, 5, 7)
+
+
+def lattice_radius(K, bits=4, e0=-9, dtype=torch.bfloat16):
+    """largest |x| such that sum_k |x||w| < 2^24 * 2^e0 for every output (and |y| < 65504 in fp16), capped at 32 (x exact in T)"""
+    wmax = (2 ** bits - 1) * max(LATTICE_MANT) * 2  # |q - z| * m * 2^(e - e0) at most
+    r = ((1 << 24) - 1) // (K * wmax)
+    if dtype == torch.float16:
+        r = min(r, int(math.ceil(65504.0 / 2.0 ** e0 / (K * wmax))) - 1)
+    return min(r, 32)
+
+
+def make_lattice_case(N, K, dtype, seed=0, M=1, bits=4, e0=-9, R=None, finite=True):
+    """host-independent (Gen) lattice case: q [N, K] uint8 over every code, z [G, N] over the same range, s = m * 2^e per (group, n), x [M, K] integers
+    in [-R, R] (R = lattice_radius unless given), the v2 / w3c buffers scales / scaled_zeros T [Gpad, N] with sz = -z * s.  The invariant
+    is asserted: sum_k |x||w| < 2^24 * 2^e0 (a bound on every partial sum) and, in fp16 unless `finite` is False (the overflow cases),
+    |y| < 65504."""
+    g = Gen(seed)
+    G = K // 128
+    levels = 2 ** bits
+    q = g.g.integers(0, levels, size=(N, K), dtype=np.uint8)
+    z = g.g.integers(0, levels, size=(G, N), dtype=np.uint8)
+    m = np.asarray(LATTICE_MANT, dtype=np.float64)[g.g.integers(0, len(LATTICE_MANT), size=(G, N))]
+    e = e0 + g.g.integers(0, 2, size=(G, N))
+    s = m * np.exp2(e)
+    if R is None:
+        R = lattice_radius(K, bits, e0, dtype if finite else torch.bfloat16)
+    assert R >= 1, (K, bits, e0)
+    x = g.g.integers(-R, R + 1, size=(M, K), dtype=np.int64)
+    bound = K * R * (levels - 1) * max(LATTICE_MANT) * 2  # units of 2^e0: |x| <= R, |q - z| <= levels - 1, s <= 7 * 2^(e0 + 1)
+    assert bound < (1 << 24), f"lattice invariant: sum |x||w| <= {bound} * 2^{e0} is not below 2^24 * 2^{e0}"
+    if dtype == torch.float16 and finite:
+        assert bound * 2.0 ** e0 < 65504, "lattice invariant: |y| < 65504 in fp16"
+    gp = O.padded_groups(K)
+    sc = torch.zeros(gp, N, dtype=torch.float64)
+    sc[:G] = torch.from_numpy(s)
+    szd = torch.zeros(gp, N, dtype=torch.float64)
+    szd[:G] = -torch.from_numpy(z.astype(np.float64)) * sc[:G]
+    scales, scaled_zeros = sc.to(dtype), szd.to(dtype)
+    assert torch.equal(scales.double(), sc) and torch.equal(scaled_zeros.double(), szd), "lattice scales must be exact in T"
+    return dict(N=N, K=K, dtype=dtype, bits=bits, e0=e0, R=R, q=q, z=z, s=s, scales=scales, scaled_zeros=scaled_zeros,
+                x=torch.from_numpy(x).to(dtype))
+
+
+def lattice_weight_f64(case, device="cpu"):
+    """W [N, K] = (q - z) * s in float64 (exact), on `device`"""
+    q = torch.from_numpy(case["q"]).to(device)
+    K = case["K"]
+    zs = torch.from_numpy(case["z"].astype(np.float64) * case["s"]).to(device)   # [G, N] z * s
+    s = torch.from_numpy(case["s"]).to(device)
+    gi = torch.arange(K, device=device) // 128
+    return q.double() * s[gi].t() - zs[gi].t()
+
+
+def lattice_bias(case, seed=1):
+    """a bias in T on the lattice (integers * 2^e0 of the size of the outputs): T(acc) + b then rounds again, so the single rounding T(acc + b)
+    and the reference's T(T(acc) + b) differ on a visible share of the outputs"""
+    g = Gen(seed)
+    span = min(1 << 12, case["K"] * case["R"] * 8)
+    b = g.g.integers(-span, span + 1, size=case["N"]).astype(np.float64) * 2.0 ** case["e0"]
+    return torch.from_numpy(b).to(case["dtype"])
+
+
+def rne_ties(y: torch.Tensor, dtype) -> torch.Tensor:
+    """bool mask: the exact values y (float, exactly representable in fp64) that lie exactly halfway between two neighbours of T"""
+    yd = y.double()
+    f, ex = torch.frexp(yd)                      # y = f 2^ex, |f| in [0.5, 1): the binade of y starts at 2^(ex - 1)
+    p = torch.clamp(ex - 1, min=MIN_EXP[dtype])  # (subnormals: the spacing of the smallest binade)
+    v = yd * torch.pow(2.0, (MANT[dtype] + 1 - p).double())   # y in units of half the spacing of T there
+    return (yd != 0) & (v == torch.round(v)) & (torch.remainder(v, 2.0) == 1.0)
+
+
+def lattice_oracle(x, case, bias=None, W=None):
+    """(y T, y32 fp32, ties): float64 product of the integers (exact in any order) on x's device, cast to fp32 (exact), then to T; with `bias`
+    T(acc) + bias in T (WQLinear.forward / O.wqlinear_forward).  `ties` = how many of the T outputs are exact RNE ties (before the bias)."""
+    if W is None:
+        W = lattice_weight_f64(case, x.device)
+    x2 = x.reshape(-1, x.shape[-1])
+    y64 = x2.double() @ W.t()
+    y32 = y64.float()
+    assert torch.equal(y32.double(), y64), "the lattice sum must be exact in fp32"
+    T = case["dtype"]
+    y = y32.to(T)
+    ties = int(rne_ties(y32, T).sum().item())
+    if bias is not None:
+        y = y + bias.to(y.device)
+    return y, y32, ties
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16)
+
+
+def assert_lattice_equal(got: torch.Tensor, want: torch.Tensor, what: str = "", ties=None):
+    """bit equality of two tensors of the same dtype (compared as integer views, so NaN poison never compares equal); the first mismatches are
+    reported with (m, n), got, expected and whether the exact value was a tie (`ties`: a bool mask of want's shape, optional)"""
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, tuple(got.shape), tuple(want.shape))
+    g2 = got.reshape(-1, got.shape[-1])
+    w2 = want.reshape(-1, want.shape[-1]).to(g2.device)
+    bad = _bits(g2) != _bits(w2)
+    if not bool(bad.any()):
+        return
+    idx = torch.nonzero(bad)[:6].tolist()
+    rows = []
+    for (m, n) in idx:
+        t = "" if ties is None else f" tie={bool(ties.reshape(-1, got.shape[-1])[m, n])}"
+        rows.append(f"(m={m}, n={n}) got {g2[m, n].item()!r} want {w2[m, n].item()!r}{t}")
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} outputs differ from the exact lattice result; " + "; ".join(rows))
+
+
+def check_fused_tail_exact(y: torch.Tensor, gate: torch.Tensor, up: torch.Tensor, what: str = "fused tail"):
+    """gate / up = the EXACT T-rounded products (lattice): y must lie in the hull over {silu -, silu, silu +} of T(T(silu(gate)) * up) -- the
+    hardware exp2 / rcp may move T(silu) by one ulp, nothing else may differ"""
+    gate, up = gate.to(y.device), up.to(y.device)
+    vals = [(sg * up).float() for sg in _nbrs(torch.nn.functional.silu(gate))]
+    lo = torch.minimum(torch.minimum(vals[0], vals[1]), vals[2])
+    hi = torch.maximum(torch.maximum(vals[0], vals[1]), vals[2])
+    yf = y.float()
+    bad = ~((yf >= lo) & (yf <= hi))   # (NaN poison is outside every hull)
+    if bool(bad.any()):
+        k = int(torch.nonzero(bad.flatten())[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {y.numel()} outputs outside the hull; first: y={yf.flatten()[k].item()!r} "
+                             f"hull=[{lo.flatten()[k].item()!r}, {hi.flatten()[k].item()!r}] gate={gate.flatten()[k].item()!r} up={up.flatten()[k].item()!r}")
+
+
+@contextlib.contextmanager
+def poisoned():
+    """every uninitialised allocation -- torch.empty here, the extension's at::empty outputs and workspaces -- is filled with NaN (integers: their
+    maximum) while inside: a kernel that skips a store can no longer pass by leaving the previous launch's result in a recycled block"""
+    import torch.utils.deterministic as det
+    prev = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(), det.fill_uninitialized_memory)
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    det.fill_uninitialized_memory = True
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(prev[0], warn_only=prev[1])
+        det.fill_uninitialized_memory = prev[2]

@@ -6,9 +6,17 @@ import pytest
 import torch
 
 from oracle import awq_oracle as O
-from tests.helpers import acc_slack, check_forward, check_fused_tail, make_case, assert_bits, record_rel, weight_row_norms, _dequant_f64
+from tests.helpers import acc_slack, check_forward, check_fused_tail, make_case, assert_bits, record_rel, weight_row_norms, _dequant_f64, poisoned
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _poison():
+    """uninitialised outputs and workspaces are NaN-filled (helpers.poisoned): a second call cannot pass on the first call's freed block"""
+    with poisoned():
+        yield
+
 
 # norm-wise distance of the fused tail from the oracle's tail: BASELINE.json's 1e-3 (measured on MI355X: <= 3.7e-4 over every case of the suite,
 # profiles/r05_test_stats.txt -- 2.7 x below it); the HARD criterion is check_fused_tail's elementwise hull
@@ -141,13 +149,6 @@ def _fused_block(cg, cu, cd, H, F, dtype):
             self.mlp = LlamaMLP()
 
     return make_fused_mlp(Block()).mlp
-
-
-def _granule_h(state, F, dtype):
-    """the activations the one-launch kernel handed over: data halves of the {2 x T, tag} granules behind the counter block of its state"""
-    from llm_awq_amd import ops
-    g = state[ops._capi.AWQ_MLP_DECODE_COUNTER_BYTES // 4:][: F].view(F // 2, 2)
-    return g[:, 0].contiguous().view(torch.int16).view(dtype).reshape(1, F).cpu(), g[:, 1].cpu()
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -6,9 +6,17 @@ split-K (gemm_cuda.cu:546-619) has the same property."""
 import pytest
 import torch
 
-from tests.helpers import assert_bits, cuda_gen
+from tests.helpers import assert_bits, cuda_gen, poisoned
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _poison():
+    """uninitialised outputs and workspaces are NaN-filled (helpers.poisoned): a second call cannot pass on the first call's freed block"""
+    with poisoned():
+        yield
+
 
 SHAPES = [(4096, 4096), (14336, 4096), (1024, 1296), (4096, 6144), (8192, 1024)]
 
