@@ -330,6 +330,27 @@ int awq_oneshot_allreduce_selftest(void* const* peer_buffers, const void* in_all
 int awq_oneshot_allreduce_f32_selftest(void* const* peer_buffers, const float* in_all_f32, const void* bias, int bias_n, void* out_all, int count,
                                        int dtype, int world, unsigned round, int max_bytes, int* status_dev, void* stream);
 
+/* ---- Decode attention over the FasterTransformer KV cache (tinychat's single_query_attention, ft_attention.cpp:112-185).
+ * One decode step of multi-head / grouped-query attention:
+ *     q [B, H, Dh], k / v [B, Hkv, Dh] (own batch strides, in elements; heads contiguous), out [B, H, Dh] contiguous
+ *     k_cache [Bc, Hkv, Dh/8, Lmax, 8], v_cache [Bc, Hkv, Lmax, Dh] (contiguous; rows b < B are used), B <= Bc
+ * tlength = length_per_sample[b] (device int32 [B], may be NULL) or timestep; positions max(0, tlength + 1 - Lmax) .. tlength are
+ * attended at cache index pos % Lmax; the rotated k and v of the current token are written at tlength % Lmax (nothing else is).
+ * rotary_dim 0 = none, neox != 0 = rotate-half, else GPT-J interleaved; alibi_slopes fp32 [H] or NULL.  With a length tensor,
+ * `timestep` is the host-side upper bound that sizes the context split.  T = fp16 / bf16 (`dtype`), 32 <= Dh <= 256, Dh % 16 == 0.
+ * Softmax weights and P.V stay in fp32; the output is bit-deterministic (csrc/awq_attn_cdna4.hip).
+ * Returns AWQ_ERR_SHAPE (head dim, H % Hkv, B > Bc, odd or too large rotary_dim, timestep < 0, ...), AWQ_ERR_DTYPE, AWQ_ERR_NULL,
+ * AWQ_ERR_ALIGN (16 bytes for the tensors and the strides, 4 for lengths / slopes), AWQ_ERR_WORKSPACE, AWQ_ERR_LAUNCH. */
+/* Host-side plan: the context is cut into *splits chunks of *chunk positions (one launch of B * Hkv * splits blocks, plus a
+ * combine launch when *splits > 1).  Depends on these host arguments only. */
+int awq_attn_decode_plan(int batch, int nheads_kv, int head_dim, int timestep, int lmax, int* splits, int* chunk);
+/* fp32 partials of the split plan: 0 when the plan has one split (workspace may then be NULL). */
+size_t awq_attn_decode_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int timestep, int lmax);
+int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, void* v_cache, const int* length_per_sample,
+                    const float* alibi_slopes, void* out, int batch, int cache_batch, int nheads, int nheads_kv, int head_dim, int lmax,
+                    long long q_batch_stride, long long k_batch_stride, long long v_batch_stride, int timestep, int rotary_dim,
+                    float rotary_base, float rotary_scale, int neox, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
  * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every

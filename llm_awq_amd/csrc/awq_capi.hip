@@ -306,6 +306,41 @@ int awq_rmsnorm(const void* x, const void* gamma, float eps, void* out, int m, i
   return finish_launch();
 }
 
+int awq_attn_decode_plan(int batch, int nheads_kv, int head_dim, int timestep, int lmax, int* splits, int* chunk) {
+  if (!splits || !chunk) return AWQ_ERR_NULL;
+  if (batch < 1 || nheads_kv < 1 || head_dim < 32 || head_dim > 256 || (head_dim % 16) != 0 || timestep < 0 || lmax < 1) return AWQ_ERR_SHAPE;
+  return awq::attn_decode_plan(batch, nheads_kv, head_dim, timestep, lmax, splits, chunk);
+}
+
+size_t awq_attn_decode_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int timestep, int lmax) {
+  if (batch < 1 || nheads_kv < 1 || nheads < nheads_kv || head_dim < 32 || head_dim > 256 || (head_dim % 16) != 0 || timestep < 0 || lmax < 1)
+    return 0;
+  return awq::attn_decode_workspace_bytes(batch, nheads, nheads_kv, head_dim, timestep, lmax);
+}
+
+int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, void* v_cache, const int* length_per_sample,
+                    const float* alibi_slopes, void* out, int batch, int cache_batch, int nheads, int nheads_kv, int head_dim, int lmax,
+                    long long q_batch_stride, long long k_batch_stride, long long v_batch_stride, int timestep, int rotary_dim,
+                    float rotary_base, float rotary_scale, int neox, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k || !v || !k_cache || !v_cache || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (batch < 1 || cache_batch < batch || nheads < 1 || nheads_kv < 1 || (nheads % nheads_kv) != 0 || head_dim < 32 || head_dim > 256 ||
+      (head_dim % 16) != 0 || lmax < 1 || timestep < 0 || rotary_dim < 0 || rotary_dim > head_dim || (rotary_dim % 2) != 0 ||
+      q_batch_stride < 0 || k_batch_stride < 0 || v_batch_stride < 0)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) ||
+      (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 || (v_batch_stride % 8) != 0 ||
+      (reinterpret_cast<uintptr_t>(length_per_sample) & 3u) || (reinterpret_cast<uintptr_t>(alibi_slopes) & 3u))
+    return AWQ_ERR_ALIGN;
+  const size_t need = awq::attn_decode_workspace_bytes(batch, nheads, nheads_kv, head_dim, timestep, lmax);
+  if (need > 0 && (!workspace || workspace_bytes < need)) return AWQ_ERR_WORKSPACE;
+  if (need > 0 && !aligned16(workspace)) return AWQ_ERR_ALIGN;
+  awq::launch_attn_decode(q, k, v, k_cache, v_cache, length_per_sample, alibi_slopes, out, batch, nheads, nheads_kv, head_dim, lmax,
+                          q_batch_stride, k_batch_stride, v_batch_stride, timestep, rotary_dim, rotary_base, rotary_scale, neox, dtype,
+                          workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
 size_t awq_w4a16_forward_cdna4_workspace_bytes(int m, int n, int k) {
   if (awq::midm_takes(m, n, k)) return awq::midm_workspace_bytes(m, n, k);  // 9 .. 255 rows: the fp32 parts of the mid-M kernel's K split
   if (m > 8 && m < 256 && !awq::gemm_cdna4_v3_takes(m, k)) return awq::skinny_splitk_workspace_bytes(m, n, k);  // (knob midm = 0) the skinny launch's K split

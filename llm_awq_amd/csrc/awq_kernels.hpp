@@ -165,6 +165,12 @@ int launch_bias_add(void* out, const void* bias, int m, int n, int dtype, hipStr
 int launch_round_bias_f32(const void* in_f32, const void* bias, void* out, int m, int n, int dtype, hipStream_t st);
 // RMSNorm of m rows of k (awq_util.hip; layernorm.cu:39-61's arithmetic); -1 if k % 8 != 0
 int launch_rmsnorm(const void* x, const void* gamma, float eps, void* out, int m, int k, int dtype, hipStream_t st);
+// decode attention over the FT KV cache (awq_attn_cdna4.hip); arguments validated by the caller
+int attn_decode_plan(int batch, int nheads_kv, int head_dim, int timestep, int lmax, int* splits, int* chunk);
+size_t attn_decode_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int timestep, int lmax);
+int launch_attn_decode(const void* q, const void* k, const void* v, void* k_cache, void* v_cache, const int* lens, const float* alibi,
+                       void* out, int B, int H, int Hkv, int Dh, int Lmax, long long q_bs, long long k_bs, long long v_bs, int timestep,
+                       int rot, float rot_base, float rot_scale, int neox, int dtype, void* workspace, hipStream_t st);
 int launch_unpack_v2(const void* qw, void* out_u8, int n, int k, hipStream_t st);
 int launch_dequant_v2(const void* qw, const void* s, const void* z, void* out, int n, int k, int dtype, hipStream_t st);
 int launch_pack_v2(const void* q_u8, void* qw, int n, int k, hipStream_t st);

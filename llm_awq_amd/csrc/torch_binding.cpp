@@ -588,6 +588,80 @@ torch::Tensor rmsnorm(torch::Tensor in_feats, torch::Tensor gamma, double eps) {
   return out;
 }
 
+// layernorm_forward_cuda(x, weight, out, eps) (awq/kernels/csrc/layernorm/layernorm.cu, called by tinychat's FTLlamaRMSNorm,
+// modules/fused_norm.py:18, and llama.py:35): the same RMSNorm launch as rmsnorm(), written into the caller's `out`.
+void layernorm_forward_cuda(torch::Tensor x, torch::Tensor weight, torch::Tensor out, double eps) {
+  TORCH_CHECK(x.is_cuda() && weight.is_cuda() && out.is_cuda(), "layernorm_forward_cuda: tensors must live on the GPU");
+  TORCH_CHECK(x.is_contiguous() && weight.is_contiguous() && out.is_contiguous(), "layernorm_forward_cuda: tensors must be contiguous");
+  TORCH_CHECK((x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) && weight.scalar_type() == x.scalar_type() &&
+                  out.scalar_type() == x.scalar_type(),
+              "layernorm_forward_cuda: float16 / bfloat16 x, weight and out of one dtype are supported");
+  const int64_t k = x.size(-1);
+  TORCH_CHECK(k > 0 && weight.numel() == k && out.sizes() == x.sizes(), "layernorm_forward_cuda: shape mismatch");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  if (x.numel() == 0) return;
+  raise_on(awq_rmsnorm(x.data_ptr(), weight.data_ptr(), (float)eps, out.data_ptr(), (int)(x.numel() / k), (int)k, dtype_code(x),
+                       (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
+// single_query_attention (awq/kernels/csrc/attention/ft_attention.cpp:112-185): one decode step over the FT KV cache
+// (csrc/awq_attn_cdna4.hip).  Same shape checks as the reference, except that the batch may be smaller than the cache's
+// (tinychat allocates the caches for max_batch_size) and q, k, v keep batch strides of their own.
+torch::Tensor single_query_attention(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, torch::Tensor k_cache,
+                                     torch::Tensor v_cache, c10::optional<const torch::Tensor> length_per_sample_,
+                                     c10::optional<const torch::Tensor> alibi_slopes_, const int timestep, const int rotary_embedding_dim,
+                                     const double rotary_base, const double rotary_scale, const bool neox_rotary_style) {
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v, &k_cache, &v_cache})
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "single_query_attention: tensors must live on the same GPU");
+  TORCH_CHECK(q.scalar_type() != at::kFloat,
+              "single_query_attention: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "single_query_attention: float16 / bfloat16 only, got ",
+              q.scalar_type());
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k, &v, &k_cache, &v_cache})
+    TORCH_CHECK(t->scalar_type() == q.scalar_type(), "single_query_attention: q, k, v and the caches must share one dtype");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3 && v_cache.dim() == 4 && k_cache.dim() == 5,
+              "single_query_attention: q / k / v [B, heads, Dh], k_cache [B, Hkv, Dh/8, L, 8], v_cache [B, Hkv, L, Dh]");
+  const int64_t cache_batch = v_cache.size(0), nheads = q.size(1), nheads_kv = v_cache.size(1), lmax = v_cache.size(2),
+                headdim = v_cache.size(3), batch = q.size(0);
+  TORCH_CHECK(batch >= 1 && batch <= cache_batch, "single_query_attention: batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(q.size(2) == headdim, "single_query_attention: q must be [B, H, ", headdim, "]");
+  TORCH_CHECK(k.size(0) == batch && k.size(1) == nheads_kv && k.size(2) == headdim, "single_query_attention: k must be [B, Hkv, Dh]");
+  TORCH_CHECK(v.size(0) == batch && v.size(1) == nheads_kv && v.size(2) == headdim, "single_query_attention: v must be [B, Hkv, Dh]");
+  TORCH_CHECK(k_cache.size(0) == cache_batch && k_cache.size(1) == nheads_kv && k_cache.size(2) == headdim / 8 && k_cache.size(3) == lmax &&
+                  k_cache.size(4) == 8 && headdim % 8 == 0,
+              "single_query_attention: k_cache must be [B, Hkv, Dh/8, L, 8]");
+  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == headdim);
+  TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == headdim);
+  TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == headdim);
+  TORCH_CHECK(v_cache.is_contiguous() && k_cache.is_contiguous(), "single_query_attention: the caches must be contiguous");
+  const int* lens = nullptr;
+  if (length_per_sample_.has_value()) {
+    const auto& l = length_per_sample_.value();
+    TORCH_CHECK(l.is_cuda() && l.device() == q.device() && l.dim() == 1 && l.size(0) >= batch && l.is_contiguous() && l.scalar_type() == at::kInt,
+                "single_query_attention: length_per_sample must be a contiguous int32 [B] tensor on the GPU");
+    lens = l.data_ptr<int>();
+  }
+  const float* slopes = nullptr;
+  if (alibi_slopes_.has_value()) {
+    const auto& a = alibi_slopes_.value();
+    TORCH_CHECK(a.is_cuda() && a.device() == q.device() && a.dim() == 1 && a.size(0) == nheads && a.is_contiguous() &&
+                    a.scalar_type() == at::kFloat,
+                "single_query_attention: alibi_slopes must be a contiguous float32 [H] tensor on the GPU");
+    slopes = a.data_ptr<float>();
+  }
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_decode_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, timestep, (int)lmax);
+  at::Tensor ws;
+  if (wsb) ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  raise_on(awq_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens, slopes, out.data_ptr(),
+                           (int)batch, (int)cache_batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)lmax, q.stride(0), k.stride(0),
+                           v.stride(0), timestep, rotary_embedding_dim, (float)rotary_base, (float)rotary_scale, neox_rotary_style ? 1 : 0,
+                           dtype_code(q), wsb ? ws.data_ptr() : nullptr, wsb,
+                           (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
 torch::Tensor rmsnorm_forward_cdna4(torch::Tensor in_feats, torch::Tensor gamma, double eps, torch::Tensor kernel, torch::Tensor sz_packed,
                                     c10::optional<torch::Tensor> bias, bool fused_gate_up) {
   TORCH_CHECK(in_feats.is_cuda() && gamma.is_cuda() && kernel.is_cuda() && sz_packed.is_cuda());
@@ -694,6 +768,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native W4A16 kernels behind llm-awq's awq_inference_engine API (hot path only)";
   m.def("gemm_forward_cuda_new", &gemm_forward_cuda_new, "New quantized GEMM kernel.");
   m.def("gemv_forward_cuda_new", &gemv_forward_cuda_new, "New quantized GEMV kernel.");
+  m.def("layernorm_forward_cuda", &layernorm_forward_cuda, "FT RMSNorm into `out` (tinychat's FTLlamaRMSNorm)", py::arg("_input"),
+        py::arg("_gamma"), py::arg("_out"), py::arg("eps"));
+  m.def("single_query_attention", &single_query_attention, "Attention with a single query", py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("length_per_sample_"), py::arg("alibi_slopes_"), py::arg("timestep"),
+        py::arg("rotary_embedding_dim") = 0, py::arg("rotary_base") = 10000.0f, py::arg("rotary_scale") = 1.0f,
+        py::arg("neox_rotary_style") = true);
   m.def("abi_version", []() { return awq_abi_version(); });
   m.def("cdna4_cache_info", []() {
     std::lock_guard<std::mutex> lock(g_cache_mu);

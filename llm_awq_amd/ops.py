@@ -494,3 +494,41 @@ def pair_lost_count(device=None) -> int:
     with torch.cuda.device(dev):
         _capi.check(_capi.lib().awq_w4a16_gemm_cdna4_pair_lost(ctypes.byref(c)))
     return int(c.value)
+
+
+def attn_decode_plan(batch: int, nheads_kv: int, head_dim: int, timestep: int, lmax: int):
+    """Host-side awq_attn_decode_plan: (splits, chunk) of the decode attention launch (no GPU needed)."""
+    import ctypes
+
+    s, c = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_decode_plan(batch, nheads_kv, head_dim, timestep, lmax, ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
+def single_query_attention(q, k, v, k_cache, v_cache, length_per_sample=None, alibi_slopes=None, timestep: int = 0,
+                           rotary_embedding_dim: int = 0, rotary_base: float = 10000.0, rotary_scale: float = 1.0,
+                           neox_rotary_style: bool = True):
+    """C-ABI awq_attn_decode: one decode step over the FasterTransformer KV cache (ft_attention.cpp:112-185).
+    q [B, H, Dh], k / v [B, Hkv, Dh] (batch strides of their own, heads contiguous), k_cache [Bc, Hkv, Dh/8, Lmax, 8],
+    v_cache [Bc, Hkv, Lmax, Dh] with B <= Bc.  Writes the current k / v into the caches; returns [B, H, Dh]."""
+    for t in (q, k, v, k_cache, v_cache, length_per_sample, alibi_slopes):
+        if t is not None and not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    for t in (q, k, v):
+        if t.dim() != 3 or t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+            raise ValueError("q / k / v must be [B, heads, Dh] with contiguous heads")
+    _need_gpu(k_cache, v_cache, length_per_sample, alibi_slopes)
+    B, H, Dh = q.shape
+    Bc, Hkv, Lmax = v_cache.shape[0], v_cache.shape[1], v_cache.shape[2]
+    out = torch.empty(B, H, Dh, dtype=q.dtype, device=q.device)
+    L = _capi.lib()
+    wsb = L.awq_attn_decode_workspace_bytes(B, H, Hkv, Dh, timestep, Lmax)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device) if wsb else None
+    with torch.cuda.device(q.device):
+        _capi.check(L.awq_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                      length_per_sample.data_ptr() if length_per_sample is not None else None,
+                                      alibi_slopes.data_ptr() if alibi_slopes is not None else None, out.data_ptr(),
+                                      B, Bc, H, Hkv, Dh, Lmax, q.stride(0), k.stride(0), v.stride(0), int(timestep),
+                                      int(rotary_embedding_dim), float(rotary_base), float(rotary_scale), int(bool(neox_rotary_style)),
+                                      _dt(q), ws.data_ptr() if wsb else None, wsb, _stream(q)))
+    return out
