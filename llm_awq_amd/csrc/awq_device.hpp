@@ -341,6 +341,22 @@ struct Cdna4DequantH {
     p.c = f32x4{cv, cv, cv, cv};
     return p;
   }
+  // prep() in two instructions less, for loops that are bound by issue slots (the one-row decode GEMV).  The offset sz - 1024 s' is ONE
+  // v_fma_mix_f32 on the two f16 halves of the dword (product and sum are exact, as in prep(): same bits) instead of the v_mov 0 + the
+  // accumulating v_dot2c hipcc picks for the dot builtin, and the upper half of the dequant MFMA's C quad is one v_mov_b64 of the lower
+  // half instead of two v_mov.  (The v_mov_b64 is asm: its result must not be the operand of the very next MFMA -- the decode loop pins
+  // the prep in front of a wait; tests/test_decode_isa.py checks the generated code.)
+  __device__ __forceinline__ Prep prep_lean(u32 szh) const {
+    Prep p;
+    p.b = u32x2{__builtin_amdgcn_perm(szh, szh, sel01), __builtin_amdgcn_perm(szh, szh, sel23)};
+    const f16x2 h = __builtin_bit_cast(f16x2, szh);
+    const float cv = __builtin_fmaf((float)h.x, -1024.0f, (float)h.y);
+    const u32x2 c01 = {__builtin_bit_cast(u32, cv), __builtin_bit_cast(u32, cv)};
+    u32x2 c23;
+    asm("v_mov_b64 %0, %1" : "=v"(c23) : "v"(c01));
+    p.c = __builtin_bit_cast(f32x4, u32x4{c01.x, c01.y, c23.x, c23.y});
+    return p;
+  }
   __device__ __forceinline__ vec8 word(u32 w, const Prep& p) const {
     typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
     const u32 w8 = w >> 8;
