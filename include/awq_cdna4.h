@@ -351,8 +351,42 @@ int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, 
                     long long q_batch_stride, long long k_batch_stride, long long v_batch_stride, int timestep, int rotary_dim,
                     float rotary_base, float rotary_scale, int neox, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Prefill attention (flash_attn_func's forward: tinychat llama.py:218, fused_attn.py:477,539).
+ *     q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (own batch and row strides, in elements; heads contiguous: head stride = Dh),
+ *     out [B, Sq, H, Dh] contiguous;  O = softmax(softmax_scale * Q K^T + mask) V, plain softmax.
+ * causal != 0: query row i attends keys j <= i + (Sk - Sq) (bottom-right aligned; needs Sq <= Sk); causal == 0: every key.
+ * H % Hkv == 0, query head h reads KV head h / (H / Hkv).  T = fp16 / bf16 (`dtype`), Dh = 64 or 128; Sq and Sk need no alignment, and
+ * no row >= Sq of q or >= Sk of k / v is read.  One pass over K / V per q tile with an online softmax on the matrix cores, fp32
+ * accumulation; each softmax weight is rounded to T once and that rounded value feeds both P.V and the row sum; O is rounded to T
+ * once.  No workspace, no atomics: bit-deterministic and capturable (csrc/awq_attn_prefill_cdna4.hip).
+ * Returns AWQ_ERR_SHAPE (head dim, H % Hkv, Sq > Sk with causal, non-positive sizes, a row stride below heads * Dh), AWQ_ERR_DTYPE,
+ * AWQ_ERR_NULL, AWQ_ERR_ALIGN (16 bytes for the pointers and the strides), AWQ_ERR_LAUNCH; all but the last without a GPU call. */
+/* Host-side plan: one launch of *blocks blocks, each a q tile of *q_tile_rows rows (64, 128 or 256) of one (batch, query head).
+ * Depends on these host arguments only; no GPU call. */
+int awq_attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
+                          int* blocks);
+int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
+                     int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                     long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+
+/* ---- Rotary embeddings of a prompt.
+ * awq_rope_with_pos (fused_rope_with_pos_forward_func, rope_new/fused_rope_with_pos.cu:33-72,263-333): input [n0, n1, nheads, head_dim]
+ * with element strides (in_stride0, in_stride1, in_stride_head, 1), out the same shape with its own strides; the angle of element
+ * (i0, i1, ., c), c < rot_dim, is freqs[(i1 * n0 + i0) * rot_dim + c] (fp32; the reference's index, quirk included); partner
+ * c + rot_dim/2 negated (first half) or c - rot_dim/2; out = T(x cos + x_rot sin) in fp32, one rounding; columns >= rot_dim are copied.
+ * rot_dim % 16 == 0, head_dim % 8 == 0, strides % 8 == 0, pointers 16-byte aligned.
+ * awq_rope_neox_inplace (rotary_embedding_neox, position_embedding/pos_encoding_kernels.cu:12-87): query and key
+ * [num_tokens, nheads, head_size] contiguous, rotated in place over the first rot_dim dims (rotate-half) at positions[token] (int64) with
+ * cos_sin_cache T [max_position, rot_dim] = cos | sin.  Evaluated in fp32 and rounded to T once (the reference rounds every product
+ * and sum); a position outside [0, max_position) is clamped into it. */
+int awq_rope_with_pos(const void* input, const float* freqs, void* out, int n0, int n1, int nheads, int head_dim, int rot_dim,
+                      long long in_stride0, long long in_stride1, long long in_stride_head, long long out_stride0, long long out_stride1,
+                      long long out_stride_head, int dtype, void* stream);
+int awq_rope_neox_inplace(const long long* positions, void* query, void* key, const void* cos_sin_cache, int num_tokens, int nheads,
+                          int head_size, int rot_dim, int max_position, int dtype, void* stream);
+
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
- * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", ...) so that tests can cover each of them; 0
+ * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every
  * call returns AWQ_ERR_SHAPE and changes nothing.  Timing probes and experiment-only kernel instantiations exist only in
  * builds made with AWQ_PROBES=1.  Returns AWQ_OK, or AWQ_ERR_SHAPE for an unknown key.  Process-global, not thread-safe. */

@@ -6,10 +6,11 @@ Only the hot path lives here: the `awq_inference_engine` e
 from __future__ import annotations
 
 import importlib
+import importlib.util
 import os
 import sys
 
-__all__ = ["load_engine", "install_as_awq_inference_engine"]
+__all__ = ["load_engine", "install_as_awq_inference_engine", "install_as_flash_attn"]
 
 _EXT_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ext")
 _engine = None
@@ -40,3 +41,21 @@ def install_as_awq_inference_engine():
     eng = load_engine()
     sys.modules["awq_inference_engine"] = eng
     return eng
+
+
+def install_as_flash_attn(force: bool = False):
+    """Make `from flash_attn import flash_attn_func` (tinychat/models/llama.py:21, modules/fused_attn.py:17) resolve to the MI355X
+    prefill attention (llm_awq_amd.flash_attn_compat).  A real, importable `flash_attn` is left alone unless `force`; a second call
+    is a no-op.  Returns the module that `import flash_attn` now yields."""
+    from . import flash_attn_compat
+
+    cur = sys.modules.get("flash_attn")
+    if cur is flash_attn_compat:
+        return cur
+    if not force:
+        if cur is not None:
+            return cur
+        if importlib.util.find_spec("flash_attn") is not None:
+            return importlib.import_module("flash_attn")
+    sys.modules["flash_attn"] = flash_attn_compat
+    return flash_attn_compat

@@ -84,6 +84,12 @@ SIGNATURES = {
     "awq_attn_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "awq_attn_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, _i, _i, ctypes.c_float, ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_prefill_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_attn_prefill": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                              ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),
+    "awq_rope_with_pos": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                               ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _vp]),
+    "awq_rope_neox_inplace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awq_tune_set": (_i, [ctypes.c_char_p, _i]),
 }
 

@@ -1,0 +1,434 @@
+// Prefill attention (flash_attn_func's forward) and the two rotary-embedding exports tinychat calls on a prompt.
+//
+//   O = softmax(scale * Q K^T + mask) V        q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh], out [B, Sq, H, Dh]
+//   causal: query row i attends keys j <= i + (Sk - Sq) (bottom-right aligned, flash-attn >= 2.1; tinychat's chunk prefill passes
+//   Sq = seqlen, Sk = start_pos + seqlen, llama.py:218 / fused_attn.py:477,539); query head h reads KV head h / (H / Hkv).
+//
+// Structure (flash attention, one pass over K / V per q tile, online softmax; nothing of size Sq x Sk exists anywhere):
+//   * One block = NW waves (NW = 4; 8 or 2 where attn_prefill_plan measured a gain; every NW exists for both head dims) = one q tile
+//     of 32 NW rows of ONE (batch, query head); wave w owns rows 32 w .. 32 w + 31.  Blocks are numbered (tile rank, batch, head) with the head fastest, so the G query heads of a KV group run
+//     next to each other and re-read their K / V from L2, and with causal masking rank 0 is the LAST q tile (the longest one): the
+//     short tiles fill the tail of the launch.
+//   * K / V are walked in tiles of 64 keys, double-buffered in LDS through registers: the global loads of tile t + 1 are issued before
+//     the MFMAs of tile t and written to the other LDS buffer after them (one barrier per tile), so their latency hides under the
+//     compute.  Rows >= Sk are never read: their address is clamped to row Sk - 1 and their score is masked.
+//   * S^T = K Q^T on v_mfma_f32_32x32x16 (A = K rows from LDS, ds_read_b128 on an XOR-swizzled image; B = Q, held in registers for the
+//     whole block): a lane then holds, for ITS query row (lane % 32), the scores of 32 of the tile's 64 keys, the lane 32 away the other
+//     32 -- the row max costs 31 v_max and one cross-half exchange, and the softmax is lane-local.
+//   * P is rounded to T once; the row sum l is accumulated from those ROUNDED weights (numerator and denominator carry the same
+//     rounding).  The rounded P registers are directly the B operand of O^T = V^T P^T (an accumulator tile's registers 8 s .. 8 s + 7
+//     are the k-step s of the next product, in the permuted key order 16 s + 8 (j / 4) + 4 (lane / 32) + j % 4); the A operand V^T comes
+//     from the row-major V image with ds_read_b64_tr_b16, two reads of 4 consecutive keys each -- exactly that permuted order.  O^T has
+//     the query row on the lane again, so the rescale by exp(m_old - m_new) is lane-local too.
+//   * Tiles wholly above the diagonal are skipped per block (loop bound) and per wave (wave-uniform test); -inf masking runs only in
+//     the tiles the diagonal or the end of K crosses.
+//   * No workspace, no atomics: bit-deterministic.  O is divided by l (IEEE division of 1 / l, once per row) and rounded to T once.
+#include "awq_device.hpp"
+#include "awq_kernels.hpp"
+
+#include <math.h>
+#include <string.h>
+
+namespace awq {
+namespace {
+
+constexpr int kKV = 64;       // keys per tile
+constexpr int kMfmaRows = 32;  // q rows per wave
+constexpr int kCUs = 256;      // the MI355X; a constant because the plan is a host-only function that CPU tests pin (as attn_decode_plan's)
+int g_force_rows = 0;          // knob attn_prefill_rows (awq_tune_set): 64 / 128 / 256 forces the q tile, 0 = the plan's choice
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+
+struct PrefillArgs {
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  uint16_t* out;
+  long long q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;  // elements
+  int B, Sq, Sk, H, G, ntiles, causal;
+  float scale_log2e;
+};
+
+// LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
+//   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
+//   V (transposed reads, a 32-lane half = 4 consecutive rows x 64 bytes): the 4 rows land on 4 different 64-byte quarters of the banks
+template <int DH>
+__device__ __forceinline__ int k_off(int row, int ch) {
+  return row * DH + ((ch ^ (DH == 128 ? (row & 15) : ((row >> 1) & 7))) << 3);
+}
+template <int DH>
+__device__ __forceinline__ int v_off(int row, int ch) {
+  return row * DH + ((ch ^ (DH == 128 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (((row >> 1) & 1) << 2))) << 3);
+}
+
+template <typename DT, int DH, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
+  using vec8 = typename DT::vec8;
+  using elem = typename DT::elem;
+  constexpr int NT = NW * 64;
+  constexpr int CPR = DH / 8;             // 16-byte chunks per row
+  constexpr int LOADS = kKV * CPR / NT;   // chunks of one K (or V) tile per thread
+  constexpr int KS = DH / 16;             // k-steps of Q K^T
+  constexpr int DB = DH / 32;             // 32-column blocks of O
+  static_assert(LOADS >= 1 && LOADS * NT == kKV * CPR, "tile does not divide over the block");
+  __shared__ __attribute__((aligned(16))) uint16_t k_s[2][kKV * DH];
+  __shared__ __attribute__((aligned(16))) uint16_t v_s[2][kKV * DH];
+
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bi = blockIdx.x;
+  const int h = bi % a.H;
+  bi /= a.H;
+  const int b = bi % a.B;
+  const int rank = bi / a.B;
+  const int tile = a.causal ? a.ntiles - 1 - rank : rank;
+  const int kvh = h / a.G;
+  const int q0 = tile * (NW * kMfmaRows);
+  const int shift = a.Sk - a.Sq;
+  const int q_last = min(q0 + NW * kMfmaRows, a.Sq) - 1;
+  const int kv_end = a.causal ? min(a.Sk, q_last + shift + 1) : a.Sk;  // keys [0, kv_end) matter to this block
+  const int nt = (kv_end + kKV - 1) / kKV;
+
+  const int wq0 = q0 + wave * kMfmaRows;
+  const bool wave_on = wq0 < a.Sq;                 // (a wave past the last row still stages K / V and meets the barriers)
+  const int qi = min(wq0 + r, a.Sq - 1);           // rows >= Sq compute row Sq - 1 again and are not stored
+  const int lim = a.causal ? qi + shift : a.Sk - 1;                                 // last key this lane's row attends
+  const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, a.Sq - 1) + shift : a.Sk - 1;  // .. any row of the wave
+  const int wave_min = a.causal ? wq0 + shift : a.Sk - 1;                           // every row of the wave attends keys <= this
+
+  // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
+  vec8 qf[KS];
+  {
+    const uint16_t* qp = a.q + (long long)b * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
+  }
+
+  const uint16_t* kb = a.k + (long long)b * a.k_bs + (long long)kvh * DH;
+  const uint16_t* vb = a.v + (long long)b * a.v_bs + (long long)kvh * DH;
+  u32x4 kr[LOADS], vr[LOADS];
+  auto stage_load = [&](int t0) {
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
+      const long long g = min(t0 + row, a.Sk - 1);
+      kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
+      vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+    }
+  };
+  auto stage_write = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
+      *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
+      *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+    }
+  };
+
+  f32x16 o[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;  // l: this lane's 32 keys of every tile; the two halves are added at the end
+
+  // transposed-read addressing: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p .. 4 p + 3 of the group's 4 x 16 block
+  const int tr_q = (lane & 15) >> 2, tr_p = lane & 3, tr_g = (lane >> 4) & 1;
+
+  stage_load(0);
+  stage_write(0);
+  // Q has arrived before the loop starts: a wait for it inside the loop would be a vmcnt(0) behind the loads the loop has just
+  // issued (the counter retires in order), which is exactly the overlap the staging exists for
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
+  __syncthreads();
+
+  for (int t = 0; t < nt; ++t) {
+    const int buf = t & 1, t0 = t * kKV;
+    const bool more = t + 1 < nt;
+    if (more) stage_load(t0 + kKV);
+
+    if (wave_on && t0 <= wave_max) {
+      // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, query row r ----
+      f32x16 s[2];
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[kb2][e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const vec8 ka = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(&k_s[buf][k_off<DH>(32 * kb2 + r, 2 * ks + hh)]));
+          s[kb2] = DT::mfma32(ka, qf[ks], s[kb2]);
+        }
+      }
+      // ---- online softmax (base 2: the logits are scaled by scale * log2 e) ----
+      const bool need_mask = t0 + kKV - 1 > wave_min;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float x = s[kb2][e] * a.scale_log2e;
+          if (need_mask) {
+            const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+            x = key <= lim ? x : -INFINITY;
+          }
+          s[kb2][e] = x;
+          mx = fmaxf(mx, x);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);  // finite from the first tile on: key 0 is attended by every row
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      m_run = m_new;
+      vec8 pf[4];
+      float sum = 0.f;
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const elem pt = (elem)__builtin_amdgcn_exp2f(s[kb2][e] - m_new);  // the ONE rounding of a weight
+          pf[2 * kb2 + (e >> 3)][e & 7] = pt;
+          sum += (float)pt;
+        }
+      l_run = l_run * alpha + sum;
+#pragma unroll
+      for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
+      // ---- O^T += V^T P^T: k-step s2 = keys 16 s2 + 8 (j >> 2) + 4 hh + (j & 3), j = operand element ----
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+          const int row = 16 * s2 + 4 * hh + tr_q, ch = 4 * db + 2 * tr_g + (tr_p >> 1);
+          const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) i16x4*)(&v_s[buf][v_off<DH>(row, ch) + 4 * (tr_p & 1)]));
+          const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) i16x4*)(&v_s[buf][v_off<DH>(row + 8, ch) + 4 * (tr_p & 1)]));
+          const i16x8 va = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          o[db] = DT::mfma32(__builtin_bit_cast(vec8, va), pf[s2], o[db]);
+        }
+      }
+    }
+
+    if (more) stage_write(buf ^ 1);  // the other buffer: its readers finished before the barrier that ended tile t - 1
+    __syncthreads();
+  }
+
+  // ---- O / l, rounded to T once; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  if (wq0 + r < a.Sq) {
+    const float inv = 1.0f / l_tot;
+    uint16_t* op = a.out + (((long long)b * a.Sq + qi) * a.H + h) * DH + 4 * hh;
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const u32 w0 = (u32)DT::from_float(o[db][4 * g4] * inv) | ((u32)DT::from_float(o[db][4 * g4 + 1] * inv) << 16);
+        const u32 w1 = (u32)DT::from_float(o[db][4 * g4 + 2] * inv) | ((u32)DT::from_float(o[db][4 * g4 + 3] * inv) << 16);
+        *reinterpret_cast<u32x2*>(op + 32 * db + 8 * g4) = u32x2{w0, w1};
+      }
+  }
+}
+
+template <typename DT, int DH>
+void launch_nw(const PrefillArgs& a, int nw, int blocks, hipStream_t st) {
+  switch (nw) {
+    case 8: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 8>), dim3(blocks), dim3(512), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 4>), dim3(blocks), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 2>), dim3(blocks), dim3(128), 0, st, a); break;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// fused_rope_with_pos_forward_func (awq/kernels/csrc/rope_new/fused_rope_with_pos.cu:33-72, 263-333).  input [n0, n1, h, d] with
+// strides (s0, s1, sh, 1); the angle of (i0, i1, ., c), c < d2, is freqs[(i1 * n0 + i0) * d2 + c] (:45 with gridDim.x = n0 -- the
+// reference's own index, meaningful when one of n0, n1 is 1); partner c + d2/2 negated for the first half, c - d2/2 for the second
+// (:51-55); x cos + x_rot sin in fp32, rounded to T once; columns >= d2 copied (:60-70).  One thread = 8 consecutive columns of one
+// (i0, i1) over all heads (the sincosf of a column is evaluated once, as in the reference), 16-byte loads and stores.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct RopePosArgs {
+  const uint16_t* in;
+  const float* freqs;
+  uint16_t* out;
+  int n0, n1, h, d, d2;
+  long long s0, s1, sh, o0, o1, oh;
+};
+
+template <typename DT>
+__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
+  const u32 ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
+    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
+  }
+}
+template <typename DT>
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+  u32 ws[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
+  return u32x4{ws[0], ws[1], ws[2], ws[3]};
+}
+
+template <typename DT>
+__global__ __launch_bounds__(256) void rope_with_pos_kernel(RopePosArgs a) {
+  const int cpr = a.d >> 3;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)a.n0 * a.n1 * cpr) return;
+  const int ch = (int)(id % cpr);
+  const long long pos = id / cpr;
+  const int i1 = (int)(pos % a.n1), i0 = (int)(pos / a.n1);
+  const int c0 = ch * 8, half = a.d2 >> 1;
+  const uint16_t* src = a.in + i0 * a.s0 + i1 * a.s1;
+  uint16_t* dst = a.out + i0 * a.o0 + i1 * a.o1;
+  if (c0 >= a.d2) {
+    for (int hd = 0; hd < a.h; ++hd)
+      *reinterpret_cast<u32x4*>(dst + hd * a.oh + c0) = *reinterpret_cast<const u32x4*>(src + hd * a.sh + c0);
+    return;
+  }
+  const float* fr = a.freqs + ((long long)i1 * a.n0 + i0) * a.d2 + c0;
+  const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
+  const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+  float cs[8], sn[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
+  const bool first = c0 + half < a.d2;
+  const int pc = first ? c0 + half : c0 - half;
+  const float sign = first ? -1.f : 1.f;
+  for (int hd = 0; hd < a.h; ++hd) {
+    float x[8], y[8], res[8];
+    unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * a.sh + c0), x);
+    unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * a.sh + pc), y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) res[e] = __builtin_fmaf(x[e], cs[e], (sign * y[e]) * sn[e]);
+    *reinterpret_cast<u32x4*>(dst + hd * a.oh + c0) = pack8<DT>(res);
+  }
+}
+
+// rotary_embedding_neox (awq/kernels/csrc/position_embedding/pos_encoding_kernels.cu:12-87): in place on query and key
+// [tokens, heads, head_size]; cos_sin_cache [max_pos, rot_dim] = cos | sin.  One thread = 8 consecutive rotation pairs of one
+// (token, head).  The rotation is evaluated in fp32 and rounded once (the reference rounds every product and sum to T).
+template <typename DT>
+__global__ __launch_bounds__(256) void rope_neox_kernel(const long long* __restrict__ positions, uint16_t* __restrict__ query,
+                                                        uint16_t* __restrict__ key, const uint16_t* __restrict__ cache, int tokens, int heads,
+                                                        int head_size, int rot_dim, int max_pos) {
+  const int embed = rot_dim >> 1, cpe = embed >> 3;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)tokens * heads * cpe) return;
+  const int ch = (int)(id % cpe);
+  const long long th = id / cpe;  // token * heads + head
+  const long long token = th / heads;
+  long long pos = positions[token];
+  pos = pos < 0 ? 0 : (pos >= max_pos ? max_pos - 1 : pos);  // (the reference reads whatever lies there)
+  const uint16_t* cp = cache + pos * rot_dim + ch * 8;
+  float cs[8], sn[8];
+  unpack8<DT>(*reinterpret_cast<const u32x4*>(cp), cs);
+  unpack8<DT>(*reinterpret_cast<const u32x4*>(cp + embed), sn);
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    uint16_t* p = (which ? key : query) + th * head_size + ch * 8;
+    float x[8], y[8], rx[8], ry[8];
+    unpack8<DT>(*reinterpret_cast<const u32x4*>(p), x);
+    unpack8<DT>(*reinterpret_cast<const u32x4*>(p + embed), y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      rx[e] = __builtin_fmaf(x[e], cs[e], -(y[e] * sn[e]));
+      ry[e] = __builtin_fmaf(y[e], cs[e], x[e] * sn[e]);
+    }
+    *reinterpret_cast<u32x4*>(p) = pack8<DT>(rx);
+    *reinterpret_cast<u32x4*>(p + embed) = pack8<DT>(ry);
+  }
+}
+
+}  // namespace
+
+// Host plan: the q tile (rows per block) of a launch, from what was measured on the MI355X (tools/attn_prefill_bench.py shapes, bf16, each
+// tile size forced in turn; DESIGN.md "Prefill attention"): 128 rows (4 waves, two blocks per CU) is the fastest or within 1 % of it
+// almost everywhere.  Dh = 128 gains 5 % from 256 rows once that still leaves two blocks per CU (Llama-3-8B at S = 4096); Dh = 64
+// never does, and prefers 64 rows while 128-row tiles leave fewer than two blocks per CU (Falcon-like at S <= 512: 12 %).  Depends on
+// host arguments only.
+int attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
+                      int* blocks) {
+  (void)nheads_kv;
+  (void)seqlen_k;
+  (void)causal;
+  const long long bh = (long long)batch * nheads;
+  auto nblocks = [&](int rows) { return bh * ((seqlen_q + rows - 1) / rows); };
+  int rows = 128;
+  if (head_dim == 128 && nblocks(256) >= 2 * kCUs) rows = 256;
+  else if (head_dim == 64 && nblocks(128) < 2 * kCUs) rows = 64;
+  if (g_force_rows) rows = g_force_rows;
+  *q_tile_rows = rows;
+  *blocks = (int)nblocks(rows);
+  return 0;
+}
+
+int attn_prefill_tune_set(const char* key, int value) {
+  if (strcmp(key, "attn_prefill_rows") != 0 || (value != 0 && value != 64 && value != 128 && value != 256)) return -1;
+  g_force_rows = value;
+  return 0;
+}
+
+int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
+                        hipStream_t st) {
+  PrefillArgs a;
+  a.q = (const uint16_t*)q;
+  a.k = (const uint16_t*)k;
+  a.v = (const uint16_t*)v;
+  a.out = (uint16_t*)out;
+  a.q_bs = q_bs;
+  a.q_rs = q_rs;
+  a.k_bs = k_bs;
+  a.k_rs = k_rs;
+  a.v_bs = v_bs;
+  a.v_rs = v_rs;
+  a.B = B;
+  a.Sq = Sq;
+  a.Sk = Sk;
+  a.H = H;
+  a.G = H / Hkv;
+  a.causal = causal ? 1 : 0;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  int rows = 0, blocks = 0;
+  attn_prefill_plan(B, H, Hkv, Dh, Sq, Sk, causal, &rows, &blocks);
+  a.ntiles = (Sq + rows - 1) / rows;
+  const int nw = rows / kMfmaRows;
+  if (dtype == 0) {
+    if (Dh == 128) launch_nw<F16, 128>(a, nw, blocks, st);
+    else launch_nw<F16, 64>(a, nw, blocks, st);
+  } else {
+    if (Dh == 128) launch_nw<BF16, 128>(a, nw, blocks, st);
+    else launch_nw<BF16, 64>(a, nw, blocks, st);
+  }
+  return 0;
+}
+
+int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
+                         long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st) {
+  RopePosArgs a{(const uint16_t*)in, freqs, (uint16_t*)out, n0, n1, h, d, d2, s0, s1, sh, o0, o1, oh};
+  const long long n = (long long)n0 * n1 * (d / 8);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL((rope_with_pos_kernel<F16>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((rope_with_pos_kernel<BF16>), grid, dim3(256), 0, st, a);
+  return 0;
+}
+
+int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,
+                     int max_pos, int dtype, hipStream_t st) {
+  const long long n = (long long)tokens * heads * (rot_dim / 16);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0)
+    hipLaunchKernelGGL((rope_neox_kernel<F16>), grid, dim3(256), 0, st, positions, (uint16_t*)query, (uint16_t*)key, (const uint16_t*)cache, tokens,
+                       heads, head_size, rot_dim, max_pos);
+  else
+    hipLaunchKernelGGL((rope_neox_kernel<BF16>), grid, dim3(256), 0, st, positions, (uint16_t*)query, (uint16_t*)key, (const uint16_t*)cache, tokens,
+                       heads, head_size, rot_dim, max_pos);
+  return 0;
+}
+
+}  // namespace awq

@@ -341,6 +341,63 @@ int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, 
   return finish_launch();
 }
 
+static bool prefill_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal) {
+  return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 && (head_dim == 64 || head_dim == 128) && seqlen_q >= 1 &&
+         seqlen_k >= 1 && !(causal && seqlen_q > seqlen_k) && (long long)batch * nheads * ((seqlen_q + 63) / 64) <= 0x7FFFFFFFll;
+}
+
+int awq_attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
+                          int* blocks) {
+  if (!q_tile_rows || !blocks) return AWQ_ERR_NULL;
+  if (!prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal)) return AWQ_ERR_SHAPE;
+  return awq::attn_prefill_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, q_tile_rows, blocks);
+}
+
+int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
+                     int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                     long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  if (!q || !k || !v || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal) || q_batch_stride < 0 || k_batch_stride < 0 ||
+      v_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
+      v_row_stride < (long long)nheads_kv * head_dim)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 ||
+      (v_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_attn_prefill(q, k, v, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_batch_stride,
+                           k_row_stride, v_batch_stride, v_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_rope_with_pos(const void* input, const float* freqs, void* out, int n0, int n1, int nheads, int head_dim, int rot_dim,
+                      long long in_stride0, long long in_stride1, long long in_stride_head, long long out_stride0, long long out_stride1,
+                      long long out_stride_head, int dtype, void* stream) {
+  if (!input || !freqs || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (n0 < 1 || n1 < 1 || nheads < 1 || head_dim < 8 || (head_dim % 8) != 0 || rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_dim ||
+      in_stride0 < 0 || in_stride1 < 0 || in_stride_head < head_dim || out_stride0 < 0 || out_stride1 < 0 || out_stride_head < head_dim)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(input) || !aligned16(freqs) || !aligned16(out) || (in_stride0 % 8) != 0 || (in_stride1 % 8) != 0 || (in_stride_head % 8) != 0 ||
+      (out_stride0 % 8) != 0 || (out_stride1 % 8) != 0 || (out_stride_head % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_with_pos(input, freqs, out, n0, n1, nheads, head_dim, rot_dim, in_stride0, in_stride1, in_stride_head, out_stride0,
+                            out_stride1, out_stride_head, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_rope_neox_inplace(const long long* positions, void* query, void* key, const void* cos_sin_cache, int num_tokens, int nheads,
+                          int head_size, int rot_dim, int max_position, int dtype, void* stream) {
+  if (!positions || !query || !key || !cos_sin_cache) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (num_tokens < 1 || nheads < 1 || head_size < 16 || (head_size % 8) != 0 || rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_size ||
+      max_position < 1)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(query) || !aligned16(key) || !aligned16(cos_sin_cache) || (reinterpret_cast<uintptr_t>(positions) & 7u)) return AWQ_ERR_ALIGN;
+  awq::launch_rope_neox(positions, query, key, cos_sin_cache, num_tokens, nheads, head_size, rot_dim, max_position, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
 size_t awq_w4a16_forward_cdna4_workspace_bytes(int m, int n, int k) {
   if (awq::midm_takes(m, n, k)) return awq::midm_workspace_bytes(m, n, k);  // 9 .. 255 rows: the fp32 parts of the mid-M kernel's K split
   if (m > 8 && m < 256 && !awq::gemm_cdna4_v3_takes(m, k)) return awq::skinny_splitk_workspace_bytes(m, n, k);  // (knob midm = 0) the skinny launch's K split
@@ -671,6 +728,7 @@ int awq_tune_set(const char* key, int value) {
   if (awq::skinny_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::midm_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::gemm_v3_tune_set(key, value) == 0) return AWQ_OK;
+  if (awq::attn_prefill_tune_set(key, value) == 0) return AWQ_OK;
   if (!strcmp(key, "w3_skinny_max")) {
     g_w3_skinny_max = value;
     return AWQ_OK;

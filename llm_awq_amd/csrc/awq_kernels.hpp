@@ -171,6 +171,17 @@ size_t attn_decode_workspace_bytes(int batch, int nheads, int nheads_kv, int hea
 int launch_attn_decode(const void* q, const void* k, const void* v, void* k_cache, void* v_cache, const int* lens, const float* alibi,
                        void* out, int B, int H, int Hkv, int Dh, int Lmax, long long q_bs, long long k_bs, long long v_bs, int timestep,
                        int rot, float rot_base, float rot_scale, int neox, int dtype, void* workspace, hipStream_t st);
+// prefill attention and the prompt-side rotary embeddings (awq_attn_prefill_cdna4.hip); arguments validated by the caller
+int attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
+                      int* blocks);
+int attn_prefill_tune_set(const char* key, int value);  // "attn_prefill_rows": force the q tile (0 = plan)
+int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
+                        hipStream_t st);
+int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
+                         long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
+int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,
+                     int max_pos, int dtype, hipStream_t st);
 int launch_unpack_v2(const void* qw, void* out_u8, int n, int k, hipStream_t st);
 int launch_dequant_v2(const void* qw, const void* s, const void* z, void* out, int n, int k, int dtype, hipStream_t st);
 int launch_pack_v2(const void* q_u8, void* qw, int n, int k, hipStream_t st);

@@ -662,6 +662,83 @@ torch::Tensor single_query_attention(const torch::Tensor q, const torch::Tensor 
   return out;
 }
 
+// flash_attn_func's forward (tinychat llama.py:218, fused_attn.py:477,539) on the gfx950 prefill kernel (csrc/awq_attn_prefill_cdna4.hip):
+// q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] with contiguous heads and batch / row strides of their own (views of one fused qkv tensor pass
+// without a copy); causal is bottom-right aligned.  Returns [B, Sq, H, Dh] contiguous.
+torch::Tensor attn_prefill(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, double softmax_scale, bool causal) {
+  TORCH_CHECK(q.scalar_type() != at::kFloat, "attn_prefill: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "attn_prefill: q, k and v must live on the same GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "attn_prefill: float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "attn_prefill: q, k and v must share one dtype");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "attn_prefill: q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), sk = k.size(1), nheads_kv = k.size(2);
+  TORCH_CHECK(headdim == 64 || headdim == 128, "attn_prefill: head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(k.size(0) == batch && k.size(3) == headdim && v.sizes() == k.sizes(), "attn_prefill: k / v must be [B, Sk, Hkv, ", headdim, "]");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && sk >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0,
+              "attn_prefill: empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(!causal || sq <= sk, "attn_prefill: causal attention needs seqlen_q <= seqlen_k, got ", sq, " > ", sk);
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == headdim,
+                "attn_prefill: the heads of q / k / v must be contiguous (stride(3) == 1, stride(2) == Dh); supported head dims: 64, 128");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  raise_on(awq_attn_prefill(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)batch, (int)sq, (int)sk, (int)nheads, (int)nheads_kv,
+                            (int)headdim, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale,
+                            causal ? 1 : 0, dtype_code(q), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
+// fused_rope_with_pos_forward_func(input, freqs, transpose_output_memory) (rope_new/fused_rope_with_pos.cu:263-333): input [n0, n1, h, d]
+// with any strides, freqs fp32 with last dim d2, read at (i1 * n0 + i0) * d2 + c -- the reference's own index.  The result has input's
+// shape; with transpose_output_memory its memory is that of a contiguous [n1, n0, h, d] tensor (:303-307).
+torch::Tensor fused_rope_with_pos_forward_func(const torch::Tensor& input, const torch::Tensor& freqs, const bool transpose_output_memory) {
+  TORCH_CHECK(input.scalar_type() != at::kFloat,
+              "fused_rope_with_pos_forward_func: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(input.is_cuda() && freqs.is_cuda() && freqs.device() == input.device(), "fused_rope_with_pos_forward_func: tensors must live on the same GPU");
+  TORCH_CHECK(input.scalar_type() == at::kHalf || input.scalar_type() == at::kBFloat16,
+              "fused_rope_with_pos_forward_func: float16 / bfloat16 only, got ", input.scalar_type());
+  TORCH_CHECK(freqs.scalar_type() == at::kFloat, "fused_rope_with_pos_forward_func: freqs must be float32");
+  TORCH_CHECK(input.dim() == 4 && freqs.dim() >= 1, "fused_rope_with_pos_forward_func: input must be 4-D");
+  const int64_t n0 = input.size(0), n1 = input.size(1), h = input.size(2), d = input.size(3), d2 = freqs.size(-1);
+  TORCH_CHECK(n0 >= 1 && n1 >= 1 && h >= 1 && d2 <= d && freqs.numel() >= n0 * n1 * d2,
+              "fused_rope_with_pos_forward_func: freqs must hold n0 * n1 * d2 angles with d2 <= head dim");
+  TORCH_CHECK(d % 8 == 0 && d2 % 16 == 0 && d2 >= 16, "fused_rope_with_pos_forward_func: head dim % 8 == 0 and rotary dim % 16 == 0 are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  // the kernel reads 16 bytes at a time: a view whose last stride is not 1, or whose strides / base are not 16-byte multiples, is copied once
+  at::Tensor x = input;
+  if (x.stride(3) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || x.stride(2) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = input.contiguous();
+  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
+  auto opt = input.options().requires_grad(false);
+  at::Tensor out = transpose_output_memory ? torch::empty({n1, n0, h, d}, opt).transpose(0, 1) : torch::empty({n0, n1, h, d}, opt);
+  raise_on(awq_rope_with_pos(x.data_ptr(), fr.data_ptr<float>(), out.data_ptr(), (int)n0, (int)n1, (int)h, (int)d, (int)d2, x.stride(0), x.stride(1),
+                             x.stride(2), out.stride(0), out.stride(1), out.stride(2), dtype_code(x),
+                             (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
+// rotary_embedding_neox(positions, query, key, head_size, cos_sin_cache) (position_embedding/pos_encoding_kernels.cu:55-87): in place on
+// contiguous query and key [.., num_heads, head_size] (the same head count, as the reference assumes), positions int64, cache [max_pos, rot_dim].
+void rotary_embedding_neox(torch::Tensor& positions, torch::Tensor& query, torch::Tensor& key, int head_size, torch::Tensor& cos_sin_cache) {
+  TORCH_CHECK(query.scalar_type() != at::kFloat, "rotary_embedding_neox: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&positions, &query, &key, &cos_sin_cache})
+    TORCH_CHECK(t->is_cuda() && t->device() == query.device() && t->is_contiguous(), "rotary_embedding_neox: contiguous tensors on one GPU are expected");
+  TORCH_CHECK((query.scalar_type() == at::kHalf || query.scalar_type() == at::kBFloat16) && key.scalar_type() == query.scalar_type() &&
+                  cos_sin_cache.scalar_type() == query.scalar_type() && positions.scalar_type() == at::kLong,
+              "rotary_embedding_neox: float16 / bfloat16 query, key and cache of one dtype and int64 positions are expected");
+  TORCH_CHECK(query.dim() >= 2 && cos_sin_cache.dim() == 2 && query.size(-1) == head_size && key.sizes() == query.sizes(),
+              "rotary_embedding_neox: query and key [.., num_heads, head_size] of one shape, cache [max_position, rot_dim]");
+  const int64_t heads = query.size(-2), rot = cos_sin_cache.size(1);
+  if (query.numel() == 0) return;
+  const int64_t tokens = query.numel() / (heads * head_size);
+  TORCH_CHECK(positions.numel() == tokens, "rotary_embedding_neox: one position per token is expected");
+  TORCH_CHECK(rot % 16 == 0 && rot >= 16 && rot <= head_size && head_size % 8 == 0, "rotary_embedding_neox: rot_dim % 16 == 0 and rot_dim <= head_size are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(query.device());
+  raise_on(awq_rope_neox_inplace((const long long*)positions.data_ptr<int64_t>(), query.data_ptr(), key.data_ptr(), cos_sin_cache.data_ptr(), (int)tokens,
+                                 (int)heads, head_size, (int)rot, (int)cos_sin_cache.size(0), dtype_code(query),
+                                 (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
 torch::Tensor rmsnorm_forward_cdna4(torch::Tensor in_feats, torch::Tensor gamma, double eps, torch::Tensor kernel, torch::Tensor sz_packed,
                                     c10::optional<torch::Tensor> bias, bool fused_gate_up) {
   TORCH_CHECK(in_feats.is_cuda() && gamma.is_cuda() && kernel.is_cuda() && sz_packed.is_cuda());
@@ -774,6 +851,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_cache"), py::arg("v_cache"), py::arg("length_per_sample_"), py::arg("alibi_slopes_"), py::arg("timestep"),
         py::arg("rotary_embedding_dim") = 0, py::arg("rotary_base") = 10000.0f, py::arg("rotary_scale") = 1.0f,
         py::arg("neox_rotary_style") = true);
+  m.def("attn_prefill", &attn_prefill, "Prefill attention (flash_attn_func's forward): q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("rotary_embedding_neox", &rotary_embedding_neox, "Apply GPT-NeoX style rotary embedding to query and key");
+  m.def("fused_rope_with_pos_forward_func", &fused_rope_with_pos_forward_func, "Fused rope forward function with B,S,D embedding");
   m.def("abi_version", []() { return awq_abi_version(); });
   m.def("cdna4_cache_info", []() {
     std::lock_guard<std::mutex> lock(g_cache_mu);

@@ -532,3 +532,78 @@ def single_query_attention(q, k, v, k_cache, v_cache, length_per_sample=None, al
                                       int(rotary_embedding_dim), float(rotary_base), float(rotary_scale), int(bool(neox_rotary_style)),
                                       _dt(q), ws.data_ptr() if wsb else None, wsb, _stream(q)))
     return out
+
+
+def attn_prefill_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, seqlen_q: int, seqlen_k: int, causal: bool = True):
+    """Host-side awq_attn_prefill_plan: (q_tile_rows, blocks) of the prefill attention launch (no GPU needed)."""
+    import ctypes
+
+    r, n = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_prefill_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, int(bool(causal)),
+                                                  ctypes.byref(r), ctypes.byref(n)))
+    return r.value, n.value
+
+
+def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
+    """C-ABI awq_attn_prefill: softmax(scale * q k^T + mask) v with flash_attn_func's layout and masking.
+    q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (batch and row strides of their own, heads contiguous -- the q / k / v slices of one
+    fused qkv tensor pass without a copy); causal is bottom-right aligned (row i attends keys j <= i + Sk - Sq).  Returns
+    [B, Sq, H, Dh] contiguous.  Dh 64 or 128, float16 / bfloat16."""
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+        if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+            raise ValueError("q / k / v must be [B, S, heads, Dh] with contiguous heads")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError("flash_attn_func: q, k and v must live on the same GPU")
+    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3] or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("flash_attn_func: q [B, Sq, H, Dh] and k / v [B, Sk, Hkv, Dh] of one dtype are expected")
+    B, Sq, H, Dh = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    with torch.cuda.device(q.device):
+        _capi.check(_capi.lib().awq_attn_prefill(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, Sk, H, Hkv, Dh,
+                                                 q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                                                 scale, int(bool(causal)), _dt(q), _stream(q)))
+    return out
+
+
+def fused_rope_with_pos(x, freqs, transpose_output_memory: bool = False):
+    """C-ABI awq_rope_with_pos (the reference's fused_rope_with_pos_forward_func): x [n0, n1, h, d] with a unit last stride, freqs fp32
+    with n0 * n1 * d2 elements read at (i1 * n0 + i0) * d2 + c.  The result has x's shape and, when transpose_output_memory, the memory of
+    a contiguous [n1, n0, h, d] tensor."""
+    for t in (x, freqs):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if freqs.device != x.device:
+        raise ValueError("fused_rope_with_pos: x and freqs must live on the same GPU")
+    if x.dim() != 4 or x.stride(3) != 1 or freqs.dtype != torch.float32 or not freqs.is_contiguous():
+        raise ValueError("fused_rope_with_pos: x [n0, n1, h, d] with a unit last stride and contiguous float32 freqs are expected")
+    n0, n1, h, d = x.shape
+    d2 = freqs.shape[-1]
+    if freqs.numel() < n0 * n1 * d2:
+        raise ValueError("fused_rope_with_pos: freqs holds fewer than n0 * n1 * d2 angles")
+    out = torch.empty(n1, n0, h, d, dtype=x.dtype, device=x.device).transpose(0, 1) if transpose_output_memory else \
+        torch.empty(n0, n1, h, d, dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_rope_with_pos(x.data_ptr(), freqs.data_ptr(), out.data_ptr(), n0, n1, h, d, d2, x.stride(0), x.stride(1),
+                                                  x.stride(2), out.stride(0), out.stride(1), out.stride(2), _dt(x), _stream(x)))
+    return out
+
+
+def rotary_embedding_neox(positions, query, key, head_size: int, cos_sin_cache):
+    """C-ABI awq_rope_neox_inplace (the reference's rotary_embedding_neox): rotates contiguous query and key [..., heads, head_size] in place."""
+    _need_gpu(positions, query, key, cos_sin_cache)
+    if any(t.device != query.device for t in (positions, key, cos_sin_cache)):
+        raise ValueError("rotary_embedding_neox: all tensors must live on the same GPU")
+    if positions.dtype != torch.int64 or key.shape != query.shape or cos_sin_cache.dtype != query.dtype or key.dtype != query.dtype:
+        raise ValueError("rotary_embedding_neox: int64 positions, query and key of one shape, cache of their dtype are expected")
+    heads = query.shape[-2]
+    tokens = query.numel() // (heads * head_size)
+    if positions.numel() != tokens or query.shape[-1] != head_size:
+        raise ValueError("rotary_embedding_neox: one position per token and query [..., heads, head_size] are expected")
+    with torch.cuda.device(query.device):
+        _capi.check(_capi.lib().awq_rope_neox_inplace(positions.data_ptr(), query.data_ptr(), key.data_ptr(), cos_sin_cache.data_ptr(), tokens,
+                                                      heads, int(head_size), cos_sin_cache.shape[1], cos_sin_cache.shape[0], _dt(query),
+                                                      _stream(query)))
