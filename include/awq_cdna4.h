@@ -385,8 +385,47 @@ int awq_rope_with_pos(const void* input, const float* freqs, void* out, int n0, 
 int awq_rope_neox_inplace(const long long* positions, void* query, void* key, const void* cos_sin_cache, int num_tokens, int nheads,
                           int head_size, int rot_dim, int max_position, int dtype, void* stream);
 
+/* ---- W8A8 linear (the reference's awq/kernels/csrc/w8a8/ family, called by the vision towers: tinychat/modules/fused_siglipdecoder.py,
+ * fused_internencoder.py, awq/quantize/w8a8_linear.py).  int8 activations and weights, fp16 scales and output.
+ *
+ * awq_w8a8_gemm replaces w8a8_gemm_forward_cuda (w8a8_gemm_cuda.cu:907-953, kernel :635-905) when bias == NULL and
+ * w8a8_gemm_fuse_bias_forward_cuda (:586-633, kernel :299-584) otherwise:
+ *     x int8 [m, k], w int8 [n, k] (both row-major, k contiguous), wscales fp16 [n], ascales fp16 [m], bias fp16 [n] or NULL, out fp16 [m, n]
+ *     acc = x . w^T in int32 on the int8 matrix cores (exact; no fp32 accumulation, no split-K, no workspace, no atomics: bit-deterministic
+ *     and capturable), then in fp32
+ *         bias:     out = half_rn(fmaf(float(acc) * float(wscales[n]), float(ascales[m]), float(bias[n])))     (:575-578)
+ *         no bias:  out = half_rn(float(acc) * (float(wscales[n]) * float(ascales[m])))                        (:896-898)
+ * k % 16 == 0 (k <= 2^20), n % 8 == 0, any m >= 1; all pointers 16-byte aligned.  Every such shape is served by both forms: the reference's
+ * no-bias launch drops a partial column tile (:73) and its fuse-bias kernel reads bias past n; neither is reproduced.  Rows >= m and columns
+ * >= n are neither read nor written.  Returns AWQ_ERR_NULL, AWQ_ERR_SHAPE, AWQ_ERR_ALIGN before any GPU call, or AWQ_ERR_LAUNCH. */
+int awq_w8a8_gemm(const void* x, const void* w, const void* wscales, const void* ascales, const void* bias, void* out, int m, int n, int k,
+                  void* stream);
+/* Host-side plan (no GPU call): the launch is ceil(m / *tile_m) * ceil(n / *tile_n) blocks, the return value; 0 if the shape is not served.
+ * Two tiles, one rule: 128 x 128 when that yields at least one block per CU (256), else 64 x 64 -- the counterpart of the reference's
+ * two tile shapes split at m = 128 (w8a8_gemm_cuda.cu:610-631).  tile_m / tile_n may be NULL. */
+int awq_w8a8_gemm_plan(int m, int n, int k, int* tile_m, int* tile_n);
+/* Replaces invoke_quant (w8a8/quantization.cu:56-112): per-token int8 quantisation of x T [m, k]:
+ *     amax = max_k |float(x)|, scale[m] = half_rn(amax / 127), out_i8 = sat_s8(rne(float(x) * (127 / amax)))
+ * in IEEE fp32 with correctly rounded divisions (independent of the reduction order).  An all-zero row gives scale 0 and zeros (the
+ * reference reaches the same through NaN -> 0).  T = fp16 / bf16, scale fp16 [m]; k % 8 == 0. */
+int awq_quant_per_token(const void* x, void* out_i8, void* scale, int m, int k, int dtype, void* stream);
+/* Replaces gelu_and_quant (w8a8/act.cu:22-96), fp16 only: g = gelu_fast(x) with every step an fp16 operation rounded on its own (:23-28),
+ * tmp[m, k] = g (fp16; the callers read it), amax = max_k (g > 0.0001h ? g : -g) starting from 0 (positive values up to 1e-4 do not count:
+ * the reference's quirk, :45,52-54, kept), scale[m] = half_rn(amax / 127), out_i8 = sat_s8(rne(float(half_rn(127 / amax) * g))) with that
+ * product in fp16 (:65-68).  k % 8 == 0. */
+int awq_gelu_quant_per_token(const void* x, void* out_i8, void* scale, void* tmp, int m, int k, void* stream);
+/* Replaces rms_norm_general (w8a8/layernorm.cu:55-188, launch :193-232) -- a LayerNorm despite the name:
+ *     v = (x - mean) * rsqrt(var + eps) * gamma (+ beta) in fp32 (centred variance; the reference's E[x^2] - mean^2 agrees in exact arithmetic)
+ *     per_token != 0 (:142-187): amax = max(max_k |T(v)|, T(1e-6)) over v rounded to T, out_i8 = sat_s8(rne(v * (127 / amax))) on the unrounded
+ *                                v, scale[m] = half_rn(amax / 127) is WRITTEN
+ *     per_token == 0 (:156-160, :224-229): out_i8 = sat_s8(rne(v * float(scale[0]))), scale[0] is READ; beta is ignored and the scale
+ *                                multiplies -- the reference's behaviour, kept
+ * T = fp16 / bf16 (x, gamma, beta), scale fp16; beta may be NULL; k % 8 == 0, k <= 16384 (the row stays on chip). */
+int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, float eps, void* out_i8, void* scale, int m, int k, int per_token,
+                        int dtype, void* stream);
+
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
- * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", ...) so that tests can cover each of them; 0
+ * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every
  * call returns AWQ_ERR_SHAPE and changes nothing.  Timing probes and experiment-only kernel instantiations exist only in
  * builds made with AWQ_PROBES=1.  Returns AWQ_OK, or AWQ_ERR_SHAPE for an unknown key.  Process-global, not thread-safe. */

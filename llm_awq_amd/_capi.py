@@ -90,6 +90,11 @@ SIGNATURES = {
     "awq_rope_with_pos": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _vp]),
     "awq_rope_neox_inplace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "awq_w8a8_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "awq_w8a8_gemm_plan": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_quant_per_token": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "awq_gelu_quant_per_token": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "awq_layernorm_quant": (_i, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_tune_set": (_i, [ctypes.c_char_p, _i]),
 }
 

@@ -398,6 +398,45 @@ int awq_rope_neox_inplace(const long long* positions, void* query, void* key, co
   return finish_launch();
 }
 
+int awq_w8a8_gemm_plan(int m, int n, int k, int* tile_m, int* tile_n) { return awq::w8a8_gemm_plan(m, n, k, tile_m, tile_n); }
+
+int awq_w8a8_gemm(const void* x, const void* w, const void* wscales, const void* ascales, const void* bias, void* out, int m, int n, int k,
+                  void* stream) {
+  if (!x || !w || !wscales || !ascales || !out) return AWQ_ERR_NULL;
+  if (awq::w8a8_gemm_plan(m, n, k, nullptr, nullptr) == 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(wscales) || !aligned16(ascales) || !aligned16(out) || (bias && !aligned16(bias)))
+    return AWQ_ERR_ALIGN;
+  if (awq::launch_w8a8_gemm(x, w, wscales, ascales, bias, out, m, n, k, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_quant_per_token(const void* x, void* out_i8, void* scale, int m, int k, int dtype, void* stream) {
+  if (!x || !out_i8 || !scale) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (m < 1 || k < 8 || (k % 8) != 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(out_i8) || !aligned16(scale)) return AWQ_ERR_ALIGN;
+  awq::launch_quant_per_token(x, out_i8, scale, m, k, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_gelu_quant_per_token(const void* x, void* out_i8, void* scale, void* tmp, int m, int k, void* stream) {
+  if (!x || !out_i8 || !scale || !tmp) return AWQ_ERR_NULL;
+  if (m < 1 || k < 8 || (k % 8) != 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(out_i8) || !aligned16(scale) || !aligned16(tmp)) return AWQ_ERR_ALIGN;
+  awq::launch_gelu_quant_per_token(x, out_i8, scale, tmp, m, k, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, float eps, void* out_i8, void* scale, int m, int k, int per_token,
+                        int dtype, void* stream) {
+  if (!x || !gamma || !out_i8 || !scale) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (m < 1 || k < 8 || (k % 8) != 0 || k > 16384) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(gamma) || (beta && !aligned16(beta)) || !aligned16(out_i8) || !aligned16(scale)) return AWQ_ERR_ALIGN;
+  if (awq::launch_layernorm_quant(x, gamma, beta, eps, out_i8, scale, m, k, per_token ? 1 : 0, dtype, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 size_t awq_w4a16_forward_cdna4_workspace_bytes(int m, int n, int k) {
   if (awq::midm_takes(m, n, k)) return awq::midm_workspace_bytes(m, n, k);  // 9 .. 255 rows: the fp32 parts of the mid-M kernel's K split
   if (m > 8 && m < 256 && !awq::gemm_cdna4_v3_takes(m, k)) return awq::skinny_splitk_workspace_bytes(m, n, k);  // (knob midm = 0) the skinny launch's K split
@@ -729,6 +768,7 @@ int awq_tune_set(const char* key, int value) {
   if (awq::midm_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::gemm_v3_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::attn_prefill_tune_set(key, value) == 0) return AWQ_OK;
+  if (awq::w8a8_tune_set(key, value) == 0) return AWQ_OK;
   if (!strcmp(key, "w3_skinny_max")) {
     g_w3_skinny_max = value;
     return AWQ_OK;

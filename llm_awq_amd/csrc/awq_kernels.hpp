@@ -182,6 +182,15 @@ int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, 
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,
                      int max_pos, int dtype, hipStream_t st);
+// W8A8 linear (awq_w8a8_cdna4.hip); arguments validated by the caller.  w8a8_gemm_plan: blocks of the launch (0 = shape not served) and its tile
+int w8a8_gemm_plan(int m, int n, int k, int* tile_m, int* tile_n);
+int w8a8_tune_set(const char* key, int value);  // "w8a8_tile": force the 64 x 64 or the 128 x 128 tile (0 = plan)
+int launch_w8a8_gemm(const void* x, const void* w, const void* wscales, const void* ascales, const void* bias, void* out, int m, int n, int k,
+                     hipStream_t st);
+int launch_quant_per_token(const void* x, void* out_i8, void* scale, int m, int k, int dtype, hipStream_t st);
+int launch_gelu_quant_per_token(const void* x, void* out_i8, void* scale, void* tmp, int m, int k, hipStream_t st);
+int launch_layernorm_quant(const void* x, const void* gamma, const void* beta, float eps, void* out_i8, void* scale, int m, int k,
+                           int per_token, int dtype, hipStream_t st);
 int launch_unpack_v2(const void* qw, void* out_u8, int n, int k, hipStream_t st);
 int launch_dequant_v2(const void* qw, const void* s, const void* z, void* out, int n, int k, int dtype, hipStream_t st);
 int launch_pack_v2(const void* q_u8, void* qw, int n, int k, hipStream_t st);

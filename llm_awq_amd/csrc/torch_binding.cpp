@@ -839,6 +839,102 @@ torch::Tensor decode_cdna4(torch::Tensor in_feats, torch::Tensor kernel, torch::
   return out;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// W8A8 family (awq/kernels/csrc/w8a8/; pybind.cpp:30-37).  Outputs are written into the caller's buffers, nothing is returned.  The
+// reference checks nothing and launches on the default stream of the current device; here every tensor is checked and the launch goes
+// to the current stream of the tensors' device.
+// ---------------------------------------------------------------------------------------------------------------
+void w8a8_check(const char* fn, std::initializer_list<const torch::Tensor*> ts) {
+  const torch::Tensor& first = **ts.begin();
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->is_cuda() && t->device() == first.device() && t->is_contiguous(), fn, ": contiguous tensors on one GPU are expected");
+}
+
+void w8a8_gemm_common(const char* fn, torch::Tensor& in_feats, torch::Tensor& kernel, torch::Tensor& wscales, torch::Tensor& ascales,
+                      torch::Tensor& out_feats, const torch::Tensor* bias) {
+  TORCH_CHECK(out_feats.scalar_type() != at::kFloat && wscales.scalar_type() != at::kFloat && ascales.scalar_type() != at::kFloat,
+              fn, ": float32 is not supported by the MI355X build (scales, bias and output are float16)");
+  w8a8_check(fn, {&in_feats, &kernel, &wscales, &ascales, &out_feats});
+  if (bias) w8a8_check(fn, {&in_feats, bias});
+  TORCH_CHECK(in_feats.scalar_type() == at::kChar && kernel.scalar_type() == at::kChar, fn, ": int8 in_feats [M, K] and kernel [N, K] are expected");
+  TORCH_CHECK(out_feats.scalar_type() == at::kHalf && wscales.scalar_type() == at::kHalf && ascales.scalar_type() == at::kHalf &&
+                  (!bias || bias->scalar_type() == at::kHalf),
+              fn, ": float16 wscales, ascales, bias and out_feats are expected");
+  TORCH_CHECK(in_feats.dim() == 2 && kernel.dim() == 2 && out_feats.dim() >= 2, fn, ": in_feats [M, K], kernel [N, K], out_feats [.., M, N] are expected");
+  const int64_t m = in_feats.size(0), k = in_feats.size(1), n = kernel.size(0);
+  TORCH_CHECK(kernel.size(1) == k && out_feats.size(-2) == m && out_feats.size(-1) == n && out_feats.numel() == m * n && wscales.numel() == n &&
+                  ascales.numel() >= m && (!bias || bias->numel() == n),
+              fn, ": shapes do not match (in_feats [M, K], kernel [N, K], wscales [N], ascales [M], bias [N], out_feats [M, N])");
+  TORCH_CHECK(m >= 1 && k % 16 == 0 && n % 8 == 0 && m <= INT32_MAX && n <= INT32_MAX && k <= INT32_MAX, fn, ": K % 16 == 0 and N % 8 == 0 are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(in_feats.device());
+  raise_on(awq_w8a8_gemm(in_feats.data_ptr(), kernel.data_ptr(), wscales.data_ptr(), ascales.data_ptr(), bias ? bias->data_ptr() : nullptr,
+                         out_feats.data_ptr(), (int)m, (int)n, (int)k, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
+// w8a8_gemm_forward_cuda(in_feats, kernel, wscales, ascales, out_feats) (w8a8_gemm_cuda.cu:907-953)
+void w8a8_gemm_forward_cuda(torch::Tensor _in_feats, torch::Tensor _kernel, torch::Tensor _wscales, torch::Tensor _ascales, torch::Tensor _out_feats) {
+  w8a8_gemm_common("w8a8_gemm_forward_cuda", _in_feats, _kernel, _wscales, _ascales, _out_feats, nullptr);
+}
+// w8a8_gemm_fuse_bias_forward_cuda(in_feats, kernel, wscales, ascales, out_feats, bias) (w8a8_gemm_cuda.cu:586-633)
+void w8a8_gemm_fuse_bias_forward_cuda(torch::Tensor _in_feats, torch::Tensor _kernel, torch::Tensor _wscales, torch::Tensor _ascales,
+                                      torch::Tensor _out_feats, torch::Tensor _bias) {
+  w8a8_gemm_common("w8a8_gemm_fuse_bias_forward_cuda", _in_feats, _kernel, _wscales, _ascales, _out_feats, &_bias);
+}
+
+// invoke_quant(out, input, scale) (quantization.cu:97-112): input T [.., hidden], out int8 of the same shape, scale fp16 [tokens]
+void invoke_quant(torch::Tensor& out, torch::Tensor& input, torch::Tensor& scale) {
+  TORCH_CHECK(input.scalar_type() != at::kFloat, "invoke_quant: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  w8a8_check("invoke_quant", {&input, &out, &scale});
+  TORCH_CHECK((input.scalar_type() == at::kHalf || input.scalar_type() == at::kBFloat16) && out.scalar_type() == at::kChar &&
+                  scale.scalar_type() == at::kHalf,
+              "invoke_quant: float16 / bfloat16 input, int8 out and float16 scale are expected");
+  TORCH_CHECK(input.dim() >= 1 && input.numel() > 0, "invoke_quant: input [.., hidden] is expected");
+  const int64_t k = input.size(-1), m = input.numel() / k;
+  TORCH_CHECK(out.numel() == input.numel() && scale.numel() >= m && k % 8 == 0 && m <= INT32_MAX && k <= INT32_MAX,
+              "invoke_quant: out of input's size, one scale per token and hidden % 8 == 0 are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  raise_on(awq_quant_per_token(input.data_ptr(), out.data_ptr(), scale.data_ptr(), (int)m, (int)k, dtype_code(input),
+                               (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
+// gelu_and_quant(out, input, scale_out, tmp) (act.cu:82-95): fp16 input [.., d]; tmp receives the fp16 GELU, out / scale_out its quantisation
+void gelu_and_quant(torch::Tensor& out, torch::Tensor& input, torch::Tensor& scale_out, torch::Tensor& tmp) {
+  TORCH_CHECK(input.scalar_type() != at::kFloat, "gelu_and_quant: float32 is not supported by the MI355X build (use float16)");
+  w8a8_check("gelu_and_quant", {&input, &out, &scale_out, &tmp});
+  TORCH_CHECK(input.scalar_type() == at::kHalf && tmp.scalar_type() == at::kHalf && scale_out.scalar_type() == at::kHalf &&
+                  out.scalar_type() == at::kChar,
+              "gelu_and_quant: float16 input, tmp and scale_out and int8 out are expected");
+  TORCH_CHECK(input.dim() >= 1 && input.numel() > 0, "gelu_and_quant: input [.., d] is expected");
+  const int64_t k = input.size(-1), m = input.numel() / k;
+  TORCH_CHECK(out.numel() == input.numel() && tmp.numel() >= input.numel() && scale_out.numel() >= m && k % 8 == 0 && m <= INT32_MAX && k <= INT32_MAX,
+              "gelu_and_quant: out and tmp of input's size, one scale per token and d % 8 == 0 are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  raise_on(awq_gelu_quant_per_token(input.data_ptr(), out.data_ptr(), scale_out.data_ptr(), tmp.data_ptr(), (int)m, (int)k,
+                                    (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
+// rms_norm_general(out, input, weight, bias, scaling, epsilon, use_per_token_quant = true) (layernorm.cu:193-232): a LayerNorm with mean
+// subtraction.  Per token: scaling fp16 [tokens] is written.  Per tensor: scaling[0] is read and multiplied, bias is ignored (:224-229).
+void rms_norm_general(torch::Tensor& out, torch::Tensor& input, torch::Tensor& weight, c10::optional<torch::Tensor> bias, torch::Tensor& scaling,
+                      double epsilon, bool use_per_token_quant) {
+  TORCH_CHECK(input.scalar_type() != at::kFloat, "rms_norm_general: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  w8a8_check("rms_norm_general", {&input, &out, &weight, &scaling});
+  const bool has_bias = bias.has_value() && bias->defined();
+  if (has_bias) w8a8_check("rms_norm_general", {&input, &*bias});
+  TORCH_CHECK((input.scalar_type() == at::kHalf || input.scalar_type() == at::kBFloat16) && weight.scalar_type() == input.scalar_type() &&
+                  (!has_bias || bias->scalar_type() == input.scalar_type()) && out.scalar_type() == at::kChar && scaling.scalar_type() == at::kHalf,
+              "rms_norm_general: float16 / bfloat16 input, weight and bias of one dtype, int8 out and float16 scaling are expected");
+  TORCH_CHECK(input.dim() >= 1 && input.numel() > 0, "rms_norm_general: input [.., hidden] is expected");
+  const int64_t k = input.size(-1), m = input.numel() / k;
+  TORCH_CHECK(out.numel() == input.numel() && weight.numel() == k && (!has_bias || bias->numel() == k) &&
+                  scaling.numel() >= (use_per_token_quant ? m : 1) && k % 8 == 0 && k <= 16384 && m <= INT32_MAX,
+              "rms_norm_general: out of input's size, weight / bias [hidden], one scale per token, hidden % 8 == 0 and hidden <= 16384 are required");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(input.device());
+  raise_on(awq_layernorm_quant(input.data_ptr(), weight.data_ptr(), has_bias ? bias->data_ptr() : nullptr, (float)epsilon, out.data_ptr(),
+                               scaling.data_ptr(), (int)m, (int)k, use_per_token_quant ? 1 : 0, dtype_code(input),
+                               (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -855,6 +951,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("rotary_embedding_neox", &rotary_embedding_neox, "Apply GPT-NeoX style rotary embedding to query and key");
   m.def("fused_rope_with_pos_forward_func", &fused_rope_with_pos_forward_func, "Fused rope forward function with B,S,D embedding");
+  m.def("w8a8_gemm_forward_cuda", &w8a8_gemm_forward_cuda, "our w8a8 gemm kernel");
+  m.def("w8a8_gemm_fuse_bias_forward_cuda", &w8a8_gemm_fuse_bias_forward_cuda, "our w8a8 gemm fused bias kernel");
+  m.def("invoke_quant", &invoke_quant, "fp16->int8 quantization");
+  m.def("rms_norm_general", &rms_norm_general, py::arg("out"), py::arg("input"), py::arg("weight"), py::arg("bias"), py::arg("scaling"),
+        py::arg("epsilon"), py::arg("use_per_token_quant") = true, "LayerNorm (mean subtracted) + int8 quantisation (TRTLLM kernel).");
+  m.def("gelu_and_quant", &gelu_and_quant, "Apply gelu act and quant output");
   m.def("abi_version", []() { return awq_abi_version(); });
   m.def("cdna4_cache_info", []() {
     std::lock_guard<std::mutex> lock(g_cache_mu);

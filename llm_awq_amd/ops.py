@@ -607,3 +607,71 @@ def rotary_embedding_neox(positions, query, key, head_size: int, cos_sin_cache):
         _capi.check(_capi.lib().awq_rope_neox_inplace(positions.data_ptr(), query.data_ptr(), key.data_ptr(), cos_sin_cache.data_ptr(), tokens,
                                                       heads, int(head_size), cos_sin_cache.shape[1], cos_sin_cache.shape[0], _dt(query),
                                                       _stream(query)))
+
+
+def w8a8_gemm_plan(m: int, n: int, k: int):
+    """Host-side awq_w8a8_gemm_plan: (blocks, tile_m, tile_n) of the W8A8 GEMM launch, (0, 0, 0) if the shape is not served (no GPU needed)."""
+    import ctypes
+
+    tm, tn = ctypes.c_int(0), ctypes.c_int(0)
+    blocks = _capi.lib().awq_w8a8_gemm_plan(int(m), int(n), int(k), ctypes.byref(tm), ctypes.byref(tn))
+    return blocks, tm.value, tn.value
+
+
+def w8a8_gemm(x_i8, w_i8, wscales, ascales, out, bias=None):
+    """C-ABI awq_w8a8_gemm: out[M, N] (fp16) = epilogue(x_i8[M, K] . w_i8[N, K]^T) with per-channel wscales [N], per-token ascales [M] and an
+    optional fp16 bias [N]; int32 accumulation on the int8 matrix cores.  Written into `out`, which is returned."""
+    _need_gpu(x_i8, w_i8, wscales, ascales, out, bias)
+    if x_i8.dtype != torch.int8 or w_i8.dtype != torch.int8 or any(t.dtype != torch.float16 for t in (wscales, ascales, out)) or \
+            (bias is not None and bias.dtype != torch.float16):
+        raise TypeError("w8a8_gemm: int8 x and w, float16 wscales, ascales, bias and out are expected")
+    m, k = x_i8.shape
+    n = w_i8.shape[0]
+    if w_i8.shape[1] != k or out.numel() != m * n or out.shape[-1] != n or wscales.numel() != n or ascales.numel() < m or \
+            (bias is not None and bias.numel() != n):
+        raise ValueError("w8a8_gemm: x [M, K], w [N, K], wscales [N], ascales [M], bias [N], out [M, N] are expected")
+    with torch.cuda.device(x_i8.device):
+        _capi.check(_capi.lib().awq_w8a8_gemm(x_i8.data_ptr(), w_i8.data_ptr(), wscales.data_ptr(), ascales.data_ptr(),
+                                               None if bias is None else bias.data_ptr(), out.data_ptr(), m, n, k, _stream(x_i8)))
+    return out
+
+
+def quant_per_token(x, out_i8, scale):
+    """C-ABI awq_quant_per_token (the reference's invoke_quant): per-token int8 quantisation of x [.., K] into out_i8, scales into scale (fp16)."""
+    _need_gpu(x, out_i8, scale)
+    if out_i8.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise TypeError("quant_per_token: int8 out and float16 scale are expected")
+    k = x.shape[-1]
+    m = x.numel() // k
+    if out_i8.numel() != x.numel() or scale.numel() < m:
+        raise ValueError("quant_per_token: out of x's size and one scale per token are expected")
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_quant_per_token(x.data_ptr(), out_i8.data_ptr(), scale.data_ptr(), m, k, _dt(x), _stream(x)))
+
+
+def gelu_quant_per_token(x, out_i8, scale, tmp):
+    """C-ABI awq_gelu_quant_per_token (the reference's gelu_and_quant): tmp = fp16 gelu_fast(x), out_i8 / scale its per-token quantisation."""
+    _need_gpu(x, out_i8, scale, tmp)
+    if x.dtype != torch.float16 or tmp.dtype != torch.float16 or out_i8.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise TypeError("gelu_quant_per_token: float16 x, tmp and scale and int8 out are expected")
+    k = x.shape[-1]
+    m = x.numel() // k
+    if out_i8.numel() != x.numel() or tmp.numel() < x.numel() or scale.numel() < m:
+        raise ValueError("gelu_quant_per_token: out and tmp of x's size and one scale per token are expected")
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_gelu_quant_per_token(x.data_ptr(), out_i8.data_ptr(), scale.data_ptr(), tmp.data_ptr(), m, k, _stream(x)))
+
+
+def layernorm_quant(x, gamma, beta, scale, out_i8, eps: float, per_token: bool = True):
+    """C-ABI awq_layernorm_quant (the reference's rms_norm_general): LayerNorm of x [.., K] followed by int8 quantisation.  per_token: scale
+    (fp16 [tokens]) is written; otherwise scale[0] is read and multiplied and beta is ignored (the reference's behaviour)."""
+    _need_gpu(x, gamma, beta, scale, out_i8)
+    if gamma.dtype != x.dtype or (beta is not None and beta.dtype != x.dtype) or out_i8.dtype != torch.int8 or scale.dtype != torch.float16:
+        raise TypeError("layernorm_quant: gamma and beta of x's dtype, int8 out and float16 scale are expected")
+    k = x.shape[-1]
+    m = x.numel() // k
+    if out_i8.numel() != x.numel() or gamma.numel() != k or (beta is not None and beta.numel() != k) or scale.numel() < (m if per_token else 1):
+        raise ValueError("layernorm_quant: out of x's size, gamma / beta [K] and one scale per token are expected")
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_layernorm_quant(x.data_ptr(), gamma.data_ptr(), None if beta is None else beta.data_ptr(), float(eps),
+                                                     out_i8.data_ptr(), scale.data_ptr(), m, k, int(bool(per_token)), _dt(x), _stream(x)))
