@@ -1,11 +1,14 @@
 """The W8A8 family without a GPU: the C entries' argument codes, the GEMM's plan, the weight quantiser of llm_awq_amd.w8a8_linear against
-its restatement (tests/w8a8_oracle.py), the modules' state-dict keys and the engine's five exports."""
+its restatement (tests/w8a8_oracle.py), the modules' state-dict keys and the engine's five exports -- and the proof that the checks of
+tests/test_gpu_w8a8.py are sound and sharp: every criterion of tests/w8a8_cases.py passes the restatement in the kernel's place and
+rejects it with any one applicable fault switched in."""
 import pytest
 import torch
 
 import llm_awq_amd
 from llm_awq_amd import _capi, ops
 from llm_awq_amd.w8a8_linear import W8A8OF16LinearDynamicInputScale, W8A8OF16LinearStaticScale, quantize_weight_per_channel
+from tests import w8a8_cases as C
 from tests import w8a8_oracle as W
 
 OK, ERR_DTYPE, ERR_SHAPE, ERR_ALIGN, ERR_NULL = 0, -3, -4, -5, -6
@@ -180,3 +183,158 @@ def test_oracle_self_checks():
     assert float(sg[1]) == 0.0 and qg[1].tolist() == [127, 127, 0, 0] * 2  # only tiny positives: amax stays 0, 127 / 0 = inf, inf * g saturates
     acc = W.acc_exact(torch.full((1, 4304), -128, dtype=torch.int8), torch.full((1, 4304), -128, dtype=torch.int8))
     assert int(acc) == 70516736
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the GPU checks are sound (the restatement passes) and sharp (the restatement with one fault does not)
+# ------------------------------------------------------------------------------------------------------------------------
+def _id(check):
+    return check["id"]
+
+
+def test_check_lists_cover_the_axes():
+    for checks in (C.GEMM_CHECKS, C.QUANT_CHECKS, C.GELU_CHECKS, C.LN_CHECKS):
+        assert len({c["id"] for c in checks}) == len(checks)
+    g = {(c["kind"], c["with_bias"]) for c in C.GEMM_CHECKS}
+    assert g == {(k, b) for k in ("lattice", "random", "exact", "needle", "bounds") for b in (False, True)}
+    assert {(c["m"], c["n"], c["k"]) for c in C.GEMM_CHECKS if c["kind"] == "exact"} == {(300, 1152, 4304), (65, 272, 208)}
+    assert {(c["dtype"], c["k"]) for c in C.QUANT_CHECKS if c["kind"] == "needle"} == {(d, k) for d in (C.F16, C.BF16) for k in (16, 80)}
+    ln = {(c["kind"], c["dtype"], c["k"], c["mode"]) for c in C.LN_CHECKS}
+    for d in (C.F16, C.BF16):
+        for k in (80, 1152):
+            assert {("eps_small", d, k, "token"), ("eps_small", d, k, "tensor"), ("eps_big", d, k, "token")} <= ln
+        for k in (8, 2048, 2056, 16376, 16384):
+            assert ("depth", d, k, "token") in ln
+    # K = 2048 fills one register vector per thread exactly, 2056 starts the second, 16384 fills all eight
+    assert 2048 == 256 * 8 and C.LN_MAX_K == 256 * 8 * 8
+
+
+@pytest.mark.parametrize("check", C.GEMM_CHECKS, ids=_id)
+def test_gemm_check_passes_the_oracle_and_sees_faults(check):
+    c, crit = C.gemm_inputs(check), C.gemm_criterion(check)
+    assert crit(C.gemm_stand_in(c), c) == {}
+    for mutant in W.GEMM_MUTANTS:
+        if C.gemm_mutant_applies(check, mutant):
+            assert crit(C.gemm_stand_in(c, mutant), c) != {}, mutant
+
+
+def test_epilogue_associations_differ_in_the_large_bit_exact_case():
+    """Each wrong association of the epilogue changes at least 4 fp16 results of the (300, 1152, 4304) case: the bit-exact GPU check has
+    something to see.  (The counts with this seed: assoc 11, nofma 8, assoc_bias 17, exact 17.)"""
+    for with_bias, mutants in ((False, ("assoc",)), (True, ("nofma", "assoc_bias", "exact"))):
+        c = C.gemm_inputs(dict(kind="exact", m=300, n=1152, k=4304, with_bias=with_bias))
+        for mutant in mutants:
+            n = C.gemm_bits(C.gemm_stand_in(c, mutant), c).get("bits", 0)
+            print(mutant, n)
+            assert n >= 4, (mutant, n)
+
+
+@pytest.mark.parametrize("check", C.QUANT_CHECKS, ids=_id)
+def test_quant_check_passes_the_oracle_and_sees_faults(check):
+    x = C.quant_check_inputs(check)
+    assert C.quant_bits(*C.quant_stand_in(x), x) == {}
+    for mutant in W.QUANT_MUTANTS:
+        if C.quant_mutant_applies(check, mutant):
+            assert C.quant_bits(*C.quant_stand_in(x, mutant), x) != {}, mutant
+
+
+@pytest.mark.parametrize("dtype", [C.F16, C.BF16])
+@pytest.mark.parametrize("k", [16, 80])
+def test_quant_needle_values_are_what_the_restatement_gives(dtype, k):
+    x, q, s = C.quant_needle(dtype, k)
+    qo, so = W.quant_per_token(x)
+    assert torch.equal(qo, q) and torch.equal(C.bits(so), C.bits(s))
+    assert qo[0, :9].tolist() == [127, 0, 2, -2, 2, -2, 126, -126, 4] and (qo[3:] == 0).all() and torch.isinf(so[3:]).all()
+    away, _ = W.quant_per_token(x, "half_away")
+    assert away[0, :9].tolist() == [127, -1, 2, -2, 3, -3, 126, -127, 4]  # what a round-half-away conversion would return
+
+
+@pytest.mark.parametrize("check", C.GELU_CHECKS, ids=_id)
+def test_gelu_check_passes_the_oracle_and_sees_faults(check):
+    x = C.gelu_check_inputs(check)
+    for hi in (False, True):  # either candidate is accepted
+        assert C.check_gelu_stage(x, *C.gelu_stand_in(x, None, hi)) == {}
+    for mutant in W.GELU_MUTANTS:
+        if C.gelu_mutant_applies(check, mutant):
+            assert C.check_gelu_stage(x, *C.gelu_stand_in(x, mutant)) != {}, mutant
+
+
+def test_gelu_overflow_rows_are_decided():
+    """On the planted values the candidates agree (tanh is exactly +-1): g = x for positive x, -0 for negative x."""
+    x, big = C.gelu_overflow_inputs()
+    lo, hi = W.gelu_candidates(x, C.TANH_DELTA)
+    assert torch.equal(C.bits(lo)[big], C.bits(hi)[big])
+    pos, neg = big & (x > 0), big & (x < 0)
+    assert pos.any() and neg.any() and torch.equal(C.bits(lo)[pos], C.bits(x)[pos])
+    assert (C.bits(lo)[neg] == C.bits(torch.tensor(-0.0, dtype=C.F16))).all()
+    u, _ = W.gelu_fast_steps(x)
+    assert torch.isinf(u[big]).all() and torch.isfinite(u[~big]).all()
+    assert torch.isfinite(lo.float()).all()
+
+
+@pytest.mark.parametrize("check", C.LN_CHECKS, ids=_id)
+def test_layernorm_check_passes_the_oracle_and_sees_faults(check):
+    c = C.ln_check_inputs(check)
+    assert C.ln_bound(*C.ln_stand_in(c), c) == {}
+    for mutant in W.LN_MUTANTS:
+        if C.ln_mutant_applies(check, mutant):
+            assert C.ln_bound(*C.ln_stand_in(c, mutant), c) != {}, mutant
+
+
+def test_every_fault_is_seen_by_some_case():
+    for mutants, checks, applies in ((W.GEMM_MUTANTS, C.GEMM_CHECKS, C.gemm_mutant_applies), (W.QUANT_MUTANTS, C.QUANT_CHECKS, C.quant_mutant_applies),
+                                     (W.GELU_MUTANTS, C.GELU_CHECKS, C.gelu_mutant_applies), (W.LN_MUTANTS, C.LN_CHECKS, C.ln_mutant_applies)):
+        seen = {m: sum(applies(c, m) for c in checks) for m in mutants}
+        assert all(v > 0 for v in seen.values()), seen
+    with pytest.raises(ValueError):
+        W.gemm_f32(torch.zeros(1, 1, dtype=torch.int64), torch.ones(1), torch.ones(1), None, mutant="no such fault")
+
+
+def _mlp_chain(gemm=None, quant=None, gelu=None):
+    """The fc1 -> GELU -> fc2 sequence with the restatements as the kernels; -> the violations of the GPU test's four stage checks."""
+    P = C.mlp_inputs()
+    xq, s0 = C.quant_stand_in(P["h"], quant)
+    c1 = dict(x=xq, w=P["w1"], ws=P["ws1"], as_=s0, bias=P["b1"])
+    fc1 = C.gemm_stand_in(c1, gemm)
+    tmp, aq, s1 = C.gelu_stand_in(fc1, gelu)
+    c2 = dict(x=aq, w=P["w2"], ws=P["ws2"], as_=s1, bias=P["b2"])
+    out = C.gemm_stand_in(c2, gemm)
+    return [C.quant_bits(xq, s0, P["h"]), C.gemm_bound(fc1, c1), C.check_gelu_stage(fc1, tmp, aq, s1), C.gemm_bound(out, c2)]
+
+
+def test_mlp_sequence_checks_pass_the_oracle_and_see_faults():
+    assert _mlp_chain() == [{}, {}, {}, {}]
+    for mutant in ("trunc", "inv_from_scale"):
+        assert _mlp_chain(quant=mutant)[0] != {}, mutant
+    for mutant in ("bias_first", "droptail"):  # (fc2 has K = 4304, K % 64 = 16)
+        assert _mlp_chain(gemm=mutant)[3] != {}, mutant
+    for mutant in ("single_rounding", "prod_f32", "inv_f32"):
+        assert _mlp_chain(gelu=mutant)[2] != {}, mutant
+
+
+def _layer_chain(ln=None, gemm=None, attn=None, quant=None):
+    """The attention half with the restatements as the kernels; -> the violations of the GPU test's five stage checks."""
+    from tests import attn_prefill_oracle as O
+
+    L = C.layer_inputs()
+    x0, s0 = C.ln_stand_in(L["ln"], ln)
+    c1 = dict(x=x0, w=L["wqkv"], ws=L["ws_qkv"], as_=s0, bias=L["b_qkv"])
+    qkv = C.gemm_stand_in(c1, gemm)
+    q, k, v = [t.reshape(L["bsz"], L["seqlen"], L["heads"], L["dh"]) for t in qkv.split(L["emb"], dim=-1)]
+    a = O.attention(q, k, v, None, False, mutant=attn).to(torch.float32).to(torch.float16).reshape(L["m"], L["emb"])
+    x1, s1 = C.quant_stand_in(a, quant)
+    out = C.gemm_stand_in(dict(x=x1, w=L["wo"], ws=L["ws_o"], as_=s1, bias=L["b_o"]), gemm)
+    return [C.ln_bound(x0, s0, L["ln"]), C.gemm_stage(qkv, x0, L["wqkv"], L["ws_qkv"], s0, L["b_qkv"]), C.attention_stage(a, qkv, L),
+            C.quant_bits(x1, s1, a), C.gemm_stage(out, x1, L["wo"], L["ws_o"], s1, L["b_o"])]
+
+
+def test_attention_half_checks_pass_the_oracle_and_see_faults():
+    assert _layer_chain() == [{}, {}, {}, {}, {}]
+    for mutant in ("rms", "nobeta_token"):
+        assert _layer_chain(ln=mutant)[0] != {}, mutant
+    r = _layer_chain(gemm="bias_first")
+    assert r[1] != {} and r[4] != {}
+    for mutant in ("kvh+1", "droptile"):  # four KV heads; 70 keys: the second tile holds six
+        assert _layer_chain(attn=mutant)[2] != {}, mutant
+    for mutant in ("trunc", "inv_from_scale"):
+        assert _layer_chain(quant=mutant)[3] != {}, mutant
