@@ -355,19 +355,39 @@ int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, 
  *     q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (own batch and row strides, in elements; heads contiguous: head stride = Dh),
  *     out [B, Sq, H, Dh] contiguous;  O = softmax(softmax_scale * Q K^T + mask) V, plain softmax.
  * causal != 0: query row i attends keys j <= i + (Sk - Sq) (bottom-right aligned; needs Sq <= Sk); causal == 0: every key.
- * H % Hkv == 0, query head h reads KV head h / (H / Hkv).  T = fp16 / bf16 (`dtype`), Dh = 64 or 128; Sq and Sk need no alignment, and
+ * H % Hkv == 0, query head h reads KV head h / (H / Hkv).  T = fp16 / bf16 (`dtype`), Dh = 64 or 128, and 72 with causal == 0 (SigLIP's
+ * head dim, served by the tower kernel below); Sq and Sk need no alignment, and
  * no row >= Sq of q or >= Sk of k / v is read.  One pass over K / V per q tile with an online softmax on the matrix cores, fp32
  * accumulation; each softmax weight is rounded to T once and that rounded value feeds both P.V and the row sum; O is rounded to T
  * once.  No workspace, no atomics: bit-deterministic and capturable (csrc/awq_attn_prefill_cdna4.hip).
  * Returns AWQ_ERR_SHAPE (head dim, H % Hkv, Sq > Sk with causal, non-positive sizes, a row stride below heads * Dh), AWQ_ERR_DTYPE,
  * AWQ_ERR_NULL, AWQ_ERR_ALIGN (16 bytes for the pointers and the strides), AWQ_ERR_LAUNCH; all but the last without a GPU call. */
-/* Host-side plan: one launch of *blocks blocks, each a q tile of *q_tile_rows rows (64, 128 or 256) of one (batch, query head).
+/* Host-side plan: one launch of *blocks blocks, each a q tile of *q_tile_rows rows (32, 64, 128 or 256) of one (batch, query head).
  * Depends on these host arguments only; no GPU call. */
 int awq_attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
                           int* blocks);
 int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
                      int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
                      long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+
+/* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
+ *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
+ *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.
+ *     cu_seqlens: int32 [nseq + 1] ON THE DEVICE; sequence s owns rows cu_seqlens[s] .. cu_seqlens[s + 1] - 1 and a row attends exactly
+ *     the keys of its own sequence: O = softmax(softmax_scale * Q K^T) V.  The host never reads cu_seqlens and never synchronises: the
+ *     grid comes from nseq and max_seqlen alone (rows of a sequence beyond max_seqlen are not computed), zero-length sequences are
+ *     allowed, and every row index is clamped into [0, total_rows - 1], so a wrong cu_seqlens cannot make the kernel leave the tensors.
+ *     Rows >= cu_seqlens[nseq] are neither read nor written.
+ * T = fp16 / bf16, Dh = 64 or 72 (no byte outside a (row, head)'s 2 Dh bytes is read), causal must be 0.  Same arithmetic as
+ * awq_attn_prefill; no workspace, no atomics: bit-deterministic and capturable (csrc/awq_attn_tower_cdna4.hip).
+ * Returns AWQ_ERR_SHAPE (head dim, causal != 0, non-positive sizes, a row stride below H * Dh), AWQ_ERR_DTYPE, AWQ_ERR_NULL (cu_seqlens
+ * included: the dense form is awq_attn_prefill), AWQ_ERR_ALIGN (16 bytes for the pointers and the strides, 4 for cu_seqlens),
+ * AWQ_ERR_LAUNCH; all but the last without a GPU call. */
+/* Host-side plan: *blocks blocks, each a q tile of *q_tile_rows rows (32, 64 or 128) of one (sequence, head); no GPU call. */
+int awq_attn_varlen_plan(int nseq, int nheads, int head_dim, int max_seqlen, int* q_tile_rows, int* blocks);
+int awq_attn_varlen(const void* q, const void* k, const void* v, void* out, const int* cu_seqlens, int nseq, int max_seqlen,
+                    long long total_rows, int nheads, int head_dim, long long q_row_stride, long long k_row_stride,
+                    long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
 
 /* ---- Rotary embeddings of a prompt.
  * awq_rope_with_pos (fused_rope_with_pos_forward_func, rope_new/fused_rope_with_pos.cu:33-72,263-333): input [n0, n1, nheads, head_dim]
@@ -425,7 +445,7 @@ int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, floa
                         int dtype, void* stream);
 
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
- * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
+ * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "tower_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every
  * call returns AWQ_ERR_SHAPE and changes nothing.  Timing probes and experiment-only kernel instantiations exist only in
  * builds made with AWQ_PROBES=1.  Returns AWQ_OK, or AWQ_ERR_SHAPE for an unknown key.  Process-global, not thread-safe. */

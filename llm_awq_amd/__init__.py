@@ -45,12 +45,19 @@ def install_as_awq_inference_engine():
 
 def install_as_flash_attn(force: bool = False):
     """Make `from flash_attn import flash_attn_func` (tinychat/models/llama.py:21, modules/fused_attn.py:17) resolve to the MI355X
-    prefill attention (llm_awq_amd.flash_attn_compat).  A real, importable `flash_attn` is left alone unless `force`; a second call
-    is a no-op.  Returns the module that `import flash_attn` now yields."""
+    attention kernels (llm_awq_amd.flash_attn_compat), and with it the two submodules the vision towers import:
+    `flash_attn.flash_attn_interface` and `flash_attn.bert_padding` (tinychat/models/internvl/internvit.py:18-20).  A real, importable
+    `flash_attn` is left alone unless `force` -- nothing of ours is then registered under its name; a second call is a no-op.
+    Returns the module that `import flash_attn` now yields."""
     from . import flash_attn_compat
+
+    def submodules():
+        for name, mod in flash_attn_compat.SUBMODULES.items():
+            sys.modules["flash_attn." + name] = mod
 
     cur = sys.modules.get("flash_attn")
     if cur is flash_attn_compat:
+        submodules()
         return cur
     if not force:
         if cur is not None:
@@ -58,4 +65,5 @@ def install_as_flash_attn(force: bool = False):
         if importlib.util.find_spec("flash_attn") is not None:
             return importlib.import_module("flash_attn")
     sys.modules["flash_attn"] = flash_attn_compat
+    submodules()
     return flash_attn_compat

@@ -342,14 +342,16 @@ int awq_attn_decode(const void* q, const void* k, const void* v, void* k_cache, 
 }
 
 static bool prefill_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal) {
-  return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 && (head_dim == 64 || head_dim == 128) && seqlen_q >= 1 &&
-         seqlen_k >= 1 && !(causal && seqlen_q > seqlen_k) && (long long)batch * nheads * ((seqlen_q + 63) / 64) <= 0x7FFFFFFFll;
+  return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 &&
+         (head_dim == 64 || head_dim == 128 || (head_dim == 72 && !causal)) && seqlen_q >= 1 && seqlen_k >= 1 &&
+         !(causal && seqlen_q > seqlen_k) && (long long)batch * nheads * (head_dim == 72 ? (seqlen_q + 31) / 32 : (seqlen_q + 63) / 64) <= 0x7FFFFFFFll;
 }
 
 int awq_attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
                           int* blocks) {
   if (!q_tile_rows || !blocks) return AWQ_ERR_NULL;
   if (!prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal)) return AWQ_ERR_SHAPE;
+  if (head_dim == 72) return awq::attn_varlen_plan(batch, nheads, head_dim, seqlen_q, q_tile_rows, blocks);  // the tower kernel's dense form
   return awq::attn_prefill_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, q_tile_rows, blocks);
 }
 
@@ -365,8 +367,41 @@ int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 ||
       (v_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
     return AWQ_ERR_ALIGN;
-  awq::launch_attn_prefill(q, k, v, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_batch_stride,
-                           k_row_stride, v_batch_stride, v_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
+  if (head_dim == 72)  // non-causal only (prefill_shape_ok): the tower kernel's dense form
+    awq::launch_attn_tower(q, k, v, out, nullptr, batch, seqlen_q, seqlen_k, (long long)batch * seqlen_q, nheads, nheads_kv, head_dim,
+                           q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, softmax_scale, dtype,
+                           (hipStream_t)stream);
+  else
+    awq::launch_attn_prefill(q, k, v, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_batch_stride,
+                             k_row_stride, v_batch_stride, v_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {
+  return nseq >= 1 && nheads >= 1 && (head_dim == 64 || head_dim == 72) && max_seqlen >= 1 &&
+         (long long)nseq * nheads * ((max_seqlen + 31) / 32) <= 0x7FFFFFFFll;
+}
+
+int awq_attn_varlen_plan(int nseq, int nheads, int head_dim, int max_seqlen, int* q_tile_rows, int* blocks) {
+  if (!q_tile_rows || !blocks) return AWQ_ERR_NULL;
+  if (!varlen_shape_ok(nseq, nheads, head_dim, max_seqlen)) return AWQ_ERR_SHAPE;
+  return awq::attn_varlen_plan(nseq, nheads, head_dim, max_seqlen, q_tile_rows, blocks);
+}
+
+int awq_attn_varlen(const void* q, const void* k, const void* v, void* out, const int* cu_seqlens, int nseq, int max_seqlen,
+                    long long total_rows, int nheads, int head_dim, long long q_row_stride, long long k_row_stride,
+                    long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  if (!q || !k || !v || !out || !cu_seqlens) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  const long long hd = (long long)nheads * head_dim;
+  if (!varlen_shape_ok(nseq, nheads, head_dim, max_seqlen) || causal != 0 || total_rows < 1 || q_row_stride < hd || k_row_stride < hd ||
+      v_row_stride < hd)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 ||
+      (v_row_stride % 8) != 0 || (reinterpret_cast<uintptr_t>(cu_seqlens) & 3u))
+    return AWQ_ERR_ALIGN;
+  awq::launch_attn_tower(q, k, v, out, cu_seqlens, nseq, max_seqlen, max_seqlen, total_rows, nheads, nheads, head_dim, 0, q_row_stride, 0,
+                         k_row_stride, 0, v_row_stride, softmax_scale, dtype, (hipStream_t)stream);
   return finish_launch();
 }
 
@@ -768,6 +803,7 @@ int awq_tune_set(const char* key, int value) {
   if (awq::midm_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::gemm_v3_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::attn_prefill_tune_set(key, value) == 0) return AWQ_OK;
+  if (awq::attn_tower_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::w8a8_tune_set(key, value) == 0) return AWQ_OK;
   if (!strcmp(key, "w3_skinny_max")) {
     g_w3_skinny_max = value;

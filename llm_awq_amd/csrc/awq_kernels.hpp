@@ -182,6 +182,13 @@ int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, 
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,
                      int max_pos, int dtype, hipStream_t st);
+// encoder-tower attention (awq_attn_tower_cdna4.hip): non-causal, head dims 64 and 72, sequences described on the device by cu_seqlens
+// (varlen) or cu_seqlens == NULL (dense: nseq x Sq x Sk with batch strides); arguments validated by the caller
+int attn_varlen_plan(int nseq, int nheads, int head_dim, int max_seqlen, int* q_tile_rows, int* blocks);
+int attn_tower_tune_set(const char* key, int value);  // "tower_rows": force the q tile (0 = plan)
+int launch_attn_tower(const void* q, const void* k, const void* v, void* out, const int* cu_seqlens, int nseq, int Sq, int Sk,
+                      long long total_rows, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs,
+                      long long v_bs, long long v_rs, float scale, int dtype, hipStream_t st);
 // W8A8 linear (awq_w8a8_cdna4.hip); arguments validated by the caller.  w8a8_gemm_plan: blocks of the launch (0 = shape not served) and its tile
 int w8a8_gemm_plan(int m, int n, int k, int* tile_m, int* tile_n);
 int w8a8_tune_set(const char* key, int value);  // "w8a8_tile": force the 64 x 64 or the 128 x 128 tile (0 = plan)

@@ -673,19 +673,49 @@ torch::Tensor attn_prefill(const torch::Tensor q, const torch::Tensor k, const t
   TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "attn_prefill: q, k and v must share one dtype");
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "attn_prefill: q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]");
   const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), sk = k.size(1), nheads_kv = k.size(2);
-  TORCH_CHECK(headdim == 64 || headdim == 128, "attn_prefill: head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(headdim == 64 || headdim == 128 || (headdim == 72 && !causal), "attn_prefill: head dim ", headdim, causal ? " (causal)" : "",
+              " is not supported (supported head dims: 64, 128, and 72 without a causal mask)");
   TORCH_CHECK(k.size(0) == batch && k.size(3) == headdim && v.sizes() == k.sizes(), "attn_prefill: k / v must be [B, Sk, Hkv, ", headdim, "]");
   TORCH_CHECK(batch >= 1 && sq >= 1 && sk >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0,
               "attn_prefill: empty tensors are not supported and H must be a multiple of Hkv");
   TORCH_CHECK(!causal || sq <= sk, "attn_prefill: causal attention needs seqlen_q <= seqlen_k, got ", sq, " > ", sk);
   for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
     TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == headdim,
-                "attn_prefill: the heads of q / k / v must be contiguous (stride(3) == 1, stride(2) == Dh); supported head dims: 64, 128");
+                "attn_prefill: the heads of q / k / v must be contiguous (stride(3) == 1, stride(2) == Dh); supported head dims: 64, 128, 72 (non-causal)");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
   raise_on(awq_attn_prefill(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)batch, (int)sq, (int)sk, (int)nheads, (int)nheads_kv,
                             (int)headdim, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale,
                             causal ? 1 : 0, dtype_code(q), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
+// flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
+// (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
+// kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
+torch::Tensor attn_varlen_qkvpacked(const torch::Tensor qkv, const torch::Tensor cu_seqlens, int64_t max_seqlen, double softmax_scale,
+                                    bool causal) {
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, "attn_varlen_qkvpacked: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && cu_seqlens.is_cuda() && cu_seqlens.device() == qkv.device(),
+              "attn_varlen_qkvpacked: qkv and cu_seqlens must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, "attn_varlen_qkvpacked: float16 / bfloat16 only, got ",
+              qkv.scalar_type());
+  TORCH_CHECK(!causal, "attn_varlen_qkvpacked: causal attention is not supported (encoder towers only)");
+  TORCH_CHECK(qkv.dim() == 4 && qkv.size(1) == 3, "attn_varlen_qkvpacked: qkv [nnz, 3, H, Dh]");
+  const int64_t nnz = qkv.size(0), nheads = qkv.size(2), headdim = qkv.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 72, "attn_varlen_qkvpacked: head dim ", headdim, " is not supported (supported head dims: 64, 72)");
+  TORCH_CHECK(cu_seqlens.scalar_type() == at::kInt && cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2 && cu_seqlens.is_contiguous(),
+              "attn_varlen_qkvpacked: cu_seqlens must be a contiguous int32 tensor of nseq + 1 entries");
+  TORCH_CHECK(nnz >= 1 && nheads >= 1 && max_seqlen >= 1 && max_seqlen <= 0x7FFFFFFF, "attn_varlen_qkvpacked: empty tensors are not supported");
+  TORCH_CHECK(qkv.stride(3) == 1 && qkv.stride(2) == headdim && qkv.stride(1) == nheads * headdim,
+              "attn_varlen_qkvpacked: the heads of qkv must be contiguous (stride(3) == 1, stride(2) == Dh, stride(1) == H * Dh)");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor out = torch::empty({nnz, nheads, headdim}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
+  const char* base = (const char*)qkv.data_ptr();
+  const int64_t step = qkv.stride(1) * (int64_t)qkv.element_size();
+  raise_on(awq_attn_varlen(base, base + step, base + 2 * step, out.data_ptr(), (const int*)cu_seqlens.data_ptr(), (int)(cu_seqlens.numel() - 1),
+                           (int)max_seqlen, nnz, (int)nheads, (int)headdim, qkv.stride(0), qkv.stride(0), qkv.stride(0), (float)softmax_scale,
+                           0, dtype_code(qkv), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
   return out;
 }
 
@@ -949,6 +979,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("neox_rotary_style") = true);
   m.def("attn_prefill", &attn_prefill, "Prefill attention (flash_attn_func's forward): q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
+        "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
+        py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("rotary_embedding_neox", &rotary_embedding_neox, "Apply GPT-NeoX style rotary embedding to query and key");
   m.def("fused_rope_with_pos_forward_func", &fused_rope_with_pos_forward_func, "Fused rope forward function with B,S,D embedding");
   m.def("w8a8_gemm_forward_cuda", &w8a8_gemm_forward_cuda, "our w8a8 gemm kernel");

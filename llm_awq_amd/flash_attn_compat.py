@@ -5,10 +5,18 @@ tinychat/modules/fused_attn.py:17) and sends every prompt through `flash_attn_fu
 fused_attn.py:477,539).  The flash-attn package is CUDA-only; `llm_awq_amd.install_as_flash_attn()` puts this module into
 `sys.modules["flash_attn"]` so that those imports resolve to the gfx950 prefill kernel of the engine (`attn_prefill`).
 
-Only what tinychat imports exists here: `flash_attn_func`, forward only, no dropout, no sliding window, no ALiBi.  Anything else
-that is asked for raises NotImplementedError naming the keyword -- never a silent approximation.
+The vision towers import more (tinychat/modules/fused_siglipdecoder.py:15 `from flash_attn import flash_attn_func` at head dim 72;
+tinychat/models/internvl/internvit.py:18-20 `from flash_attn.bert_padding import pad_input, unpad_input` and
+`from flash_attn.flash_attn_interface import flash_attn_varlen_qkvpacked_func` inside a `try:` whose failure silently selects a naive
+O(S^2) attention).  `flash_attn_interface` and `bert_padding` below are those two submodules; `install_as_flash_attn()` registers
+them under `flash_attn.` as well.
+
+Only what tinychat imports exists here: `flash_attn_func` and `flash_attn_varlen_qkvpacked_func`, forward only, no dropout, no sliding
+window, no ALiBi.  Anything else that is asked for raises NotImplementedError naming the keyword -- never a silent approximation.
 """
 from __future__ import annotations
+
+import types
 
 __version__ = "0+llm_awq_amd"
 
@@ -41,4 +49,61 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, **
     return load_engine().attn_prefill(q, k, v, scale, bool(causal))
 
 
-__all__ = ["flash_attn_func"]
+def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, **kw):
+    """flash_attn.flash_attn_varlen_qkvpacked_func's forward: qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1] on the GPU -> [nnz, H, Dh].
+    Encoder attention only: every row attends the keys of its own sequence."""
+    if dropout_p:
+        raise NotImplementedError("flash_attn_varlen_qkvpacked_func on MI355X: dropout_p != 0 is not implemented (inference only)")
+    if causal:
+        raise NotImplementedError("flash_attn_varlen_qkvpacked_func on MI355X: causal=True is not implemented (encoder towers only)")
+    kw.pop("deterministic", None)  # the kernel is always bit-deterministic
+    for name, value in kw.items():
+        if not _is_off(name, value):
+            raise NotImplementedError(f"flash_attn_varlen_qkvpacked_func on MI355X: keyword {name}={value!r} is not implemented")
+    from . import load_engine
+
+    scale = float(qkv.shape[-1]) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    return load_engine().attn_varlen_qkvpacked(qkv, cu_seqlens, int(max_seqlen), scale, False)
+
+
+# ---- flash_attn.bert_padding: plain torch, any device ----
+def index_first_axis(input, indices):
+    """input [n, ...] -> input[indices] (flash_attn.bert_padding.index_first_axis's forward)."""
+    return input[indices]
+
+
+def unpad_input(hidden_states, attention_mask):
+    """hidden_states [B, S, ...], attention_mask [B, S] (nonzero = kept) -> (hidden_states of the kept tokens [nnz, ...], their indices
+    into the flattened [B * S] axis, cu_seqlens int32 [B + 1], the longest sequence as an int): the four values internvit.py:74 unpacks."""
+    import torch
+
+    lens = attention_mask.sum(dim=-1, dtype=torch.int32)
+    indices = torch.nonzero(attention_mask.flatten(), as_tuple=False).flatten()
+    max_seqlen = int(lens.max().item())
+    cu_seqlens = torch.nn.functional.pad(torch.cumsum(lens, dim=0, dtype=torch.int32), (1, 0))
+    flat = hidden_states.reshape(hidden_states.shape[0] * hidden_states.shape[1], *hidden_states.shape[2:])
+    return index_first_axis(flat, indices), indices, cu_seqlens, max_seqlen
+
+
+def pad_input(hidden_states, indices, batch, seqlen):
+    """The inverse of unpad_input: hidden_states [nnz, ...] -> [batch, seqlen, ...] with zeros at the dropped positions."""
+    import torch
+
+    out = torch.zeros(batch * seqlen, *hidden_states.shape[1:], dtype=hidden_states.dtype, device=hidden_states.device)
+    out[indices] = hidden_states
+    return out.view(batch, seqlen, *hidden_states.shape[1:])
+
+
+def _namespace(name, **members):
+    m = types.ModuleType(__name__ + "." + name)
+    m.__dict__.update(members)
+    m.__all__ = sorted(members)
+    return m
+
+
+flash_attn_interface = _namespace("flash_attn_interface", flash_attn_func=flash_attn_func,
+                                  flash_attn_varlen_qkvpacked_func=flash_attn_varlen_qkvpacked_func)
+bert_padding = _namespace("bert_padding", unpad_input=unpad_input, pad_input=pad_input, index_first_axis=index_first_axis)
+SUBMODULES = {"flash_attn_interface": flash_attn_interface, "bert_padding": bert_padding}
+
+__all__ = ["flash_attn_func", "flash_attn_varlen_qkvpacked_func", "flash_attn_interface", "bert_padding"]

@@ -548,7 +548,7 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
     """C-ABI awq_attn_prefill: softmax(scale * q k^T + mask) v with flash_attn_func's layout and masking.
     q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (batch and row strides of their own, heads contiguous -- the q / k / v slices of one
     fused qkv tensor pass without a copy); causal is bottom-right aligned (row i attends keys j <= i + Sk - Sq).  Returns
-    [B, Sq, H, Dh] contiguous.  Dh 64 or 128, float16 / bfloat16."""
+    [B, Sq, H, Dh] contiguous.  Dh 64 or 128 (72 too when not causal), float16 / bfloat16."""
     for t in (q, k, v):
         if not t.is_cuda:
             raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
@@ -566,6 +566,45 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
         _capi.check(_capi.lib().awq_attn_prefill(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, Sk, H, Hkv, Dh,
                                                  q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
                                                  scale, int(bool(causal)), _dt(q), _stream(q)))
+    return out
+
+
+def attn_varlen_plan(nseq: int, nheads: int, head_dim: int, max_seqlen: int):
+    """Host-side awq_attn_varlen_plan: (q_tile_rows, blocks) of the tower attention launch (no GPU needed)."""
+    import ctypes
+
+    r, n = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_varlen_plan(nseq, nheads, head_dim, max_seqlen, ctypes.byref(r), ctypes.byref(n)))
+    return r.value, n.value
+
+
+def attn_varlen(q, k, v, cu_seqlens, max_seqlen: int, softmax_scale=None, causal: bool = False, out=None):
+    """C-ABI awq_attn_varlen: non-causal attention over packed sequences.  q / k / v [total_rows, H, Dh] with row strides of their own and
+    contiguous heads (the three slices qkv[:, i] of a packed [total_rows, 3, H, Dh] tensor pass without a copy), cu_seqlens int32
+    [nseq + 1] on the same GPU (read by the kernel only).  Returns [total_rows, H, Dh] contiguous (`out` if given); rows >=
+    cu_seqlens[-1] are not written.  Dh 64 or 72, float16 / bfloat16."""
+    for t in (q, k, v, cu_seqlens):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+        if t.device != q.device:
+            raise ValueError("attn_varlen: q, k, v and cu_seqlens must live on the same GPU")
+    for t in (q, k, v):
+        if t.dim() != 3 or t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+            raise ValueError("q / k / v must be [total_rows, heads, Dh] with contiguous heads")
+    if k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("attn_varlen: q, k and v of one shape and dtype are expected")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or not cu_seqlens.is_contiguous():
+        raise ValueError("attn_varlen: cu_seqlens must be a contiguous int32 tensor of nseq + 1 entries")
+    T, H, Dh = q.shape
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    if out is None:
+        out = torch.empty(T, H, Dh, dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or not out.is_contiguous() or out.device != q.device:
+        raise ValueError("attn_varlen: out must be a contiguous [total_rows, H, Dh] tensor of q's dtype and device")
+    with torch.cuda.device(q.device):
+        _capi.check(_capi.lib().awq_attn_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), cu_seqlens.data_ptr(),
+                                                cu_seqlens.numel() - 1, int(max_seqlen), T, H, Dh, q.stride(0), k.stride(0), v.stride(0),
+                                                scale, int(bool(causal)), _dt(q), _stream(q)))
     return out
 
 
