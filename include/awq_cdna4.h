@@ -370,6 +370,31 @@ int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int
                      int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
                      long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
 
+/* ---- Chunk prefill on the FasterTransformer KV cache (tinychat/modules/fused_attn.py:248-302, 439-483): the prompt side in two launches,
+ *      with no copy whose size grows with the history.
+ *     k_cache [cache_batch, Hkv, Dh/8, lmax, 8], v_cache [cache_batch, Hkv, lmax, Dh], contiguous: the caches awq_attn_decode reads and writes.
+ * awq_rope_kv_store: qkv [B, S, (H + 2 Hkv) Dh] (own batch and row strides, in elements; q heads, then k heads, then v heads), freqs fp32
+ *     with B * S * rot_dim angles.  q_out [B, S, H, Dh] contiguous <- rotated q; k_cache[b, kvh, ch, start_pos + s, 0..7] <- rotated k;
+ *     v_cache[b, kvh, start_pos + s, :] <- v.  The rotation is awq_rope_with_pos's with n0 = B, n1 = S (angle index
+ *     (s * B + b) * rot_dim + c, one rounding, columns >= rot_dim copied): the results are bit-identical to two awq_rope_with_pos calls
+ *     followed by the stores.  Nothing outside positions [start_pos, start_pos + S) of rows b < B is written; no wrap on the prompt side.
+ *     Returns AWQ_ERR_SHAPE (Dh not 64 / 128, rot_dim % 16 != 0 or > Dh, B > cache_batch, start_pos < 0, start_pos + S > lmax, a row
+ *     stride below (H + 2 Hkv) Dh, non-positive sizes), AWQ_ERR_DTYPE, AWQ_ERR_NULL, AWQ_ERR_ALIGN (16 bytes for the pointers and the
+ *     strides), AWQ_ERR_LAUNCH; all but the last without a GPU call (csrc/awq_attn_chunk_cdna4.hip).
+ * awq_attn_prefill_ftcache: awq_attn_prefill with K / V read from the caches: key j of the attention is cache position kv_start + j,
+ *     j < seqlen_k.  kv_start = 0, seqlen_k = start_pos + S is chunk prefill; kv_start = start_pos, seqlen_k = S attends the new chunk
+ *     only.  q [B, Sq, H, Dh] with its own batch and row strides, out [B, Sq, H, Dh] contiguous.  Same plan (awq_attn_prefill_plan), tile
+ *     walk, masks and rounding points: the output is bit-identical to awq_attn_prefill on a contiguous copy of the same keys and values.
+ *     No cache position outside [kv_start, kv_start + seqlen_k) and no cache row >= B is read.  No workspace, no atomics; capturable.
+ *     Returns the codes of awq_attn_prefill, with AWQ_ERR_SHAPE also for Dh not 64 / 128, kv_start < 0, kv_start + seqlen_k > lmax and
+ *     B > cache_batch; all but AWQ_ERR_LAUNCH without a GPU call. */
+int awq_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int batch, int cache_batch, int seqlen,
+                      int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
+                      long long qkv_row_stride, int dtype, void* stream);
+int awq_attn_prefill_ftcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int cache_batch, int seqlen_q,
+                             int kv_start, int seqlen_k, int nheads, int nheads_kv, int head_dim, int lmax, long long q_batch_stride,
+                             long long q_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

@@ -10,7 +10,17 @@ import importlib.util
 import os
 import sys
 
-__all__ = ["load_engine", "install_as_awq_inference_engine", "install_as_flash_attn"]
+__all__ = ["load_engine", "install_as_awq_inference_engine", "install_as_flash_attn", "QuantLlamaAttentionFused",
+           "QuantLlamaAttentionFusedFlash", "make_quant_attn"]
+_LAZY = {"QuantLlamaAttentionFused": "fused_attn", "QuantLlamaAttentionFusedFlash": "fused_attn", "make_quant_attn": "fused_attn"}
+
+
+def __getattr__(name):
+    """The module-layer exports, imported on first use (the package itself imports without torch)."""
+    if name in _LAZY:
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
 
 _EXT_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ext")
 _engine = None

@@ -87,6 +87,9 @@ SIGNATURES = {
     "awq_attn_prefill_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_prefill": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                               ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),
+    "awq_rope_kv_store": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _i, _vp]),
+    "awq_attn_prefill_ftcache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
+                                      ctypes.c_float, _i, _i, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

@@ -1,0 +1,132 @@
+// Prompt-side preparation of a chunk on the FasterTransformer KV cache, one launch (tinychat/modules/fused_attn.py:248-267, 439-454: two
+// fused_rope_with_pos_forward_func calls, a reshape / permute / contiguous of K and two strided slice-assigns into the caches).
+//
+//   qkv [B, S, (H + 2 Hkv) Dh] (batch and row strides of its own)  ->  q_out [B, S, H, Dh]             rotated
+//                                                                      k_cache[b, kvh, ch, start_pos + s, 0..7]   rotated
+//                                                                      v_cache[b, kvh, start_pos + s, :]          copied
+//
+// The arithmetic is rope_with_pos_kernel's (awq_attn_prefill_cdna4.hip), expression for expression: the angle of (b, s, ., c), c < rot, is
+// freqs[(s * B + b) * rot + c] (the reference's own flat index), sincosf once per column, fmaf(x, cos, (+-x_rot) * sin) rounded to T once,
+// columns >= rot copied -- so q_out and the caches hold the bits the two rope calls followed by the torch stores would have left.
+//
+// Two thread mappings, one per half of the grid (the role is uniform over a block), every access 16 bytes:
+//   * q / v blocks: one thread = 8 consecutive columns of one (b, s), the column chunk fastest, over the H query heads and then the Hkv
+//     value heads.  The qkv row, the q_out row and the v_cache row are all contiguous along the chunk, so loads and stores coalesce.
+//   * k blocks: one thread = 8 consecutive columns of one (b, s) over the Hkv key heads, the POSITION fastest: consecutive lanes write
+//     consecutive positions of one chunk, which lie 16 bytes apart in k_cache [Bc, Hkv, Dh/8, Lmax, 8] (consecutive chunks of one position
+//     would be Lmax * 16 bytes apart).  Their loads are 16 bytes per row of qkv; K is Hkv / (H + 2 Hkv) of the tensor.
+// Nothing outside positions [start_pos, start_pos + S) of cache rows b < B is written.
+#include "awq_device.hpp"
+#include "awq_kernels.hpp"
+
+#include <math.h>
+
+namespace awq {
+namespace {
+
+struct RopeStoreArgs {
+  const uint16_t* qkv;
+  const float* freqs;
+  uint16_t* q_out;
+  uint16_t* k_cache;
+  uint16_t* v_cache;
+  long long bs, rs;  // qkv batch / row strides, elements
+  int B, S, H, Hkv, rot, lmax, start, qv_blocks;
+};
+
+template <typename DT>
+__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
+  const u32 ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
+    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
+  }
+}
+template <typename DT>
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+  u32 ws[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
+  return u32x4{ws[0], ws[1], ws[2], ws[3]};
+}
+
+template <typename DT, int DH>
+__global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
+  constexpr int CPR = DH / 8;
+  const bool k_role = (int)blockIdx.x >= a.qv_blocks;
+  const long long id = (long long)(k_role ? blockIdx.x - a.qv_blocks : blockIdx.x) * 256 + threadIdx.x;
+  if (id >= (long long)a.B * a.S * CPR) return;
+  int b, s, ch;
+  if (k_role) {
+    s = (int)(id % a.S);
+    ch = (int)((id / a.S) % CPR);
+    b = (int)(id / ((long long)a.S * CPR));
+  } else {
+    ch = (int)(id % CPR);
+    s = (int)((id / CPR) % a.S);
+    b = (int)(id / ((long long)a.S * CPR));
+  }
+  const int c0 = ch * 8, half = a.rot >> 1;
+  const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
+  const uint16_t* src = row + (k_role ? (long long)a.H * DH : 0);  // the K heads follow the H query heads
+  const int heads = k_role ? a.Hkv : a.H;
+  const long long pos = a.start + s;
+  uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
+  uint16_t* kd = a.k_cache + (((long long)b * a.Hkv * CPR + ch) * a.lmax + pos) * 8;  // + kvh * CPR * lmax * 8
+  const long long k_hs = (long long)CPR * a.lmax * 8;
+
+  if (c0 >= a.rot) {
+    for (int hd = 0; hd < heads; ++hd) {
+      const u32x4 w = *reinterpret_cast<const u32x4*>(src + hd * DH + c0);
+      if (k_role) *reinterpret_cast<u32x4*>(kd + hd * k_hs) = w;
+      else *reinterpret_cast<u32x4*>(qd + hd * DH) = w;
+    }
+  } else {
+    const float* fr = a.freqs + ((long long)s * a.B + b) * a.rot + c0;
+    const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
+    const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+    float cs[8], sn[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
+    const bool first = c0 + half < a.rot;
+    const int pc = first ? c0 + half : c0 - half;
+    const float sign = first ? -1.f : 1.f;
+    for (int hd = 0; hd < heads; ++hd) {
+      float x[8], y[8], res[8];
+      unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * DH + c0), x);
+      unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * DH + pc), y);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) res[e] = __builtin_fmaf(x[e], cs[e], (sign * y[e]) * sn[e]);
+      if (k_role) *reinterpret_cast<u32x4*>(kd + hd * k_hs) = pack8<DT>(res);
+      else *reinterpret_cast<u32x4*>(qd + hd * DH) = pack8<DT>(res);
+    }
+  }
+  if (!k_role) {
+    const uint16_t* vs = row + (long long)(a.H + a.Hkv) * DH + c0;
+    uint16_t* vd = a.v_cache + ((long long)b * a.Hkv * a.lmax + pos) * DH + c0;  // + kvh * lmax * DH
+    for (int hd = 0; hd < a.Hkv; ++hd)
+      *reinterpret_cast<u32x4*>(vd + (long long)hd * a.lmax * DH) = *reinterpret_cast<const u32x4*>(vs + hd * DH);
+  }
+}
+
+}  // namespace
+
+int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv, int Dh,
+                         int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  const int nb = (int)((n + 255) / 256);
+  RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
+                  start_pos, nb};
+  const dim3 grid((unsigned)(2 * nb));
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<F16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_kernel<F16, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+}  // namespace awq

@@ -63,8 +63,28 @@ __device__ __forceinline__ int v_off(int row, int ch) {
   return row * DH + ((ch ^ (DH == 128 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (((row >> 1) & 1) << 2))) << 3);
 }
 
+// FT = true: K / V are staged straight from the FasterTransformer caches the decode kernel reads and writes, k_cache [Bc, Hkv, DH/8, Lmax, 8]
+// and v_cache [Bc, Hkv, Lmax, DH] (launch_attn_prefill_ftcache below).  a.k / a.v then point at cache position kv_start of row 0, head 0,
+// a.k_rs is the stride between two 8-column chunks of K (Lmax * 8), a.k_bs = a.v_bs the row stride Hkv * Lmax * DH, and the head stride of
+// both caches is a.k_rs * DH / 8.  Only the global addresses of the staging differ: the LDS images, the tile walk and every rounding
+// are those of the natural-layout form, so the two give the same bits on the same keys and values.
+//
+// The FT form is selected by the element traits -- FtCache<F16> / FtCache<BF16>, the same traits under another name -- so it is a
+// separate instantiation and the natural-layout kernels keep their names, their compile-time strides and their code.
+template <typename DT>
+struct FtCache : DT {};
+template <typename DT>
+struct IsFtCache {
+  static constexpr bool value = false;
+};
+template <typename DT>
+struct IsFtCache<FtCache<DT>> {
+  static constexpr bool value = true;
+};
+
 template <typename DT, int DH, int NW>
 __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
+  constexpr bool FT = IsFtCache<DT>::value;
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = NW * 64;
@@ -106,23 +126,34 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
   }
 
-  const uint16_t* kb = a.k + (long long)b * a.k_bs + (long long)kvh * DH;
-  const uint16_t* vb = a.v + (long long)b * a.v_bs + (long long)kvh * DH;
+  const uint16_t* kb = a.k + (long long)b * a.k_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
+  const uint16_t* vb = a.v + (long long)b * a.v_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
   u32x4 kr[LOADS], vr[LOADS];
+  // FT: the K chunks of a tile go to the threads with the KEY fastest (NT is a multiple of 64, so a wave reads 64 consecutive positions
+  // of one chunk index: 1 KiB contiguous in the cache) and land in the same LDS image; V rows are DH contiguous elements in the cache
+  // too, so V keeps the chunk-fastest mapping.  Keys >= Sk are clamped to Sk - 1 like rows: no position outside the Sk keys is read.
   auto stage_load = [&](int t0) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
       const long long g = min(t0 + row, a.Sk - 1);
-      kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
-      vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+      if constexpr (FT) {
+        const int krow = c % kKV, kch = c / kKV;
+        const long long kg = min(t0 + krow, a.Sk - 1);
+        kr[i] = *reinterpret_cast<const u32x4*>(kb + kch * a.k_rs + kg * 8);
+        vr[i] = *reinterpret_cast<const u32x4*>(vb + g * DH + ch * 8);
+      } else {
+        kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
+        vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+      }
     }
   };
   auto stage_write = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-      *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
+      if constexpr (FT) *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(c % kKV, c / kKV)]) = kr[i];
+      else *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
       *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
     }
   };
@@ -404,6 +435,41 @@ int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, 
   } else {
     if (Dh == 128) launch_nw<BF16, 128>(a, nw, blocks, st);
     else launch_nw<BF16, 64>(a, nw, blocks, st);
+  }
+  return 0;
+}
+
+// The same launch with K / V read from the FT caches: key j of the attention is cache position kv_start + j.  The plan is asked with the
+// same arguments as the natural-layout launch of the same problem, so the q tile -- and with it every bit of the result -- is the same.
+int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* v_cache, void* out, int B, int Sq, int kv_start, int Sk, int H,
+                                int Hkv, int Dh, int Lmax, long long q_bs, long long q_rs, float scale, int causal, int dtype, hipStream_t st) {
+  PrefillArgs a;
+  a.q = (const uint16_t*)q;
+  a.k = (const uint16_t*)k_cache + (long long)kv_start * 8;
+  a.v = (const uint16_t*)v_cache + (long long)kv_start * Dh;
+  a.out = (uint16_t*)out;
+  a.q_bs = q_bs;
+  a.q_rs = q_rs;
+  a.k_bs = a.v_bs = (long long)Hkv * Lmax * Dh;
+  a.k_rs = (long long)Lmax * 8;
+  a.v_rs = Dh;
+  a.B = B;
+  a.Sq = Sq;
+  a.Sk = Sk;
+  a.H = H;
+  a.G = H / Hkv;
+  a.causal = causal ? 1 : 0;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  int rows = 0, blocks = 0;
+  attn_prefill_plan(B, H, Hkv, Dh, Sq, Sk, causal, &rows, &blocks);
+  a.ntiles = (Sq + rows - 1) / rows;
+  const int nw = rows / kMfmaRows;
+  if (dtype == 0) {
+    if (Dh == 128) launch_nw<FtCache<F16>, 128>(a, nw, blocks, st);
+    else launch_nw<FtCache<F16>, 64>(a, nw, blocks, st);
+  } else {
+    if (Dh == 128) launch_nw<FtCache<BF16>, 128>(a, nw, blocks, st);
+    else launch_nw<FtCache<BF16>, 64>(a, nw, blocks, st);
   }
   return 0;
 }

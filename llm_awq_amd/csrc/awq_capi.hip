@@ -377,6 +377,40 @@ int awq_attn_prefill(const void* q, const void* k, const void* v, void* out, int
   return finish_launch();
 }
 
+int awq_attn_prefill_ftcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int cache_batch, int seqlen_q,
+                             int kv_start, int seqlen_k, int nheads, int nheads_kv, int head_dim, int lmax, long long q_batch_stride,
+                             long long q_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  if (!q || !k_cache || !v_cache || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if ((head_dim != 64 && head_dim != 128) || !prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal) ||
+      cache_batch < batch || lmax < 1 || kv_start < 0 || (long long)kv_start + seqlen_k > lmax || q_batch_stride < 0 ||
+      q_row_stride < (long long)nheads * head_dim)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_attn_prefill_ftcache(q, k_cache, v_cache, out, batch, seqlen_q, kv_start, seqlen_k, nheads, nheads_kv, head_dim, lmax,
+                                   q_batch_stride, q_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int batch, int cache_batch, int seqlen,
+                      int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
+                      long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs || !q_out || !k_cache || !v_cache) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (batch < 1 || cache_batch < batch || seqlen < 1 || nheads < 1 || nheads_kv < 1 || (head_dim != 64 && head_dim != 128) ||
+      (head_dim % 8) != 0 || rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_dim || lmax < 1 || start_pos < 0 ||
+      (long long)start_pos + seqlen > lmax || qkv_batch_stride < 0 ||
+      qkv_row_stride < ((long long)nheads + 2ll * nheads_kv) * head_dim || (long long)batch * seqlen * (head_dim / 8) > 0x3FFFFFFFll * 256)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
+      (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store(qkv, freqs, q_out, k_cache, v_cache, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, start_pos,
+                            qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {
   return nseq >= 1 && nheads >= 1 && (head_dim == 64 || head_dim == 72) && max_seqlen >= 1 &&
          (long long)nseq * nheads * ((max_seqlen + 31) / 32) <= 0x7FFFFFFFll;

@@ -178,6 +178,12 @@ int attn_prefill_tune_set(const char* key, int value);  // "attn_prefill_rows": 
 int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
                         long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
                         hipStream_t st);
+// the same attention with K / V staged from the FT caches (k_cache [Bc, Hkv, Dh/8, Lmax, 8], v_cache [Bc, Hkv, Lmax, Dh]): key j = cache position kv_start + j
+int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* v_cache, void* out, int B, int Sq, int kv_start, int Sk, int H,
+                                int Hkv, int Dh, int Lmax, long long q_bs, long long q_rs, float scale, int causal, int dtype, hipStream_t st);
+// prompt-side chunk preparation (awq_attn_chunk_cdna4.hip): rope of q and k, K / V stored into the FT caches, one launch
+int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv, int Dh,
+                         int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

@@ -690,6 +690,83 @@ torch::Tensor attn_prefill(const torch::Tensor q, const torch::Tensor k, const t
   return out;
 }
 
+// The caches of tinychat's QuantLlamaAttentionFused (fused_attn.py:197-224): v_cache [Bc, Hkv, Lmax, Dh], k_cache [Bc, Hkv, Dh/8, Lmax, 8].
+static void check_ft_caches(const char* who, const torch::Tensor& ref, const torch::Tensor& k_cache, const torch::Tensor& v_cache) {
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == ref.device(), who, ": the caches must live on the GPU of the input");
+    TORCH_CHECK(t->scalar_type() == ref.scalar_type(), who, ": the caches must have the dtype of the input");
+  }
+  TORCH_CHECK(v_cache.dim() == 4 && k_cache.dim() == 5, who, ": k_cache [Bc, Hkv, Dh/8, Lmax, 8], v_cache [Bc, Hkv, Lmax, Dh]");
+  const int64_t headdim = v_cache.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(k_cache.size(0) == v_cache.size(0) && k_cache.size(1) == v_cache.size(1) && k_cache.size(2) == headdim / 8 &&
+                  k_cache.size(3) == v_cache.size(2) && k_cache.size(4) == 8,
+              who, ": k_cache must be [Bc, Hkv, Dh/8, Lmax, 8] for v_cache [Bc, Hkv, Lmax, Dh]");
+  TORCH_CHECK(v_cache.is_contiguous() && k_cache.is_contiguous(), who, ": the caches must be contiguous");
+}
+
+// rope_kv_store(qkv, freqs, k_cache, v_cache, start_pos, nheads, nheads_kv) -> q_out: the prompt side of QuantLlamaAttentionFused.forward
+// before the attention (fused_attn.py:248-267, 439-454) in one launch (csrc/awq_attn_chunk_cdna4.hip).  qkv [B, S, (H + 2 Hkv) Dh] with a
+// unit last stride (a slice of a wider buffer passes), freqs fp32 with last dim rot_dim and B * S * rot_dim angles.  Returns the rotated
+// q [B, S, H, Dh] contiguous; the rotated k and v are written into the caches at positions start_pos .. start_pos + S - 1.
+torch::Tensor rope_kv_store(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, int64_t start_pos,
+                            int64_t nheads, int64_t nheads_kv) {
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, "rope_kv_store: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), "rope_kv_store: tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, "rope_kv_store: float16 / bfloat16 only, got ", qkv.scalar_type());
+  TORCH_CHECK(freqs.scalar_type() == at::kFloat, "rope_kv_store: freqs must be float32");
+  check_ft_caches("rope_kv_store", qkv, k_cache, v_cache);
+  TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, "rope_kv_store: qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  const int64_t batch = qkv.size(0), seqlen = qkv.size(1), cache_batch = v_cache.size(0), lmax = v_cache.size(2), headdim = v_cache.size(3),
+                rot = freqs.size(-1);
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(1) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim,
+              "rope_kv_store: qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
+  TORCH_CHECK(batch <= cache_batch, "rope_kv_store: batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= lmax, "rope_kv_store: positions ", start_pos, " .. ", start_pos + seqlen,
+              " do not fit the cache of ", lmax, " (no wrap on the prompt side)");
+  TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot,
+              "rope_kv_store: freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  // the kernel reads 16 bytes at a time: a view whose last stride is not 1, or whose strides / base are not 16-byte multiples, is copied once
+  at::Tensor x = qkv;
+  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
+  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  raise_on(awq_rope_kv_store(x.data_ptr(), fr.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), (int)batch,
+                             (int)cache_batch, (int)seqlen, (int)nheads, (int)nheads_kv, (int)headdim, (int)rot, (int)lmax, (int)start_pos,
+                             x.stride(0), x.stride(1), dtype_code(x), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return q_out;
+}
+
+// attn_prefill_ftcache(q, k_cache, v_cache, kv_start, seqlen_k, softmax_scale, causal) -> out: attn_prefill with K / V read from the FT
+// caches, key j = cache position kv_start + j (csrc/awq_attn_prefill_cdna4.hip).  q [B, Sq, H, Dh] with contiguous heads and batch / row
+// strides of its own; returns [B, Sq, H, Dh] contiguous, bit-identical to attn_prefill on the gathered keys and values.
+torch::Tensor attn_prefill_ftcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, int64_t kv_start,
+                                   int64_t seqlen_k, double softmax_scale, bool causal) {
+  TORCH_CHECK(q.scalar_type() != at::kFloat, "attn_prefill_ftcache: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), "attn_prefill_ftcache: q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "attn_prefill_ftcache: float16 / bfloat16 only, got ", q.scalar_type());
+  check_ft_caches("attn_prefill_ftcache", q, k_cache, v_cache);
+  TORCH_CHECK(q.dim() == 4, "attn_prefill_ftcache: q [B, Sq, H, Dh]");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), cache_batch = v_cache.size(0),
+                nheads_kv = v_cache.size(1), lmax = v_cache.size(2);
+  TORCH_CHECK(headdim == v_cache.size(3), "attn_prefill_ftcache: q has head dim ", headdim, ", the caches ", v_cache.size(3));
+  TORCH_CHECK(batch >= 1 && sq >= 1 && seqlen_k >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0,
+              "attn_prefill_ftcache: empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(batch <= cache_batch, "attn_prefill_ftcache: batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(kv_start >= 0 && kv_start + seqlen_k <= lmax, "attn_prefill_ftcache: keys ", kv_start, " .. ", kv_start + seqlen_k,
+              " do not lie in the cache of ", lmax);
+  TORCH_CHECK(!causal || sq <= seqlen_k, "attn_prefill_ftcache: causal attention needs seqlen_q <= seqlen_k, got ", sq, " > ", seqlen_k);
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(2) == headdim, "attn_prefill_ftcache: the heads of q must be contiguous (stride(3) == 1, stride(2) == Dh)");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  raise_on(awq_attn_prefill_ftcache(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), (int)batch, (int)cache_batch, (int)sq,
+                                    (int)kv_start, (int)seqlen_k, (int)nheads, (int)nheads_kv, (int)headdim, (int)lmax, q.stride(0), q.stride(1),
+                                    (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+                                    (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
 // (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
 // kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
@@ -979,6 +1056,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("neox_rotary_style") = true);
   m.def("attn_prefill", &attn_prefill, "Prefill attention (flash_attn_func's forward): q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("rope_kv_store", &rope_kv_store, "Rotate q and k of a fused qkv chunk, store k / v into the FT caches; returns q [B, S, H, Dh]", py::arg("qkv"),
+        py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"));
+  m.def("attn_prefill_ftcache", &attn_prefill_ftcache, "Prefill attention with K / V read from the FT caches at positions kv_start .. kv_start + seqlen_k",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_start"), py::arg("seqlen_k"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

@@ -1,0 +1,135 @@
+"""QuantLlamaAttentionFused / make_quant_attn -- the MI355X build of tinychat/modules/fused_attn.py:169-324, 327-503, 549-634.
+
+The reference module prepares every prompt chunk in torch: two `fused_rope_with_pos_forward_func` launches, a reshape / permute /
+contiguous of K, two strided slice-assigns into the FasterTransformer (FT) caches and, with `chunk_prefilling`, a permute / reshape /
+contiguous of the whole cached history back to [B, Sk, Hkv, Dh] for K and for V -- a copy that grows with the history -- before
+`flash_attn_func` can run.  Here the prompt side is two launches and nothing proportional to the history is copied:
+
+  * `rope_kv_store` rotates q and k of the fused qkv tensor, writes k and v straight into `cache_k` / `cache_v` at positions
+    start_pos .. start_pos + seqlen - 1 and returns the rotated q (csrc/awq_attn_chunk_cdna4.hip);
+  * `attn_prefill_ftcache` is the prefill attention kernel with K / V staged from those caches (csrc/awq_attn_prefill_cdna4.hip):
+    keys 0 .. start_pos + seqlen - 1 with `chunk_prefilling`, keys start_pos .. start_pos + seqlen - 1 without (the reference then
+    attends the new chunk only).
+
+Both give the bits of the reference's composition on this package's kernels (rope x 2, the torch stores, `flash_attn_func` on the
+gathered copies).  One token (`seqlen == 1`) goes to `single_query_attention` exactly as the reference calls it.
+
+`QuantLlamaAttentionFusedFlash` is an alias: its `short_forward` is this data flow.  The reference's long-context variant (natural-layout
+caches and `long_forward` for kv_max_seq_len > 8192) is out of scope here; those callers keep `flash_attn_func` on their own caches.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import load_engine
+
+
+class QuantLlamaAttentionFused(nn.Module):
+    """Same constructor, attributes and forward as the reference class (fused_attn.py:169-324); `max_batch_size` is the module-level
+    global there (:21) and a keyword here.  `cache_k` [max_batch_size, Hkv, Dh/8, kv_max_seq_len, 8] and `cache_v`
+    [max_batch_size, Hkv, kv_max_seq_len, Dh] are the FT caches the decode kernel reads and writes."""
+
+    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1):
+        super().__init__()
+        self.args = args
+        self.n_local_heads = args.num_attention_heads
+        self.hidden_size = args.hidden_size
+        self.num_heads = args.num_attention_heads
+        self.head_dim = self.hidden_size // self.num_heads
+        self.num_key_value_heads = args.num_key_value_heads
+        self.num_key_value_groups = self.num_heads // self.num_key_value_heads
+        self.max_position_embeddings = getattr(args, "max_position_embeddings", None)
+        self.rope_theta = args.rope_theta
+        self.rope_scaling = getattr(args, "rope_scaling", None)
+        if self.rope_scaling is None:
+            self.rope_scaling = 1.0
+        if isinstance(self.rope_scaling, dict):
+            self.rope_scaling = self.rope_scaling.get("factor", 1.0)
+        if self.head_dim not in (64, 128):
+            raise ValueError(f"QuantLlamaAttentionFused: head dim {self.head_dim} is not supported (supported head dims: 64, 128)")
+        self.qkv_proj = qkv_layer
+        self.o_proj = o_proj
+        self.kv_max_seq_len = kv_max_seq_len
+        self.max_batch_size = max_batch_size
+        # following the FasterTransformer definition (fused_attn.py:196-224); 8 = the fp16 / bf16 elements of one 16-byte chunk
+        self.cache_v = torch.zeros((max_batch_size, self.num_key_value_heads, kv_max_seq_len, self.head_dim), dtype=torch.float16, device=dev)
+        self.cache_k = torch.zeros((max_batch_size, self.num_key_value_heads, self.head_dim // 8, kv_max_seq_len, 8), dtype=torch.float16,
+                                   device=dev)
+
+    @torch.no_grad()
+    def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False):
+        """`mask` is accepted and ignored, as in the reference's short_forward: the attention is causal."""
+        eng = load_engine()
+        bsz, seqlen, _ = x.shape
+        xqkv = self.qkv_proj(x)
+        if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:  # the reference's .to(xq) (:256-257)
+            self.cache_k = self.cache_k.to(xqkv)
+            self.cache_v = self.cache_v.to(xqkv)
+        if seqlen > 1:
+            xq = eng.rope_kv_store(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
+                                   self.num_key_value_heads)
+            kv_start, seqlen_k = (0, start_pos + seqlen) if chunk_prefilling else (start_pos, seqlen)
+            output = eng.attn_prefill_ftcache(xq, self.cache_k, self.cache_v, kv_start, seqlen_k, self.head_dim ** -0.5, True)
+            output = output.view(bsz, seqlen, -1)
+        else:
+            xqkv = xqkv.view(bsz, self.n_local_heads + self.num_key_value_heads * 2, self.head_dim)
+            xq = xqkv[:, :self.n_local_heads]
+            xk = xqkv[:, self.n_local_heads:self.n_local_heads + self.num_key_value_heads]
+            xv = xqkv[:, -self.num_key_value_heads:]
+            output = eng.single_query_attention(xq, xk, xv, self.cache_k, self.cache_v, None, None, start_pos, self.head_dim, self.rope_theta,
+                                                self.rope_scaling, True)
+            output = output.reshape(bsz, 1, -1)
+        return self.o_proj(output)
+
+
+QuantLlamaAttentionFusedFlash = QuantLlamaAttentionFused
+
+
+def fuse_qkv(q_proj, k_proj, v_proj):
+    """The three projections' v2 buffers concatenated as the reference does (fused_attn.py:566-594: qweight on dim 0, scales and
+    scaled_zeros on dim 1, bias on dim 0) into one WQLinear."""
+    from .qmodule import WQLinear
+
+    for name, p in (("q_proj", q_proj), ("k_proj", k_proj), ("v_proj", v_proj)):
+        if getattr(p, "layout", "v2") != "v2":
+            raise RuntimeError(f"make_quant_attn: {name} is in the {p.layout} layout; the projections are stacked as v2 (reference layout) "
+                               "buffers -- call to_v2() on it first (or awq_inference_engine.cdna4_restore(qweight) for a qweight the "
+                               "engine cache converted in place)")
+        if hasattr(p, "engine_converted") and p.engine_converted():
+            raise RuntimeError(f"make_quant_attn: the qweight of {name} was converted in place by the engine cache (AWQ_CDNA4_INPLACE); "
+                               "call awq_inference_engine.cdna4_restore(qweight) first")
+    if not (q_proj.w_bit == k_proj.w_bit == v_proj.w_bit == 4) or not (q_proj.group_size == k_proj.group_size == v_proj.group_size) or \
+            not (q_proj.in_features == k_proj.in_features == v_proj.in_features):
+        raise ValueError("make_quant_attn: q_proj, k_proj and v_proj must be 4-bit projections of one input width and group size")
+    if (q_proj.bias is None) != (k_proj.bias is None) or (q_proj.bias is None) != (v_proj.bias is None):
+        raise ValueError("make_quant_attn: q_proj, k_proj and v_proj must all carry a bias or none")
+    qkv = WQLinear(q_proj.w_bit, q_proj.group_size, q_proj.in_features, q_proj.out_features + k_proj.out_features + v_proj.out_features,
+                   q_proj.bias is not None, q_proj.qweight.device, dtype=q_proj.scales.dtype)
+    qkv.qweight = torch.cat([q_proj.qweight, k_proj.qweight, v_proj.qweight], dim=0)
+    qkv.scales = torch.cat([q_proj.scales, k_proj.scales, v_proj.scales], dim=1).contiguous()
+    qkv.scaled_zeros = torch.cat([q_proj.scaled_zeros, k_proj.scaled_zeros, v_proj.scaled_zeros], dim=1).contiguous()
+    if q_proj.bias is not None:
+        qkv.bias = torch.cat([q_proj.bias, k_proj.bias, v_proj.bias], dim=0)
+    qkv.split_k_iters = q_proj.split_k_iters
+    return qkv
+
+
+def make_quant_attn(model, dev, max_batch_size=1):
+    """tinychat/modules/fused_attn.py:549-634: replace every module that carries q_proj, k_proj, v_proj, o_proj, `args` and
+    `kv_max_seq_len` (the reference's LlamaAttentionFused / Qwen2AttentionFused) by a QuantLlamaAttentionFused over one fused
+    qkv WQLinear, then move the model to `dev`."""
+    want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
+    for name, m in list(model.named_modules()):
+        if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
+            continue
+        qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
+        attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
+                                        max_batch_size=max_batch_size)
+        if "." in name:
+            parent_name, child_name = name.rsplit(".", 1)
+            parent = model.get_submodule(parent_name)
+        else:
+            parent, child_name = model, name
+        setattr(parent, child_name, attn)
+    return model.to(dev)

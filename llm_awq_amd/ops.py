@@ -569,6 +569,62 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
     return out
 
 
+def _ft_caches(who, ref, k_cache, v_cache):
+    """(Bc, Hkv, Lmax, Dh) of the FT caches k_cache [Bc, Hkv, Dh/8, Lmax, 8] / v_cache [Bc, Hkv, Lmax, Dh], checked against `ref`."""
+    for t in (ref, k_cache, v_cache):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if k_cache.device != ref.device or v_cache.device != ref.device or k_cache.dtype != ref.dtype or v_cache.dtype != ref.dtype:
+        raise ValueError(f"{who}: the caches must have the device and dtype of the input")
+    if v_cache.dim() != 4 or k_cache.dim() != 5 or not v_cache.is_contiguous() or not k_cache.is_contiguous():
+        raise ValueError(f"{who}: contiguous k_cache [Bc, Hkv, Dh/8, Lmax, 8] and v_cache [Bc, Hkv, Lmax, Dh] are expected")
+    Bc, Hkv, Lmax, Dh = v_cache.shape
+    if tuple(k_cache.shape) != (Bc, Hkv, Dh // 8, Lmax, 8) or Dh % 8:
+        raise ValueError(f"{who}: k_cache must be [Bc, Hkv, Dh/8, Lmax, 8] for v_cache [Bc, Hkv, Lmax, Dh]")
+    return Bc, Hkv, Lmax, Dh
+
+
+def rope_kv_store(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nheads_kv: int):
+    """C-ABI awq_rope_kv_store: the prompt side of tinychat's QuantLlamaAttentionFused before the attention, in one launch.
+    qkv [B, S, (H + 2 Hkv) Dh] with a unit last stride (batch and row strides of its own), freqs contiguous fp32 with last dim rot_dim
+    and B * S * rot_dim angles, read at (s * B + b) * rot_dim + c as fused_rope_with_pos does.  Writes the rotated k into
+    k_cache[b, kvh, :, start_pos + s, :] and v into v_cache[b, kvh, start_pos + s, :]; returns the rotated q [B, S, H, Dh]."""
+    if not freqs.is_cuda:
+        raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    Bc, Hkv, Lmax, Dh = _ft_caches("rope_kv_store", qkv, k_cache, v_cache)
+    if freqs.device != qkv.device or freqs.dtype != torch.float32 or not freqs.is_contiguous():
+        raise ValueError("rope_kv_store: contiguous float32 freqs on the GPU of qkv are expected")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
+        raise ValueError("rope_kv_store: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
+    B, S = qkv.shape[0], qkv.shape[1]
+    rot = freqs.shape[-1]
+    if freqs.numel() < B * S * rot:
+        raise ValueError("rope_kv_store: freqs holds fewer than B * S * rot_dim angles")
+    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _capi.check(_capi.lib().awq_rope_kv_store(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                                  B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax, int(start_pos), qkv.stride(0),
+                                                  qkv.stride(1), _dt(qkv), _stream(qkv)))
+    return q_out
+
+
+def attn_prefill_ftcache(q, k_cache, v_cache, kv_start: int, seqlen_k: int, softmax_scale=None, causal: bool = True):
+    """C-ABI awq_attn_prefill_ftcache: flash_attn_func with K / V read straight from the FT caches; key j of the attention is cache
+    position kv_start + j, j < seqlen_k.  q [B, Sq, H, Dh] (batch and row strides of its own, heads contiguous), B <= Bc.  Returns
+    [B, Sq, H, Dh] contiguous, bit-identical to flash_attn_func on a contiguous copy of the same keys and values.  Dh 64 or 128."""
+    Bc, Hkv, Lmax, Dh = _ft_caches("attn_prefill_ftcache", q, k_cache, v_cache)
+    if q.dim() != 4 or q.stride(3) != 1 or q.stride(2) != q.shape[3] or q.shape[3] != Dh:
+        raise ValueError("attn_prefill_ftcache: q must be [B, Sq, H, Dh] with contiguous heads and the caches' Dh")
+    B, Sq, H, _ = q.shape
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    with torch.cuda.device(q.device):
+        _capi.check(_capi.lib().awq_attn_prefill_ftcache(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), B, Bc, Sq,
+                                                         int(kv_start), int(seqlen_k), H, Hkv, Dh, Lmax, q.stride(0), q.stride(1), scale,
+                                                         int(bool(causal)), _dt(q), _stream(q)))
+    return out
+
+
 def attn_varlen_plan(nseq: int, nheads: int, head_dim: int, max_seqlen: int):
     """Host-side awq_attn_varlen_plan: (q_tile_rows, blocks) of the tower attention launch (no GPU needed)."""
     import ctypes
