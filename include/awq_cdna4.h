@@ -395,6 +395,37 @@ int awq_attn_prefill_ftcache(const void* q, const void* k_cache, const void* v_c
                              int kv_start, int seqlen_k, int nheads, int nheads_kv, int head_dim, int lmax, long long q_batch_stride,
                              long long q_row_stride, float softmax_scale, int causal, int dtype, void* stream);
 
+/* ---- Split-KV attention (flash-decoding) for few query rows over a long natural-layout history: the decode phase of tinychat's long-context
+ *      path (fused_attn.py:389-415, 505-546: flash_attn_func(q, cache_k[:, :pos], cache_v[:, :pos], causal=True) with Sq = 1).
+ * awq_attn_splitkv: awq_attn_prefill's contract and arguments, plus a workspace.  Where the plan splits, one block serves one (batch, KV
+ *     head, split of *chunk keys): the Sq * G query rows of the KV head's group (G = H / Hkv) share one fetch of K / V, each block writes an
+ *     unnormalised fp32 partial (O, running max, row sum) per (row, split), and a second launch combines them in ascending split order
+ *     with 2^(m_s - M) weights, one division, one rounding to T.  Same rounding points as awq_attn_prefill inside a split.  No atomics:
+ *     bit-deterministic and capturable, workspace included (csrc/awq_attn_splitkv_cdna4.hip).  Where the plan does not split, the call IS
+ *     awq_attn_prefill (same launch, same bits) and the workspace may be NULL.
+ *     Returns the codes of awq_attn_prefill, plus AWQ_ERR_WORKSPACE (NULL or smaller than awq_attn_splitkv_workspace_bytes; a workspace
+ *     that is not 16-byte aligned is AWQ_ERR_ALIGN); all but AWQ_ERR_LAUNCH without a GPU call.
+ * awq_attn_splitkv_plan: host only, no GPU call.  *splits == 1: not taken -- always so for seqlen_k < 2048, Sq * G > 128, a head dim other
+ *     than 64 / 128, or a one-pass launch (awq_attn_prefill_plan) of at least 256 blocks.  Otherwise *chunk % 64 == 0, *chunk >= 1024,
+ *     (*splits - 1) * *chunk < seqlen_k <= *splits * *chunk, and batch * nheads_kv * *splits >= 256 wherever seqlen_k / 1024 allows.
+ *     Knob "attn_splitkv_chunk" (awq_tune_set): a multiple of 64 forces the chunk for any seqlen_k (the Sq * G and head dim limits hold).
+ * awq_attn_splitkv_workspace_bytes: batch * nheads * seqlen_q * splits * (head_dim + 2) * 4 (fp32 O [n][Dh] | m [n] | l [n], n = batch *
+ *     nheads * seqlen_q * splits), 0 when the plan does not split; follows the knob. */
+int awq_attn_splitkv_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* splits, int* chunk);
+size_t awq_attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal);
+int awq_attn_splitkv(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
+                     int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                     long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* awq_rope_kv_store for natural-layout caches k_cache / v_cache [cache_batch, lmax, Hkv, Dh] (tinychat's long_forward, fused_attn.py:527-537),
+ * one launch: q_out [B, S, H, Dh] <- rotated q, k_cache[b, start_pos + s, kvh, :] <- rotated k, v_cache[b, start_pos + s, kvh, :] <- v.
+ * Same arithmetic and freqs index as awq_rope_with_pos (quirk included): bit-identical to two awq_rope_with_pos calls followed by the two
+ * slice stores.  Nothing outside positions [start_pos, start_pos + S) of rows b < B is written.  Same error rules as awq_rope_kv_store
+ * (csrc/awq_attn_chunk_cdna4.hip). */
+int awq_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int batch, int cache_batch,
+                              int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos,
+                              long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.
@@ -470,7 +501,7 @@ int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, floa
                         int dtype, void* stream);
 
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
- * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "tower_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
+ * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "attn_splitkv_chunk", "tower_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every
  * call returns AWQ_ERR_SHAPE and changes nothing.  Timing probes and experiment-only kernel instantiations exist only in
  * builds made with AWQ_PROBES=1.  Returns AWQ_OK, or AWQ_ERR_SHAPE for an unknown key.  Process-global, not thread-safe. */

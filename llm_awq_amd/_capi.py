@@ -90,6 +90,12 @@ SIGNATURES = {
     "awq_rope_kv_store": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _i, _vp]),
     "awq_attn_prefill_ftcache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                                       ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_splitkv_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_attn_splitkv_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "awq_attn_splitkv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                              ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_rope_kv_store_natural": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _i,
+                                       _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

@@ -110,6 +110,53 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
   }
 }
 
+// The same preparation for natural-layout caches k_cache / v_cache [Bc, lmax, Hkv, DH] (tinychat's long-context path, fused_attn.py:527-537:
+// two rope calls and two slice stores cache[:B, start : start + S] = x).  A cache row is Hkv * DH contiguous elements, like the K and the
+// V part of a qkv row, so one mapping serves all three outputs: one thread = 8 consecutive columns of one (b, s), the column chunk
+// fastest, over the H query heads, the Hkv key heads and the Hkv value heads.  The rotation is the expression above, unchanged.
+template <typename DT, int DH>
+__global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArgs a) {
+  constexpr int CPR = DH / 8;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)a.B * a.S * CPR) return;
+  const int ch = (int)(id % CPR);
+  const int s = (int)((id / CPR) % a.S);
+  const int b = (int)(id / ((long long)a.S * CPR));
+  const int c0 = ch * 8, half = a.rot >> 1;
+  const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
+  const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
+  uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
+  const long long crow = ((long long)b * a.lmax + a.start + s) * a.Hkv * DH + c0;
+  uint16_t* kd = a.k_cache + crow;
+  uint16_t* vd = a.v_cache + crow;
+
+  if (c0 >= a.rot) {
+    for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = *reinterpret_cast<const u32x4*>(row + hd * DH + c0);
+    for (int hd = 0; hd < a.Hkv; ++hd) *reinterpret_cast<u32x4*>(kd + hd * DH) = *reinterpret_cast<const u32x4*>(ks + hd * DH + c0);
+  } else {
+    const float* fr = a.freqs + ((long long)s * a.B + b) * a.rot + c0;
+    const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
+    const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+    float cs[8], sn[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
+    const bool first = c0 + half < a.rot;
+    const int pc = first ? c0 + half : c0 - half;
+    const float sign = first ? -1.f : 1.f;
+    for (int hd = 0; hd < a.H + a.Hkv; ++hd) {  // heads H .. H + Hkv - 1 of the row are the K heads
+      float x[8], y[8], res[8];
+      unpack8<DT>(*reinterpret_cast<const u32x4*>(row + hd * DH + c0), x);
+      unpack8<DT>(*reinterpret_cast<const u32x4*>(row + hd * DH + pc), y);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) res[e] = __builtin_fmaf(x[e], cs[e], (sign * y[e]) * sn[e]);
+      if (hd < a.H) *reinterpret_cast<u32x4*>(qd + hd * DH) = pack8<DT>(res);
+      else *reinterpret_cast<u32x4*>(kd + (hd - a.H) * DH) = pack8<DT>(res);
+    }
+  }
+  const uint16_t* vs = row + (long long)(a.H + a.Hkv) * DH + c0;
+  for (int hd = 0; hd < a.Hkv; ++hd) *reinterpret_cast<u32x4*>(vd + hd * DH) = *reinterpret_cast<const u32x4*>(vs + hd * DH);
+}
+
 }  // namespace
 
 int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv, int Dh,
@@ -125,6 +172,23 @@ int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void*
   } else {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv,
+                                 int Dh, int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  const int nb = (int)((n + 255) / 256);
+  RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
+                  start_pos, nb};
+  const dim3 grid((unsigned)nb);
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<F16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<F16, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
   }
   return 0;
 }

@@ -1,0 +1,388 @@
+// Split-KV attention (flash-decoding) for flash_attn_func's natural layout: a few query rows over a long history.
+//
+//   O = softmax(scale * Q K^T + mask) V        q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh], out [B, Sq, H, Dh]
+//   awq_attn_prefill's contract (bottom-right aligned causal mask, query head h reads KV head h / G, G = H / Hkv), restricted to
+//   R = Sq * G <= 128 packed rows per KV head.  This is the whole decode phase of tinychat's long-context path (fused_attn.py:505-546):
+//   at Sq = 1 the one-pass kernel runs B * H blocks, each walking all of K / V for one live MFMA row, the G heads of a group each
+//   fetching the same keys again.
+//
+// Two launches, no atomics:
+//   1. attn_splitkv_kernel, B * Hkv * splits blocks.  One block = one (batch, KV head, split): keys [split * chunk, min(Sk, .. + chunk)),
+//      chunk % 64 == 0, walked in the prefill kernel's 64-key tiles (same LDS images and swizzles k_off / v_off, same double buffering
+//      through registers, same MFMA operand layouts, restated here so that the prefill unit stays untouched).  The MFMA query rows
+//      are the R rows of the KV head's group, packed row = i * G + g (query position i, head g of the group): K and V of the chunk are
+//      fetched from HBM ONCE for the whole group.  Wave w owns packed rows 32 w .. 32 w + 31.  Rounding points are the prefill
+//      kernel's: fp32 scores and accumulation on v_mfma_f32_32x32x16, every weight rounded to T once, that rounded value feeding both
+//      P.V and the row sum.  The block writes, per (row, split), an UNNORMALISED fp32 partial: O [Dh], the running max m (of the
+//      scaled base-2 logits) and the row sum l.  A row that attends nothing of the chunk (causal: the last chunk is shorter than
+//      Sq - 1 - i keys) writes O = 0, l = 0, m = -inf.  Rows >= Sk of k / v are never read: address clamped to Sk - 1, score masked.
+//   2. attn_splitkv_combine_kernel: one thread = 8 columns of one row.  M = max_s m_s; O = sum_s 2^(m_s - M) O_s and
+//      L = sum_s 2^(m_s - M) l_s in ascending split order (fmaf, fp32); out = T(O * (1 / L)): one division, one rounding.  A partial
+//      with m_s = -inf is skipped: it contributes exactly nothing and no Inf - Inf is ever formed.  Split 0 holds key 0, which every
+//      row attends, so M is finite and L > 0.
+//
+// Workspace (fp32, 16-byte aligned), n = B * Hkv * R * splits = B * H * Sq * splits entries, entry e = ((b * Hkv + kvh) * R + row) * splits + s:
+//      O [n][Dh] | m [n] | l [n]                                   = n * (Dh + 2) * 4 bytes
+//
+// Work split inside a block -- the form kept: row split, every wave staging.  All 4 waves of a block load and stage every K / V
+// tile; only the ceil(R / 32) waves that own rows compute.  At R <= 32 three waves are then load helpers.  The alternative (the waves
+// split the chunk's key tiles, partials merged in LDS in wave order) keeps four tiles per block in LDS at once -- four times the LDS
+// per block, one resident block per CU at Dh = 128 -- for the same bytes in flight per CU, and the compute it would spread (32 MFMAs and
+// one 64-key softmax per tile on one wave) is several times shorter than the HBM time of a tile at one or two blocks per CU.  This is
+// reasoning from the code, not an A/B: the key-split form was not built.  tools/splitkv_attn_bench.py times the kernel as a whole
+// (README.md: 0.46 of 8 TB/s at 131072 keys, 16x the one-pass kernel at 32768 keys, Llama-3-8B, one token).
+#include "awq_device.hpp"
+#include "awq_kernels.hpp"
+
+#include <math.h>
+#include <string.h>
+
+namespace awq {
+namespace {
+
+constexpr int kKV = 64;        // keys per tile
+constexpr int kMfmaRows = 32;  // packed rows per wave
+constexpr int kNW = 4;         // waves per block
+constexpr int kMaxRows = kNW * kMfmaRows;
+constexpr int kCUs = 256;      // the MI355X; a constant because the plan is a host-only function that CPU tests pin
+constexpr int kMinKeys = 2048;   // below this the one-pass kernel serves (a walk of <= 32 tiles is not worth a second launch)
+constexpr int kMinChunk = 1024;  // keys per split of the plan, at least
+int g_force_chunk = 0;         // knob attn_splitkv_chunk (awq_tune_set): a multiple of 64 forces the chunk, 0 = the plan
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short i16x4 __attribute__((ext_vector_type(4)));
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+
+struct SplitArgs {
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  uint16_t* out;
+  float* ws_o;
+  float* ws_m;
+  float* ws_l;
+  long long q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;  // elements
+  int B, Sq, Sk, H, Hkv, G, R, splits, chunk, causal;
+  float scale_log2e;
+};
+
+// LDS images of awq_attn_prefill_cdna4.hip, restated: rows of DH elements, the 16-byte chunks of a row permuted by an XOR of the row.
+//   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
+//   V (transposed reads, a 32-lane half = 4 consecutive rows x 64 bytes): the 4 rows land on 4 different 64-byte quarters of the banks
+template <int DH>
+__device__ __forceinline__ int k_off(int row, int ch) {
+  return row * DH + ((ch ^ (DH == 128 ? (row & 15) : ((row >> 1) & 7))) << 3);
+}
+template <int DH>
+__device__ __forceinline__ int v_off(int row, int ch) {
+  return row * DH + ((ch ^ (DH == 128 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (((row >> 1) & 1) << 2))) << 3);
+}
+
+template <typename DT, int DH>
+__global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
+  using vec8 = typename DT::vec8;
+  using elem = typename DT::elem;
+  constexpr int NT = kNW * 64;
+  constexpr int CPR = DH / 8;            // 16-byte chunks per row
+  constexpr int LOADS = kKV * CPR / NT;  // chunks of one K (or V) tile per thread
+  constexpr int KS = DH / 16;            // k-steps of Q K^T
+  constexpr int DB = DH / 32;            // 32-column blocks of O
+  static_assert(LOADS >= 1 && LOADS * NT == kKV * CPR, "tile does not divide over the block");
+  __shared__ __attribute__((aligned(16))) uint16_t k_s[2][kKV * DH];
+  __shared__ __attribute__((aligned(16))) uint16_t v_s[2][kKV * DH];
+
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int bi = blockIdx.x;
+  const int split = bi % a.splits;
+  bi /= a.splits;
+  const int kvh = bi % a.Hkv;
+  const int b = bi / a.Hkv;
+  const int shift = a.Sk - a.Sq;
+  const int k_begin = split * a.chunk;                  // < Sk: (splits - 1) * chunk < Sk
+  const int k_end = min(a.Sk, k_begin + a.chunk);       // keys [k_begin, k_end) are this block's
+  const int nt = (k_end - k_begin + kKV - 1) / kKV;
+
+  const int wr0 = wave * kMfmaRows;                     // first packed row of the wave
+  const bool wave_on = wr0 < a.R;                       // (a wave without rows still stages K / V and meets the barriers)
+  const int pr = min(wr0 + r, a.R - 1);                 // rows >= R compute row R - 1 again and are not stored
+  const int qi = pr / a.G, h = kvh * a.G + pr % a.G;    // packed row = i * G + g
+  const int lim = a.causal ? qi + shift : a.Sk - 1;                                   // last key this lane's row attends
+  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, a.R - 1) / a.G + shift : a.Sk - 1;  // .. any row of the wave
+  const int wave_min = a.causal ? wr0 / a.G + shift : a.Sk - 1;                       // every row of the wave attends keys <= this
+
+  // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
+  vec8 qf[KS];
+  {
+    const uint16_t* qp = a.q + (long long)b * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
+  }
+
+  const uint16_t* kb = a.k + (long long)b * a.k_bs + (long long)kvh * DH;
+  const uint16_t* vb = a.v + (long long)b * a.v_bs + (long long)kvh * DH;
+  u32x4 kr[LOADS], vr[LOADS];
+  auto stage_load = [&](int t0) {
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
+      const long long g = min(t0 + row, a.Sk - 1);  // no row >= Sk is read
+      kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
+      vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+    }
+  };
+  auto stage_write = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
+      *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
+      *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+    }
+  };
+
+  f32x16 o[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;  // l: this lane's 32 keys of every tile; the two halves are added at the end
+
+  // transposed-read addressing: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p .. 4 p + 3 of the group's 4 x 16 block
+  const int tr_q = (lane & 15) >> 2, tr_p = lane & 3, tr_g = (lane >> 4) & 1;
+
+  stage_load(k_begin);
+  stage_write(0);
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));  // Q has arrived before the loop (no vmcnt(0) behind the loop's loads)
+  __syncthreads();
+
+  for (int t = 0; t < nt; ++t) {
+    const int buf = t & 1, t0 = k_begin + t * kKV;
+    const bool more = t + 1 < nt;
+    if (more) stage_load(t0 + kKV);
+
+    if (wave_on && t0 <= wave_max) {  // wave-uniform: every lane of the wave takes part in the transposed reads
+      // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, packed row r ----
+      f32x16 s[2];
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[kb2][e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const vec8 ka = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(&k_s[buf][k_off<DH>(32 * kb2 + r, 2 * ks + hh)]));
+          s[kb2] = DT::mfma32(ka, qf[ks], s[kb2]);
+        }
+      }
+      // ---- online softmax (base 2: the logits are scaled by scale * log2 e) ----
+      const bool need_mask = t0 + kKV - 1 > wave_min;  // (wave_min <= Sk - 1: the end of K is covered too)
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float x = s[kb2][e] * a.scale_log2e;
+          if (need_mask) {
+            const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+            x = key <= lim ? x : -INFINITY;
+          }
+          s[kb2][e] = x;
+          mx = fmaxf(mx, x);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);
+      // a row may attend nothing of the chunk so far (m_new = -inf): subtract 0 instead, every weight is then exp2(-inf) = 0 and
+      // alpha = exp2(-inf) = 0 multiplies an O and an l that are still 0 -- no Inf - Inf.  With m_new finite this is the prefill kernel's code
+      const float m_sub = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_sub);
+      m_run = m_new;
+      vec8 pf[4];
+      float sum = 0.f;
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const elem pt = (elem)__builtin_amdgcn_exp2f(s[kb2][e] - m_sub);  // the ONE rounding of a weight
+          pf[2 * kb2 + (e >> 3)][e & 7] = pt;
+          sum += (float)pt;
+        }
+      l_run = l_run * alpha + sum;
+#pragma unroll
+      for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
+      // ---- O^T += V^T P^T: k-step s2 = keys 16 s2 + 8 (j >> 2) + 4 hh + (j & 3), j = operand element ----
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+          const int row = 16 * s2 + 4 * hh + tr_q, ch = 4 * db + 2 * tr_g + (tr_p >> 1);
+          const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) i16x4*)(&v_s[buf][v_off<DH>(row, ch) + 4 * (tr_p & 1)]));
+          const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (__attribute__((address_space(3))) i16x4*)(&v_s[buf][v_off<DH>(row + 8, ch) + 4 * (tr_p & 1)]));
+          const i16x8 va = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          o[db] = DT::mfma32(__builtin_bit_cast(vec8, va), pf[s2], o[db]);
+        }
+      }
+    }
+
+    if (more) stage_write(buf ^ 1);  // the other buffer: its readers finished before the barrier that ended tile t - 1
+    __syncthreads();
+  }
+
+  // ---- the unnormalised partial; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  if (wr0 + r < a.R) {
+    const long long e = (((long long)b * a.Hkv + kvh) * a.R + pr) * a.splits + split;
+    float* op = a.ws_o + e * DH + 4 * hh;
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+        *reinterpret_cast<f32x4*>(op + 32 * db + 8 * g4) = f32x4{o[db][4 * g4], o[db][4 * g4 + 1], o[db][4 * g4 + 2], o[db][4 * g4 + 3]};
+    if (hh == 0) {
+      a.ws_m[e] = m_run;
+      a.ws_l[e] = l_tot;
+    }
+  }
+}
+
+template <typename DT, int DH>
+__global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) {
+  constexpr int CPR = DH / 8;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)a.B * a.Hkv * a.R * CPR) return;
+  const int ch = (int)(id % CPR);
+  const long long row = id / CPR;  // (b * Hkv + kvh) * R + packed row
+  const int pr = (int)(row % a.R);
+  const long long bk = row / a.R;
+  const int kvh = (int)(bk % a.Hkv);
+  const long long b = bk / a.Hkv;
+  const float* pm = a.ws_m + row * a.splits;
+  const float* pl = a.ws_l + row * a.splits;
+  const float* po = a.ws_o + row * a.splits * DH + ch * 8;
+  float M = -INFINITY;
+  for (int s = 0; s < a.splits; ++s) M = fmaxf(M, pm[s]);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float L = 0.f;
+  for (int s = 0; s < a.splits; ++s) {
+    const float m = pm[s];
+    if (m == -INFINITY) continue;  // nothing attended in this split: contributes exactly nothing
+    const float w = __builtin_amdgcn_exp2f(m - M);
+    const f32x4 o0 = *reinterpret_cast<const f32x4*>(po + (long long)s * DH), o1 = *reinterpret_cast<const f32x4*>(po + (long long)s * DH + 4);
+    L = __builtin_fmaf(w, pl[s], L);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[e] = __builtin_fmaf(w, o0[e], acc[e]);
+      acc[4 + e] = __builtin_fmaf(w, o1[e], acc[4 + e]);
+    }
+  }
+  const float inv = 1.0f / L;
+  u32 ws[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(acc[2 * e] * inv) | ((u32)DT::from_float(acc[2 * e + 1] * inv) << 16);
+  const int qi = pr / a.G, h = kvh * a.G + pr % a.G;
+  *reinterpret_cast<u32x4*>(a.out + ((b * a.Sq + qi) * a.H + h) * DH + ch * 8) = u32x4{ws[0], ws[1], ws[2], ws[3]};
+}
+
+}  // namespace
+
+// Host plan.  *splits == 1: not taken, the one-pass kernel serves (then *chunk = Sk rounded up to 64).  Taken only for Sk >= 2048,
+// Sq * G <= 128, Dh 64 / 128 and a one-pass launch of fewer than kCUs blocks.  Beyond that: aim at two blocks per CU (the LDS of two
+// Dh = 128 blocks fits a CU), B * Hkv * splits >= 2 kCUs, with chunks of at least 1024 keys; chunk is the largest multiple of 64 that still
+// yields that many splits.  Measured on the MI355X for B * Hkv = 8 (tools/splitkv_attn_bench.py --sweep-chunk, Llama-3-8B, bf16, Sq = 1,
+// profiles/splitkv_attn_sweep.json): among chunks >= 1024 the rule's choice is the fastest or within noise of it -- 1024 at 32768 keys
+// (52.6 us; 2048: 71.2), 2048 at 131072 (142 us; 4096: 142, 1024: 205).  Below 32768 keys chunks of 256 / 512 are faster still; the
+// 1024-key floor is a fixed condition of the plan.  Other B * Hkv are not swept.  Depends on host arguments only (and on the knob).
+int attn_splitkv_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* splits, int* chunk) {
+  *splits = 1;
+  *chunk = (int)((((long long)seqlen_k + kKV - 1) / kKV) * kKV);
+  const long long rows = (long long)seqlen_q * (nheads / nheads_kv);
+  if (rows > kMaxRows || (head_dim != 64 && head_dim != 128)) return 0;
+  int c = 0;
+  if (g_force_chunk) {
+    c = g_force_chunk;
+  } else {
+    if (seqlen_k < kMinKeys) return 0;
+    int q_tile = 0, one_pass_blocks = 0;
+    attn_prefill_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, &q_tile, &one_pass_blocks);
+    if (one_pass_blocks >= kCUs) return 0;
+    const long long groups = (long long)batch * nheads_kv;  // < kCUs here
+    const int want = (int)((2 * kCUs + groups - 1) / groups);
+    c = seqlen_k / want / kKV * kKV;
+    if (c < kMinChunk) c = kMinChunk;
+  }
+  const int n = (int)(((long long)seqlen_k + c - 1) / c);
+  if (n <= 1) return 0;
+  *splits = n;
+  *chunk = c;
+  return 0;
+}
+
+size_t attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal) {
+  int splits = 1, chunk = 0;
+  attn_splitkv_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, &splits, &chunk);
+  if (splits <= 1) return 0;
+  return (size_t)batch * nheads * seqlen_q * splits * (head_dim + 2) * sizeof(float);
+}
+
+int attn_splitkv_tune_set(const char* key, int value) {
+  if (strcmp(key, "attn_splitkv_chunk") != 0 || value < 0 || (value % kKV) != 0) return -1;
+  g_force_chunk = value;
+  return 0;
+}
+
+// The caller has validated the arguments, found splits > 1 in the plan and a workspace of attn_splitkv_workspace_bytes.
+int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
+                        int splits, int chunk, void* workspace, hipStream_t st) {
+  SplitArgs a;
+  a.q = (const uint16_t*)q;
+  a.k = (const uint16_t*)k;
+  a.v = (const uint16_t*)v;
+  a.out = (uint16_t*)out;
+  a.q_bs = q_bs;
+  a.q_rs = q_rs;
+  a.k_bs = k_bs;
+  a.k_rs = k_rs;
+  a.v_bs = v_bs;
+  a.v_rs = v_rs;
+  a.B = B;
+  a.Sq = Sq;
+  a.Sk = Sk;
+  a.H = H;
+  a.Hkv = Hkv;
+  a.G = H / Hkv;
+  a.R = Sq * a.G;
+  a.splits = splits;
+  a.chunk = chunk;
+  a.causal = causal ? 1 : 0;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  const long long n = (long long)B * Hkv * a.R * splits;
+  a.ws_o = (float*)workspace;
+  a.ws_m = a.ws_o + n * Dh;
+  a.ws_l = a.ws_m + n;
+  const dim3 grid((unsigned)((long long)B * Hkv * splits));
+  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
+  if (dtype == 0) {
+    if (Dh == 128) {
+      hipLaunchKernelGGL((attn_splitkv_kernel<F16, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 128>), cgrid, dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_splitkv_kernel<F16, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 64>), cgrid, dim3(256), 0, st, a);
+    }
+  } else {
+    if (Dh == 128) {
+      hipLaunchKernelGGL((attn_splitkv_kernel<BF16, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 128>), cgrid, dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_splitkv_kernel<BF16, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 64>), cgrid, dim3(256), 0, st, a);
+    }
+  }
+  return 0;
+}
+
+}  // namespace awq

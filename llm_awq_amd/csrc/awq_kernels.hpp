@@ -184,6 +184,15 @@ int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* 
 // prompt-side chunk preparation (awq_attn_chunk_cdna4.hip): rope of q and k, K / V stored into the FT caches, one launch
 int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv, int Dh,
                          int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st);
+int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv,
+                                 int Dh, int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st);
+// split-KV attention for few query rows over a long natural-layout history (awq_attn_splitkv_cdna4.hip); arguments validated by the caller
+int attn_splitkv_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* splits, int* chunk);
+size_t attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal);
+int attn_splitkv_tune_set(const char* key, int value);  // "attn_splitkv_chunk": force the chunk, a multiple of 64 (0 = plan)
+int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
+                        int splits, int chunk, void* workspace, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

@@ -767,6 +767,85 @@ torch::Tensor attn_prefill_ftcache(const torch::Tensor q, const torch::Tensor k_
   return out;
 }
 
+// attn_splitkv(q, k, v, softmax_scale, causal) -> out: attn_prefill's arguments and result on the split-KV kernel pair where
+// awq_attn_splitkv_plan splits (few query rows over a long history: csrc/awq_attn_splitkv_cdna4.hip), on the one-pass kernel otherwise
+// (then bit-identical to attn_prefill).  The fp32 partials live in a buffer of torch's caching allocator: capturable.
+torch::Tensor attn_splitkv(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, double softmax_scale, bool causal) {
+  TORCH_CHECK(q.scalar_type() != at::kFloat, "attn_splitkv: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), "attn_splitkv: q, k and v must live on the same GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "attn_splitkv: float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "attn_splitkv: q, k and v must share one dtype");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "attn_splitkv: q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh]");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), sk = k.size(1), nheads_kv = k.size(2);
+  TORCH_CHECK(headdim == 64 || headdim == 128 || (headdim == 72 && !causal), "attn_splitkv: head dim ", headdim, causal ? " (causal)" : "",
+              " is not supported (supported head dims: 64, 128, and 72 without a causal mask)");
+  TORCH_CHECK(k.size(0) == batch && k.size(3) == headdim && v.sizes() == k.sizes(), "attn_splitkv: k / v must be [B, Sk, Hkv, ", headdim, "]");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && sk >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0,
+              "attn_splitkv: empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(!causal || sq <= sk, "attn_splitkv: causal attention needs seqlen_q <= seqlen_k, got ", sq, " > ", sk);
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == headdim,
+                "attn_splitkv: the heads of q / k / v must be contiguous (stride(3) == 1, stride(2) == Dh); supported head dims: 64, 128, 72 (non-causal)");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_splitkv_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)sk, causal ? 1 : 0);
+  at::Tensor ws;
+  if (wsb) ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  raise_on(awq_attn_splitkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)batch, (int)sq, (int)sk, (int)nheads, (int)nheads_kv,
+                            (int)headdim, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale,
+                            causal ? 1 : 0, dtype_code(q), wsb ? ws.data_ptr() : nullptr, wsb,
+                            (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
+// (splits, chunk) of awq_attn_splitkv_plan; splits == 1: the one-pass kernel serves.  Host only.
+std::tuple<int64_t, int64_t> attn_splitkv_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t seqlen_q,
+                                               int64_t seqlen_k, bool causal) {
+  int splits = 1, chunk = 0;
+  raise_on(awq_attn_splitkv_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)seqlen_q, (int)seqlen_k, causal ? 1 : 0, &splits,
+                                 &chunk));
+  return {splits, chunk};
+}
+
+// rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos, nheads, nheads_kv) -> q_out: rope_kv_store for the natural-layout caches
+// k_cache / v_cache [Bc, Lmax, Hkv, Dh] of tinychat's long-context path (fused_attn.py:527-537), one launch (csrc/awq_attn_chunk_cdna4.hip).
+torch::Tensor rope_kv_store_natural(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
+                                    int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, "rope_kv_store_natural: float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), "rope_kv_store_natural: tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, "rope_kv_store_natural: float16 / bfloat16 only, got ",
+              qkv.scalar_type());
+  TORCH_CHECK(freqs.scalar_type() == at::kFloat, "rope_kv_store_natural: freqs must be float32");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device(), "rope_kv_store_natural: the caches must live on the GPU of the input");
+    TORCH_CHECK(t->scalar_type() == qkv.scalar_type(), "rope_kv_store_natural: the caches must have the dtype of the input");
+    TORCH_CHECK(t->dim() == 4 && t->is_contiguous(), "rope_kv_store_natural: contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] are expected");
+  }
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "rope_kv_store_natural: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
+  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rot = freqs.size(-1);
+  TORCH_CHECK(headdim == 64 || headdim == 128, "rope_kv_store_natural: head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, "rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim,
+              "rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
+  TORCH_CHECK(batch <= cache_batch, "rope_kv_store_natural: batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= lmax, "rope_kv_store_natural: positions ", start_pos, " .. ", start_pos + seqlen,
+              " do not fit the cache of ", lmax);
+  TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot,
+              "rope_kv_store_natural: freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor x = qkv;
+  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
+  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  raise_on(awq_rope_kv_store_natural(x.data_ptr(), fr.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), (int)batch,
+                                     (int)cache_batch, (int)seqlen, (int)nheads, (int)nheads_kv, (int)headdim, (int)rot, (int)lmax,
+                                     (int)start_pos, x.stride(0), x.stride(1), dtype_code(x),
+                                     (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return q_out;
+}
+
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
 // (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
 // kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
@@ -1060,6 +1139,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"));
   m.def("attn_prefill_ftcache", &attn_prefill_ftcache, "Prefill attention with K / V read from the FT caches at positions kv_start .. kv_start + seqlen_k",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_start"), py::arg("seqlen_k"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_splitkv", &attn_splitkv, "attn_prefill on the split-KV kernel pair where attn_splitkv_plan splits (few query rows, long history)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_splitkv_plan", &attn_splitkv_plan, "(splits, chunk) of the split-KV attention plan; splits == 1: the one-pass kernel serves",
+        py::arg("batch"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("seqlen_q"), py::arg("seqlen_k"), py::arg("causal"));
+  m.def("rope_kv_store_natural", &rope_kv_store_natural,
+        "Rotate q and k of a fused qkv chunk, store k / v into natural-layout caches [Bc, Lmax, Hkv, Dh]; returns q [B, S, H, Dh]", py::arg("qkv"),
+        py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

@@ -3,7 +3,8 @@
 tinychat imports `from flash_attn import flash_attn_func` at module level (tinychat/models/llama.py:21,
 tinychat/modules/fused_attn.py:17) and sends every prompt through `flash_attn_func(q, k, v, causal=True)` (llama.py:218,
 fused_attn.py:477,539).  The flash-attn package is CUDA-only; `llm_awq_amd.install_as_flash_attn()` puts this module into
-`sys.modules["flash_attn"]` so that those imports resolve to the gfx950 prefill kernel of the engine (`attn_prefill`).
+`sys.modules["flash_attn"]` so that those imports resolve to the gfx950 prefill kernel of the engine (`attn_prefill`) -- and, for a few
+query rows over at least 2048 keys (every decode step of tinychat's long-context path), to the split-KV kernels (`attn_splitkv`).
 
 The vision towers import more (tinychat/modules/fused_siglipdecoder.py:15 `from flash_attn import flash_attn_func` at head dim 72;
 tinychat/models/internvl/internvit.py:18-20 `from flash_attn.bert_padding import pad_input, unpad_input` and
@@ -46,7 +47,23 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, **
     from . import load_engine
 
     scale = float(q.shape[-1]) ** -0.5 if softmax_scale is None else float(softmax_scale)
-    return load_engine().attn_prefill(q, k, v, scale, bool(causal))
+    eng = load_engine()
+    # few query rows over a long history (the decode phase of tinychat's long_forward): the split-KV kernels where their plan splits
+    if _plan_splits(eng, q, k, causal):
+        return eng.attn_splitkv(q, k, v, scale, bool(causal))
+    return eng.attn_prefill(q, k, v, scale, bool(causal))
+
+
+def _plan_splits(eng, q, k, causal) -> bool:
+    """Whether attn_splitkv_plan splits this call: never below 2048 keys (unless the test knob attn_splitkv_chunk forces a chunk).
+    Shapes the plan would refuse go to attn_prefill, which names what is wrong with them."""
+    if getattr(q, "dim", lambda: 0)() != 4 or getattr(k, "dim", lambda: 0)() != 4:
+        return False
+    B, Sq, H, Dh = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    if min(B, Sq, Sk, Hkv) < 1 or Dh not in (64, 128) or H % Hkv or (causal and Sq > Sk):
+        return False
+    return eng.attn_splitkv_plan(B, H, Hkv, Dh, Sq, Sk, bool(causal))[0] > 1
 
 
 def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, **kw):

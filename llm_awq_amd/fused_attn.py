@@ -15,7 +15,10 @@ Both give the bits of the reference's composition on this package's kernels (rop
 gathered copies).  One token (`seqlen == 1`) goes to `single_query_attention` exactly as the reference calls it.
 
 `QuantLlamaAttentionFusedFlash` is an alias: its `short_forward` is this data flow.  The reference's long-context variant (natural-layout
-caches and `long_forward` for kv_max_seq_len > 8192) is out of scope here; those callers keep `flash_attn_func` on their own caches.
+caches [B, L, Hkv, Dh] and `long_forward` for kv_max_seq_len > 8192, fused_attn.py:389-415, 505-546) is `kv_layout="natural"`: every call,
+one token included, is `rope_kv_store_natural` (q and k rotated, k and v stored, one launch) followed by
+`flash_attn_func(q, cache_k[:, :pos], cache_v[:, :pos], causal=True)`, which takes the split-KV kernels (csrc/awq_attn_splitkv_cdna4.hip)
+once the history reaches 2048 keys and few query rows ask -- the decode phase -- and the one-pass prefill kernel otherwise.
 """
 from __future__ import annotations
 
@@ -28,10 +31,15 @@ from . import load_engine
 class QuantLlamaAttentionFused(nn.Module):
     """Same constructor, attributes and forward as the reference class (fused_attn.py:169-324); `max_batch_size` is the module-level
     global there (:21) and a keyword here.  `cache_k` [max_batch_size, Hkv, Dh/8, kv_max_seq_len, 8] and `cache_v`
-    [max_batch_size, Hkv, kv_max_seq_len, Dh] are the FT caches the decode kernel reads and writes."""
+    [max_batch_size, Hkv, kv_max_seq_len, Dh] are the FT caches the decode kernel reads and writes.  `kv_layout="natural"` is the
+    reference's long-context mode (QuantLlamaAttentionFusedFlash with kv_max_seq_len > 8192): both caches are
+    [max_batch_size, kv_max_seq_len, Hkv, Dh] and forward is long_forward's data flow for every seqlen."""
 
-    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1):
+    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft"):
         super().__init__()
+        if kv_layout not in ("ft", "natural"):
+            raise ValueError(f"QuantLlamaAttentionFused: kv_layout {kv_layout!r} is not supported (supported: 'ft', 'natural')")
+        self.kv_layout = kv_layout
         self.args = args
         self.n_local_heads = args.num_attention_heads
         self.hidden_size = args.hidden_size
@@ -52,6 +60,11 @@ class QuantLlamaAttentionFused(nn.Module):
         self.o_proj = o_proj
         self.kv_max_seq_len = kv_max_seq_len
         self.max_batch_size = max_batch_size
+        if kv_layout == "natural":  # fused_attn.py:389-415
+            shape = (max_batch_size, kv_max_seq_len, self.num_key_value_heads, self.head_dim)
+            self.cache_v = torch.zeros(shape, dtype=torch.float16, device=dev)
+            self.cache_k = torch.zeros(shape, dtype=torch.float16, device=dev)
+            return
         # following the FasterTransformer definition (fused_attn.py:196-224); 8 = the fp16 / bf16 elements of one 16-byte chunk
         self.cache_v = torch.zeros((max_batch_size, self.num_key_value_heads, kv_max_seq_len, self.head_dim), dtype=torch.float16, device=dev)
         self.cache_k = torch.zeros((max_batch_size, self.num_key_value_heads, self.head_dim // 8, kv_max_seq_len, 8), dtype=torch.float16,
@@ -66,6 +79,13 @@ class QuantLlamaAttentionFused(nn.Module):
         if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:  # the reference's .to(xq) (:256-257)
             self.cache_k = self.cache_k.to(xqkv)
             self.cache_v = self.cache_v.to(xqkv)
+        if self.kv_layout == "natural":  # long_forward (fused_attn.py:505-546); `chunk_prefilling` changes nothing there: the history is attended
+            from .flash_attn_compat import flash_attn_func
+
+            xq = eng.rope_kv_store_natural(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
+                                           self.num_key_value_heads)
+            output = flash_attn_func(xq, self.cache_k[:bsz, :start_pos + seqlen], self.cache_v[:bsz, :start_pos + seqlen], causal=True)
+            return self.o_proj(output.view(bsz, seqlen, -1))
         if seqlen > 1:
             xq = eng.rope_kv_store(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
                                    self.num_key_value_heads)
@@ -115,17 +135,17 @@ def fuse_qkv(q_proj, k_proj, v_proj):
     return qkv
 
 
-def make_quant_attn(model, dev, max_batch_size=1):
+def make_quant_attn(model, dev, max_batch_size=1, kv_layout="ft"):
     """tinychat/modules/fused_attn.py:549-634: replace every module that carries q_proj, k_proj, v_proj, o_proj, `args` and
     `kv_max_seq_len` (the reference's LlamaAttentionFused / Qwen2AttentionFused) by a QuantLlamaAttentionFused over one fused
-    qkv WQLinear, then move the model to `dev`."""
+    qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode."""
     want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
     for name, m in list(model.named_modules()):
         if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
             continue
         qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
         attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
-                                        max_batch_size=max_batch_size)
+                                        max_batch_size=max_batch_size, kv_layout=kv_layout)
         if "." in name:
             parent_name, child_name = name.rsplit(".", 1)
             parent = model.get_submodule(parent_name)

@@ -544,22 +544,61 @@ def attn_prefill_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, se
     return r.value, n.value
 
 
-def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
-    """C-ABI awq_attn_prefill: softmax(scale * q k^T + mask) v with flash_attn_func's layout and masking.
-    q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (batch and row strides of their own, heads contiguous -- the q / k / v slices of one
-    fused qkv tensor pass without a copy); causal is bottom-right aligned (row i attends keys j <= i + Sk - Sq).  Returns
-    [B, Sq, H, Dh] contiguous.  Dh 64 or 128 (72 too when not causal), float16 / bfloat16."""
+def _check_qkv(who, q, k, v):
     for t in (q, k, v):
         if not t.is_cuda:
             raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
         if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
             raise ValueError("q / k / v must be [B, S, heads, Dh] with contiguous heads")
     if k.device != q.device or v.device != q.device:
-        raise ValueError("flash_attn_func: q, k and v must live on the same GPU")
+        raise ValueError(f"{who}: q, k and v must live on the same GPU")
     if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3] or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError("flash_attn_func: q [B, Sq, H, Dh] and k / v [B, Sk, Hkv, Dh] of one dtype are expected")
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k / v [B, Sk, Hkv, Dh] of one dtype are expected")
+
+
+def attn_splitkv_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, seqlen_q: int, seqlen_k: int, causal: bool = True):
+    """Host-side awq_attn_splitkv_plan: (splits, chunk) of the split-KV attention launch (no GPU needed).  splits == 1: the one-pass
+    prefill kernel serves."""
+    import ctypes
+
+    s, c = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_splitkv_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, int(bool(causal)),
+                                                  ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
+def attn_splitkv(q, k, v, softmax_scale=None, causal: bool = False):
+    """C-ABI awq_attn_splitkv: flash_attn_func's contract (see below) for few query rows over a long history.  Where attn_splitkv_plan
+    splits, the G query heads of a KV group share one fetch of K / V, the keys are cut over blocks and fp32 partials are combined by a
+    second launch; otherwise this is the one-pass launch, bit for bit."""
+    _check_qkv("attn_splitkv", q, k, v)
     B, Sq, H, Dh = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    L = _capi.lib()
+    wsb = L.awq_attn_splitkv_workspace_bytes(B, H, Hkv, Dh, Sq, Sk, int(bool(causal)))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device) if wsb else None
+    with torch.cuda.device(q.device):
+        _capi.check(L.awq_attn_splitkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, Sk, H, Hkv, Dh,
+                                       q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                                       scale, int(bool(causal)), _dt(q), ws.data_ptr() if wsb else None, wsb, _stream(q)))
+    return out
+
+
+def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
+    """C-ABI awq_attn_prefill: softmax(scale * q k^T + mask) v with flash_attn_func's layout and masking.
+    q [B, Sq, H, Dh], k / v [B, Sk, Hkv, Dh] (batch and row strides of their own, heads contiguous -- the q / k / v slices of one
+    fused qkv tensor pass without a copy); causal is bottom-right aligned (row i attends keys j <= i + Sk - Sq).  Returns
+    [B, Sq, H, Dh] contiguous.  Dh 64 or 128 (72 too when not causal), float16 / bfloat16.  A call for which attn_splitkv_plan splits
+    (few query rows, Sk >= 2048) goes to attn_splitkv."""
+    _check_qkv("flash_attn_func", q, k, v)
+    B, Sq, H, Dh = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    # (the plan never splits below 2048 keys unless the knob attn_splitkv_chunk forces a chunk; shapes it refuses go on to awq_attn_prefill)
+    if min(B, Sq, Sk, Hkv) >= 1 and Dh in (64, 128) and H % Hkv == 0 and not (causal and Sq > Sk) and \
+            attn_splitkv_plan(B, H, Hkv, Dh, Sq, Sk, causal)[0] > 1:
+        return attn_splitkv(q, k, v, softmax_scale, causal)
     scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
     out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
     with torch.cuda.device(q.device):
@@ -605,6 +644,34 @@ def rope_kv_store(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nhe
         _capi.check(_capi.lib().awq_rope_kv_store(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                                   B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax, int(start_pos), qkv.stride(0),
                                                   qkv.stride(1), _dt(qkv), _stream(qkv)))
+    return q_out
+
+
+def rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nheads_kv: int):
+    """C-ABI awq_rope_kv_store_natural: rope_kv_store for natural-layout caches k_cache / v_cache [Bc, Lmax, Hkv, Dh] (tinychat's
+    long-context path).  Writes the rotated k into k_cache[b, start_pos + s] and v into v_cache[b, start_pos + s]; returns the rotated
+    q [B, S, H, Dh]."""
+    for t in (qkv, freqs, k_cache, v_cache):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if k_cache.device != qkv.device or v_cache.device != qkv.device or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
+        raise ValueError("rope_kv_store_natural: the caches must have the device and dtype of the input")
+    if v_cache.dim() != 4 or k_cache.shape != v_cache.shape or not v_cache.is_contiguous() or not k_cache.is_contiguous():
+        raise ValueError("rope_kv_store_natural: contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] of one shape are expected")
+    Bc, Lmax, Hkv, Dh = v_cache.shape
+    if freqs.device != qkv.device or freqs.dtype != torch.float32 or not freqs.is_contiguous():
+        raise ValueError("rope_kv_store_natural: contiguous float32 freqs on the GPU of qkv are expected")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
+        raise ValueError("rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
+    B, S = qkv.shape[0], qkv.shape[1]
+    rot = freqs.shape[-1]
+    if freqs.numel() < B * S * rot:
+        raise ValueError("rope_kv_store_natural: freqs holds fewer than B * S * rot_dim angles")
+    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _capi.check(_capi.lib().awq_rope_kv_store_natural(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+                                                          v_cache.data_ptr(), B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax,
+                                                          int(start_pos), qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv)))
     return q_out
 
 
