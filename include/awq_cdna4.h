@@ -426,6 +426,35 @@ int awq_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, 
                               int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos,
                               long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
 
+/* ---- FP8 KV cache on the natural layout (csrc/awq_kv8.hpp).  k_cache / v_cache [cache_batch, lmax, Hkv, Dh] hold one byte per element, an
+ *      OCP e4m3fn code (not fnuz); k_scale / v_scale [cache_batch, lmax, Hkv] hold one fp32 scale per (token, KV head).  A head row x of T is
+ *      quantised as s = max(max|x|, 2^-60) / 448 (IEEE division), code = e4m3fn_RNE(clamp(x / s, -448, 448)), and dequantised as
+ *      T(float(code) * s): one fp32 multiply, one rounding to T.  Head dims 64 and 128.
+ * awq_rope_kv_store_natural_fp8: awq_rope_kv_store_natural with quantised stores.  q_out holds awq_rope_kv_store_natural's bits; the K
+ *     row that is quantised is the rotated row after its rounding to T (the bits that entry would have stored), the V row is the qkv
+ *     tensor's.  Nothing outside positions [start_pos, start_pos + S) of rows b < B is written, in the caches or in the scales.  Same
+ *     error rules as awq_rope_kv_store_natural; the scale pointers must be 4-byte aligned (AWQ_ERR_ALIGN) and non-NULL.
+ * awq_attn_prefill_kv8 / awq_attn_splitkv_kv8: awq_attn_prefill / awq_attn_splitkv with k / v read from the codes and the scales.  k / v
+ *     strides count codes (bytes) and must be multiples of 16, the scale strides count floats (row stride >= Hkv); head dim 72 is
+ *     AWQ_ERR_SHAPE.  The kernels dequantise between their global load and their LDS write and are the T kernels behind it: the result
+ *     is bit-identical to awq_attn_prefill / awq_attn_splitkv on the dequantised T tensors.  Same plans (awq_attn_prefill_plan,
+ *     awq_attn_splitkv_plan), same workspace (awq_attn_splitkv_workspace_bytes), same knobs; where the plan does not split,
+ *     awq_attn_splitkv_kv8 IS awq_attn_prefill_kv8.  Every code but AWQ_ERR_LAUNCH is returned without a GPU call. */
+int awq_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
+int awq_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

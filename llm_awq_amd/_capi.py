@@ -96,6 +96,11 @@ SIGNATURES = {
                               ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_rope_kv_store_natural": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, _i,
                                        _vp]),
+    "awq_rope_kv_store_natural_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong,
+                                           ctypes.c_longlong, _i, _vp]),
+    "awq_attn_prefill_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 + [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_splitkv_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
+                             [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

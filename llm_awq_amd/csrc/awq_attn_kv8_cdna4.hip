@@ -1,0 +1,138 @@
+// rope_kv_store_natural on the FP8 KV cache (awq_kv8.hpp): rotate q and k of a fused qkv chunk, quantise k and v per (token, KV head) and
+// store codes and scales, one launch.
+//
+//   qkv [B, S, (H + 2 Hkv) Dh] (batch and row strides of its own)  ->  q_out   [B, S, H, Dh]                          rotated, T
+//                                                                      k_cache [b, start_pos + s, kvh, :]  e4m3 codes of the rotated k
+//                                                                      v_cache [b, start_pos + s, kvh, :]  e4m3 codes of v
+//                                                                      k_scale / v_scale [b, start_pos + s, kvh]       fp32
+//
+// The rotation is rope_kv_store_natural_kernel's (awq_attn_chunk_cdna4.hip), expression for expression: the angle of (b, s, ., c), c < rot,
+// is freqs[(s * B + b) * rot + c] (the reference's own flat index), sincosf once per column, fmaf(x, cos, (+-x_rot) * sin) rounded to T
+// once, columns >= rot copied.  q_out therefore holds that kernel's bits, and the K row that is quantised is, after its rounding to T, the
+// row that kernel would have stored.
+//
+// Mapping: that kernel's, one thread = 8 consecutive columns of one (b, s), the column chunk fastest, walking the H query heads, the Hkv
+// key heads and the Hkv value heads -- so a column's sincosf is still evaluated once.  The Dh / 8 threads of a (b, s) are consecutive
+// lanes of one wave (Dh / 8 = 8 or 16 divides 64 and the block size): for every K and V head they own the head row together, and its
+// max |x| is a butterfly of __shfl_xor over those lanes -- no LDS, no barrier; every lane ends up with the row's scale.  A lane stores the
+// 8 code bytes of its chunk (8 or 16 lanes write one contiguous 64- or 128-byte row); the lane of chunk 0 stores the scale, an ordinary
+// 4-byte store.  Nothing outside positions [start_pos, start_pos + S) of cache rows b < B is written, in the caches or in the scales.
+#include "awq_device.hpp"
+#include "awq_kernels.hpp"
+#include "awq_kv8.hpp"
+
+#include <math.h>
+
+namespace awq {
+namespace {
+
+struct RopeStoreFp8Args {
+  const uint16_t* qkv;
+  const float* freqs;
+  uint16_t* q_out;
+  uint8_t* k_cache;
+  uint8_t* v_cache;
+  float* k_scale;
+  float* v_scale;
+  long long bs, rs;  // qkv batch / row strides, elements
+  int B, S, H, Hkv, rot, lmax, start;
+};
+
+template <typename DT>
+__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
+  const u32 ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
+    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
+  }
+}
+template <typename DT>
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+  u32 ws[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
+  return u32x4{ws[0], ws[1], ws[2], ws[3]};
+}
+
+template <typename DT, int DH>
+__global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStoreFp8Args a) {
+  constexpr int CPR = DH / 8;
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)a.B * a.S * CPR) return;  // (the CPR lanes of a (b, s) leave or stay together)
+  const int ch = (int)(id % CPR);
+  const int s = (int)((id / CPR) % a.S);
+  const int b = (int)(id / ((long long)a.S * CPR));
+  const int c0 = ch * 8, half = a.rot >> 1;
+  const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
+  const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
+  const uint16_t* vs = row + (long long)(a.H + a.Hkv) * DH;
+  uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
+  const long long tok = ((long long)b * a.lmax + a.start + s) * a.Hkv;  // (token, head 0) of the caches and of the scales
+
+  // one head row of T (this lane's chunk w of it) -> codes and scale
+  auto quant_store = [&](const u32x4& w, uint8_t* cache, float* scale, int hd) {
+    float x[8];
+    unpack8<DT>(w, x);
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(x[e]));
+#pragma unroll
+    for (int m = 1; m < CPR; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
+    const float sc = kv8_scale(amax);
+    *reinterpret_cast<u32x2*>(cache + (tok + hd) * DH + c0) = kv8_quant8(x, sc);
+    if (ch == 0) scale[tok + hd] = sc;
+  };
+
+  // this lane's chunk of one head row after the rotation, as T bits (columns >= rot are copied); lanes of one row may take either side
+  // and meet again behind it
+  const bool rot_lane = c0 < a.rot;
+  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sn[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int pc = c0;
+  float sign = 1.f;
+  if (rot_lane) {
+    const float* fr = a.freqs + ((long long)s * a.B + b) * a.rot + c0;
+    const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
+    const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
+    const bool first = c0 + half < a.rot;
+    pc = first ? c0 + half : c0 - half;
+    sign = first ? -1.f : 1.f;
+  }
+  auto rotated = [&](const uint16_t* hp) -> u32x4 {
+    const u32x4 w = *reinterpret_cast<const u32x4*>(hp + c0);
+    if (!rot_lane) return w;
+    float x[8], y[8], res[8];
+    unpack8<DT>(w, x);
+    unpack8<DT>(*reinterpret_cast<const u32x4*>(hp + pc), y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) res[e] = __builtin_fmaf(x[e], cs[e], (sign * y[e]) * sn[e]);
+    return pack8<DT>(res);
+  };
+
+  for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = rotated(row + hd * DH);
+  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(rotated(ks + hd * DH), a.k_cache, a.k_scale, hd);
+  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), a.v_cache, a.v_scale, hd);
+}
+
+}  // namespace
+
+int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                     float* v_scale, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int start_pos, long long bs,
+                                     long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, bs, rs, B, S, H, Hkv,
+                     rot, lmax, start_pos};
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<F16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<F16, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+}  // namespace awq

@@ -25,9 +25,12 @@
 //   * No workspace, no atomics: bit-deterministic.  O is divided by l (IEEE division of 1 / l, once per row) and rounded to T once.
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
+#include "awq_kv8.hpp"
 
 #include <math.h>
 #include <string.h>
+
+#include <type_traits>
 
 namespace awq {
 namespace {
@@ -49,6 +52,11 @@ struct PrefillArgs {
   long long q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;  // elements
   int B, Sq, Sk, H, G, ntiles, causal;
   float scale_log2e;
+  // Kv8 only (awq_kv8.hpp): the scales [B, Sk, Hkv] of the e4m3 codes a.k / a.v point at, batch / row strides in floats; a.k_bs .. a.v_rs
+  // are then in codes (bytes)
+  const float* k_scale;
+  const float* v_scale;
+  long long ks_bs, ks_rs, vs_bs, vs_rs;
 };
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
@@ -71,6 +79,12 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 //
 // The FT form is selected by the element traits -- FtCache<F16> / FtCache<BF16>, the same traits under another name -- so it is a
 // separate instantiation and the natural-layout kernels keep their names, their compile-time strides and their code.
+//
+// Kv8<DT> (awq_kv8.hpp) selects the FP8 cache the same way: K / V are e4m3 codes [B, Sk, Hkv, DH] with one fp32 scale per (key, KV head).
+// A thread keeps the c = tid + i * NT mapping and loads the 8 bytes of its chunk and the row's scale; the dequantisation T(float(code) * s)
+// sits between the global load and the LDS write, which stores the same 16 bytes into the same slot.  The 8-byte form is kept over 16 bytes
+// per lane (two chunks): at DH = 64 with eight waves a tile has 256 sixteen-byte code chunks for 512 threads, which would idle half the
+// loaders, and the mapping, the clamp and the LDS slots stay those of the T cache.
 template <typename DT>
 struct FtCache : DT {};
 template <typename DT>
@@ -85,6 +99,7 @@ struct IsFtCache<FtCache<DT>> {
 template <typename DT, int DH, int NW>
 __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
   constexpr bool FT = IsFtCache<DT>::value;
+  constexpr bool KV8 = IsKv8<DT>::value;
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = NW * 64;
@@ -128,7 +143,13 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
 
   const uint16_t* kb = a.k + (long long)b * a.k_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
   const uint16_t* vb = a.v + (long long)b * a.v_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
-  u32x4 kr[LOADS], vr[LOADS];
+  using stage_t = typename std::conditional<KV8, u32x2, u32x4>::type;
+  stage_t kr[LOADS], vr[LOADS];
+  float ksc[KV8 ? LOADS : 1], vsc[KV8 ? LOADS : 1];  // Kv8: the scale of the chunk's row
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + (long long)b * a.k_bs + (long long)kvh * DH;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + (long long)b * a.v_bs + (long long)kvh * DH;
+  const float* ksb = KV8 ? a.k_scale + (long long)b * a.ks_bs + kvh : nullptr;
+  const float* vsb = KV8 ? a.v_scale + (long long)b * a.vs_bs + kvh : nullptr;
   // FT: the K chunks of a tile go to the threads with the KEY fastest (NT is a multiple of 64, so a wave reads 64 consecutive positions
   // of one chunk index: 1 KiB contiguous in the cache) and land in the same LDS image; V rows are DH contiguous elements in the cache
   // too, so V keeps the chunk-fastest mapping.  Keys >= Sk are clamped to Sk - 1 like rows: no position outside the Sk keys is read.
@@ -142,6 +163,11 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
         const long long kg = min(t0 + krow, a.Sk - 1);
         kr[i] = *reinterpret_cast<const u32x4*>(kb + kch * a.k_rs + kg * 8);
         vr[i] = *reinterpret_cast<const u32x4*>(vb + g * DH + ch * 8);
+      } else if constexpr (KV8) {
+        kr[i] = *reinterpret_cast<const u32x2*>(kb8 + g * a.k_rs + ch * 8);
+        vr[i] = *reinterpret_cast<const u32x2*>(vb8 + g * a.v_rs + ch * 8);
+        ksc[i] = ksb[g * a.ks_rs];
+        vsc[i] = vsb[g * a.vs_rs];
       } else {
         kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
         vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
@@ -152,9 +178,16 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-      if constexpr (FT) *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(c % kKV, c / kKV)]) = kr[i];
-      else *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
-      *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+      if constexpr (FT) {
+        *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(c % kKV, c / kKV)]) = kr[i];
+        *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+      } else if constexpr (KV8) {
+        *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kv8_dequant8<DT>(kr[i], ksc[i]);
+        *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = kv8_dequant8<DT>(vr[i], vsc[i]);
+      } else {
+        *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
+        *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+      }
     }
   };
 
@@ -425,6 +458,8 @@ int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, 
   a.G = H / Hkv;
   a.causal = causal ? 1 : 0;
   a.scale_log2e = scale * 1.4426950408889634f;
+  a.k_scale = a.v_scale = nullptr;
+  a.ks_bs = a.ks_rs = a.vs_bs = a.vs_rs = 0;
   int rows = 0, blocks = 0;
   attn_prefill_plan(B, H, Hkv, Dh, Sq, Sk, causal, &rows, &blocks);
   a.ntiles = (Sq + rows - 1) / rows;
@@ -460,6 +495,8 @@ int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* 
   a.G = H / Hkv;
   a.causal = causal ? 1 : 0;
   a.scale_log2e = scale * 1.4426950408889634f;
+  a.k_scale = a.v_scale = nullptr;
+  a.ks_bs = a.ks_rs = a.vs_bs = a.vs_rs = 0;
   int rows = 0, blocks = 0;
   attn_prefill_plan(B, H, Hkv, Dh, Sq, Sk, causal, &rows, &blocks);
   a.ntiles = (Sq + rows - 1) / rows;
@@ -470,6 +507,51 @@ int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* 
   } else {
     if (Dh == 128) launch_nw<FtCache<BF16>, 128>(a, nw, blocks, st);
     else launch_nw<FtCache<BF16>, 64>(a, nw, blocks, st);
+  }
+  return 0;
+}
+
+// The same launch on the FP8 cache: k / v are e4m3 codes [B, Sk, Hkv, Dh] (strides in bytes), k_scale / v_scale their fp32 scales
+// [B, Sk, Hkv] (strides in floats).  The plan is asked with the same arguments, so the q tile and every bit behind the staging are those of
+// launch_attn_prefill on the dequantised tensors.
+int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
+                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
+                            hipStream_t st) {
+  PrefillArgs a;
+  a.q = (const uint16_t*)q;
+  a.k = (const uint16_t*)k;
+  a.v = (const uint16_t*)v;
+  a.out = (uint16_t*)out;
+  a.q_bs = q_bs;
+  a.q_rs = q_rs;
+  a.k_bs = k_bs;
+  a.k_rs = k_rs;
+  a.v_bs = v_bs;
+  a.v_rs = v_rs;
+  a.B = B;
+  a.Sq = Sq;
+  a.Sk = Sk;
+  a.H = H;
+  a.G = H / Hkv;
+  a.causal = causal ? 1 : 0;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  a.k_scale = k_scale;
+  a.v_scale = v_scale;
+  a.ks_bs = ks_bs;
+  a.ks_rs = ks_rs;
+  a.vs_bs = vs_bs;
+  a.vs_rs = vs_rs;
+  int rows = 0, blocks = 0;
+  attn_prefill_plan(B, H, Hkv, Dh, Sq, Sk, causal, &rows, &blocks);
+  a.ntiles = (Sq + rows - 1) / rows;
+  const int nw = rows / kMfmaRows;
+  if (dtype == 0) {
+    if (Dh == 128) launch_nw<Kv8<F16>, 128>(a, nw, blocks, st);
+    else launch_nw<Kv8<F16>, 64>(a, nw, blocks, st);
+  } else {
+    if (Dh == 128) launch_nw<Kv8<BF16>, 128>(a, nw, blocks, st);
+    else launch_nw<Kv8<BF16>, 64>(a, nw, blocks, st);
   }
   return 0;
 }

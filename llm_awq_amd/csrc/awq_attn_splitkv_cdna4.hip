@@ -33,9 +33,12 @@
 // (README.md: 0.46 of 8 TB/s at 131072 keys, 16x the one-pass kernel at 32768 keys, Llama-3-8B, one token).
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
+#include "awq_kv8.hpp"
 
 #include <math.h>
 #include <string.h>
+
+#include <type_traits>
 
 namespace awq {
 namespace {
@@ -64,6 +67,11 @@ struct SplitArgs {
   long long q_bs, q_rs, k_bs, k_rs, v_bs, v_rs;  // elements
   int B, Sq, Sk, H, Hkv, G, R, splits, chunk, causal;
   float scale_log2e;
+  // Kv8 only (awq_kv8.hpp): the scales [B, Sk, Hkv] of the e4m3 codes k / v point at, batch / row strides in floats; k_bs .. v_rs are then
+  // in codes (bytes)
+  const float* k_scale;
+  const float* v_scale;
+  long long ks_bs, ks_rs, vs_bs, vs_rs;
 };
 
 // LDS images of awq_attn_prefill_cdna4.hip, restated: rows of DH elements, the 16-byte chunks of a row permuted by an XOR of the row.
@@ -78,8 +86,12 @@ __device__ __forceinline__ int v_off(int row, int ch) {
   return row * DH + ((ch ^ (DH == 128 ? (((row & 3) << 2) | ((row >> 2) & 3)) : (((row >> 1) & 1) << 2))) << 3);
 }
 
+// Kv8<DT> (awq_kv8.hpp) is the FP8 cache: the staging loads the 8 code bytes of the thread's chunk and the row's scale (same
+// c = tid + i * NT mapping, same clamp to Sk - 1), dequantises T(float(code) * s) and writes the same 16 bytes into the same LDS slot.
+// The 8-byte form is the one kept in both attention kernels (the reason is the prefill kernel's: awq_attn_prefill_cdna4.hip).
 template <typename DT, int DH>
 __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
+  constexpr bool KV8 = IsKv8<DT>::value;
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -121,22 +133,40 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
 
   const uint16_t* kb = a.k + (long long)b * a.k_bs + (long long)kvh * DH;
   const uint16_t* vb = a.v + (long long)b * a.v_bs + (long long)kvh * DH;
-  u32x4 kr[LOADS], vr[LOADS];
+  using stage_t = typename std::conditional<KV8, u32x2, u32x4>::type;
+  stage_t kr[LOADS], vr[LOADS];
+  float ksc[KV8 ? LOADS : 1], vsc[KV8 ? LOADS : 1];  // Kv8: the scale of the chunk's row
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + (long long)b * a.k_bs + (long long)kvh * DH;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + (long long)b * a.v_bs + (long long)kvh * DH;
+  const float* ksb = KV8 ? a.k_scale + (long long)b * a.ks_bs + kvh : nullptr;
+  const float* vsb = KV8 ? a.v_scale + (long long)b * a.vs_bs + kvh : nullptr;
   auto stage_load = [&](int t0) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
       const long long g = min(t0 + row, a.Sk - 1);  // no row >= Sk is read
-      kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
-      vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+      if constexpr (KV8) {
+        kr[i] = *reinterpret_cast<const u32x2*>(kb8 + g * a.k_rs + ch * 8);
+        vr[i] = *reinterpret_cast<const u32x2*>(vb8 + g * a.v_rs + ch * 8);
+        ksc[i] = ksb[g * a.ks_rs];
+        vsc[i] = vsb[g * a.vs_rs];
+      } else {
+        kr[i] = *reinterpret_cast<const u32x4*>(kb + g * a.k_rs + ch * 8);
+        vr[i] = *reinterpret_cast<const u32x4*>(vb + g * a.v_rs + ch * 8);
+      }
     }
   };
   auto stage_write = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-      *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
-      *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+      if constexpr (KV8) {
+        *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kv8_dequant8<DT>(kr[i], ksc[i]);
+        *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = kv8_dequant8<DT>(vr[i], vsc[i]);
+      } else {
+        *reinterpret_cast<u32x4*>(&k_s[buf][k_off<DH>(row, ch)]) = kr[i];
+        *reinterpret_cast<u32x4*>(&v_s[buf][v_off<DH>(row, ch)]) = vr[i];
+      }
     }
   };
 
@@ -333,10 +363,37 @@ int attn_splitkv_tune_set(const char* key, int value) {
   return 0;
 }
 
-// The caller has validated the arguments, found splits > 1 in the plan and a workspace of attn_splitkv_workspace_bytes.
-int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
-                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
-                        int splits, int chunk, void* workspace, hipStream_t st) {
+namespace {
+
+// Both launches of one call.  K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
+// partials only, so it is the T cache's in either case.
+template <template <typename> class K>
+void launch_pair(const SplitArgs& a, int Dh, int dtype, dim3 grid, dim3 cgrid, hipStream_t st) {
+  if (dtype == 0) {
+    if (Dh == 128) {
+      hipLaunchKernelGGL((attn_splitkv_kernel<K<F16>, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 128>), cgrid, dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_splitkv_kernel<K<F16>, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 64>), cgrid, dim3(256), 0, st, a);
+    }
+  } else {
+    if (Dh == 128) {
+      hipLaunchKernelGGL((attn_splitkv_kernel<K<BF16>, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 128>), cgrid, dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((attn_splitkv_kernel<K<BF16>, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 64>), cgrid, dim3(256), 0, st, a);
+    }
+  }
+}
+template <typename DT>
+using TCache = DT;  // the T cache: the element traits themselves
+
+// the arguments both cache formats share; the scale fields are left to the caller
+SplitArgs split_args(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                     long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int splits, int chunk,
+                     void* workspace) {
   SplitArgs a;
   a.q = (const uint16_t*)q;
   a.k = (const uint16_t*)k;
@@ -363,25 +420,40 @@ int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, 
   a.ws_o = (float*)workspace;
   a.ws_m = a.ws_o + n * Dh;
   a.ws_l = a.ws_m + n;
+  a.k_scale = a.v_scale = nullptr;
+  a.ks_bs = a.ks_rs = a.vs_bs = a.vs_rs = 0;
+  return a;
+}
+
+}  // namespace
+
+// The caller has validated the arguments, found splits > 1 in the plan and a workspace of attn_splitkv_workspace_bytes.
+int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
+                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
+                        int splits, int chunk, void* workspace, hipStream_t st) {
+  const SplitArgs a = split_args(q, k, v, out, B, Sq, Sk, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk, workspace);
   const dim3 grid((unsigned)((long long)B * Hkv * splits));
   const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
-  if (dtype == 0) {
-    if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<F16, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 128>), cgrid, dim3(256), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<F16, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 64>), cgrid, dim3(256), 0, st, a);
-    }
-  } else {
-    if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<BF16, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 128>), cgrid, dim3(256), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<BF16, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 64>), cgrid, dim3(256), 0, st, a);
-    }
-  }
+  launch_pair<TCache>(a, Dh, dtype, grid, cgrid, st);
+  return 0;
+}
+
+// The same pair on the FP8 cache: k / v are e4m3 codes with strides in bytes, k_scale / v_scale their fp32 scales [B, Sk, Hkv] with strides
+// in floats (awq_kv8.hpp).  Same plan, same workspace.
+int launch_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
+                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
+                            int splits, int chunk, void* workspace, hipStream_t st) {
+  SplitArgs a = split_args(q, k, v, out, B, Sq, Sk, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk, workspace);
+  a.k_scale = k_scale;
+  a.v_scale = v_scale;
+  a.ks_bs = ks_bs;
+  a.ks_rs = ks_rs;
+  a.vs_bs = vs_bs;
+  a.vs_rs = vs_rs;
+  const dim3 grid((unsigned)((long long)B * Hkv * splits));
+  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
+  launch_pair<Kv8>(a, Dh, dtype, grid, cgrid, st);
   return 0;
 }
 

@@ -468,6 +468,88 @@ int awq_attn_splitkv(const void* q, const void* k, const void* v, void* out, int
   return finish_launch();
 }
 
+// ---- FP8 KV cache on the natural layout (awq_kv8.hpp) ----
+int awq_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs || !q_out || !k_cache || !v_cache || !k_scale || !v_scale) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (batch < 1 || cache_batch < batch || seqlen < 1 || nheads < 1 || nheads_kv < 1 || (head_dim != 64 && head_dim != 128) ||
+      rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_dim || lmax < 1 || start_pos < 0 ||
+      (long long)start_pos + seqlen > lmax || qkv_batch_stride < 0 ||
+      qkv_row_stride < ((long long)nheads + 2ll * nheads_kv) * head_dim || (long long)batch * seqlen * (head_dim / 8) > 0x3FFFFFFFll * 256)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
+      (reinterpret_cast<uintptr_t>(k_scale) & 3u) || (reinterpret_cast<uintptr_t>(v_scale) & 3u) || (qkv_batch_stride % 8) != 0 ||
+      (qkv_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store_natural_fp8(qkv, freqs, q_out, k_cache, v_cache, k_scale, v_scale, batch, seqlen, nheads, nheads_kv, head_dim,
+                                        rot_dim, lmax, start_pos, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+// the argument checks both FP8 attention entries share; AWQ_OK: the launch may go on
+static int kv8_attn_check(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, const void* out, int batch,
+                          int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                          long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                          long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                          long long v_scale_row_stride, int causal, int dtype) {
+  if (!q || !k || !v || !k_scale || !v_scale || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if ((head_dim != 64 && head_dim != 128) || !prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal) ||
+      q_batch_stride < 0 || k_batch_stride < 0 || v_batch_stride < 0 || k_scale_batch_stride < 0 || v_scale_batch_stride < 0 ||
+      q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
+      v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv || v_scale_row_stride < nheads_kv)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (reinterpret_cast<uintptr_t>(k_scale) & 3u) ||
+      (reinterpret_cast<uintptr_t>(v_scale) & 3u) || (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_batch_stride % 16) != 0 ||
+      (k_row_stride % 16) != 0 || (v_batch_stride % 16) != 0 || (v_row_stride % 16) != 0)
+    return AWQ_ERR_ALIGN;
+  return AWQ_OK;
+}
+
+int awq_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  const int rc = kv8_attn_check(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, causal, dtype);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_prefill_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                               q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                               k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  const int rc = kv8_attn_check(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, causal, dtype);
+  if (rc != AWQ_OK) return rc;
+  int splits = 1, chunk = 0;
+  awq::attn_splitkv_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, &splits, &chunk);
+  if (splits <= 1)  // not taken: the one-pass launch, bit for bit
+    return awq_attn_prefill_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, stream);
+  const size_t need = awq::attn_splitkv_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal);
+  if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
+  if ((long long)batch * nheads_kv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
+  awq::launch_attn_splitkv_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                               q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                               k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, splits, chunk,
+                               workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {
   return nseq >= 1 && nheads >= 1 && (head_dim == 64 || head_dim == 72) && max_seqlen >= 1 &&
          (long long)nseq * nheads * ((max_seqlen + 31) / 32) <= 0x7FFFFFFFll;

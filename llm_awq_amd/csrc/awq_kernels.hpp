@@ -193,6 +193,19 @@ int attn_splitkv_tune_set(const char* key, int value);  // "attn_splitkv_chunk":
 int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
                         long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
                         int splits, int chunk, void* workspace, hipStream_t st);
+// FP8 KV cache (awq_kv8.hpp): k / v are e4m3 codes [B, Sk, Hkv, Dh] with strides in bytes, k_scale / v_scale fp32 [B, Sk, Hkv] with strides in
+// floats.  The split form, the one-pass form and the store launch (awq_attn_kv8_cdna4.hip):
+int launch_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
+                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
+                            int splits, int chunk, void* workspace, hipStream_t st);
+int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
+                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
+                            hipStream_t st);
+int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                     float* v_scale, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int start_pos, long long bs,
+                                     long long rs, int dtype, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

@@ -846,6 +846,128 @@ torch::Tensor rope_kv_store_natural(const torch::Tensor qkv, const torch::Tensor
   return q_out;
 }
 
+// ---- FP8 KV cache on the natural layout (csrc/awq_kv8.hpp): codes [.., L, Hkv, Dh] as float8_e4m3fn or uint8, scales [.., L, Hkv] float32 ----
+static bool is_kv8_code(const torch::Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte; }
+
+// rope_kv_store_natural_fp8(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos, nheads, nheads_kv) -> q_out: rope_kv_store_natural
+// with k and v quantised per (token, KV head) on their way into the caches, one launch (csrc/awq_attn_kv8_cdna4.hip).  q_out holds
+// rope_kv_store_natural's bits.
+torch::Tensor rope_kv_store_natural_fp8(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
+                                        torch::Tensor k_scale, torch::Tensor v_scale, int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
+  const char* who = "rope_kv_store_natural_fp8";
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
+  TORCH_CHECK(freqs.scalar_type() == at::kFloat, who, ": freqs must be float32");
+  const char* cname[2] = {"k_cache", "v_cache"};
+  const char* sname[2] = {"k_scale", "v_scale"};
+  const torch::Tensor* caches[2] = {&k_cache, &v_cache};
+  const torch::Tensor* scales[2] = {&k_scale, &v_scale};
+  for (int i = 0; i < 2; ++i) {
+    TORCH_CHECK(caches[i]->is_cuda() && caches[i]->device() == qkv.device(), who, ": ", cname[i], " must live on the GPU of the input");
+    TORCH_CHECK(is_kv8_code(*caches[i]), who, ": ", cname[i], " must be float8_e4m3fn or uint8, got ", caches[i]->scalar_type());
+    TORCH_CHECK(caches[i]->dim() == 4 && caches[i]->is_contiguous(), who, ": ", cname[i], " must be contiguous [Bc, Lmax, Hkv, Dh]");
+    TORCH_CHECK(scales[i]->is_cuda() && scales[i]->device() == qkv.device(), who, ": ", sname[i], " must live on the GPU of the input");
+    TORCH_CHECK(scales[i]->scalar_type() == at::kFloat, who, ": ", sname[i], " must be float32, got ", scales[i]->scalar_type());
+    TORCH_CHECK(scales[i]->dim() == 3 && scales[i]->is_contiguous(), who, ": ", sname[i], " must be contiguous [Bc, Lmax, Hkv]");
+  }
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who, ": k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
+  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rot = freqs.size(-1);
+  for (int i = 0; i < 2; ++i)
+    TORCH_CHECK(scales[i]->size(0) == cache_batch && scales[i]->size(1) == lmax && scales[i]->size(2) == v_cache.size(2), who, ": ", sname[i],
+                " must be [Bc, Lmax, Hkv] of the caches");
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
+              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
+  TORCH_CHECK(batch <= cache_batch, who, ": batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= lmax, who, ": positions ", start_pos, " .. ", start_pos + seqlen, " do not fit the cache of ",
+              lmax);
+  TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot, who,
+              ": freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor x = qkv;
+  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
+  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  raise_on(awq_rope_kv_store_natural_fp8(x.data_ptr(), fr.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                         k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)batch, (int)cache_batch, (int)seqlen,
+                                         (int)nheads, (int)nheads_kv, (int)headdim, (int)rot, (int)lmax, (int)start_pos, x.stride(0), x.stride(1),
+                                         dtype_code(x), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return q_out;
+}
+
+// the checks attn_prefill_kv8 and attn_splitkv_kv8 share: q [B, Sq, H, Dh] of T, k / v codes [B, Sk, Hkv, Dh], k_scale / v_scale [B, Sk, Hkv]
+static void check_kv8_attn(const char* who, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor& k_scale,
+                           const torch::Tensor& v_scale, bool causal) {
+  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  const char* cname[2] = {"k", "v"};
+  const char* sname[2] = {"k_scale", "v_scale"};
+  const torch::Tensor* codes[2] = {&k, &v};
+  const torch::Tensor* scales[2] = {&k_scale, &v_scale};
+  TORCH_CHECK(q.dim() == 4, who, ": q must be [B, Sq, H, Dh]");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(q.stride(3) == 1 && q.stride(2) == headdim, who, ": the heads of q must be contiguous (stride(3) == 1, stride(2) == Dh)");
+  for (int i = 0; i < 2; ++i) {
+    TORCH_CHECK(codes[i]->is_cuda() && codes[i]->device() == q.device(), who, ": ", cname[i], " must live on the GPU of q");
+    TORCH_CHECK(is_kv8_code(*codes[i]), who, ": ", cname[i], " must be float8_e4m3fn or uint8, got ", codes[i]->scalar_type());
+    TORCH_CHECK(codes[i]->dim() == 4 && codes[i]->size(0) == batch && codes[i]->size(3) == headdim, who, ": ", cname[i], " must be [B, Sk, Hkv, ",
+                headdim, "]");
+    TORCH_CHECK(codes[i]->stride(3) == 1 && codes[i]->stride(2) == headdim, who, ": the heads of ", cname[i],
+                " must be contiguous (stride(3) == 1, stride(2) == Dh)");
+    TORCH_CHECK(scales[i]->is_cuda() && scales[i]->device() == q.device(), who, ": ", sname[i], " must live on the GPU of q");
+    TORCH_CHECK(scales[i]->scalar_type() == at::kFloat, who, ": ", sname[i], " must be float32, got ", scales[i]->scalar_type());
+    TORCH_CHECK(scales[i]->dim() == 3 && scales[i]->size(0) == batch && scales[i]->size(1) == codes[i]->size(1) &&
+                    scales[i]->size(2) == codes[i]->size(2) && scales[i]->stride(2) == 1,
+                who, ": ", sname[i], " must be [B, Sk, Hkv] of ", cname[i], " with a unit last stride");
+  }
+  TORCH_CHECK(v.sizes() == k.sizes(), who, ": k and v must have one shape [B, Sk, Hkv, Dh]");
+  const int64_t sk = k.size(1), nheads_kv = k.size(2);
+  TORCH_CHECK(batch >= 1 && sq >= 1 && sk >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+              ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(!causal || sq <= sk, who, ": causal attention needs seqlen_q <= seqlen_k, got ", sq, " > ", sk);
+}
+
+// attn_splitkv_kv8(q, k, v, k_scale, v_scale, softmax_scale, causal) -> out: attn_splitkv on the FP8 cache; attn_prefill_kv8 where the plan
+// does not split.  Bit-identical to attn_splitkv / attn_prefill on the dequantised tensors.  The workspace is the caching allocator's: capturable.
+static torch::Tensor attn_kv8_impl(const char* who, bool split, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+                                   const torch::Tensor& k_scale, const torch::Tensor& v_scale, double softmax_scale, bool causal) {
+  check_kv8_attn(who, q, k, v, k_scale, v_scale, causal);
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), sk = k.size(1), nheads_kv = k.size(2);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (!split) {
+    raise_on(awq_attn_prefill_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), out.data_ptr(),
+                                  (int)batch, (int)sq, (int)sk, (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0),
+                                  k.stride(1), v.stride(0), v.stride(1), k_scale.stride(0), k_scale.stride(1), v_scale.stride(0),
+                                  v_scale.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q), st));
+    return out;
+  }
+  const size_t wsb = awq_attn_splitkv_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)sk, causal ? 1 : 0);
+  at::Tensor ws;
+  if (wsb) ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  raise_on(awq_attn_splitkv_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), out.data_ptr(),
+                                (int)batch, (int)sq, (int)sk, (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0),
+                                k.stride(1), v.stride(0), v.stride(1), k_scale.stride(0), k_scale.stride(1), v_scale.stride(0), v_scale.stride(1),
+                                (float)softmax_scale, causal ? 1 : 0, dtype_code(q), wsb ? ws.data_ptr() : nullptr, wsb, st));
+  return out;
+}
+
+torch::Tensor attn_prefill_kv8(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, const torch::Tensor k_scale,
+                               const torch::Tensor v_scale, double softmax_scale, bool causal) {
+  return attn_kv8_impl("attn_prefill_kv8", false, q, k, v, k_scale, v_scale, softmax_scale, causal);
+}
+
+torch::Tensor attn_splitkv_kv8(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, const torch::Tensor k_scale,
+                               const torch::Tensor v_scale, double softmax_scale, bool causal) {
+  return attn_kv8_impl("attn_splitkv_kv8", true, q, k, v, k_scale, v_scale, softmax_scale, causal);
+}
+
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
 // (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
 // kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
@@ -1146,6 +1268,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_store_natural", &rope_kv_store_natural,
         "Rotate q and k of a fused qkv chunk, store k / v into natural-layout caches [Bc, Lmax, Hkv, Dh]; returns q [B, S, H, Dh]", py::arg("qkv"),
         py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"));
+  m.def("rope_kv_store_natural_fp8", &rope_kv_store_natural_fp8,
+        "rope_kv_store_natural on the FP8 cache: k / v stored as e4m3 codes [Bc, Lmax, Hkv, Dh] with fp32 scales [Bc, Lmax, Hkv]; returns q", py::arg("qkv"),
+        py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("start_pos"), py::arg("nheads"),
+        py::arg("nheads_kv"));
+  m.def("attn_prefill_kv8", &attn_prefill_kv8, "attn_prefill with k / v read from e4m3 codes and per-(key, KV head) fp32 scales", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("k_scale"), py::arg("v_scale"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_splitkv_kv8", &attn_splitkv_kv8, "attn_splitkv with k / v read from e4m3 codes and per-(key, KV head) fp32 scales", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("k_scale"), py::arg("v_scale"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

@@ -19,6 +19,12 @@ caches [B, L, Hkv, Dh] and `long_forward` for kv_max_seq_len > 8192, fused_attn.
 one token included, is `rope_kv_store_natural` (q and k rotated, k and v stored, one launch) followed by
 `flash_attn_func(q, cache_k[:, :pos], cache_v[:, :pos], causal=True)`, which takes the split-KV kernels (csrc/awq_attn_splitkv_cdna4.hip)
 once the history reaches 2048 keys and few query rows ask -- the decode phase -- and the one-pass prefill kernel otherwise.
+
+`kv_dtype="fp8"` (natural layout only) keeps that path on an FP8 cache: `cache_k` / `cache_v` hold OCP e4m3fn codes, one byte per element,
+and `cache_k_scale` / `cache_v_scale` [B, L, Hkv] one fp32 scale per (token, KV head) -- half the memory and half the bytes a decode step
+streams.  Every call is `rope_kv_store_natural_fp8` (rotation, quantisation and store in one launch) followed by `ops.attn_kv8`, the same
+two attention kernels with the dequantisation in their staging step (csrc/awq_kv8.hpp); the result is, bit for bit, the T-cache path's on
+the dequantised caches.
 """
 from __future__ import annotations
 
@@ -33,13 +39,21 @@ class QuantLlamaAttentionFused(nn.Module):
     global there (:21) and a keyword here.  `cache_k` [max_batch_size, Hkv, Dh/8, kv_max_seq_len, 8] and `cache_v`
     [max_batch_size, Hkv, kv_max_seq_len, Dh] are the FT caches the decode kernel reads and writes.  `kv_layout="natural"` is the
     reference's long-context mode (QuantLlamaAttentionFusedFlash with kv_max_seq_len > 8192): both caches are
-    [max_batch_size, kv_max_seq_len, Hkv, Dh] and forward is long_forward's data flow for every seqlen."""
+    [max_batch_size, kv_max_seq_len, Hkv, Dh] and forward is long_forward's data flow for every seqlen.  `kv_dtype="fp8"` (with
+    `kv_layout="natural"`) makes them float8_e4m3fn and adds `cache_k_scale` / `cache_v_scale` [max_batch_size, kv_max_seq_len, Hkv]
+    float32; `kv_dtype=None` is the cache of the activations' dtype."""
 
-    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft"):
+    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft", kv_dtype=None):
         super().__init__()
         if kv_layout not in ("ft", "natural"):
             raise ValueError(f"QuantLlamaAttentionFused: kv_layout {kv_layout!r} is not supported (supported: 'ft', 'natural')")
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"QuantLlamaAttentionFused: kv_dtype {kv_dtype!r} is not supported (supported: None, 'fp8')")
+        if kv_dtype == "fp8" and kv_layout != "natural":
+            raise ValueError("QuantLlamaAttentionFused: kv_dtype 'fp8' needs kv_layout 'natural' (the FT decode kernel reads a cache of the "
+                             "activations' dtype)")
         self.kv_layout = kv_layout
+        self.kv_dtype = kv_dtype
         self.args = args
         self.n_local_heads = args.num_attention_heads
         self.hidden_size = args.hidden_size
@@ -62,6 +76,12 @@ class QuantLlamaAttentionFused(nn.Module):
         self.max_batch_size = max_batch_size
         if kv_layout == "natural":  # fused_attn.py:389-415
             shape = (max_batch_size, kv_max_seq_len, self.num_key_value_heads, self.head_dim)
+            if kv_dtype == "fp8":
+                self.cache_v = torch.zeros(shape, dtype=torch.float8_e4m3fn, device=dev)
+                self.cache_k = torch.zeros(shape, dtype=torch.float8_e4m3fn, device=dev)
+                self.cache_v_scale = torch.zeros(shape[:3], dtype=torch.float32, device=dev)
+                self.cache_k_scale = torch.zeros(shape[:3], dtype=torch.float32, device=dev)
+                return
             self.cache_v = torch.zeros(shape, dtype=torch.float16, device=dev)
             self.cache_k = torch.zeros(shape, dtype=torch.float16, device=dev)
             return
@@ -76,6 +96,18 @@ class QuantLlamaAttentionFused(nn.Module):
         eng = load_engine()
         bsz, seqlen, _ = x.shape
         xqkv = self.qkv_proj(x)
+        if self.kv_dtype == "fp8":  # the caches keep their dtype: only the device follows the activations
+            from . import ops
+
+            if self.cache_k.device != xqkv.device:
+                for name in ("cache_k", "cache_v", "cache_k_scale", "cache_v_scale"):
+                    setattr(self, name, getattr(self, name).to(xqkv.device))
+            xq = eng.rope_kv_store_natural_fp8(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, self.cache_k_scale,
+                                               self.cache_v_scale, start_pos, self.n_local_heads, self.num_key_value_heads)
+            end = start_pos + seqlen
+            output = ops.attn_kv8(xq, self.cache_k[:bsz, :end], self.cache_v[:bsz, :end], self.cache_k_scale[:bsz, :end],
+                                  self.cache_v_scale[:bsz, :end], causal=True)
+            return self.o_proj(output.view(bsz, seqlen, -1))
         if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:  # the reference's .to(xq) (:256-257)
             self.cache_k = self.cache_k.to(xqkv)
             self.cache_v = self.cache_v.to(xqkv)
@@ -135,17 +167,17 @@ def fuse_qkv(q_proj, k_proj, v_proj):
     return qkv
 
 
-def make_quant_attn(model, dev, max_batch_size=1, kv_layout="ft"):
+def make_quant_attn(model, dev, max_batch_size=1, kv_layout="ft", kv_dtype=None):
     """tinychat/modules/fused_attn.py:549-634: replace every module that carries q_proj, k_proj, v_proj, o_proj, `args` and
     `kv_max_seq_len` (the reference's LlamaAttentionFused / Qwen2AttentionFused) by a QuantLlamaAttentionFused over one fused
-    qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode."""
+    qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode, `kv_dtype="fp8"` its FP8 cache."""
     want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
     for name, m in list(model.named_modules()):
         if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
             continue
         qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
         attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
-                                        max_batch_size=max_batch_size, kv_layout=kv_layout)
+                                        max_batch_size=max_batch_size, kv_layout=kv_layout, kv_dtype=kv_dtype)
         if "." in name:
             parent_name, child_name = name.rsplit(".", 1)
             parent = model.get_submodule(parent_name)

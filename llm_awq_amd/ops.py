@@ -608,6 +608,140 @@ def flash_attn_func(q, k, v, softmax_scale=None, causal: bool = False):
     return out
 
 
+# ---- FP8 KV cache on the natural layout (csrc/awq_kv8.hpp) --------------------------------------------------------------------------
+KV8_MAX = 448.0          # the largest finite e4m3fn value
+KV8_AMAX_FLOOR = 2.0 ** -60  # a row's max |x| is raised to this: no special case for a zero row, no fp32 denormal scale
+
+
+def kv8_quant(x):
+    """The FP8 KV-cache format, in plain torch on any device: x [..., Dh] of float16 / bfloat16 -> (codes [..., Dh] float8_e4m3fn,
+    scale [...] float32), one scale per head row.  s = max(max|x|, 2^-60) / 448 as an fp32 division, code = e4m3fn_RNE(clamp(x / s,
+    -448, 448)) with x / s a correctly rounded fp32 division.  Rows with NaN / Inf are outside the contract."""
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"kv8_quant: expected float16/bfloat16, got {x.dtype}")
+    xf = x.to(torch.float32)
+    amax = xf.abs().amax(dim=-1).clamp_min(KV8_AMAX_FLOOR)
+    scale = amax / torch.tensor(KV8_MAX, dtype=torch.float32, device=x.device)
+    codes = (xf / scale.unsqueeze(-1)).clamp(-KV8_MAX, KV8_MAX).to(torch.float8_e4m3fn)
+    return codes, scale
+
+
+def kv8_dequant(codes, scale, dtype):
+    """codes [..., Dh] (float8_e4m3fn, or uint8 holding the same bytes), scale [...] float32 -> T(float(code) * s): one fp32 multiply, one
+    rounding to `dtype`.  This is what the FP8 attention kernels put into LDS, so attn_kv8 equals flash_attn_func on this tensor bit for bit."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"kv8_dequant: expected float16/bfloat16, got {dtype}")
+    if codes.dtype == torch.uint8:
+        codes = codes.view(torch.float8_e4m3fn)
+    if codes.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32 or tuple(scale.shape) != tuple(codes.shape[:-1]):
+        raise ValueError("kv8_dequant: codes [..., Dh] of float8_e4m3fn / uint8 and scale [...] of float32 are expected")
+    return (codes.to(torch.float32) * scale.unsqueeze(-1)).to(dtype)
+
+
+def _kv8_codes(who, name, t):
+    if t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise ValueError(f"{who}: {name} must be float8_e4m3fn or uint8, got {t.dtype}")
+
+
+def rope_kv_store_natural_fp8(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos: int, nheads: int, nheads_kv: int):
+    """C-ABI awq_rope_kv_store_natural_fp8: rope_kv_store_natural with k and v quantised on their way into the FP8 caches (kv8_quant's
+    format).  k_cache / v_cache [Bc, Lmax, Hkv, Dh] float8_e4m3fn or uint8, k_scale / v_scale [Bc, Lmax, Hkv] float32.  Writes codes and
+    scales at [b, start_pos + s]; returns the rotated q [B, S, H, Dh], rope_kv_store_natural's bits."""
+    who = "rope_kv_store_natural_fp8"
+    for t in (qkv, freqs, k_cache, v_cache, k_scale, v_scale):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        _kv8_codes(who, name, t)
+        if t.device != qkv.device or t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous [Bc, Lmax, Hkv, Dh] tensor on the GPU of qkv")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"{who}: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]")
+    Bc, Lmax, Hkv, Dh = v_cache.shape
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.device != qkv.device or t.dtype != torch.float32 or tuple(t.shape) != (Bc, Lmax, Hkv) or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous float32 [Bc, Lmax, Hkv] tensor on the GPU of qkv")
+    if freqs.device != qkv.device or freqs.dtype != torch.float32 or not freqs.is_contiguous():
+        raise ValueError(f"{who}: contiguous float32 freqs on the GPU of qkv are expected")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
+        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
+    B, S = qkv.shape[0], qkv.shape[1]
+    rot = freqs.shape[-1]
+    if freqs.numel() < B * S * rot:
+        raise ValueError(f"{who}: freqs holds fewer than B * S * rot_dim angles")
+    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _capi.check(_capi.lib().awq_rope_kv_store_natural_fp8(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+                                                              v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), B, Bc, S, int(nheads),
+                                                              int(nheads_kv), Dh, rot, Lmax, int(start_pos), qkv.stride(0), qkv.stride(1),
+                                                              _dt(qkv), _stream(qkv)))
+    return q_out
+
+
+def _check_kv8(who, q, k, v, k_scale, v_scale):
+    for t in (q, k, v, k_scale, v_scale):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+        if t.device != q.device:
+            raise ValueError(f"{who}: q, k, v and the scales must live on the same GPU")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+            raise ValueError(f"{who}: {name} must be [B, S, heads, Dh] with contiguous heads")
+    _kv8_codes(who, "k", k)
+    _kv8_codes(who, "v", v)
+    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k / v [B, Sk, Hkv, Dh] are expected")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(k.shape[:3]) or t.stride(2) != 1:
+            raise ValueError(f"{who}: {name} must be float32 [B, Sk, Hkv] with a unit last stride")
+
+
+def _attn_kv8(entry, q, k, v, k_scale, v_scale, softmax_scale, causal, checked=False):
+    if not checked:  # (attn_kv8 has checked the tensors already)
+        _check_kv8("attn_" + entry + "_kv8", q, k, v, k_scale, v_scale)
+    B, Sq, H, Dh = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    L = _capi.lib()
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), out.data_ptr(), B, Sq, Sk, H, Hkv, Dh,
+            q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), k_scale.stride(0), k_scale.stride(1),
+            v_scale.stride(0), v_scale.stride(1), scale, int(bool(causal)), _dt(q))
+    with torch.cuda.device(q.device):
+        if entry == "prefill":
+            _capi.check(L.awq_attn_prefill_kv8(*head, _stream(q)))
+        else:
+            wsb = L.awq_attn_splitkv_workspace_bytes(B, H, Hkv, Dh, Sq, Sk, int(bool(causal)))
+            ws = torch.empty(wsb, dtype=torch.uint8, device=q.device) if wsb else None
+            _capi.check(L.awq_attn_splitkv_kv8(*head, ws.data_ptr() if wsb else None, wsb, _stream(q)))
+    return out
+
+
+def attn_prefill_kv8(q, k, v, k_scale, v_scale, softmax_scale=None, causal: bool = False):
+    """C-ABI awq_attn_prefill_kv8: flash_attn_func's one-pass kernel with K / V read from the FP8 cache.  q [B, Sq, H, Dh] float16 /
+    bfloat16, k / v [B, Sk, Hkv, Dh] float8_e4m3fn or uint8 (batch and row strides of their own, multiples of 16), k_scale / v_scale
+    [B, Sk, Hkv] float32.  Bit-identical to the one-pass kernel on kv8_dequant(k, k_scale, q.dtype), kv8_dequant(v, v_scale, q.dtype)."""
+    return _attn_kv8("prefill", q, k, v, k_scale, v_scale, softmax_scale, causal)
+
+
+def attn_splitkv_kv8(q, k, v, k_scale, v_scale, softmax_scale=None, causal: bool = False):
+    """C-ABI awq_attn_splitkv_kv8: attn_splitkv with K / V read from the FP8 cache (attn_prefill_kv8's arguments); the one-pass launch
+    where attn_splitkv_plan does not split.  Bit-identical to attn_splitkv on the dequantised tensors."""
+    return _attn_kv8("splitkv", q, k, v, k_scale, v_scale, softmax_scale, causal)
+
+
+def attn_kv8(q, k, v, k_scale, v_scale, softmax_scale=None, causal: bool = False):
+    """flash_attn_func on the FP8 cache: routed by attn_splitkv_plan exactly as flash_attn_func routes (the split-KV kernels where the plan
+    splits, the one-pass kernel otherwise).  Dh 64 or 128."""
+    _check_kv8("attn_kv8", q, k, v, k_scale, v_scale)
+    B, Sq, H, Dh = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    if min(B, Sq, Sk, Hkv) >= 1 and Dh in (64, 128) and H % Hkv == 0 and not (causal and Sq > Sk) and \
+            attn_splitkv_plan(B, H, Hkv, Dh, Sq, Sk, causal)[0] > 1:
+        return _attn_kv8("splitkv", q, k, v, k_scale, v_scale, softmax_scale, causal, checked=True)
+    return _attn_kv8("prefill", q, k, v, k_scale, v_scale, softmax_scale, causal, checked=True)
+
+
 def _ft_caches(who, ref, k_cache, v_cache):
     """(Bc, Hkv, Lmax, Dh) of the FT caches k_cache [Bc, Hkv, Dh/8, Lmax, 8] / v_cache [Bc, Hkv, Lmax, Dh], checked against `ref`."""
     for t in (ref, k_cache, v_cache):
