@@ -189,19 +189,30 @@ __device__ __forceinline__ u32x4 ldg_nt_u32x4(const u32* p) {
 
 
 // QuantLlamaMLP's elementwise tail on eight packed T values (fused_mlp.py:79-82): c = T(T(silu(gate)) * up), silu in fp32 on the
-// T-rounded gate -- the same roundings as the reference's separate F.silu and multiply, and as the decode epilogues.  This is
-// the prefill form: 32 k evaluations per 256 x 256 tile sit in the tile's exposed epilogue, so silu is x * rcp(1 + exp2(-x log2 e))
-// on the hardware transcendentals (5 VALU, ~3 ulp of fp32 -- it changes the T rounding of ~0.05 % (bf16) / 0.2 % (fp16) of the
-// outputs by one ulp of T against an exact silu, which is also how far torch's own GPU silu sits from its CPU one); libm's expf and
-// an IEEE division cost ~40 instructions = +9 % on the gate/up GEMM at M = 2048.  The decode epilogues use the same form (silu_f32).
+// T-rounded gate -- the same roundings as the reference's separate F.silu and multiply, and as the decode epilogues.
 // The ONE fp32 silu of the library (decode and prefill epilogues alike, so a row's QuantLlamaMLP output does not depend on how many
-// rows were batched with it): x * rcp(1 + exp2(-x log2 e)) on the hardware transcendentals.  Below x = -64 the reciprocal of 1 + e^-x (~1e-38 at
-// x = -87.5) falls under the smallest normal fp32 number and the hardware returns 0, while torch's x / (1 + e^-x) keeps silu ~ -9e-37, a normal
-// bf16 value: there the denominator is scaled by 2^-64 before the reciprocal and the product by 2^-64 after it -- exact power-of-two scalings,
-// so every other input gives the same bits as the unscaled form.
+// rows were batched with it): x * rcp(1 + exp2(-x log2 e)) on the hardware transcendentals -- libm's expf and an IEEE division cost ~40
+// instructions = +9 % on the gate/up GEMM at M = 2048 (32 k evaluations per 256 x 256 tile sit in the tile's exposed epilogue).
+// Accuracy: relative error <= (4 + |x| w) 2^-23 with w = e^-x / (1 + e^-x) -- the rounded product x log2 e costs |x| 2^-24 in the exponential
+// (~40 ulp of fp32 at x = -80, not the "~3 ulp" once claimed here; it is damped by w, so positive gates stay within ~4 ulp), v_exp_f32 and
+// v_rcp_f32 one ulp each, the add and the multiplies half an ulp each.  Against an exact silu that changes the T rounding of 0.4 % of the bf16
+// and 0.1 % of the fp16 gate values by one code (tests/tail_oracle.py silu_hull; swept over every gate pattern by tests/test_gpu_tails.py).
+// Below x = -64 the reciprocal of 1 + e^-x (~1e-38 at x = -87.5) falls under the smallest normal fp32 number and the hardware returns 0, and
+// from x = -88.73 on exp2 itself overflows, while x / (1 + e^-x) keeps a nonzero bf16 value down to x = -97: there the whole denominator is
+// scaled by 2^-64 -- exp2(a - 64) + 2^-64, the same bits as (1 + exp2(a)) 2^-64 wherever that does not overflow -- and the product by 2^-64
+// after the reciprocal.  Exact power-of-two scalings, so every other input gives the same bits as the unscaled form.
+// The two empty asm statements pin roundings the compiler would otherwise merge: x log2 e must be rounded before the -64 is added (contracted
+// into one fma the exponent of the -88.7 .. -64 band would round differently), and the result must exist in fp32 before it is rounded to T
+// (fused into v_fma_mixlo_f16, which adds +0, a product of -0 -- every fp16 gate below the exp2 overflow -- came out as +0).
 __device__ __forceinline__ float silu_f32(float x) {
-  const float k = x < -64.0f ? 0x1p-64f : 1.0f;
-  return x * __builtin_amdgcn_rcpf((1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f)) * k) * k;
+  const bool deep = x < -64.0f;
+  const float k = deep ? 0x1p-64f : 1.0f;
+  float a = x * -1.4426950408889634f;
+  asm("" : "+v"(a));
+  const float e = __builtin_amdgcn_exp2f(a + (deep ? -64.0f : 0.0f));
+  float s = x * __builtin_amdgcn_rcpf(k + e) * k;
+  asm("" : "+v"(s));
+  return s;
 }
 template <typename DT>
 __device__ __forceinline__ u32 silu_mul_pair(u32 gate2, u32 up2) {

@@ -436,9 +436,13 @@ def assert_lattice_equal(got: torch.Tensor, want: torch.Tensor, what: str = "", 
 
 def check_fused_tail_exact(y: torch.Tensor, gate: torch.Tensor, up: torch.Tensor, what: str = "fused tail"):
     """gate / up = the EXACT T-rounded products (lattice): y must lie in the hull over {silu -, silu, silu +} of T(T(silu(gate)) * up) -- the
-    hardware exp2 / rcp may move T(silu) by one ulp, nothing else may differ"""
+    hardware exp2 / rcp may move T(silu) by one ulp, nothing else may differ.  silu is torch's on the GPU, except below -88 where torch's own
+    fp32 evaluation x / (1 + exp(-x)) overflows and returns -0 for gates whose silu is a nonzero bf16 value (down to -97): there it is the float64
+    value rounded to T (tests/test_gpu_tails.py holds every gate to the float64 hull)."""
     gate, up = gate.to(y.device), up.to(y.device)
-    vals = [(sg * up).float() for sg in _nbrs(torch.nn.functional.silu(gate))]
+    gd = gate.double()
+    silu = torch.where(gd < -88.0, (gd / (1.0 + torch.exp(-gd))).to(gate.dtype), torch.nn.functional.silu(gate))
+    vals = [(sg * up).float() for sg in _nbrs(silu)]
     lo = torch.minimum(torch.minimum(vals[0], vals[1]), vals[2])
     hi = torch.maximum(torch.maximum(vals[0], vals[1]), vals[2])
     yf = y.float()
