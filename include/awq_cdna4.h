@@ -455,6 +455,62 @@ int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const floa
                          long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- The natural-layout decode path with per-sequence lengths read ON THE DEVICE (flash_attn_with_kvcache's cache_seqlens): a batch whose
+ *      sequences have different lengths in one call, and one captured graph for the whole decode phase (nothing that changes from token to
+ *      token is a launch argument).  The host never reads the length arrays and never synchronises.
+ * awq_rope_kv_store_natural_pos[_fp8]: awq_rope_kv_store_natural[_fp8] with cache_seqlens (device int32 [batch], 4-byte aligned: the tokens
+ *     already in each sequence's cache) in the place of start_pos, and freqs_table (fp32 [table_rows, rot_dim], contiguous, 16-byte
+ *     aligned: the model's whole angle table) in the place of the call's angles.  Token s of sequence b is written at cache position
+ *     cache_seqlens[b] + s with the angles freqs_table[(cache_seqlens[b] + s) * rot_dim + c].  The arithmetic is the host-position kernel's,
+ *     expression for expression: for every active sequence q_out[b], the written cache rows and scales hold the bits
+ *     awq_rope_kv_store_natural[_fp8] leaves when called with batch = 1, start_pos = cache_seqlens[b] and freqs = freqs_table + start_pos *
+ *     rot_dim.  A sequence is ACTIVE iff 0 <= cache_seqlens[b] and cache_seqlens[b] + seqlen <= min(lmax, table_rows).  For an inactive
+ *     sequence (a finished slot of a static batch, -1, or a corrupt length) nothing is written to the caches or the scales, its q_out rows
+ *     are written as zeros and no address outside the tensors is formed.  Error rules of awq_rope_kv_store_natural[_fp8] without those of
+ *     start_pos; table_rows < 1 is AWQ_ERR_SHAPE, cache_seqlens NULL is AWQ_ERR_NULL, not 4-byte aligned AWQ_ERR_ALIGN.
+ * awq_attn_kvcache[_kv8]: the split-KV kernel pair of awq_attn_splitkv[_kv8] with seqlen_k replaced by seqlens_k (device int32 [batch],
+ *     4-byte aligned), seqlen_offset (a host int added to every entry: pass seqlen_q with the cache_seqlens the store launch took, 0 when
+ *     the caller holds total lengths) and max_seqlen_k (the host bound that sizes the plan, as timestep does in awq_attn_decode).  k_cache /
+ *     v_cache are the caches [>= batch, lmax, Hkv, Dh] with their batch and row strides; max_seqlen_k <= lmax.
+ *     Sk_b = seqlens_k[b] + seqlen_offset; sequence b is ACTIVE iff 1 <= Sk_b <= max_seqlen_k.  The causal mask is bottom-right aligned per
+ *     sequence: row i attends keys j <= i + Sk_b - seqlen_q; a row whose limit is negative (Sk_b < seqlen_q) attends nothing and returns
+ *     zeros; an inactive sequence returns zeros and nothing of its cache rows is read.  No NaN or Inf is produced from finite attended
+ *     inputs, and the combine never divides by L = 0.  Cache rows >= Sk_b are never read.
+ *     ALWAYS the split pair: seqlen_q * (nheads / nheads_kv) <= 128 and head_dim 64 / 128 are requirements (AWQ_ERR_SHAPE otherwise); a
+ *     longer prompt goes through the host-length entries.  Both launches run for any *splits, 1 included.  A block whose split begins at
+ *     or beyond Sk_b, or whose sequence is inactive, writes m = -inf, l = 0 and leaves before its first load of K / V: a ragged batch
+ *     costs what its lengths cost.  The per-split arithmetic is awq_attn_splitkv's and the combine skips m = -inf partials in ascending
+ *     order, so for every active sequence with Sk_b > *chunk, out[b] is bit-identical to awq_attn_splitkv on that sequence alone (batch
+ *     1, seqlen_k = Sk_b) under the same forced chunk; the _kv8 form is bit-identical to the T form on the dequantised caches.  No atomics:
+ *     bit-deterministic and capturable, workspace included.
+ *     Returns the codes of awq_attn_splitkv[_kv8], all but AWQ_ERR_LAUNCH without a GPU call; in addition AWQ_ERR_NULL for seqlens_k,
+ *     AWQ_ERR_ALIGN when it is not 4-byte aligned, AWQ_ERR_SHAPE for max_seqlen_k < 1, max_seqlen_k > lmax or seqlen_offset < 0.  The
+ *     workspace is always needed (AWQ_ERR_WORKSPACE when NULL or smaller than awq_attn_kvcache_workspace_bytes).
+ * awq_attn_kvcache_plan: host only, made from the bound alone (never from a length).  awq_attn_splitkv_plan's chunk rule -- two blocks per
+ *     CU, *chunk % 64 == 0, *chunk >= 1024 -- without the 2048-key floor and the one-pass test: *splits >= 1, *splits * *chunk >=
+ *     max_seqlen_k.  The rule counts the nheads_kv groups of ONE sequence: batch is validated but does not enter, because any sequence
+ *     of a ragged batch may be the only long one.  Follows the knob "attn_splitkv_chunk".
+ * awq_attn_kvcache_workspace_bytes: batch * nheads * seqlen_q * splits * (head_dim + 2) * 4; 0 for a shape the plan refuses. */
+int awq_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                      float* v_scale, const int* cache_seqlens, int batch, int cache_batch, int seqlen, int nheads,
+                                      int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
+                                      long long qkv_row_stride, int dtype, void* stream);
+int awq_attn_kvcache_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k, int* splits, int* chunk);
+size_t awq_attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k);
+int awq_attn_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
+                     int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                     long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                     float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                         long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                         long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

@@ -101,6 +101,16 @@ SIGNATURES = {
     "awq_attn_prefill_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 + [ctypes.c_float, _i, _i, _vp]),
     "awq_attn_splitkv_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
                              [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_rope_kv_store_natural_pos": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong,
+                                           ctypes.c_longlong, _i, _vp]),
+    "awq_rope_kv_store_natural_pos_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong,
+                                               ctypes.c_longlong, _i, _vp]),
+    "awq_attn_kvcache_plan": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_attn_kvcache_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "awq_attn_kvcache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 6 +
+                         [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_kvcache_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
+                             [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

@@ -17,6 +17,7 @@
 //     would be Lmax * 16 bytes apart).  Their loads are 16 bytes per row of qkv; K is Hkv / (H + 2 Hkv) of the tensor.
 // Nothing outside positions [start_pos, start_pos + S) of cache rows b < B is written.
 #include "awq_device.hpp"
+#include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 
 #include <math.h>
@@ -32,6 +33,7 @@ struct RopeStoreArgs {
   uint16_t* v_cache;
   long long bs, rs;  // qkv batch / row strides, elements
   int B, S, H, Hkv, rot, lmax, start, qv_blocks;
+  const int* seqlens;  // DevLen only: device int32 [B], the tokens already in each sequence's cache
 };
 
 template <typename DT>
@@ -114,8 +116,14 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
 // two rope calls and two slice stores cache[:B, start : start + S] = x).  A cache row is Hkv * DH contiguous elements, like the K and the
 // V part of a qkv row, so one mapping serves all three outputs: one thread = 8 consecutive columns of one (b, s), the column chunk
 // fastest, over the H query heads, the Hkv key heads and the Hkv value heads.  The rotation is the expression above, unchanged.
+//
+// DevLen<..> (awq_devlen.hpp, awq_rope_kv_store_natural_pos): the position of sequence b is read on the device.  a.freqs is then the model's
+// whole angle table [table rows, rot] (a.start carries the row count) and pos_b = a.seqlens[b]: token s goes to cache position pos_b + s and
+// takes the angles of table row pos_b + s.  A sequence with pos_b < 0 or pos_b + S > min(lmax, table rows) is inactive: its q_out rows are
+// written as zeros, nothing else is written and no address is formed from pos_b.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArgs a) {
+  constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.S * CPR) return;
@@ -126,7 +134,15 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArg
   const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
   const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
   uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
-  const long long crow = ((long long)b * a.lmax + a.start + s) * a.Hkv * DH + c0;
+  int start = a.start;
+  if constexpr (DEVLEN) {
+    start = a.seqlens[b];
+    if (start < 0 || (long long)start + a.S > (long long)min(a.lmax, a.start)) {
+      for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = u32x4{0u, 0u, 0u, 0u};
+      return;
+    }
+  }
+  const long long crow = ((long long)b * a.lmax + start + s) * a.Hkv * DH + c0;
   uint16_t* kd = a.k_cache + crow;
   uint16_t* vd = a.v_cache + crow;
 
@@ -134,7 +150,7 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArg
     for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = *reinterpret_cast<const u32x4*>(row + hd * DH + c0);
     for (int hd = 0; hd < a.Hkv; ++hd) *reinterpret_cast<u32x4*>(kd + hd * DH) = *reinterpret_cast<const u32x4*>(ks + hd * DH + c0);
   } else {
-    const float* fr = a.freqs + ((long long)s * a.B + b) * a.rot + c0;
+    const float* fr = a.freqs + (DEVLEN ? (long long)start + s : (long long)s * a.B + b) * a.rot + c0;
     const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
     const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
     float cs[8], sn[8];
@@ -164,7 +180,7 @@ int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void*
   const long long n = (long long)B * S * (Dh / 8);
   const int nb = (int)((n + 255) / 256);
   RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
-                  start_pos, nb};
+                  start_pos, nb, nullptr};
   const dim3 grid((unsigned)(2 * nb));
   if (dtype == 0) {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<F16, 128>), grid, dim3(256), 0, st, a);
@@ -181,7 +197,7 @@ int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_ou
   const long long n = (long long)B * S * (Dh / 8);
   const int nb = (int)((n + 255) / 256);
   RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
-                  start_pos, nb};
+                  start_pos, nb, nullptr};
   const dim3 grid((unsigned)nb);
   if (dtype == 0) {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<F16, 128>), grid, dim3(256), 0, st, a);
@@ -189,6 +205,25 @@ int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_ou
   } else {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+// cache_seqlens on the device in the place of start_pos, the whole angle table [table_rows, rot] in the place of the call's angles
+int launch_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache,
+                                     const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int table_rows,
+                                     long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  const int nb = (int)((n + 255) / 256);
+  RopeStoreArgs a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot,
+                  lmax, table_rows, nb, cache_seqlens};
+  const dim3 grid((unsigned)nb);
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<F16>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<F16>, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
   }
   return 0;
 }

@@ -18,6 +18,7 @@
 // 8 code bytes of its chunk (8 or 16 lanes write one contiguous 64- or 128-byte row); the lane of chunk 0 stores the scale, an ordinary
 // 4-byte store.  Nothing outside positions [start_pos, start_pos + S) of cache rows b < B is written, in the caches or in the scales.
 #include "awq_device.hpp"
+#include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
 
@@ -36,6 +37,7 @@ struct RopeStoreFp8Args {
   float* v_scale;
   long long bs, rs;  // qkv batch / row strides, elements
   int B, S, H, Hkv, rot, lmax, start;
+  const int* seqlens;  // DevLen only: device int32 [B], the tokens already in each sequence's cache
 };
 
 template <typename DT>
@@ -55,8 +57,14 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
   return u32x4{ws[0], ws[1], ws[2], ws[3]};
 }
 
+//
+// DevLen<..> (awq_devlen.hpp, awq_rope_kv_store_natural_pos_fp8): rope_kv_store_natural_kernel's device positions.  a.freqs is the whole
+// angle table [a.start rows, rot], pos_b = a.seqlens[b]; an inactive sequence (pos_b < 0 or pos_b + S > min(lmax, table rows)) gets a zero
+// q_out and nothing else.  The CPR lanes of a (b, s) share b, so they leave or stay together and the butterflies below never meet a lane
+// that has left.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStoreFp8Args a) {
+  constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.S * CPR) return;  // (the CPR lanes of a (b, s) leave or stay together)
@@ -68,7 +76,15 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
   const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
   const uint16_t* vs = row + (long long)(a.H + a.Hkv) * DH;
   uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
-  const long long tok = ((long long)b * a.lmax + a.start + s) * a.Hkv;  // (token, head 0) of the caches and of the scales
+  int start = a.start;
+  if constexpr (DEVLEN) {
+    start = a.seqlens[b];
+    if (start < 0 || (long long)start + a.S > (long long)min(a.lmax, a.start)) {
+      for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = u32x4{0u, 0u, 0u, 0u};
+      return;
+    }
+  }
+  const long long tok = ((long long)b * a.lmax + start + s) * a.Hkv;  // (token, head 0) of the caches and of the scales
 
   // one head row of T (this lane's chunk w of it) -> codes and scale
   auto quant_store = [&](const u32x4& w, uint8_t* cache, float* scale, int hd) {
@@ -91,7 +107,7 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
   int pc = c0;
   float sign = 1.f;
   if (rot_lane) {
-    const float* fr = a.freqs + ((long long)s * a.B + b) * a.rot + c0;
+    const float* fr = a.freqs + (DEVLEN ? (long long)start + s : (long long)s * a.B + b) * a.rot + c0;
     const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
     const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
 #pragma unroll
@@ -123,7 +139,7 @@ int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* 
                                      long long rs, int dtype, hipStream_t st) {
   const long long n = (long long)B * S * (Dh / 8);
   RopeStoreFp8Args a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, bs, rs, B, S, H, Hkv,
-                     rot, lmax, start_pos};
+                     rot, lmax, start_pos, nullptr};
   const dim3 grid((unsigned)((n + 255) / 256));
   if (dtype == 0) {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<F16, 128>), grid, dim3(256), 0, st, a);
@@ -131,6 +147,23 @@ int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* 
   } else {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+int launch_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                         float* v_scale, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax,
+                                         int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, bs, rs, B, S, H,
+                     Hkv, rot, lmax, table_rows, cache_seqlens};
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<F16>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<F16>, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
   }
   return 0;
 }

@@ -31,7 +31,12 @@
 // one 64-key softmax per tile on one wave) is several times shorter than the HBM time of a tile at one or two blocks per CU.  This is
 // reasoning from the code, not an A/B: the key-split form was not built.  tools/splitkv_attn_bench.py times the kernel as a whole
 // (README.md: 0.46 of 8 TB/s at 131072 keys, 16x the one-pass kernel at 32768 keys, Llama-3-8B, one token).
+//
+// awq_attn_kvcache[_kv8] is the same pair with every sequence's length read on the device (DevLen<..> instantiations, awq_devlen.hpp): the
+// grid and the chunk come from a host bound (attn_kvcache_plan), blocks beyond a sequence's length leave at once, and the pair runs for
+// any number of splits.  tools/kvcache_attn_bench.py prices it (README.md "Device-side lengths").
 #include "awq_device.hpp"
+#include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
 
@@ -72,6 +77,10 @@ struct SplitArgs {
   const float* k_scale;
   const float* v_scale;
   long long ks_bs, ks_rs, vs_bs, vs_rs;
+  // DevLen only (awq_devlen.hpp): the length of sequence b is seqlens_k[b] + seqlen_offset, read by the kernel; Sk above is then the
+  // host's bound max_seqlen_k, which sized the grid
+  const int* seqlens_k;
+  int seqlen_offset;
 };
 
 // LDS images of awq_attn_prefill_cdna4.hip, restated: rows of DH elements, the 16-byte chunks of a row permuted by an XOR of the row.
@@ -89,9 +98,15 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // Kv8<DT> (awq_kv8.hpp) is the FP8 cache: the staging loads the 8 code bytes of the thread's chunk and the row's scale (same
 // c = tid + i * NT mapping, same clamp to Sk - 1), dequantises T(float(code) * s) and writes the same 16 bytes into the same LDS slot.
 // The 8-byte form is the one kept in both attention kernels (the reason is the prefill kernel's: awq_attn_prefill_cdna4.hip).
+//
+// DevLen<..> (awq_devlen.hpp, awq_attn_kvcache): Sk_b = seqlens_k[b] + seqlen_offset stands wherever a.Sk stands in the host-length form.
+// A block whose sequence is inactive (Sk_b < 1 or Sk_b > a.Sk, the bound) or whose first key lies at or beyond Sk_b is EMPTY: it writes
+// m = -inf, l = 0 for its rows and leaves before its first load of q, K, V or a scale.  The test is uniform over the block (b comes from
+// blockIdx, the length is one scalar load) and no barrier precedes it.  A ragged batch therefore costs what its lengths cost.
 template <typename DT, int DH>
 __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
   constexpr bool KV8 = IsKv8<DT>::value;
+  constexpr bool DEVLEN = IsDevLen<DT>::value;
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -110,18 +125,31 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
   bi /= a.splits;
   const int kvh = bi % a.Hkv;
   const int b = bi / a.Hkv;
-  const int shift = a.Sk - a.Sq;
-  const int k_begin = split * a.chunk;                  // < Sk: (splits - 1) * chunk < Sk
-  const int k_end = min(a.Sk, k_begin + a.chunk);       // keys [k_begin, k_end) are this block's
+  const int k_begin = split * a.chunk;                  // < Sk: (splits - 1) * chunk < Sk (DevLen: or the block is empty)
+  int Sk = a.Sk;
+  if constexpr (DEVLEN) {
+    const long long len = (long long)a.seqlens_k[b] + a.seqlen_offset;  // 64 bits: no entry can wrap into an active length
+    Sk = (int)len;
+    if (len < 1 || len > a.Sk || k_begin >= Sk) {  // empty
+      if (tid < a.R) {
+        const long long e = (((long long)b * a.Hkv + kvh) * a.R + tid) * a.splits + split;
+        a.ws_m[e] = -INFINITY;
+        a.ws_l[e] = 0.f;
+      }
+      return;
+    }
+  }
+  const int shift = Sk - a.Sq;
+  const int k_end = min(Sk, k_begin + a.chunk);         // keys [k_begin, k_end) are this block's
   const int nt = (k_end - k_begin + kKV - 1) / kKV;
 
   const int wr0 = wave * kMfmaRows;                     // first packed row of the wave
   const bool wave_on = wr0 < a.R;                       // (a wave without rows still stages K / V and meets the barriers)
   const int pr = min(wr0 + r, a.R - 1);                 // rows >= R compute row R - 1 again and are not stored
   const int qi = pr / a.G, h = kvh * a.G + pr % a.G;    // packed row = i * G + g
-  const int lim = a.causal ? qi + shift : a.Sk - 1;                                   // last key this lane's row attends
-  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, a.R - 1) / a.G + shift : a.Sk - 1;  // .. any row of the wave
-  const int wave_min = a.causal ? wr0 / a.G + shift : a.Sk - 1;                       // every row of the wave attends keys <= this
+  const int lim = a.causal ? qi + shift : Sk - 1;                                     // last key this lane's row attends
+  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, a.R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
+  const int wave_min = a.causal ? wr0 / a.G + shift : Sk - 1;                         // every row of the wave attends keys <= this
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   vec8 qf[KS];
@@ -144,7 +172,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-      const long long g = min(t0 + row, a.Sk - 1);  // no row >= Sk is read
+      const long long g = min(t0 + row, Sk - 1);    // no row >= Sk is read
       if constexpr (KV8) {
         kr[i] = *reinterpret_cast<const u32x2*>(kb8 + g * a.k_rs + ch * 8);
         vr[i] = *reinterpret_cast<const u32x2*>(vb8 + g * a.v_rs + ch * 8);
@@ -278,6 +306,8 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
   }
 }
 
+// DevLen<..>: a row may have attended nothing at all (its sequence is inactive, or Sk_b < Sq and the row's causal limit is negative); then
+// every m_s is -inf, M = -inf and L = 0, and the row is written as zeros without the division.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) {
   constexpr int CPR = DH / 8;
@@ -306,6 +336,12 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) 
     for (int e = 0; e < 4; ++e) {
       acc[e] = __builtin_fmaf(w, o0[e], acc[e]);
       acc[4 + e] = __builtin_fmaf(w, o1[e], acc[4 + e]);
+    }
+  }
+  if constexpr (IsDevLen<DT>::value) {
+    if (M == -INFINITY) {  // nothing attended: zeros, never 0 / 0
+      *reinterpret_cast<u32x4*>(a.out + ((b * a.Sq + pr / a.G) * a.H + kvh * a.G + pr % a.G) * DH + ch * 8) = u32x4{0u, 0u, 0u, 0u};
+      return;
     }
   }
   const float inv = 1.0f / L;
@@ -363,27 +399,59 @@ int attn_splitkv_tune_set(const char* key, int value) {
   return 0;
 }
 
+// Host plan of the device-length form (awq_attn_kvcache): made from the bound max_seqlen_k alone, never from a length.  The chunk rule
+// above (two blocks per CU, a multiple of 64, at least 1024 keys, or the knob) without the 2048-key floor and the one-pass test: the
+// split pair always runs, splits >= 1 and splits * chunk >= max_seqlen_k.
+// The rule counts the KV heads of ONE sequence, not batch * nheads_kv: the plan cannot know how many sequences of the batch are long, and
+// a batch is as slow as its longest sequence.  Counting the batch (the first form of this plan) gave the 131072-key sequence of the
+// ragged batch of tools/kvcache_attn_bench.py 8 splits of 16384 keys, 64 live blocks on 256 CUs: 444 us against 320 us for the seven
+// per-sequence calls (profiles/kvcache_attn_bench.json keeps that row as "ragged_batch_rule").  Sized for one sequence, a full batch of
+// long sequences gets batch times as many blocks of the same chunk as a single sequence does; the blocks beyond a sequence's length leave
+// at once.  The 1024-key floor is carried over from the host-length plan; under a loose bound it is not the best choice (README.md).
+int attn_kvcache_plan(int batch, int nheads_kv, int max_seqlen_k, int* splits, int* chunk) {
+  (void)batch;
+  int c = g_force_chunk;
+  if (!c) {
+    const long long groups = nheads_kv;
+    const long long want = groups >= 2 * kCUs ? 1 : (2 * kCUs + groups - 1) / groups;
+    c = (int)(max_seqlen_k / want / kKV * kKV);
+    if (c < kMinChunk) c = kMinChunk;
+  }
+  *splits = (int)(((long long)max_seqlen_k + c - 1) / c);
+  *chunk = c;
+  return 0;
+}
+
+size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k) {
+  int splits = 1, chunk = 0;
+  attn_kvcache_plan(batch, nheads_kv, max_seqlen_k, &splits, &chunk);
+  return (size_t)batch * nheads * seqlen_q * splits * (head_dim + 2) * sizeof(float);
+}
+
 namespace {
 
 // Both launches of one call.  K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
 // partials only, so it is the T cache's in either case.
-template <template <typename> class K>
+// L is the identity for host lengths and DevLen for lengths on the device.
+template <typename DT>
+using HostLen = DT;
+template <template <typename> class K, template <typename> class L = HostLen>
 void launch_pair(const SplitArgs& a, int Dh, int dtype, dim3 grid, dim3 cgrid, hipStream_t st) {
   if (dtype == 0) {
     if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<K<F16>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 128>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<F16>, 128>), cgrid, dim3(256), 0, st, a);
     } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<K<F16>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<F16, 64>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<F16>, 64>), cgrid, dim3(256), 0, st, a);
     }
   } else {
     if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<K<BF16>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 128>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<BF16>, 128>), cgrid, dim3(256), 0, st, a);
     } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<K<BF16>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<BF16, 64>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<BF16>, 64>), cgrid, dim3(256), 0, st, a);
     }
   }
 }
@@ -422,6 +490,8 @@ SplitArgs split_args(const void* q, const void* k, const void* v, void* out, int
   a.ws_l = a.ws_m + n;
   a.k_scale = a.v_scale = nullptr;
   a.ks_bs = a.ks_rs = a.vs_bs = a.vs_rs = 0;
+  a.seqlens_k = nullptr;
+  a.seqlen_offset = 0;
   return a;
 }
 
@@ -454,6 +524,33 @@ int launch_attn_splitkv_kv8(const void* q, const void* k, const void* v, const f
   const dim3 grid((unsigned)((long long)B * Hkv * splits));
   const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
   launch_pair<Kv8>(a, Dh, dtype, grid, cgrid, st);
+  return 0;
+}
+
+// The device-length pair (awq_attn_kvcache[_kv8]): k / v are the caches, the Sk of the arguments is the bound max_seqlen_k (<= the cache
+// length, so the clamp to Sk_b - 1 <= max_seqlen_k - 1 stays inside the sequence's cache rows), k_scale == nullptr selects the T cache.
+// The caller has validated the arguments and holds a workspace of attn_kvcache_workspace_bytes.
+int launch_attn_kvcache(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                        const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
+                        long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs,
+                        long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st) {
+  SplitArgs a = split_args(q, k, v, out, B, Sq, max_seqlen_k, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk,
+                           workspace);
+  a.seqlens_k = seqlens_k;
+  a.seqlen_offset = seqlen_offset;
+  const dim3 grid((unsigned)((long long)B * Hkv * splits));
+  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
+  if (k_scale) {
+    a.k_scale = k_scale;
+    a.v_scale = v_scale;
+    a.ks_bs = ks_bs;
+    a.ks_rs = ks_rs;
+    a.vs_bs = vs_bs;
+    a.vs_rs = vs_rs;
+    launch_pair<Kv8, DevLen>(a, Dh, dtype, grid, cgrid, st);
+  } else {
+    launch_pair<TCache, DevLen>(a, Dh, dtype, grid, cgrid, st);
+  }
   return 0;
 }
 

@@ -550,6 +550,131 @@ int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const floa
   return finish_launch();
 }
 
+// ---- lengths on the device: the natural-layout decode path for ragged batches and whole-phase graph capture (awq_devlen.hpp) ----
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// the shape rules both store entries share (awq_rope_kv_store_natural's, with table_rows in the place of start_pos)
+static bool store_pos_shape_ok(int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                               int table_rows, long long qkv_batch_stride, long long qkv_row_stride) {
+  return batch >= 1 && cache_batch >= batch && seqlen >= 1 && nheads >= 1 && nheads_kv >= 1 && (head_dim == 64 || head_dim == 128) &&
+         rot_dim >= 16 && (rot_dim % 16) == 0 && rot_dim <= head_dim && lmax >= 1 && table_rows >= 1 && qkv_batch_stride >= 0 &&
+         qkv_row_stride >= ((long long)nheads + 2ll * nheads_kv) * head_dim && (long long)batch * seqlen * (head_dim / 8) <= 0x3FFFFFFFll * 256;
+}
+
+int awq_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs_table || !q_out || !k_cache || !v_cache || !cache_seqlens) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!store_pos_shape_ok(batch, cache_batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride))
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
+      !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store_natural_pos(qkv, freqs_table, q_out, k_cache, v_cache, cache_seqlens, batch, seqlen, nheads, nheads_kv, head_dim,
+                                        rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                      float* v_scale, const int* cache_seqlens, int batch, int cache_batch, int seqlen, int nheads,
+                                      int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
+                                      long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs_table || !q_out || !k_cache || !v_cache || !k_scale || !v_scale || !cache_seqlens) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!store_pos_shape_ok(batch, cache_batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride))
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned4(k_scale) ||
+      !aligned4(v_scale) || !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store_natural_pos_fp8(qkv, freqs_table, q_out, k_cache, v_cache, k_scale, v_scale, cache_seqlens, batch, seqlen, nheads,
+                                            nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride, dtype,
+                                            (hipStream_t)stream);
+  return finish_launch();
+}
+
+// the split pair always runs here: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions
+static bool kvcache_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k) {
+  return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 && (head_dim == 64 || head_dim == 128) && seqlen_q >= 1 &&
+         (long long)seqlen_q * (nheads / nheads_kv) <= 128 && max_seqlen_k >= 1;
+}
+
+int awq_attn_kvcache_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k, int* splits, int* chunk) {
+  if (!splits || !chunk) return AWQ_ERR_NULL;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k)) return AWQ_ERR_SHAPE;
+  return awq::attn_kvcache_plan(batch, nheads_kv, max_seqlen_k, splits, chunk);
+}
+
+size_t awq_attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k) {
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k)) return 0;
+  return awq::attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k);
+}
+
+// the checks both cache formats share behind their pointer / stride checks; AWQ_OK: *splits / *chunk hold the plan and the launch may go on
+static int kvcache_check(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, const int* seqlens_k, int seqlen_offset,
+                         int max_seqlen_k, int lmax, const void* workspace, size_t workspace_bytes, int* splits, int* chunk) {
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || max_seqlen_k > lmax || seqlen_offset < 0)
+    return AWQ_ERR_SHAPE;
+  if (!aligned4(seqlens_k)) return AWQ_ERR_ALIGN;
+  awq::attn_kvcache_plan(batch, nheads_kv, max_seqlen_k, splits, chunk);
+  if (!workspace || workspace_bytes < awq::attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k))
+    return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
+  if ((long long)batch * nheads_kv * *splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
+  return AWQ_OK;
+}
+
+int awq_attn_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
+                     int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                     long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                     float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k_cache || !v_cache || !out || !seqlens_k) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || q_batch_stride < 0 || k_batch_stride < 0 ||
+      v_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
+      v_row_stride < (long long)nheads_kv * head_dim)
+    return AWQ_ERR_SHAPE;
+  int splits = 1, chunk = 0;
+  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 ||
+      (v_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, lmax, workspace,
+                               workspace_bytes, &splits, &chunk);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_kvcache(q, k_cache, v_cache, nullptr, nullptr, out, batch, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv,
+                           head_dim, q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, 0, 0, 0, 0,
+                           softmax_scale, causal, dtype, splits, chunk, workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                         long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                         long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k_cache || !v_cache || !k_scale || !v_scale || !out || !seqlens_k) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || q_batch_stride < 0 || k_batch_stride < 0 ||
+      v_batch_stride < 0 || k_scale_batch_stride < 0 || v_scale_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim ||
+      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv ||
+      v_scale_row_stride < nheads_kv)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || !aligned4(k_scale) || !aligned4(v_scale) ||
+      (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_batch_stride % 16) != 0 || (k_row_stride % 16) != 0 ||
+      (v_batch_stride % 16) != 0 || (v_row_stride % 16) != 0)
+    return AWQ_ERR_ALIGN;
+  int splits = 1, chunk = 0;
+  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, lmax, workspace,
+                               workspace_bytes, &splits, &chunk);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_kvcache(q, k_cache, v_cache, k_scale, v_scale, out, batch, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv,
+                           head_dim, q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride,
+                           k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, splits,
+                           chunk, workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {
   return nseq >= 1 && nheads >= 1 && (head_dim == 64 || head_dim == 72) && max_seqlen >= 1 &&
          (long long)nseq * nheads * ((max_seqlen + 31) / 32) <= 0x7FFFFFFFll;

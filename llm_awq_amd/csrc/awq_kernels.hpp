@@ -206,6 +206,20 @@ int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const f
 int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale,
                                      float* v_scale, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int start_pos, long long bs,
                                      long long rs, int dtype, hipStream_t st);
+// lengths on the device (awq_devlen.hpp): the store launch with cache_seqlens [B] and the whole angle table, and the split-KV pair with
+// seqlens_k [B] under a host bound max_seqlen_k (k_scale == nullptr: the T cache); arguments validated by the caller
+int launch_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache,
+                                     const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int table_rows,
+                                     long long bs, long long rs, int dtype, hipStream_t st);
+int launch_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                         float* v_scale, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax,
+                                         int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
+int attn_kvcache_plan(int batch, int nheads_kv, int max_seqlen_k, int* splits, int* chunk);
+size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k);
+int launch_attn_kvcache(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
+                        const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
+                        long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs,
+                        long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

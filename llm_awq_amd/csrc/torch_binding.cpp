@@ -968,6 +968,152 @@ torch::Tensor attn_splitkv_kv8(const torch::Tensor q, const torch::Tensor k, con
   return attn_kv8_impl("attn_splitkv_kv8", true, q, k, v, k_scale, v_scale, softmax_scale, causal);
 }
 
+// ---- lengths on the device (include/awq_cdna4.h: awq_rope_kv_store_natural_pos[_fp8], awq_attn_kvcache[_kv8]) ----
+static void check_seqlens(const char* who, const char* name, const torch::Tensor& t, const torch::Tensor& ref, int64_t batch) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), who, ": ", name, " must live on the GPU of the input (it is read by the kernel only)");
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 1 && t.size(0) == batch && t.is_contiguous(), who, ": ", name,
+              " must be a contiguous int32 [B] tensor");
+}
+
+// the store launch of both cache formats; fp8: the caches hold codes and k_scale / v_scale are defined
+static torch::Tensor rope_store_pos_impl(const char* who, bool fp8, const torch::Tensor& qkv, const torch::Tensor& freqs_table,
+                                         torch::Tensor& k_cache, torch::Tensor& v_cache, torch::Tensor* k_scale, torch::Tensor* v_scale,
+                                         const torch::Tensor& cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs_table.is_cuda() && freqs_table.device() == qkv.device(), who, ": tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
+  TORCH_CHECK(freqs_table.scalar_type() == at::kFloat && freqs_table.dim() == 2 && freqs_table.is_contiguous() &&
+                  (reinterpret_cast<uintptr_t>(freqs_table.data_ptr()) & 15) == 0,
+              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device(), who, ": the caches must live on the GPU of the input");
+    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == qkv.scalar_type(), who,
+                fp8 ? ": the caches must be float8_e4m3fn or uint8, got " : ": the caches must have the dtype of the input, got ", t->scalar_type());
+    TORCH_CHECK(t->dim() == 4 && t->is_contiguous(), who, ": contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] are expected");
+  }
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who, ": k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
+  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rows = freqs_table.size(0),
+                rot = freqs_table.size(1);
+  if (fp8)
+    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
+      TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->is_contiguous() &&
+                      t->size(0) == cache_batch && t->size(1) == lmax && t->size(2) == v_cache.size(2),
+                  who, ": k_scale / v_scale must be contiguous float32 [Bc, Lmax, Hkv] tensors on the GPU of the input");
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(qkv.dim() == 3, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
+              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
+  TORCH_CHECK(batch <= cache_batch, who, ": batch ", batch, " exceeds the cache batch ", cache_batch);
+  TORCH_CHECK(rows >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
+              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
+  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor x = qkv;
+  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (fp8)
+    raise_on(awq_rope_kv_store_natural_pos_fp8(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(),
+                                               v_cache.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
+                                               cache_seqlens.data_ptr<int>(), (int)batch, (int)cache_batch, (int)seqlen, (int)nheads,
+                                               (int)nheads_kv, (int)headdim, (int)rot, (int)lmax, (int)rows, x.stride(0), x.stride(1),
+                                               dtype_code(x), st));
+  else
+    raise_on(awq_rope_kv_store_natural_pos(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                           cache_seqlens.data_ptr<int>(), (int)batch, (int)cache_batch, (int)seqlen, (int)nheads, (int)nheads_kv,
+                                           (int)headdim, (int)rot, (int)lmax, (int)rows, x.stride(0), x.stride(1), dtype_code(x), st));
+  return q_out;
+}
+
+// rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural with each
+// sequence's position read on the device (cache_seqlens int32 [B]) and the angles taken from the whole table freqs_table [P, rot_dim].
+torch::Tensor rope_kv_store_natural_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                        const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_pos_impl("rope_kv_store_natural_pos", false, qkv, freqs_table, k_cache, v_cache, nullptr, nullptr, cache_seqlens, nheads,
+                             nheads_kv);
+}
+
+torch::Tensor rope_kv_store_natural_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                            torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cache_seqlens, int64_t nheads,
+                                            int64_t nheads_kv) {
+  return rope_store_pos_impl("rope_kv_store_natural_pos_fp8", true, qkv, freqs_table, k_cache, v_cache, &k_scale, &v_scale, cache_seqlens, nheads,
+                             nheads_kv);
+}
+
+// attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: the split-KV pair over the
+// natural-layout caches with Sk_b = seqlens_k[b] + seqlen_offset read on the device.  The fp32 partials live in a buffer of torch's caching
+// allocator, so a graph capture owns them.
+static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+                                       const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& seqlens_k,
+                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  const bool fp8 = k_scale != nullptr;
+  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who, ": q [B, Sq, H, Dh], k_cache / v_cache [Bc, Lmax, Hkv, Dh]");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), lmax = k.size(1), nheads_kv = k.size(2);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k, &v}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), who, ": the caches must live on the GPU of q");
+    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == q.scalar_type(), who,
+                fp8 ? ": the caches must be float8_e4m3fn or uint8, got " : ": the caches must have the dtype of q, got ", t->scalar_type());
+  }
+  TORCH_CHECK(v.sizes() == k.sizes() && k.size(0) >= batch && k.size(3) == headdim, who, ": k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ", headdim,
+              "] of one shape");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+              ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
+              " exceeds 128 (the split kernels serve few query rows; a prompt goes through the host-length path)");
+  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= lmax, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", lmax, " (the cache length)");
+  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == headdim, who, ": the heads of q and of the caches must be contiguous");
+  if (fp8)
+    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
+      TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == k.size(0) &&
+                      t->size(1) == lmax && t->size(2) == nheads_kv && t->stride(2) == 1,
+                  who, ": k_scale / v_scale must be float32 [Bc, Lmax, Hkv] of the caches with a unit last stride");
+  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
+  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (fp8)
+    raise_on(awq_attn_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(), out.data_ptr(),
+                                  (int)batch, (int)sq, seqlens_k.data_ptr<int>(), (int)seqlen_offset, (int)max_seqlen_k, (int)lmax, (int)nheads,
+                                  (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                                  k_scale->stride(0), k_scale->stride(1), v_scale->stride(0), v_scale->stride(1), (float)softmax_scale,
+                                  causal ? 1 : 0, dtype_code(q), ws.data_ptr(), wsb, st));
+  else
+    raise_on(awq_attn_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)batch, (int)sq, seqlens_k.data_ptr<int>(),
+                              (int)seqlen_offset, (int)max_seqlen_k, (int)lmax, (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1),
+                              k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+                              ws.data_ptr(), wsb, st));
+  return out;
+}
+
+torch::Tensor attn_kvcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor seqlens_k,
+                           int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache", q, k_cache, v_cache, nullptr, nullptr, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal);
+}
+
+torch::Tensor attn_kvcache_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                               const torch::Tensor v_scale, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset,
+                               double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache_kv8", q, k_cache, v_cache, &k_scale, &v_scale, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale,
+                           causal);
+}
+
+// (splits, chunk) of awq_attn_kvcache_plan, made from the bound alone.  Host only.
+std::tuple<int64_t, int64_t> attn_kvcache_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t seqlen_q,
+                                               int64_t max_seqlen_k) {
+  int splits = 1, chunk = 0;
+  raise_on(awq_attn_kvcache_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)seqlen_q, (int)max_seqlen_k, &splits, &chunk));
+  return {splits, chunk};
+}
+
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
 // (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
 // kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
@@ -1276,6 +1422,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("k_scale"), py::arg("v_scale"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_splitkv_kv8", &attn_splitkv_kv8, "attn_splitkv with k / v read from e4m3 codes and per-(key, KV head) fp32 scales", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("k_scale"), py::arg("v_scale"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("rope_kv_store_natural_pos", &rope_kv_store_natural_pos,
+        "rope_kv_store_natural with positions read on the device: cache_seqlens int32 [B], freqs_table [P, rot_dim] the whole angle table",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_seqlens"), py::arg("nheads"),
+        py::arg("nheads_kv"));
+  m.def("rope_kv_store_natural_pos_fp8", &rope_kv_store_natural_pos_fp8, "rope_kv_store_natural_pos on the FP8 cache", py::arg("qkv"),
+        py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cache_seqlens"),
+        py::arg("nheads"), py::arg("nheads_kv"));
+  m.def("attn_kvcache", &attn_kvcache,
+        "Split-KV attention over natural-layout caches with per-sequence lengths seqlens_k[b] + seqlen_offset read on the device", py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"),
+        py::arg("causal"));
+  m.def("attn_kvcache_kv8", &attn_kvcache_kv8, "attn_kvcache with the caches read from e4m3 codes and per-(key, KV head) fp32 scales",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_kvcache_plan", &attn_kvcache_plan, "(splits, chunk) of attn_kvcache, made from the bound max_seqlen_k alone", py::arg("batch"),
+        py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("seqlen_q"), py::arg("max_seqlen_k"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

@@ -14,6 +14,10 @@ them under `flash_attn.` as well.
 
 Only what tinychat imports exists here: `flash_attn_func` and `flash_attn_varlen_qkvpacked_func`, forward only, no dropout, no sliding
 window, no ALiBi.  Anything else that is asked for raises NotImplementedError naming the keyword -- never a silent approximation.
+
+`flash_attn_with_kvcache` is what a decode engine with continuous batching or a captured decode graph asks of flash-attn: per-sequence
+lengths in a device tensor.  It is served for an already updated cache (`k` / `v` None) by the split-KV kernels with device-side lengths
+(`attn_kvcache`, csrc/awq_attn_splitkv_cdna4.hip).
 """
 from __future__ import annotations
 
@@ -52,6 +56,36 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, **
     if _plan_splits(eng, q, k, causal):
         return eng.attn_splitkv(q, k, v, scale, bool(causal))
     return eng.attn_prefill(q, k, v, scale, bool(causal))
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None, cache_batch_idx=None,
+                            cache_leftpad=None, block_table=None, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                            rotary_interleaved=True, alibi_slopes=None, num_splits=0, return_softmax_lse=False):
+    """flash_attn.flash_attn_with_kvcache's forward for a cache that is already up to date: q [B, Sq, H, Dh], k_cache / v_cache
+    [Bc >= B, Lmax, Hkv, Dh], cache_seqlens the TOTAL length of every sequence as an int32 tensor [B] on the GPU (read by the kernels only:
+    no host copy, no sync, capturable) or an int -> [B, Sq, H, Dh].  Served by `attn_kvcache` with max_seqlen_k = Lmax: Sq * (H / Hkv) <= 128,
+    Dh 64 or 128.  A sequence whose length is < 1 or > Lmax returns zeros.  `cache_seqlens=None` attends the whole cache
+    (`flash_attn_func`).  Appending k / v, rotary_cos / rotary_sin, block_table, cache_batch_idx, cache_leftpad, a window, softcap, ALiBi
+    and the softmax LSE are not implemented and raise NotImplementedError naming the argument (`rotary_interleaved` and `num_splits`
+    have nothing to act on and are ignored: there is no rotation here, and the split count is the plan's)."""
+    asked = {"k": k, "v": v, "rotary_cos": rotary_cos, "rotary_sin": rotary_sin, "cache_batch_idx": cache_batch_idx,
+             "cache_leftpad": cache_leftpad, "block_table": block_table, "window_size": window_size, "softcap": softcap,
+             "alibi_slopes": alibi_slopes, "return_softmax_lse": return_softmax_lse}
+    for name, value in asked.items():
+        if not _is_off(name, value):
+            shown = f"tensor{tuple(value.shape)}" if hasattr(value, "shape") else repr(value)
+            raise NotImplementedError(f"flash_attn_with_kvcache on MI355X: {name}={shown} is not implemented (the cache must already hold "
+                                      "the new tokens; cache_seqlens are total lengths)")
+    if cache_seqlens is None:
+        return flash_attn_func(q, k_cache[:q.shape[0]], v_cache[:q.shape[0]], softmax_scale=softmax_scale, causal=causal)
+    import torch
+
+    from . import load_engine
+
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
+    scale = float(q.shape[-1]) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    return load_engine().attn_kvcache(q, k_cache, v_cache, cache_seqlens, int(k_cache.shape[1]), 0, scale, bool(causal))
 
 
 def _plan_splits(eng, q, k, causal) -> bool:
@@ -119,8 +153,9 @@ def _namespace(name, **members):
 
 
 flash_attn_interface = _namespace("flash_attn_interface", flash_attn_func=flash_attn_func,
-                                  flash_attn_varlen_qkvpacked_func=flash_attn_varlen_qkvpacked_func)
+                                  flash_attn_varlen_qkvpacked_func=flash_attn_varlen_qkvpacked_func,
+                                  flash_attn_with_kvcache=flash_attn_with_kvcache)
 bert_padding = _namespace("bert_padding", unpad_input=unpad_input, pad_input=pad_input, index_first_axis=index_first_axis)
 SUBMODULES = {"flash_attn_interface": flash_attn_interface, "bert_padding": bert_padding}
 
-__all__ = ["flash_attn_func", "flash_attn_varlen_qkvpacked_func", "flash_attn_interface", "bert_padding"]
+__all__ = ["flash_attn_func", "flash_attn_varlen_qkvpacked_func", "flash_attn_with_kvcache", "flash_attn_interface", "bert_padding"]

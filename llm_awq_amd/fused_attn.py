@@ -25,6 +25,11 @@ and `cache_k_scale` / `cache_v_scale` [B, L, Hkv] one fp32 scale per (token, KV 
 streams.  Every call is `rope_kv_store_natural_fp8` (rotation, quantisation and store in one launch) followed by `ops.attn_kv8`, the same
 two attention kernels with the dequantisation in their staging step (csrc/awq_kv8.hpp); the result is, bit for bit, the T-cache path's on
 the dequantised caches.
+
+With `kv_layout="natural"`, `forward` also takes `start_pos` as an int32 device tensor [bsz] (and `freqs` as the whole angle table): the
+store launch and the split-KV attention then read every sequence's position on the device (`rope_kv_store_natural_pos[_fp8]`,
+`attn_kvcache[_kv8]`).  One call serves a batch whose sequences have different lengths, and one captured graph replays the whole decode
+phase while the caller advances the tensor in place.  An int `start_pos` takes the path above, bit for bit.
 """
 from __future__ import annotations
 
@@ -91,10 +96,17 @@ class QuantLlamaAttentionFused(nn.Module):
                                    device=dev)
 
     @torch.no_grad()
-    def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False):
-        """`mask` is accepted and ignored, as in the reference's short_forward: the attention is causal."""
+    def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False, decode_max_seqlen=None):
+        """`mask` is accepted and ignored, as in the reference's short_forward: the attention is causal.
+
+        With `kv_layout="natural"`, `start_pos` may be an int32 tensor [bsz] on the GPU: the tokens already in each sequence's cache, read
+        by the kernels only (a ragged batch in one call; a captured graph replays any position).  `freqs` is then the model's whole angle
+        table [P, rot_dim] and `decode_max_seqlen` (default `kv_max_seq_len`) the host bound on start_pos + seqlen that sizes the attention
+        launch.  A sequence with start_pos[b] < 0 is a finished slot: nothing is stored for it and its attention rows are zeros."""
         eng = load_engine()
         bsz, seqlen, _ = x.shape
+        if isinstance(start_pos, torch.Tensor):
+            return self._forward_device_pos(eng, x, start_pos, freqs, decode_max_seqlen)
         xqkv = self.qkv_proj(x)
         if self.kv_dtype == "fp8":  # the caches keep their dtype: only the device follows the activations
             from . import ops
@@ -133,6 +145,31 @@ class QuantLlamaAttentionFused(nn.Module):
                                                 self.rope_scaling, True)
             output = output.reshape(bsz, 1, -1)
         return self.o_proj(output)
+
+    def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen):
+        """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host."""
+        if self.kv_layout != "natural":
+            raise ValueError("QuantLlamaAttentionFused: a tensor start_pos needs kv_layout 'natural' (the FT-layout path takes start_pos as "
+                             "an int; its decode kernel reads per-sequence lengths through single_query_attention's length_per_sample)")
+        bsz, seqlen, _ = x.shape
+        bound = self.kv_max_seq_len if decode_max_seqlen is None else int(decode_max_seqlen)
+        xqkv = self.qkv_proj(x).reshape(bsz, seqlen, -1)
+        scale = self.head_dim ** -0.5
+        if self.kv_dtype == "fp8":
+            if self.cache_k.device != xqkv.device:
+                for name in ("cache_k", "cache_v", "cache_k_scale", "cache_v_scale"):
+                    setattr(self, name, getattr(self, name).to(xqkv.device))
+            xq = eng.rope_kv_store_natural_pos_fp8(xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos,
+                                                   self.n_local_heads, self.num_key_value_heads)
+            output = eng.attn_kvcache_kv8(xq, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos, bound, seqlen,
+                                          scale, True)
+        else:
+            if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:
+                self.cache_k = self.cache_k.to(xqkv)
+                self.cache_v = self.cache_v.to(xqkv)
+            xq = eng.rope_kv_store_natural_pos(xqkv, freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads, self.num_key_value_heads)
+            output = eng.attn_kvcache(xq, self.cache_k, self.cache_v, start_pos, bound, seqlen, scale, True)
+        return self.o_proj(output.view(bsz, seqlen, -1))
 
 
 QuantLlamaAttentionFusedFlash = QuantLlamaAttentionFused

@@ -742,6 +742,118 @@ def attn_kv8(q, k, v, k_scale, v_scale, softmax_scale=None, causal: bool = False
     return _attn_kv8("prefill", q, k, v, k_scale, v_scale, softmax_scale, causal, checked=True)
 
 
+# ---- lengths on the device: ragged batched decode and whole-phase graph capture on the natural-layout caches ------------------------
+def attn_kvcache_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, seqlen_q: int, max_seqlen_k: int):
+    """Host-side awq_attn_kvcache_plan: (splits, chunk) of attn_kvcache, made from the bound max_seqlen_k alone (no GPU needed).  splits >= 1
+    and splits * chunk >= max_seqlen_k; the split kernel pair runs for any splits.  Sized for one sequence at the bound: `batch` does
+    not change it."""
+    import ctypes
+
+    s, c = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_kvcache_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k, ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
+def _check_seqlens(who, name, t, ref, batch):
+    if not t.is_cuda:
+        raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if t.device != ref.device or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != batch or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous int32 [B] tensor on the GPU of the input")
+
+
+def attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None, causal: bool = True,
+                 k_scale=None, v_scale=None):
+    """C-ABI awq_attn_kvcache[_kv8]: split-KV attention of q [B, Sq, H, Dh] over the natural-layout caches k_cache / v_cache
+    [Bc >= B, Lmax, Hkv, Dh] with each sequence's length read on the device: Sk_b = seqlens_k[b] + seqlen_offset, seqlens_k int32 [B].
+    max_seqlen_k <= Lmax is the host bound that sizes the launch; a sequence with Sk_b < 1 or Sk_b > max_seqlen_k is inactive and returns
+    zeros.  Causal rows attend keys j <= i + Sk_b - Sq.  Sq * (H / Hkv) <= 128, Dh 64 or 128.  With k_scale / v_scale [Bc, Lmax, Hkv]
+    float32 the caches are FP8 codes (kv8_quant's format).  The host never reads seqlens_k: the call is capturable and a replay follows the
+    lengths the tensor holds then."""
+    who = "attn_kvcache"
+    fp8 = k_scale is not None or v_scale is not None
+    if fp8:
+        if k_scale is None or v_scale is None:
+            raise ValueError(f"{who}: k_scale and v_scale come together")
+        nb = q.shape[0]  # (the checks of the host-length FP8 entries, on the batch rows this call reads)
+        _check_kv8(who, q, k_cache[:nb], v_cache[:nb], k_scale[:nb], v_scale[:nb])
+    else:
+        for t in (q, k_cache, v_cache):
+            if not t.is_cuda:
+                raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+            if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+                raise ValueError(f"{who}: q / k_cache / v_cache must be [B, S, heads, Dh] with contiguous heads")
+        if k_cache.device != q.device or v_cache.device != q.device or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+            raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
+        if k_cache.shape != v_cache.shape or k_cache.shape[0] < q.shape[0] or k_cache.shape[3] != q.shape[3]:
+            raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_cache / v_cache [Bc >= B, Lmax, Hkv, Dh] are expected")
+    B, Sq, H, Dh = q.shape
+    Lmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    L = _capi.lib()
+    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, Hkv, Dh, Sq, int(max_seqlen_k))
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
+    lens = (B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k), Lmax, H, Hkv, Dh)
+    strides = (q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1))
+    tail = (scale, int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q))
+    with torch.cuda.device(q.device):
+        if fp8:
+            _capi.check(L.awq_attn_kvcache_kv8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+                                               out.data_ptr(), *lens, *strides, k_scale.stride(0), k_scale.stride(1), v_scale.stride(0),
+                                               v_scale.stride(1), *tail))
+        else:
+            _capi.check(L.awq_attn_kvcache(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), *lens, *strides, *tail))
+    return out
+
+
+def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
+    """C-ABI awq_rope_kv_store_natural_pos[_fp8]: rope_kv_store_natural[_fp8] with each sequence's position read on the device.
+    cache_seqlens int32 [B] holds the tokens already in each sequence's cache; token s of sequence b is rotated by row
+    cache_seqlens[b] + s of freqs_table [P, rot_dim] (float32, the model's whole angle table) and stored at that cache position.  A
+    sequence with cache_seqlens[b] < 0 or cache_seqlens[b] + S > min(Lmax, P) is inactive: nothing of it is stored and its q rows are
+    zeros.  With k_scale / v_scale the caches are FP8 (rope_kv_store_natural_fp8's arguments).  Returns the rotated q [B, S, H, Dh]."""
+    who = "rope_kv_store_natural_pos"
+    fp8 = k_scale is not None or v_scale is not None
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError(f"{who}: k_scale and v_scale come together")
+    for t in (qkv, freqs_table, k_cache, v_cache, cache_seqlens) + ((k_scale, v_scale) if fp8 else ()):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if fp8:
+            _kv8_codes(who, name, t)
+        elif t.dtype != qkv.dtype:
+            raise ValueError(f"{who}: the caches must have the dtype of the input")
+        if t.device != qkv.device or t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous [Bc, Lmax, Hkv, Dh] tensor on the GPU of qkv")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"{who}: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]")
+    Bc, Lmax, Hkv, Dh = v_cache.shape
+    if fp8:
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.device != qkv.device or t.dtype != torch.float32 or tuple(t.shape) != (Bc, Lmax, Hkv) or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous float32 [Bc, Lmax, Hkv] tensor on the GPU of qkv")
+    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
+        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
+        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
+    B, S = qkv.shape[0], qkv.shape[1]
+    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
+    P, rot = freqs_table.shape
+    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
+    tail = (B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax, P, qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
+    with torch.cuda.device(qkv.device):
+        if fp8:
+            _capi.check(_capi.lib().awq_rope_kv_store_natural_pos_fp8(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+                                                                      v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+                                                                      cache_seqlens.data_ptr(), *tail))
+        else:
+            _capi.check(_capi.lib().awq_rope_kv_store_natural_pos(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
+                                                                  v_cache.data_ptr(), cache_seqlens.data_ptr(), *tail))
+    return q_out
+
+
 def _ft_caches(who, ref, k_cache, v_cache):
     """(Bc, Hkv, Lmax, Dh) of the FT caches k_cache [Bc, Hkv, Dh/8, Lmax, 8] / v_cache [Bc, Hkv, Lmax, Dh], checked against `ref`."""
     for t in (ref, k_cache, v_cache):
