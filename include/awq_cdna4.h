@@ -511,6 +511,57 @@ int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache
                          long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The same decode path over a PAGED KV cache (flash_attn_with_kvcache's block_table): a pool of fixed-size pages and a per-sequence
+ *      block table in the place of the dense [batch, lmax, Hkv, Dh] rectangle, so a sequence holds the pages its tokens need and a finished
+ *      slot holds none.  Nothing about the table or the lengths reaches the host: capturable, and a replay follows the table's contents.
+ * Pool: k_pool / v_pool [num_pages, page_size, Hkv, Dh] of T (the _fp8 / _kv8 entries: e4m3 codes) with a page stride and a row stride each,
+ *     in elements (codes: bytes), heads contiguous; the scale pools k_scale / v_scale [num_pages, page_size, Hkv] fp32 with a page and a row
+ *     stride each, in floats.  page_size >= 64 and page_size % 64 == 0 (the key tile of the kernels is 64 keys and every chunk is a multiple
+ *     of 64, so a tile never straddles a page).
+ * Table: block_table, device int32 [batch, pages_per_seq], 4-byte aligned, row stride table_row_stride >= pages_per_seq (entries).  Logical
+ *     position p of sequence b is row p % page_size of page block_table[b * table_row_stride + p / page_size].  A page id is clamped into
+ *     [0, num_pages) before it forms an address, so no address outside the pools is ever formed; the result for a sequence with such an
+ *     entry inside its live range is unspecified.  No entry at index >= ceil(Sk_b / page_size) (store: >= ceil((pos_b + seqlen) /
+ *     page_size)) is read.  Two sequences may name the same page (a shared prefix): the attention only reads.
+ * awq_rope_kv_store_paged_pos[_fp8]: awq_rope_kv_store_natural_pos[_fp8] writing token s of sequence b at logical position p =
+ *     cache_seqlens[b] + s through the table, the page looked up per token (a chunk may cross page edges).  A sequence is ACTIVE iff
+ *     0 <= cache_seqlens[b] and cache_seqlens[b] + seqlen <= min(pages_per_seq * page_size, table_rows); an inactive sequence gets zero
+ *     q_out rows and nothing else.  The pool rows (and scale rows) the table names hold the bits awq_rope_kv_store_natural_pos[_fp8] leaves
+ *     in the dense cache, q_out is that entry's, and no other byte of the pools or the scale pools is written.
+ * awq_attn_kvcache_paged[_kv8]: awq_attn_kvcache[_kv8] with the K / V rows and the scales fetched through the table: same plan
+ *     (awq_attn_kvcache_plan from max_seqlen_k alone), same workspace (awq_attn_kvcache_workspace_bytes), same combine launch, empty-block
+ *     rule, masks and rounding points.  For every active sequence out[b] is bit-identical to awq_attn_kvcache[_kv8] on the dense gather
+ *     cache[b, p] = pool[block_table[b, p / page_size], p % page_size] under the same (forced or planned) chunk.  The page id of a 64-key
+ *     tile is one scalar load, issued a tile ahead of the K / V loads that use it.  No atomics: bit-deterministic, workspace included.
+ * Returns the codes of the dense entries (without those of cache_batch and lmax), all but AWQ_ERR_LAUNCH without a GPU call; in addition
+ *     AWQ_ERR_NULL for block_table, AWQ_ERR_ALIGN when it is not 4-byte aligned or a pool stride is not a multiple of 16 bytes,
+ *     AWQ_ERR_SHAPE for page_size < 64 or page_size % 64 != 0, num_pages < 1, pages_per_seq < 1, table_row_stride < pages_per_seq, a negative
+ *     page stride, a row stride below Hkv * Dh (scales: below Hkv) and, for the attention, max_seqlen_k > pages_per_seq * page_size. */
+int awq_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                const int* cache_seqlens, int batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                    float* v_scale, const int* block_table, const int* cache_seqlens, int batch, int seqlen, int nheads,
+                                    int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                    long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                    long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                    long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_batch_stride,
+                                    long long qkv_row_stride, int dtype, void* stream);
+int awq_attn_kvcache_paged(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch, int seqlen_q,
+                           const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size, int pages_per_seq,
+                           long long table_row_stride, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, float softmax_scale,
+                           int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                               const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                               int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                               int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                               long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

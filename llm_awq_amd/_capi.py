@@ -111,6 +111,12 @@ SIGNATURES = {
                          [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_kvcache_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
                              [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_rope_kv_store_paged_pos": (_i, [_vp] * 7 + [_i] * 10 + [ctypes.c_longlong] * 7 + [_i, _vp]),
+    "awq_rope_kv_store_paged_pos_fp8": (_i, [_vp] * 9 + [_i] * 10 + [ctypes.c_longlong] * 11 + [_i, _vp]),
+    "awq_attn_kvcache_paged": (_i, [_vp] * 5 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 6 +
+                               [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_kvcache_paged_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
+                                   [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

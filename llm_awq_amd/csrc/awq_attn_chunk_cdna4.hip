@@ -19,6 +19,7 @@
 #include "awq_device.hpp"
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
+#include "awq_paged.hpp"
 
 #include <math.h>
 
@@ -34,6 +35,9 @@ struct RopeStoreArgs {
   long long bs, rs;  // qkv batch / row strides, elements
   int B, S, H, Hkv, rot, lmax, start, qv_blocks;
   const int* seqlens;  // DevLen only: device int32 [B], the tokens already in each sequence's cache
+  // Paged only (awq_paged.hpp): k_cache / v_cache are the pools, page and row strides in elements; lmax = min(pages_per_seq * page_size, INT_MAX)
+  PageArgs pg;
+  long long k_ps, k_rs, v_ps, v_rs;
 };
 
 template <typename DT>
@@ -121,9 +125,15 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
 // whole angle table [table rows, rot] (a.start carries the row count) and pos_b = a.seqlens[b]: token s goes to cache position pos_b + s and
 // takes the angles of table row pos_b + s.  A sequence with pos_b < 0 or pos_b + S > min(lmax, table rows) is inactive: its q_out rows are
 // written as zeros, nothing else is written and no address is formed from pos_b.
+//
+// Paged<DevLen<..>> (awq_paged.hpp, awq_rope_kv_store_paged_pos): token s of an active sequence goes to row p % page_size of page
+// table[b][p / page_size], p = pos_b + s -- looked up per TOKEN, a chunk may cross page edges.  p < pages_per_seq * page_size for an active
+// sequence, so the table index lies inside the row; the id is clamped into the pool.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArgs a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
+  constexpr bool PAGED = IsPaged<DT>::value;
+  static_assert(!PAGED || DEVLEN, "the paged form reads its positions on the device");
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.S * CPR) return;
@@ -142,9 +152,15 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArg
       return;
     }
   }
-  const long long crow = ((long long)b * a.lmax + start + s) * a.Hkv * DH + c0;
+  long long crow = ((long long)b * a.lmax + start + s) * a.Hkv * DH + c0, vrow = crow;
+  if constexpr (PAGED) {
+    const int p = start + s, pi = p / a.pg.page_size;
+    const long long page = page_id(a.pg.block_table + (long long)b * a.pg.bt_rs, pi, a.pg.num_pages), pr = p - pi * a.pg.page_size;
+    crow = page * a.k_ps + pr * a.k_rs + c0;
+    vrow = page * a.v_ps + pr * a.v_rs + c0;
+  }
   uint16_t* kd = a.k_cache + crow;
-  uint16_t* vd = a.v_cache + crow;
+  uint16_t* vd = a.v_cache + vrow;
 
   if (c0 >= a.rot) {
     for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = *reinterpret_cast<const u32x4*>(row + hd * DH + c0);
@@ -224,6 +240,28 @@ int launch_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, 
   } else {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+// the pools and their table in the place of the caches: lmax = pages_per_seq * page_size (capped at INT_MAX: positions are int32)
+int launch_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                   long long table_row_stride, int page_size, int num_pages, int pages_per_seq, long long k_ps, long long k_rs,
+                                   long long v_ps, long long v_rs, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot,
+                                   int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  const int nb = (int)((n + 255) / 256);
+  const long long cap = (long long)pages_per_seq * page_size;
+  RopeStoreArgs a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint16_t*)k_pool, (uint16_t*)v_pool, bs, rs, B, S, H, Hkv, rot,
+                  (int)(cap < 0x7FFFFFFFll ? cap : 0x7FFFFFFFll), table_rows, nb, cache_seqlens,
+                  PageArgs{block_table, table_row_stride, page_size, num_pages}, k_ps, k_rs, v_ps, v_rs};
+  const dim3 grid((unsigned)nb);
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<F16>>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<F16>>, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<BF16>>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<BF16>>, 64>), grid, dim3(256), 0, st, a);
   }
   return 0;
 }

@@ -21,6 +21,7 @@
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
+#include "awq_paged.hpp"
 
 #include <math.h>
 
@@ -38,6 +39,10 @@ struct RopeStoreFp8Args {
   long long bs, rs;  // qkv batch / row strides, elements
   int B, S, H, Hkv, rot, lmax, start;
   const int* seqlens;  // DevLen only: device int32 [B], the tokens already in each sequence's cache
+  // Paged only (awq_paged.hpp): the caches and the scales are pools, page and row strides in codes (bytes) / in floats; lmax =
+  // min(pages_per_seq * page_size, INT_MAX)
+  PageArgs pg;
+  long long k_ps, k_rs, v_ps, v_rs, ks_ps, ks_rs, vs_ps, vs_rs;
 };
 
 template <typename DT>
@@ -62,9 +67,14 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
 // angle table [a.start rows, rot], pos_b = a.seqlens[b]; an inactive sequence (pos_b < 0 or pos_b + S > min(lmax, table rows)) gets a zero
 // q_out and nothing else.  The CPR lanes of a (b, s) share b, so they leave or stay together and the butterflies below never meet a lane
 // that has left.
+//
+// Paged<DevLen<..>> (awq_paged.hpp, awq_rope_kv_store_paged_pos_fp8): rope_kv_store_natural_kernel's paged form -- the token's page is looked
+// up in the table, codes and scales go to row p % page_size of that page in their pools.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStoreFp8Args a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
+  constexpr bool PAGED = IsPaged<DT>::value;
+  static_assert(!PAGED || DEVLEN, "the paged form reads its positions on the device");
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.S * CPR) return;  // (the CPR lanes of a (b, s) leave or stay together)
@@ -84,7 +94,18 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
       return;
     }
   }
-  const long long tok = ((long long)b * a.lmax + start + s) * a.Hkv;  // (token, head 0) of the caches and of the scales
+  // (token, head 0) of the caches and of the scales; Paged: 0, the pointers below carry the token's row of each pool
+  const long long tok = PAGED ? 0 : ((long long)b * a.lmax + start + s) * a.Hkv;
+  uint8_t *kc = a.k_cache, *vc = a.v_cache;
+  float *ksc = a.k_scale, *vsc = a.v_scale;
+  if constexpr (PAGED) {
+    const int p = start + s, pi = p / a.pg.page_size;
+    const long long page = page_id(a.pg.block_table + (long long)b * a.pg.bt_rs, pi, a.pg.num_pages), pr = p - pi * a.pg.page_size;
+    kc += page * a.k_ps + pr * a.k_rs;
+    vc += page * a.v_ps + pr * a.v_rs;
+    ksc += page * a.ks_ps + pr * a.ks_rs;
+    vsc += page * a.vs_ps + pr * a.vs_rs;
+  }
 
   // one head row of T (this lane's chunk w of it) -> codes and scale
   auto quant_store = [&](const u32x4& w, uint8_t* cache, float* scale, int hd) {
@@ -128,8 +149,8 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
   };
 
   for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = rotated(row + hd * DH);
-  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(rotated(ks + hd * DH), a.k_cache, a.k_scale, hd);
-  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), a.v_cache, a.v_scale, hd);
+  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(rotated(ks + hd * DH), kc, ksc, hd);
+  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), vc, vsc, hd);
 }
 
 }  // namespace
@@ -164,6 +185,27 @@ int launch_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_tab
   } else {
     if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
+  }
+  return 0;
+}
+
+int launch_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                       float* v_scale, const int* block_table, long long table_row_stride, int page_size, int num_pages,
+                                       int pages_per_seq, long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps,
+                                       long long ks_rs, long long vs_ps, long long vs_rs, const int* cache_seqlens, int B, int S, int H, int Hkv,
+                                       int Dh, int rot, int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
+  const long long n = (long long)B * S * (Dh / 8);
+  const long long cap = (long long)pages_per_seq * page_size;
+  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint8_t*)k_pool, (uint8_t*)v_pool, k_scale, v_scale, bs, rs, B, S, H,
+                     Hkv, rot, (int)(cap < 0x7FFFFFFFll ? cap : 0x7FFFFFFFll), table_rows, cache_seqlens,
+                     PageArgs{block_table, table_row_stride, page_size, num_pages}, k_ps, k_rs, v_ps, v_rs, ks_ps, ks_rs, vs_ps, vs_rs};
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0) {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<F16>>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<F16>>, 64>), grid, dim3(256), 0, st, a);
+  } else {
+    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<BF16>>, 128>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<BF16>>, 64>), grid, dim3(256), 0, st, a);
   }
   return 0;
 }

@@ -35,10 +35,14 @@
 // awq_attn_kvcache[_kv8] is the same pair with every sequence's length read on the device (DevLen<..> instantiations, awq_devlen.hpp): the
 // grid and the chunk come from a host bound (attn_kvcache_plan), blocks beyond a sequence's length leave at once, and the pair runs for
 // any number of splits.  tools/kvcache_attn_bench.py prices it (README.md "Device-side lengths").
+//
+// awq_attn_kvcache_paged[_kv8] is that pair again with K / V (and the scales) fetched from a pool of pages through a block table
+// (Paged<DevLen<..>> instantiations of the split kernel, awq_paged.hpp; the combine launch is the dense form's).
 #include "awq_device.hpp"
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
+#include "awq_paged.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -82,6 +86,15 @@ struct SplitArgs {
   const int* seqlens_k;
   int seqlen_offset;
 };
+// Paged only (awq_paged.hpp): k / v are the pools, k_bs / v_bs (ks_bs / vs_bs) their PAGE strides.  A struct of its own, so that the
+// argument block of the dense kernels -- and with it their register assignment and schedule -- stays what it was.
+struct PagedSplitArgs : SplitArgs {
+  PageArgs pg;
+};
+template <typename DT>
+using SplitArgsOf = typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type;
+__device__ __forceinline__ PageArgs page_args(const SplitArgs&) { return PageArgs{nullptr, 0, 0, 0}; }
+__device__ __forceinline__ PageArgs page_args(const PagedSplitArgs& a) { return a.pg; }
 
 // LDS images of awq_attn_prefill_cdna4.hip, restated: rows of DH elements, the 16-byte chunks of a row permuted by an XOR of the row.
 //   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
@@ -103,10 +116,20 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // A block whose sequence is inactive (Sk_b < 1 or Sk_b > a.Sk, the bound) or whose first key lies at or beyond Sk_b is EMPTY: it writes
 // m = -inf, l = 0 for its rows and leaves before its first load of q, K, V or a scale.  The test is uniform over the block (b comes from
 // blockIdx, the length is one scalar load) and no barrier precedes it.  A ragged batch therefore costs what its lengths cost.
+//
+// Paged<DevLen<..>> (awq_paged.hpp, awq_attn_kvcache_paged): key g of the sequence is row g % page_size of page table[b][g / page_size].  A
+// tile begins at a multiple of 64 and page_size % 64 == 0, so the 64 keys of a tile (and the clamp to Sk_b - 1, which stays inside the
+// tile) share ONE page: its id is uniform over the block, one scalar load per tile.  The ids run a tile ahead of the loads that use them:
+// tile t + 1's K / V loads of iteration t take an id that was loaded in iteration t - 1 (the first two in front of the loop), so no table
+// load stands between a barrier and the K / V loads behind it.  (pg_i, pg_ro) = (table index, first row inside the page) of the tile last
+// looked up; they advance by 64 rows, so the one division is the block's first.  Only tiles j < nt are looked up: their first key lies
+// below Sk_b, so no entry at or behind ceil(Sk_b / page_size) is read.  Everything behind the staging loads is the dense kernel.
 template <typename DT, int DH>
-__global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
+__global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> a) {
   constexpr bool KV8 = IsKv8<DT>::value;
   constexpr bool DEVLEN = IsDevLen<DT>::value;
+  constexpr bool PAGED = IsPaged<DT>::value;
+  static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -159,21 +182,34 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
   }
 
-  const uint16_t* kb = a.k + (long long)b * a.k_bs + (long long)kvh * DH;
-  const uint16_t* vb = a.v + (long long)b * a.v_bs + (long long)kvh * DH;
+  const long long pool_b = PAGED ? 0 : b;  // Paged: the pools have no batch dimension, the page offset is added per tile
+  const uint16_t* kb = a.k + pool_b * a.k_bs + (long long)kvh * DH;
+  const uint16_t* vb = a.v + pool_b * a.v_bs + (long long)kvh * DH;
   using stage_t = typename std::conditional<KV8, u32x2, u32x4>::type;
   stage_t kr[LOADS], vr[LOADS];
   float ksc[KV8 ? LOADS : 1], vsc[KV8 ? LOADS : 1];  // Kv8: the scale of the chunk's row
-  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + (long long)b * a.k_bs + (long long)kvh * DH;
-  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + (long long)b * a.v_bs + (long long)kvh * DH;
-  const float* ksb = KV8 ? a.k_scale + (long long)b * a.ks_bs + kvh : nullptr;
-  const float* vsb = KV8 ? a.v_scale + (long long)b * a.vs_bs + kvh : nullptr;
-  auto stage_load = [&](int t0) {
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + pool_b * a.k_bs + (long long)kvh * DH;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + pool_b * a.v_bs + (long long)kvh * DH;
+  const float* ksb = KV8 ? a.k_scale + pool_b * a.ks_bs + kvh : nullptr;
+  const float* vsb = KV8 ? a.v_scale + pool_b * a.vs_bs + kvh : nullptr;
+  // Paged: page = the (clamped) id of the tile's page, ro = the tile's first row inside it; unused otherwise
+  auto stage_load = [&](int t0, int page, int ro) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
       const long long g = min(t0 + row, Sk - 1);    // no row >= Sk is read
-      if constexpr (KV8) {
+      if constexpr (PAGED) {
+        const long long prow = ro + (g - t0);        // row of the page: < page_size, the tile does not straddle
+        if constexpr (KV8) {
+          kr[i] = *reinterpret_cast<const u32x2*>(kb8 + page * a.k_bs + prow * a.k_rs + ch * 8);
+          vr[i] = *reinterpret_cast<const u32x2*>(vb8 + page * a.v_bs + prow * a.v_rs + ch * 8);
+          ksc[i] = ksb[page * a.ks_bs + prow * a.ks_rs];
+          vsc[i] = vsb[page * a.vs_bs + prow * a.vs_rs];
+        } else {
+          kr[i] = *reinterpret_cast<const u32x4*>(kb + page * a.k_bs + prow * a.k_rs + ch * 8);
+          vr[i] = *reinterpret_cast<const u32x4*>(vb + page * a.v_bs + prow * a.v_rs + ch * 8);
+        }
+      } else if constexpr (KV8) {
         kr[i] = *reinterpret_cast<const u32x2*>(kb8 + g * a.k_rs + ch * 8);
         vr[i] = *reinterpret_cast<const u32x2*>(vb8 + g * a.v_rs + ch * 8);
         ksc[i] = ksb[g * a.ks_rs];
@@ -208,7 +244,30 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
   // transposed-read addressing: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p .. 4 p + 3 of the group's 4 x 16 block
   const int tr_q = (lane & 15) >> 2, tr_p = lane & 3, tr_g = (lane >> 4) & 1;
 
-  stage_load(k_begin);
+  // Paged: the ids of tiles 0 and 1, both in flight before the first K / V load is issued
+  const PageArgs pg = page_args(a);
+  const int* table = PAGED ? pg.block_table + (long long)b * pg.bt_rs : nullptr;
+  int pg_i = 0, pg_ro = 0, pg_cur = 0, ro_cur = 0, pg_nxt = 0, ro_nxt = 0;
+  auto next_page = [&]() {  // (pg_i, pg_ro) -> the tile 64 keys on; returns its page id
+    pg_ro += kKV;
+    if (pg_ro == pg.page_size) {
+      pg_ro = 0;
+      ++pg_i;
+    }
+    return page_id(table, pg_i, pg.num_pages);
+  };
+  if constexpr (PAGED) {
+    pg_i = k_begin / pg.page_size;
+    pg_ro = k_begin - pg_i * pg.page_size;
+    pg_cur = page_id(table, pg_i, pg.num_pages);
+    ro_cur = pg_ro;
+    if (nt > 1) {
+      pg_nxt = next_page();
+      ro_nxt = pg_ro;
+    }
+  }
+
+  stage_load(k_begin, pg_cur, ro_cur);
   stage_write(0);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));  // Q has arrived before the loop (no vmcnt(0) behind the loop's loads)
@@ -217,7 +276,14 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
   for (int t = 0; t < nt; ++t) {
     const int buf = t & 1, t0 = k_begin + t * kKV;
     const bool more = t + 1 < nt;
-    if (more) stage_load(t0 + kKV);
+    int pg_n2 = pg_nxt, ro_n2 = ro_nxt;
+    if constexpr (PAGED) {
+      if (t + 2 < nt) {  // the id tile t + 2 will load with in the next iteration: a whole tile ahead of its use
+        pg_n2 = next_page();
+        ro_n2 = pg_ro;
+      }
+    }
+    if (more) stage_load(t0 + kKV, pg_nxt, ro_nxt);
 
     if (wave_on && t0 <= wave_max) {  // wave-uniform: every lane of the wave takes part in the transposed reads
       // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, packed row r ----
@@ -287,6 +353,8 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgs a) {
 
     if (more) stage_write(buf ^ 1);  // the other buffer: its readers finished before the barrier that ended tile t - 1
     __syncthreads();
+    pg_nxt = pg_n2;
+    ro_nxt = ro_n2;
   }
 
   // ---- the unnormalised partial; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
@@ -432,26 +500,29 @@ namespace {
 
 // Both launches of one call.  K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
 // partials only, so it is the T cache's in either case.
-// L is the identity for host lengths and DevLen for lengths on the device.
+// L is the identity for host lengths, DevLen for lengths on the device and PagedDevLen for those over a pool of pages; C is what L is to
+// the combine launch (the paged form combines with the dense DevLen kernel: the partials do not know where K / V came from).
 template <typename DT>
 using HostLen = DT;
-template <template <typename> class K, template <typename> class L = HostLen>
-void launch_pair(const SplitArgs& a, int Dh, int dtype, dim3 grid, dim3 cgrid, hipStream_t st) {
+template <typename DT>
+using PagedDevLen = Paged<DevLen<DT>>;
+template <template <typename> class K, template <typename> class L = HostLen, template <typename> class C = L, typename A = SplitArgs>
+void launch_pair(const A& a, int Dh, int dtype, dim3 grid, dim3 cgrid, hipStream_t st) {
   if (dtype == 0) {
     if (Dh == 128) {
       hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<F16>, 128>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<F16>, 128>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
     } else {
       hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<F16>, 64>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<F16>, 64>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
     }
   } else {
     if (Dh == 128) {
       hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<BF16>, 128>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<BF16>, 128>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
     } else {
       hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<L<BF16>, 64>), cgrid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<BF16>, 64>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
     }
   }
 }
@@ -550,6 +621,36 @@ int launch_attn_kvcache(const void* q, const void* k, const void* v, const float
     launch_pair<Kv8, DevLen>(a, Dh, dtype, grid, cgrid, st);
   } else {
     launch_pair<TCache, DevLen>(a, Dh, dtype, grid, cgrid, st);
+  }
+  return 0;
+}
+
+// The paged pair (awq_attn_kvcache_paged[_kv8]): k / v are the pools [num_pages, page_size, Hkv, Dh] with their page and row strides, the
+// scale strides likewise; max_seqlen_k <= pages_per_seq * page_size, so every table index the kernel forms lies inside a table row.
+// launch_attn_kvcache's plan, workspace and combine launch.
+int launch_attn_kvcache_paged(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out,
+                              const int* block_table, long long table_row_stride, int page_size, int num_pages, int B, int Sq,
+                              const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
+                              long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps, long long ks_rs, long long vs_ps,
+                              long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st) {
+  PagedSplitArgs a;
+  static_cast<SplitArgs&>(a) = split_args(q, k, v, out, B, Sq, max_seqlen_k, H, Hkv, Dh, q_bs, q_rs, k_ps, k_rs, v_ps, v_rs, scale, causal, splits,
+                                          chunk, workspace);
+  a.seqlens_k = seqlens_k;
+  a.seqlen_offset = seqlen_offset;
+  a.pg = PageArgs{block_table, table_row_stride, page_size, num_pages};
+  const dim3 grid((unsigned)((long long)B * Hkv * splits));
+  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
+  if (k_scale) {
+    a.k_scale = k_scale;
+    a.v_scale = v_scale;
+    a.ks_bs = ks_ps;
+    a.ks_rs = ks_rs;
+    a.vs_bs = vs_ps;
+    a.vs_rs = vs_rs;
+    launch_pair<Kv8, PagedDevLen, DevLen>(a, Dh, dtype, grid, cgrid, st);
+  } else {
+    launch_pair<TCache, PagedDevLen, DevLen>(a, Dh, dtype, grid, cgrid, st);
   }
   return 0;
 }

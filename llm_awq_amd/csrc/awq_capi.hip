@@ -675,6 +675,118 @@ int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache
   return finish_launch();
 }
 
+// ---- the paged KV cache: the two device-length entries above over a pool of pages and a block table (awq_paged.hpp) ----
+static bool paged_shape_ok(int num_pages, int page_size, int pages_per_seq, long long table_row_stride) {
+  return page_size >= 64 && (page_size % 64) == 0 && num_pages >= 1 && pages_per_seq >= 1 && table_row_stride >= pages_per_seq;
+}
+// keys a table row can name, as an int (positions and lengths are int32)
+static int paged_capacity(int page_size, int pages_per_seq) {
+  const long long cap = (long long)pages_per_seq * page_size;
+  return cap < 0x7FFFFFFFll ? (int)cap : 0x7FFFFFFF;
+}
+
+int awq_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                const int* cache_seqlens, int batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs_table || !q_out || !k_pool || !v_pool || !block_table || !cache_seqlens) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!store_pos_shape_ok(batch, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, 1, table_rows, qkv_batch_stride, qkv_row_stride) ||
+      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || k_page_stride < 0 || v_page_stride < 0 ||
+      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned4(block_table) ||
+      !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0 || (k_page_stride % 8) != 0 ||
+      (k_row_stride % 8) != 0 || (v_page_stride % 8) != 0 || (v_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store_paged_pos(qkv, freqs_table, q_out, k_pool, v_pool, block_table, table_row_stride, page_size, num_pages, pages_per_seq,
+                                      k_page_stride, k_row_stride, v_page_stride, v_row_stride, cache_seqlens, batch, seqlen, nheads, nheads_kv,
+                                      head_dim, rot_dim, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                    float* v_scale, const int* block_table, const int* cache_seqlens, int batch, int seqlen, int nheads,
+                                    int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                    long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                    long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                    long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_batch_stride,
+                                    long long qkv_row_stride, int dtype, void* stream) {
+  if (!qkv || !freqs_table || !q_out || !k_pool || !v_pool || !k_scale || !v_scale || !block_table || !cache_seqlens) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!store_pos_shape_ok(batch, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, 1, table_rows, qkv_batch_stride, qkv_row_stride) ||
+      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || k_page_stride < 0 || v_page_stride < 0 ||
+      k_scale_page_stride < 0 || v_scale_page_stride < 0 || k_row_stride < (long long)nheads_kv * head_dim ||
+      v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv || v_scale_row_stride < nheads_kv)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned4(k_scale) ||
+      !aligned4(v_scale) || !aligned4(block_table) || !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0 ||
+      (k_page_stride % 16) != 0 || (k_row_stride % 16) != 0 || (v_page_stride % 16) != 0 || (v_row_stride % 16) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_rope_kv_store_paged_pos_fp8(qkv, freqs_table, q_out, k_pool, v_pool, k_scale, v_scale, block_table, table_row_stride, page_size,
+                                          num_pages, pages_per_seq, k_page_stride, k_row_stride, v_page_stride, v_row_stride, k_scale_page_stride,
+                                          k_scale_row_stride, v_scale_page_stride, v_scale_row_stride, cache_seqlens, batch, seqlen, nheads,
+                                          nheads_kv, head_dim, rot_dim, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_attn_kvcache_paged(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch, int seqlen_q,
+                           const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size, int pages_per_seq,
+                           long long table_row_stride, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, float softmax_scale,
+                           int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k_pool || !v_pool || !out || !block_table || !seqlens_k) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) ||
+      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || q_batch_stride < 0 || k_page_stride < 0 || v_page_stride < 0 ||
+      q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
+      v_row_stride < (long long)nheads_kv * head_dim)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || !aligned4(block_table) || (q_batch_stride % 8) != 0 ||
+      (k_page_stride % 8) != 0 || (v_page_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  int splits = 1, chunk = 0;
+  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k,
+                               paged_capacity(page_size, pages_per_seq), workspace, workspace_bytes, &splits, &chunk);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_kvcache_paged(q, k_pool, v_pool, nullptr, nullptr, out, block_table, table_row_stride, page_size, num_pages, batch, seqlen_q,
+                                 seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_page_stride,
+                                 k_row_stride, v_page_stride, v_row_stride, 0, 0, 0, 0, softmax_scale, causal, dtype, splits, chunk, workspace,
+                                 (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                               const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                               int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                               int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                               long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k_pool || !v_pool || !k_scale || !v_scale || !out || !block_table || !seqlens_k) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) ||
+      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || q_batch_stride < 0 || k_page_stride < 0 || v_page_stride < 0 ||
+      k_scale_page_stride < 0 || v_scale_page_stride < 0 || q_row_stride < (long long)nheads * head_dim ||
+      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv ||
+      v_scale_row_stride < nheads_kv)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || !aligned4(k_scale) || !aligned4(v_scale) ||
+      !aligned4(block_table) || (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_page_stride % 16) != 0 || (k_row_stride % 16) != 0 ||
+      (v_page_stride % 16) != 0 || (v_row_stride % 16) != 0)
+    return AWQ_ERR_ALIGN;
+  int splits = 1, chunk = 0;
+  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k,
+                               paged_capacity(page_size, pages_per_seq), workspace, workspace_bytes, &splits, &chunk);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_kvcache_paged(q, k_pool, v_pool, k_scale, v_scale, out, block_table, table_row_stride, page_size, num_pages, batch, seqlen_q,
+                                 seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_page_stride,
+                                 k_row_stride, v_page_stride, v_row_stride, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride,
+                                 v_scale_row_stride, softmax_scale, causal, dtype, splits, chunk, workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {
   return nseq >= 1 && nheads >= 1 && (head_dim == 64 || head_dim == 72) && max_seqlen >= 1 &&
          (long long)nseq * nheads * ((max_seqlen + 31) / 32) <= 0x7FFFFFFFll;

@@ -220,6 +220,22 @@ int launch_attn_kvcache(const void* q, const void* k, const void* v, const float
                         const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
                         long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs,
                         long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st);
+// the same launches over a pool of pages and a block table (awq_paged.hpp): k / v [num_pages, page_size, Hkv, Dh] with page and row strides
+// (elements, bytes for codes), the scale pools likewise (floats); arguments validated by the caller
+int launch_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                   long long table_row_stride, int page_size, int num_pages, int pages_per_seq, long long k_ps, long long k_rs,
+                                   long long v_ps, long long v_rs, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot,
+                                   int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
+int launch_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                       float* v_scale, const int* block_table, long long table_row_stride, int page_size, int num_pages,
+                                       int pages_per_seq, long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps,
+                                       long long ks_rs, long long vs_ps, long long vs_rs, const int* cache_seqlens, int B, int S, int H, int Hkv,
+                                       int Dh, int rot, int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
+int launch_attn_kvcache_paged(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out,
+                              const int* block_table, long long table_row_stride, int page_size, int num_pages, int B, int Sq,
+                              const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
+                              long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps, long long ks_rs, long long vs_ps,
+                              long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

@@ -1114,6 +1114,147 @@ std::tuple<int64_t, int64_t> attn_kvcache_plan(int64_t batch, int64_t nheads, in
   return {splits, chunk};
 }
 
+// ---- the paged KV cache (include/awq_cdna4.h: awq_rope_kv_store_paged_pos[_fp8], awq_attn_kvcache_paged[_kv8]) ----
+// the pools [num_pages, page_size, Hkv, Dh] (and the scale pools [num_pages, page_size, Hkv]) and the table [>= B, pages_per_seq] of one call
+static void check_pools(const char* who, bool fp8, const torch::Tensor& ref, const torch::Tensor& k, const torch::Tensor& v,
+                        const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& block_table, int64_t batch) {
+  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k, &v}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == ref.device(), who, ": the pools must live on the GPU of the input");
+    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == ref.scalar_type(), who,
+                fp8 ? ": the pools must be float8_e4m3fn or uint8, got " : ": the pools must have the dtype of the input, got ", t->scalar_type());
+    TORCH_CHECK(t->dim() == 4 && t->stride(3) == 1 && t->stride(2) == t->size(3), who,
+                ": k_pool / v_pool [num_pages, page_size, Hkv, Dh] with contiguous heads are expected");
+  }
+  TORCH_CHECK(k.sizes() == v.sizes(), who, ": k_pool and v_pool must have one shape [num_pages, page_size, Hkv, Dh]");
+  TORCH_CHECK(k.size(0) >= 1 && k.size(1) >= 64 && k.size(1) % 64 == 0, who, ": page size ", k.size(1),
+              " is not supported (a multiple of 64, at least 64) or the pool is empty");
+  if (fp8)
+    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
+      TORCH_CHECK(t->is_cuda() && t->device() == ref.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == k.size(0) &&
+                      t->size(1) == k.size(1) && t->size(2) == k.size(2) && t->stride(2) == 1,
+                  who, ": k_scale / v_scale must be float32 [num_pages, page_size, Hkv] of the pools with a unit last stride");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == ref.device(), who,
+              ": block_table must live on the GPU of the input (it is read by the kernel only)");
+  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.dim() == 2 && block_table.size(0) >= batch && block_table.size(1) >= 1 &&
+                  block_table.stride(1) == 1 && block_table.stride(0) >= block_table.size(1),
+              who, ": block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride");
+}
+
+static torch::Tensor rope_store_paged_impl(const char* who, bool fp8, const torch::Tensor& qkv, const torch::Tensor& freqs_table,
+                                           torch::Tensor& k_pool, torch::Tensor& v_pool, torch::Tensor* k_scale, torch::Tensor* v_scale,
+                                           const torch::Tensor& block_table, const torch::Tensor& cache_seqlens, int64_t nheads,
+                                           int64_t nheads_kv) {
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs_table.is_cuda() && freqs_table.device() == qkv.device(), who, ": tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
+  TORCH_CHECK(freqs_table.scalar_type() == at::kFloat && freqs_table.dim() == 2 && freqs_table.is_contiguous() &&
+                  (reinterpret_cast<uintptr_t>(freqs_table.data_ptr()) & 15) == 0,
+              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
+  TORCH_CHECK(qkv.dim() == 3, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
+  check_pools(who, fp8, qkv, k_pool, v_pool, k_scale, v_scale, block_table, batch);
+  const int64_t headdim = v_pool.size(3), rows = freqs_table.size(0), rot = freqs_table.size(1);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_pool.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
+              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the pools' Hkv and Dh");
+  TORCH_CHECK(rows >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
+              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
+  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor x = qkv;
+  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (fp8)
+    raise_on(awq_rope_kv_store_paged_pos_fp8(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                             k_scale->data_ptr<float>(), v_scale->data_ptr<float>(), block_table.data_ptr<int>(),
+                                             cache_seqlens.data_ptr<int>(), (int)batch, (int)seqlen, (int)nheads, (int)nheads_kv, (int)headdim,
+                                             (int)rot, (int)rows, (int)k_pool.size(0), (int)k_pool.size(1), (int)block_table.size(1),
+                                             block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1),
+                                             k_scale->stride(0), k_scale->stride(1), v_scale->stride(0), v_scale->stride(1), x.stride(0),
+                                             x.stride(1), dtype_code(x), st));
+  else
+    raise_on(awq_rope_kv_store_paged_pos(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                         block_table.data_ptr<int>(), cache_seqlens.data_ptr<int>(), (int)batch, (int)seqlen, (int)nheads,
+                                         (int)nheads_kv, (int)headdim, (int)rot, (int)rows, (int)k_pool.size(0), (int)k_pool.size(1),
+                                         (int)block_table.size(1), block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0),
+                                         v_pool.stride(1), x.stride(0), x.stride(1), dtype_code(x), st));
+  return q_out;
+}
+
+// rope_kv_store_paged_pos(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural_pos
+// writing token s of sequence b at logical position cache_seqlens[b] + s of the pages block_table[b] names.
+torch::Tensor rope_kv_store_paged_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                      const torch::Tensor block_table, const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_paged_impl("rope_kv_store_paged_pos", false, qkv, freqs_table, k_pool, v_pool, nullptr, nullptr, block_table, cache_seqlens,
+                               nheads, nheads_kv);
+}
+
+torch::Tensor rope_kv_store_paged_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                          torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table,
+                                          const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_paged_impl("rope_kv_store_paged_pos_fp8", true, qkv, freqs_table, k_pool, v_pool, &k_scale, &v_scale, block_table,
+                               cache_seqlens, nheads, nheads_kv);
+}
+
+// attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: attn_kvcache with
+// K / V fetched from the pools through the table.  The fp32 partials live in a buffer of torch's caching allocator, so a capture owns them.
+static torch::Tensor attn_kvcache_paged_impl(const char* who, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+                                             const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& block_table,
+                                             const torch::Tensor& seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale,
+                                             bool causal) {
+  const bool fp8 = k_scale != nullptr;
+  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  check_pools(who, fp8, q, k, v, k_scale, v_scale, block_table, batch);
+  const int64_t page_size = k.size(1), nheads_kv = k.size(2), pages_per_seq = block_table.size(1);
+  TORCH_CHECK(k.size(3) == headdim, who, ": k_pool / v_pool must be [num_pages, page_size, Hkv, ", headdim, "]");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+              ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
+              " exceeds 128 (the split kernels serve few query rows; feed a longer prompt in pieces)");
+  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= pages_per_seq * page_size, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ",
+              pages_per_seq * page_size, " (pages_per_seq * page_size)");
+  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
+  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
+  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (fp8)
+    raise_on(awq_attn_kvcache_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
+                                        out.data_ptr(), block_table.data_ptr<int>(), (int)batch, (int)sq, seqlens_k.data_ptr<int>(),
+                                        (int)seqlen_offset, (int)max_seqlen_k, (int)k.size(0), (int)page_size, (int)pages_per_seq,
+                                        block_table.stride(0), (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0),
+                                        k.stride(1), v.stride(0), v.stride(1), k_scale->stride(0), k_scale->stride(1), v_scale->stride(0),
+                                        v_scale->stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q), ws.data_ptr(), wsb, st));
+  else
+    raise_on(awq_attn_kvcache_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), block_table.data_ptr<int>(), (int)batch, (int)sq,
+                                    seqlens_k.data_ptr<int>(), (int)seqlen_offset, (int)max_seqlen_k, (int)k.size(0), (int)page_size,
+                                    (int)pages_per_seq, block_table.stride(0), (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1),
+                                    k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+                                    ws.data_ptr(), wsb, st));
+  return out;
+}
+
+torch::Tensor attn_kvcache_paged(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                 const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_paged_impl("attn_kvcache_paged", q, k_pool, v_pool, nullptr, nullptr, block_table, seqlens_k, max_seqlen_k, seqlen_offset,
+                                 softmax_scale, causal);
+}
+
+torch::Tensor attn_kvcache_paged_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                     const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor seqlens_k,
+                                     int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_paged_impl("attn_kvcache_paged_kv8", q, k_pool, v_pool, &k_scale, &v_scale, block_table, seqlens_k, max_seqlen_k,
+                                 seqlen_offset, softmax_scale, causal);
+}
+
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel
 // (csrc/awq_attn_tower_cdna4.hip): qkv [nnz, 3, H, Dh] with contiguous heads, cu_seqlens int32 [nseq + 1] on the same GPU, read by the
 // kernel only (no host copy, no sync).  Returns [nnz, H, Dh] contiguous; rows >= cu_seqlens[-1] are left unwritten.
@@ -1438,6 +1579,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_kvcache_plan", &attn_kvcache_plan, "(splits, chunk) of attn_kvcache, made from the bound max_seqlen_k alone", py::arg("batch"),
         py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("seqlen_q"), py::arg("max_seqlen_k"));
+  m.def("rope_kv_store_paged_pos", &rope_kv_store_paged_pos,
+        "rope_kv_store_natural_pos over a paged KV cache: pools [num_pages, page_size, Hkv, Dh], block_table int32 [B, pages_per_seq]",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("cache_seqlens"),
+        py::arg("nheads"), py::arg("nheads_kv"));
+  m.def("rope_kv_store_paged_pos_fp8", &rope_kv_store_paged_pos_fp8, "rope_kv_store_paged_pos on FP8 pools", py::arg("qkv"),
+        py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+        py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"));
+  m.def("attn_kvcache_paged", &attn_kvcache_paged,
+        "attn_kvcache over a paged KV cache: K / V fetched from pools [num_pages, page_size, Hkv, Dh] through block_table [B, pages_per_seq]",
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_kvcache_paged_kv8", &attn_kvcache_paged_kv8, "attn_kvcache_paged on FP8 pools with per-(key, KV head) fp32 scale pools",
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

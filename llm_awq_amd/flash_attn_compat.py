@@ -74,8 +74,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     for name, value in asked.items():
         if not _is_off(name, value):
             shown = f"tensor{tuple(value.shape)}" if hasattr(value, "shape") else repr(value)
+            hint = " -- a paged cache is served by llm_awq_amd.ops.attn_kvcache_paged, whose pools are [num_pages, page_size, Hkv, Dh]" \
+                if name == "block_table" else ""
             raise NotImplementedError(f"flash_attn_with_kvcache on MI355X: {name}={shown} is not implemented (the cache must already hold "
-                                      "the new tokens; cache_seqlens are total lengths)")
+                                      f"the new tokens; cache_seqlens are total lengths){hint}")
     if cache_seqlens is None:
         return flash_attn_func(q, k_cache[:q.shape[0]], v_cache[:q.shape[0]], softmax_scale=softmax_scale, causal=causal)
     import torch

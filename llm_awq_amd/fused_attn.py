@@ -30,6 +30,11 @@ With `kv_layout="natural"`, `forward` also takes `start_pos` as an int32 device 
 store launch and the split-KV attention then read every sequence's position on the device (`rope_kv_store_natural_pos[_fp8]`,
 `attn_kvcache[_kv8]`).  One call serves a batch whose sequences have different lengths, and one captured graph replays the whole decode
 phase while the caller advances the tensor in place.  An int `start_pos` takes the path above, bit for bit.
+
+With `block_table=` and `page_size=` (and a tensor `start_pos`) the module's caches are read and written as a POOL of
+max_batch_size * kv_max_seq_len / page_size pages -- a view, nothing is copied or allocated -- through the per-sequence block table
+(`rope_kv_store_paged_pos[_fp8]`, `attn_kvcache_paged[_kv8]`; `llm_awq_amd.paged_kv.PageTable` hands the pages out): a sequence holds the
+pages its tokens need, not kv_max_seq_len rows, and one sequence may grow past kv_max_seq_len while others are short.
 """
 from __future__ import annotations
 
@@ -96,17 +101,24 @@ class QuantLlamaAttentionFused(nn.Module):
                                    device=dev)
 
     @torch.no_grad()
-    def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False, decode_max_seqlen=None):
+    def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False, decode_max_seqlen=None, block_table=None, page_size=None):
         """`mask` is accepted and ignored, as in the reference's short_forward: the attention is causal.
 
         With `kv_layout="natural"`, `start_pos` may be an int32 tensor [bsz] on the GPU: the tokens already in each sequence's cache, read
         by the kernels only (a ragged batch in one call; a captured graph replays any position).  `freqs` is then the model's whole angle
         table [P, rot_dim] and `decode_max_seqlen` (default `kv_max_seq_len`) the host bound on start_pos + seqlen that sizes the attention
-        launch.  A sequence with start_pos[b] < 0 is a finished slot: nothing is stored for it and its attention rows are zeros."""
+        launch.  A sequence with start_pos[b] < 0 is a finished slot: nothing is stored for it and its attention rows are zeros.
+
+        `block_table` (int32 [>= bsz, pages_per_seq] on the GPU) and `page_size` (a multiple of 64 that divides `kv_max_seq_len`) come
+        together and with a tensor `start_pos`: the caches are then a pool of max_batch_size * kv_max_seq_len / page_size pages and token
+        p of sequence b lives in row p % page_size of page block_table[b, p // page_size].  `decode_max_seqlen` defaults to
+        pages_per_seq * page_size."""
+        if block_table is not None or page_size is not None:
+            self._check_paged(start_pos, block_table, page_size)
         eng = load_engine()
         bsz, seqlen, _ = x.shape
         if isinstance(start_pos, torch.Tensor):
-            return self._forward_device_pos(eng, x, start_pos, freqs, decode_max_seqlen)
+            return self._forward_device_pos(eng, x, start_pos, freqs, decode_max_seqlen, block_table, page_size)
         xqkv = self.qkv_proj(x)
         if self.kv_dtype == "fp8":  # the caches keep their dtype: only the device follows the activations
             from . import ops
@@ -146,8 +158,23 @@ class QuantLlamaAttentionFused(nn.Module):
             output = output.reshape(bsz, 1, -1)
         return self.o_proj(output)
 
-    def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen):
-        """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host."""
+    def _check_paged(self, start_pos, block_table, page_size):
+        """The paged call's conditions, before any work."""
+        who = "QuantLlamaAttentionFused"
+        if self.kv_layout != "natural":
+            raise ValueError(f"{who}: block_table needs kv_layout 'natural' (the FT-layout cache is not paged)")
+        if not isinstance(start_pos, torch.Tensor):
+            raise ValueError(f"{who}: block_table needs start_pos as an int32 tensor [bsz] on the GPU (the paged kernels read every "
+                             "sequence's position on the device)")
+        if block_table is None or page_size is None:
+            raise ValueError(f"{who}: block_table and page_size come together")
+        page_size = int(page_size)
+        if page_size < 64 or page_size % 64 or self.kv_max_seq_len % page_size:
+            raise ValueError(f"{who}: page_size {page_size} must be a multiple of 64 that divides kv_max_seq_len {self.kv_max_seq_len}")
+
+    def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None):
+        """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host.  With a
+        block table: rope_kv_store_paged_pos[_fp8] followed by attn_kvcache_paged[_kv8] on the caches viewed as pages."""
         if self.kv_layout != "natural":
             raise ValueError("QuantLlamaAttentionFused: a tensor start_pos needs kv_layout 'natural' (the FT-layout path takes start_pos as "
                              "an int; its decode kernel reads per-sequence lengths through single_query_attention's length_per_sample)")
@@ -159,14 +186,29 @@ class QuantLlamaAttentionFused(nn.Module):
             if self.cache_k.device != xqkv.device:
                 for name in ("cache_k", "cache_v", "cache_k_scale", "cache_v_scale"):
                     setattr(self, name, getattr(self, name).to(xqkv.device))
+        elif self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:
+            self.cache_k = self.cache_k.to(xqkv)
+            self.cache_v = self.cache_v.to(xqkv)
+        if block_table is not None:
+            ps = int(page_size)
+            pool = (-1, ps, self.num_key_value_heads, self.head_dim)
+            if decode_max_seqlen is None:
+                bound = block_table.shape[1] * ps
+            if self.kv_dtype == "fp8":
+                pools = (self.cache_k.view(pool), self.cache_v.view(pool), self.cache_k_scale.view(pool[:3]), self.cache_v_scale.view(pool[:3]))
+                xq = eng.rope_kv_store_paged_pos_fp8(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
+                output = eng.attn_kvcache_paged_kv8(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+            else:
+                pools = (self.cache_k.view(pool), self.cache_v.view(pool))
+                xq = eng.rope_kv_store_paged_pos(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
+                output = eng.attn_kvcache_paged(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+            return self.o_proj(output.view(bsz, seqlen, -1))
+        if self.kv_dtype == "fp8":
             xq = eng.rope_kv_store_natural_pos_fp8(xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos,
                                                    self.n_local_heads, self.num_key_value_heads)
             output = eng.attn_kvcache_kv8(xq, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos, bound, seqlen,
                                           scale, True)
         else:
-            if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:
-                self.cache_k = self.cache_k.to(xqkv)
-                self.cache_v = self.cache_v.to(xqkv)
             xq = eng.rope_kv_store_natural_pos(xqkv, freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads, self.num_key_value_heads)
             output = eng.attn_kvcache(xq, self.cache_k, self.cache_v, start_pos, bound, seqlen, scale, True)
         return self.o_proj(output.view(bsz, seqlen, -1))

@@ -854,6 +854,114 @@ def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens,
     return q_out
 
 
+# ---- the paged KV cache: the two calls above over a pool of pages and a per-sequence block table ------------------------------------
+def _check_pools(who, ref, k_pool, v_pool, block_table, k_scale, v_scale, batch):
+    """(num_pages, page_size, Hkv, Dh, pages_per_seq) of the pools [num_pages, page_size, Hkv, Dh] and the table [>= B, pages_per_seq]."""
+    fp8 = k_scale is not None or v_scale is not None
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError(f"{who}: k_scale and v_scale come together")
+    for t in (ref, k_pool, v_pool, block_table) + ((k_scale, v_scale) if fp8 else ()):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
+        if fp8:
+            _kv8_codes(who, name, t)
+        elif t.dtype != ref.dtype:
+            raise ValueError(f"{who}: the pools must have the dtype of the input")
+        if t.device != ref.device or t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+            raise ValueError(f"{who}: {name} must be a [num_pages, page_size, Hkv, Dh] tensor with contiguous heads on the GPU of the input")
+    if k_pool.shape != v_pool.shape:
+        raise ValueError(f"{who}: k_pool and v_pool must have one shape [num_pages, page_size, Hkv, Dh]")
+    num_pages, page_size, Hkv, Dh = v_pool.shape
+    if num_pages < 1 or page_size < 64 or page_size % 64:
+        raise ValueError(f"{who}: pools [num_pages >= 1, page_size, Hkv, Dh] with page_size a multiple of 64 are expected, got "
+                         f"{tuple(v_pool.shape)}")
+    if fp8:
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.device != ref.device or t.dtype != torch.float32 or tuple(t.shape) != (num_pages, page_size, Hkv) or t.stride(2) != 1:
+                raise ValueError(f"{who}: {name} must be a float32 [num_pages, page_size, Hkv] tensor with a unit last stride on the GPU of "
+                                 "the input")
+    if block_table.device != ref.device or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] < batch or \
+            block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.stride(0) < block_table.shape[1]:
+        raise ValueError(f"{who}: block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride on the GPU of the input")
+    return num_pages, page_size, Hkv, Dh, block_table.shape[1]
+
+
+def attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None,
+                       causal: bool = True, k_scale=None, v_scale=None):
+    """C-ABI awq_attn_kvcache_paged[_kv8]: `attn_kvcache` over a paged KV cache.  k_pool / v_pool [num_pages, page_size, Hkv, Dh] (page_size a
+    multiple of 64), block_table int32 [>= B, pages_per_seq] on the GPU: key p of sequence b is row p % page_size of page
+    block_table[b, p // page_size].  max_seqlen_k <= pages_per_seq * page_size.  For every active sequence the result is bit-identical to
+    `attn_kvcache` on the dense gather of its pages.  Entries behind a sequence's live range are never read; a page id is clamped into the
+    pool.  With k_scale / v_scale [num_pages, page_size, Hkv] float32 the pools are FP8 codes.  The host reads neither the table nor the
+    lengths: capturable, and a replay follows what the tensors hold then."""
+    who = "attn_kvcache_paged"
+    if not q.is_cuda:
+        raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if q.dim() != 4 or q.stride(3) != 1 or q.stride(2) != q.shape[3]:
+        raise ValueError(f"{who}: q must be [B, Sq, H, Dh] with contiguous heads")
+    B, Sq, H, Dh = q.shape
+    num_pages, page_size, Hkv, Dhp, pps = _check_pools(who, q, k_pool, v_pool, block_table, k_scale, v_scale, B)
+    if Dhp != Dh:
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_pool / v_pool [num_pages, page_size, Hkv, Dh] must share Dh, got {Dh} and {Dhp}")
+    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
+    fp8 = k_scale is not None
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    L = _capi.lib()
+    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, Hkv, Dh, Sq, int(max_seqlen_k))
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
+    lens = (block_table.data_ptr(), B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k), num_pages, page_size, pps,
+            block_table.stride(0), H, Hkv, Dh)
+    strides = (q.stride(0), q.stride(1), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1))
+    tail = (scale, int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q))
+    with torch.cuda.device(q.device):
+        if fp8:
+            _capi.check(L.awq_attn_kvcache_paged_kv8(q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+                                                     out.data_ptr(), *lens, *strides, k_scale.stride(0), k_scale.stride(1), v_scale.stride(0),
+                                                     v_scale.stride(1), *tail))
+        else:
+            _capi.check(L.awq_attn_kvcache_paged(q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), out.data_ptr(), *lens, *strides, *tail))
+    return out
+
+
+def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
+    """C-ABI awq_rope_kv_store_paged_pos[_fp8]: `rope_kv_store_natural_pos` over a paged KV cache.  Token s of sequence b is rotated by row
+    p = cache_seqlens[b] + s of freqs_table and stored in row p % page_size of page block_table[b, p // page_size] of the pools
+    [num_pages, page_size, Hkv, Dh] (the page is looked up per token: a chunk may cross page edges).  A sequence with cache_seqlens[b] < 0
+    or cache_seqlens[b] + S > min(pages_per_seq * page_size, P) is inactive: nothing of it is stored and its q rows are zeros.  With
+    k_scale / v_scale [num_pages, page_size, Hkv] the pools are FP8.  Returns the rotated q [B, S, H, Dh]."""
+    who = "rope_kv_store_paged"
+    for t in (qkv, freqs_table, cache_seqlens):
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    if qkv.dim() != 3 or qkv.stride(2) != 1:
+        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride")
+    B, S = qkv.shape[0], qkv.shape[1]
+    num_pages, page_size, Hkv, Dh, pps = _check_pools(who, qkv, k_pool, v_pool, block_table, k_scale, v_scale, B)
+    fp8 = k_scale is not None
+    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
+        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
+    if nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
+        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with the pools' Hkv and Dh")
+    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
+    P, rot = freqs_table.shape
+    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
+    head = (block_table.data_ptr(), cache_seqlens.data_ptr(), B, S, int(nheads), int(nheads_kv), Dh, rot, P, num_pages, page_size, pps,
+            block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1))
+    tail = (qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
+    with torch.cuda.device(qkv.device):
+        if fp8:
+            _capi.check(_capi.lib().awq_rope_kv_store_paged_pos_fp8(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_pool.data_ptr(),
+                                                                    v_pool.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), *head,
+                                                                    k_scale.stride(0), k_scale.stride(1), v_scale.stride(0), v_scale.stride(1),
+                                                                    *tail))
+        else:
+            _capi.check(_capi.lib().awq_rope_kv_store_paged_pos(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_pool.data_ptr(),
+                                                                v_pool.data_ptr(), *head, *tail))
+    return q_out
+
+
 def _ft_caches(who, ref, k_cache, v_cache):
     """(Bc, Hkv, Lmax, Dh) of the FT caches k_cache [Bc, Hkv, Dh/8, Lmax, 8] / v_cache [Bc, Hkv, Lmax, Dh], checked against `ref`."""
     for t in (ref, k_cache, v_cache):
