@@ -19,6 +19,7 @@
 #include "awq_device.hpp"
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
+#include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
 
 #include <math.h>
@@ -197,71 +198,38 @@ int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void*
   const int nb = (int)((n + 255) / 256);
   RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
                   start_pos, nb, nullptr};
-  const dim3 grid((unsigned)(2 * nb));
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<F16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_kernel<F16, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
-  }
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((rope_kv_store_kernel<decltype(dt), decltype(dh)::value>), dim3((unsigned)(2 * nb)), dim3(256), 0, st, a);
+  });
   return 0;
 }
 
-int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv,
-                                 int Dh, int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  const int nb = (int)((n + 255) / 256);
-  RopeStoreArgs a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot, lmax,
-                  start_pos, nb, nullptr};
-  const dim3 grid((unsigned)nb);
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<F16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<F16, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
-  }
-  return 0;
+namespace {
+template <template <typename> class L>
+void launch_store(const RopeStoreArgs& a, int dtype, int Dh, hipStream_t st) {
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((rope_kv_store_natural_kernel<L<decltype(dt)>, decltype(dh)::value>), dim3((unsigned)a.qv_blocks), dim3(256), 0, st, a);
+  });
 }
+}  // namespace
 
-// cache_seqlens on the device in the place of start_pos, the whole angle table [table_rows, rot] in the place of the call's angles
-int launch_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache,
-                                     const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int table_rows,
-                                     long long bs, long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  const int nb = (int)((n + 255) / 256);
-  RopeStoreArgs a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint16_t*)k_cache, (uint16_t*)v_cache, bs, rs, B, S, H, Hkv, rot,
-                  lmax, table_rows, nb, cache_seqlens};
-  const dim3 grid((unsigned)nb);
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<F16>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<F16>, 64>), grid, dim3(256), 0, st, a);
+// The natural-layout store on the T cache (a view with scales goes to awq_attn_kv8_cdna4.hip).  Device positions: cache_seqlens in the
+// place of start_pos and the whole angle table [table_rows, rot] in the place of the call's angles.  Paged: the pools and their table in
+// the place of the caches, lmax = the capacity of a table row.
+int launch_kv_store(const KvStoreCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  if (kv.k_scale) return launch_kv_store_fp8(c, st);
+  const int nb = (int)(((long long)c.B * c.S * (c.Dh / 8) + 255) / 256);
+  RopeStoreArgs a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint16_t*)kv.k, (uint16_t*)kv.v, c.bs, c.rs, c.B, c.S, c.H, c.Hkv,
+                  c.rot, kv.capacity(), c.cache_seqlens ? c.table_rows : c.start_pos, nb, c.cache_seqlens};
+  if (kv.block_table) {
+    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
+    launch_store<PagedDevLen>(a, c.dtype, c.Dh, st);
+  } else if (c.cache_seqlens) {
+    launch_store<DevLen>(a, c.dtype, c.Dh, st);
   } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
-  }
-  return 0;
-}
-
-// the pools and their table in the place of the caches: lmax = pages_per_seq * page_size (capped at INT_MAX: positions are int32)
-int launch_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
-                                   long long table_row_stride, int page_size, int num_pages, int pages_per_seq, long long k_ps, long long k_rs,
-                                   long long v_ps, long long v_rs, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot,
-                                   int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  const int nb = (int)((n + 255) / 256);
-  const long long cap = (long long)pages_per_seq * page_size;
-  RopeStoreArgs a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint16_t*)k_pool, (uint16_t*)v_pool, bs, rs, B, S, H, Hkv, rot,
-                  (int)(cap < 0x7FFFFFFFll ? cap : 0x7FFFFFFFll), table_rows, nb, cache_seqlens,
-                  PageArgs{block_table, table_row_stride, page_size, num_pages}, k_ps, k_rs, v_ps, v_rs};
-  const dim3 grid((unsigned)nb);
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<F16>>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<F16>>, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<BF16>>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_kernel<Paged<DevLen<BF16>>, 64>), grid, dim3(256), 0, st, a);
+    launch_store<HostLen>(a, c.dtype, c.Dh, st);
   }
   return 0;
 }

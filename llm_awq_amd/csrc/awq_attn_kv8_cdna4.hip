@@ -21,6 +21,7 @@
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
+#include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
 
 #include <math.h>
@@ -153,59 +154,30 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
   for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), vc, vsc, hd);
 }
 
+template <template <typename> class L>
+void launch_store(const RopeStoreFp8Args& a, int dtype, int Dh, hipStream_t st) {
+  const dim3 grid((unsigned)(((long long)a.B * a.S * (Dh / 8) + 255) / 256));
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<L<decltype(dt)>, decltype(dh)::value>), grid, dim3(256), 0, st, a);
+  });
+}
+
 }  // namespace
 
-int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale,
-                                     float* v_scale, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int start_pos, long long bs,
-                                     long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs, (uint16_t*)q_out, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, bs, rs, B, S, H, Hkv,
-                     rot, lmax, start_pos, nullptr};
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<F16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<F16, 64>), grid, dim3(256), 0, st, a);
+// launch_kv_store's FP8 half: the same three forms (host position, device positions, device positions over pools) with codes and scales
+int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  RopeStoreFp8Args a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint8_t*)kv.k, (uint8_t*)kv.v, (float*)kv.k_scale, (float*)kv.v_scale,
+                     c.bs, c.rs, c.B, c.S, c.H, c.Hkv, c.rot, kv.capacity(), c.cache_seqlens ? c.table_rows : c.start_pos, c.cache_seqlens};
+  if (kv.block_table) {
+    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
+    a.ks_ps = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_ps = kv.vs_os, a.vs_rs = kv.vs_rs;
+    launch_store<PagedDevLen>(a, c.dtype, c.Dh, st);
+  } else if (c.cache_seqlens) {
+    launch_store<DevLen>(a, c.dtype, c.Dh, st);
   } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<BF16, 64>), grid, dim3(256), 0, st, a);
-  }
-  return 0;
-}
-
-int launch_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
-                                         float* v_scale, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax,
-                                         int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint8_t*)k_cache, (uint8_t*)v_cache, k_scale, v_scale, bs, rs, B, S, H,
-                     Hkv, rot, lmax, table_rows, cache_seqlens};
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<F16>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<F16>, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DevLen<BF16>, 64>), grid, dim3(256), 0, st, a);
-  }
-  return 0;
-}
-
-int launch_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
-                                       float* v_scale, const int* block_table, long long table_row_stride, int page_size, int num_pages,
-                                       int pages_per_seq, long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps,
-                                       long long ks_rs, long long vs_ps, long long vs_rs, const int* cache_seqlens, int B, int S, int H, int Hkv,
-                                       int Dh, int rot, int table_rows, long long bs, long long rs, int dtype, hipStream_t st) {
-  const long long n = (long long)B * S * (Dh / 8);
-  const long long cap = (long long)pages_per_seq * page_size;
-  RopeStoreFp8Args a{(const uint16_t*)qkv, freqs_table, (uint16_t*)q_out, (uint8_t*)k_pool, (uint8_t*)v_pool, k_scale, v_scale, bs, rs, B, S, H,
-                     Hkv, rot, (int)(cap < 0x7FFFFFFFll ? cap : 0x7FFFFFFFll), table_rows, cache_seqlens,
-                     PageArgs{block_table, table_row_stride, page_size, num_pages}, k_ps, k_rs, v_ps, v_rs, ks_ps, ks_rs, vs_ps, vs_rs};
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == 0) {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<F16>>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<F16>>, 64>), grid, dim3(256), 0, st, a);
-  } else {
-    if (Dh == 128) hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<BF16>>, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<Paged<DevLen<BF16>>, 64>), grid, dim3(256), 0, st, a);
+    launch_store<HostLen>(a, c.dtype, c.Dh, st);
   }
   return 0;
 }

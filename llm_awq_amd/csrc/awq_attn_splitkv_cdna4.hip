@@ -42,6 +42,7 @@
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
+#include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
 
 #include <math.h>
@@ -502,156 +503,67 @@ namespace {
 // partials only, so it is the T cache's in either case.
 // L is the identity for host lengths, DevLen for lengths on the device and PagedDevLen for those over a pool of pages; C is what L is to
 // the combine launch (the paged form combines with the dense DevLen kernel: the partials do not know where K / V came from).
-template <typename DT>
-using HostLen = DT;
-template <typename DT>
-using PagedDevLen = Paged<DevLen<DT>>;
-template <template <typename> class K, template <typename> class L = HostLen, template <typename> class C = L, typename A = SplitArgs>
-void launch_pair(const A& a, int Dh, int dtype, dim3 grid, dim3 cgrid, hipStream_t st) {
-  if (dtype == 0) {
-    if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<F16>, 128>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
-    } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<F16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<F16>, 64>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
-    }
-  } else {
-    if (Dh == 128) {
-      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 128>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<BF16>, 128>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
-    } else {
-      hipLaunchKernelGGL((attn_splitkv_kernel<L<K<BF16>>, 64>), grid, dim3(kNW * 64), 0, st, a);
-      hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<BF16>, 64>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
-    }
-  }
+template <template <typename> class K, template <typename> class L, template <typename> class C, typename A>
+void launch_pair(const A& a, int Dh, int dtype, hipStream_t st) {
+  const dim3 grid((unsigned)((long long)a.B * a.Hkv * a.splits));
+  const dim3 cgrid((unsigned)(((long long)a.B * a.Hkv * a.R * (Dh / 8) + 255) / 256));
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    using DT = decltype(dt);
+    constexpr int DH = decltype(dh)::value;
+    hipLaunchKernelGGL((attn_splitkv_kernel<L<K<DT>>, DH>), grid, dim3(kNW * 64), 0, st, a);
+    hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<DT>, DH>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
+  });
 }
 template <typename DT>
 using TCache = DT;  // the T cache: the element traits themselves
-
-// the arguments both cache formats share; the scale fields are left to the caller
-SplitArgs split_args(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
-                     long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int splits, int chunk,
-                     void* workspace) {
-  SplitArgs a;
-  a.q = (const uint16_t*)q;
-  a.k = (const uint16_t*)k;
-  a.v = (const uint16_t*)v;
-  a.out = (uint16_t*)out;
-  a.q_bs = q_bs;
-  a.q_rs = q_rs;
-  a.k_bs = k_bs;
-  a.k_rs = k_rs;
-  a.v_bs = v_bs;
-  a.v_rs = v_rs;
-  a.B = B;
-  a.Sq = Sq;
-  a.Sk = Sk;
-  a.H = H;
-  a.Hkv = Hkv;
-  a.G = H / Hkv;
-  a.R = Sq * a.G;
-  a.splits = splits;
-  a.chunk = chunk;
-  a.causal = causal ? 1 : 0;
-  a.scale_log2e = scale * 1.4426950408889634f;
-  const long long n = (long long)B * Hkv * a.R * splits;
-  a.ws_o = (float*)workspace;
-  a.ws_m = a.ws_o + n * Dh;
-  a.ws_l = a.ws_m + n;
-  a.k_scale = a.v_scale = nullptr;
-  a.ks_bs = a.ks_rs = a.vs_bs = a.vs_rs = 0;
-  a.seqlens_k = nullptr;
-  a.seqlen_offset = 0;
-  return a;
+template <template <typename> class L, template <typename> class C, typename A>
+void launch_for_cache(const A& a, int Dh, int dtype, hipStream_t st) {
+  if (a.k_scale) launch_pair<Kv8, L, C>(a, Dh, dtype, st);
+  else launch_pair<TCache, L, C>(a, Dh, dtype, st);
 }
 
 }  // namespace
 
-// The caller has validated the arguments, found splits > 1 in the plan and a workspace of attn_splitkv_workspace_bytes.
-int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
-                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
-                        int splits, int chunk, void* workspace, hipStream_t st) {
-  const SplitArgs a = split_args(q, k, v, out, B, Sq, Sk, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk, workspace);
-  const dim3 grid((unsigned)((long long)B * Hkv * splits));
-  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
-  launch_pair<TCache>(a, Dh, dtype, grid, cgrid, st);
-  return 0;
-}
-
-// The same pair on the FP8 cache: k / v are e4m3 codes with strides in bytes, k_scale / v_scale their fp32 scales [B, Sk, Hkv] with strides
-// in floats (awq_kv8.hpp).  Same plan, same workspace.
-int launch_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
-                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
-                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
-                            int splits, int chunk, void* workspace, hipStream_t st) {
-  SplitArgs a = split_args(q, k, v, out, B, Sq, Sk, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk, workspace);
-  a.k_scale = k_scale;
-  a.v_scale = v_scale;
-  a.ks_bs = ks_bs;
-  a.ks_rs = ks_rs;
-  a.vs_bs = vs_bs;
-  a.vs_rs = vs_rs;
-  const dim3 grid((unsigned)((long long)B * Hkv * splits));
-  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
-  launch_pair<Kv8>(a, Dh, dtype, grid, cgrid, st);
-  return 0;
-}
-
-// The device-length pair (awq_attn_kvcache[_kv8]): k / v are the caches, the Sk of the arguments is the bound max_seqlen_k (<= the cache
-// length, so the clamp to Sk_b - 1 <= max_seqlen_k - 1 stays inside the sequence's cache rows), k_scale == nullptr selects the T cache.
-// The caller has validated the arguments and holds a workspace of attn_kvcache_workspace_bytes.
-int launch_attn_kvcache(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
-                        const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
-                        long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs,
-                        long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st) {
-  SplitArgs a = split_args(q, k, v, out, B, Sq, max_seqlen_k, H, Hkv, Dh, q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, scale, causal, splits, chunk,
-                           workspace);
-  a.seqlens_k = seqlens_k;
-  a.seqlen_offset = seqlen_offset;
-  const dim3 grid((unsigned)((long long)B * Hkv * splits));
-  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
-  if (k_scale) {
-    a.k_scale = k_scale;
-    a.v_scale = v_scale;
-    a.ks_bs = ks_bs;
-    a.ks_rs = ks_rs;
-    a.vs_bs = vs_bs;
-    a.vs_rs = vs_rs;
-    launch_pair<Kv8, DevLen>(a, Dh, dtype, grid, cgrid, st);
-  } else {
-    launch_pair<TCache, DevLen>(a, Dh, dtype, grid, cgrid, st);
-  }
-  return 0;
-}
-
-// The paged pair (awq_attn_kvcache_paged[_kv8]): k / v are the pools [num_pages, page_size, Hkv, Dh] with their page and row strides, the
-// scale strides likewise; max_seqlen_k <= pages_per_seq * page_size, so every table index the kernel forms lies inside a table row.
-// launch_attn_kvcache's plan, workspace and combine launch.
-int launch_attn_kvcache_paged(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out,
-                              const int* block_table, long long table_row_stride, int page_size, int num_pages, int B, int Sq,
-                              const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
-                              long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps, long long ks_rs, long long vs_ps,
-                              long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st) {
+// The split pair over a view.  Host length: Sk keys of every sequence.  Device lengths (awq_attn_kvcache[_kv8]): the Sk of the kernel
+// arguments is the bound max_seqlen_k (<= the capacity of the view, so the clamp to Sk_b - 1 <= max_seqlen_k - 1 stays inside the
+// sequence's rows).  Paged (awq_attn_kvcache_paged[_kv8]): k / v are the pools and the outer strides their page strides; max_seqlen_k <=
+// pages_per_seq * page_size, so every table index the kernel forms lies inside a table row.  Scales in the view select the FP8 cache
+// (awq_kv8.hpp: codes with strides in bytes, scales with strides in floats).  The caller has validated the arguments and holds the plan
+// (splits > 1 for a host length) and a workspace of its size.
+int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st) {
+  const KvView& kv = c.kv;
   PagedSplitArgs a;
-  static_cast<SplitArgs&>(a) = split_args(q, k, v, out, B, Sq, max_seqlen_k, H, Hkv, Dh, q_bs, q_rs, k_ps, k_rs, v_ps, v_rs, scale, causal, splits,
-                                          chunk, workspace);
-  a.seqlens_k = seqlens_k;
-  a.seqlen_offset = seqlen_offset;
-  a.pg = PageArgs{block_table, table_row_stride, page_size, num_pages};
-  const dim3 grid((unsigned)((long long)B * Hkv * splits));
-  const dim3 cgrid((unsigned)(((long long)B * Hkv * a.R * (Dh / 8) + 255) / 256));
-  if (k_scale) {
-    a.k_scale = k_scale;
-    a.v_scale = v_scale;
-    a.ks_bs = ks_ps;
-    a.ks_rs = ks_rs;
-    a.vs_bs = vs_ps;
-    a.vs_rs = vs_rs;
-    launch_pair<Kv8, PagedDevLen, DevLen>(a, Dh, dtype, grid, cgrid, st);
-  } else {
-    launch_pair<TCache, PagedDevLen, DevLen>(a, Dh, dtype, grid, cgrid, st);
-  }
+  a.q = (const uint16_t*)c.q;
+  a.k = (const uint16_t*)kv.k;
+  a.v = (const uint16_t*)kv.v;
+  a.out = (uint16_t*)c.out;
+  a.q_bs = c.q_bs, a.q_rs = c.q_rs;
+  a.k_bs = kv.k_os, a.k_rs = kv.k_rs, a.v_bs = kv.v_os, a.v_rs = kv.v_rs;
+  a.B = c.B;
+  a.Sq = c.Sq;
+  a.Sk = c.seqlens_k ? c.max_seqlen_k : c.Sk;
+  a.H = c.H;
+  a.Hkv = c.Hkv;
+  a.G = c.H / c.Hkv;
+  a.R = c.Sq * a.G;
+  a.splits = splits;
+  a.chunk = chunk;
+  a.causal = c.causal ? 1 : 0;
+  a.scale_log2e = c.scale * 1.4426950408889634f;
+  const long long n = (long long)c.B * c.Hkv * a.R * splits;
+  a.ws_o = (float*)workspace;
+  a.ws_m = a.ws_o + n * c.Dh;
+  a.ws_l = a.ws_m + n;
+  a.k_scale = kv.k_scale;
+  a.v_scale = kv.v_scale;
+  a.ks_bs = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_bs = kv.vs_os, a.vs_rs = kv.vs_rs;
+  a.seqlens_k = c.seqlens_k;
+  a.seqlen_offset = c.seqlens_k ? c.seqlen_offset : 0;
+  a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+  const SplitArgs& dense = a;
+  if (kv.block_table) launch_for_cache<PagedDevLen, DevLen>(a, c.Dh, c.dtype, st);
+  else if (c.seqlens_k) launch_for_cache<DevLen, DevLen>(dense, c.Dh, c.dtype, st);
+  else launch_for_cache<HostLen, HostLen>(dense, c.Dh, c.dtype, st);
   return 0;
 }
 

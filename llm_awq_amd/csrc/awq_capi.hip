@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "awq_kernels.hpp"
+#include "awq_kvcache.hpp"
 
 namespace {
 thread_local char g_last_hip_error[256] = "";
@@ -411,24 +412,6 @@ int awq_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_
   return finish_launch();
 }
 
-int awq_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int batch, int cache_batch,
-                              int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
-                              long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs || !q_out || !k_cache || !v_cache) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (batch < 1 || cache_batch < batch || seqlen < 1 || nheads < 1 || nheads_kv < 1 || (head_dim != 64 && head_dim != 128) ||
-      (head_dim % 8) != 0 || rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_dim || lmax < 1 || start_pos < 0 ||
-      (long long)start_pos + seqlen > lmax || qkv_batch_stride < 0 ||
-      qkv_row_stride < ((long long)nheads + 2ll * nheads_kv) * head_dim || (long long)batch * seqlen * (head_dim / 8) > 0x3FFFFFFFll * 256)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
-      (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_natural(qkv, freqs, q_out, k_cache, v_cache, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, start_pos,
-                                    qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
-  return finish_launch();
-}
-
 int awq_attn_splitkv_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* splits, int* chunk) {
   if (!splits || !chunk) return AWQ_ERR_NULL;
   if (!prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal)) return AWQ_ERR_SHAPE;
@@ -440,160 +423,73 @@ size_t awq_attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, in
   return awq::attn_splitkv_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal);
 }
 
-int awq_attn_splitkv(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
-                     int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
-                     long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-  if (!q || !k || !v || !out) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal) || q_batch_stride < 0 || k_batch_stride < 0 ||
-      v_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
-      v_row_stride < (long long)nheads_kv * head_dim)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 ||
-      (v_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  int splits = 1, chunk = 0;
-  awq::attn_splitkv_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, &splits, &chunk);
-  if (splits <= 1)  // not taken: the one-pass launch, bit for bit
-    return awq_attn_prefill(q, k, v, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_batch_stride,
-                            k_row_stride, v_batch_stride, v_row_stride, softmax_scale, causal, dtype, stream);
-  const size_t need = awq::attn_splitkv_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal);
-  if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
-  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
-  if ((long long)batch * nheads_kv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
-  awq::launch_attn_splitkv(q, k, v, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_batch_stride,
-                           k_row_stride, v_batch_stride, v_row_stride, softmax_scale, causal, dtype, splits, chunk, workspace,
-                           (hipStream_t)stream);
-  return finish_launch();
-}
+// ---- The natural-layout KV cache family (awq_kvcache.hpp): the rope + store of a chunk and the split-KV attention of few query rows, over
+//      dense caches or a pool of pages (awq_paged.hpp), T or FP8 (awq_kv8.hpp), positions / lengths from the host or read on the device
+//      (awq_devlen.hpp).  Every entry below builds one descriptor from its positional arguments; the checks exist once per phase -- null,
+//      dtype, shape, alignment, then the attention tail -- and take the format-dependent terms from the descriptor and the entry's format.
+using awq::KvAttnCall;
+using awq::KvStoreCall;
+using awq::KvView;
+enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4 };  // what an entry requires of its descriptor
 
-// ---- FP8 KV cache on the natural layout (awq_kv8.hpp) ----
-int awq_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
-                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
-                                  int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs || !q_out || !k_cache || !v_cache || !k_scale || !v_scale) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (batch < 1 || cache_batch < batch || seqlen < 1 || nheads < 1 || nheads_kv < 1 || (head_dim != 64 && head_dim != 128) ||
-      rot_dim < 16 || (rot_dim % 16) != 0 || rot_dim > head_dim || lmax < 1 || start_pos < 0 ||
-      (long long)start_pos + seqlen > lmax || qkv_batch_stride < 0 ||
-      qkv_row_stride < ((long long)nheads + 2ll * nheads_kv) * head_dim || (long long)batch * seqlen * (head_dim / 8) > 0x3FFFFFFFll * 256)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
-      (reinterpret_cast<uintptr_t>(k_scale) & 3u) || (reinterpret_cast<uintptr_t>(v_scale) & 3u) || (qkv_batch_stride % 8) != 0 ||
-      (qkv_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_natural_fp8(qkv, freqs, q_out, k_cache, v_cache, k_scale, v_scale, batch, seqlen, nheads, nheads_kv, head_dim,
-                                        rot_dim, lmax, start_pos, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
-  return finish_launch();
-}
-
-// the argument checks both FP8 attention entries share; AWQ_OK: the launch may go on
-static int kv8_attn_check(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, const void* out, int batch,
-                          int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
-                          long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
-                          long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
-                          long long v_scale_row_stride, int causal, int dtype) {
-  if (!q || !k || !v || !k_scale || !v_scale || !out) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if ((head_dim != 64 && head_dim != 128) || !prefill_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal) ||
-      q_batch_stride < 0 || k_batch_stride < 0 || v_batch_stride < 0 || k_scale_batch_stride < 0 || v_scale_batch_stride < 0 ||
-      q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
-      v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv || v_scale_row_stride < nheads_kv)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || (reinterpret_cast<uintptr_t>(k_scale) & 3u) ||
-      (reinterpret_cast<uintptr_t>(v_scale) & 3u) || (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_batch_stride % 16) != 0 ||
-      (k_row_stride % 16) != 0 || (v_batch_stride % 16) != 0 || (v_row_stride % 16) != 0)
-    return AWQ_ERR_ALIGN;
-  return AWQ_OK;
-}
-
-int awq_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
-                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
-                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
-                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
-                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
-  const int rc = kv8_attn_check(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
-                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
-                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, causal, dtype);
-  if (rc != AWQ_OK) return rc;
-  awq::launch_attn_prefill_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
-                               q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
-                               k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
-  return finish_launch();
-}
-
-int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
-                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
-                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
-                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
-                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-  const int rc = kv8_attn_check(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
-                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
-                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, causal, dtype);
-  if (rc != AWQ_OK) return rc;
-  int splits = 1, chunk = 0;
-  awq::attn_splitkv_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal, &splits, &chunk);
-  if (splits <= 1)  // not taken: the one-pass launch, bit for bit
-    return awq_attn_prefill_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
-                                q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
-                                k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, stream);
-  const size_t need = awq::attn_splitkv_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlen_k, causal);
-  if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
-  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
-  if ((long long)batch * nheads_kv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
-  awq::launch_attn_splitkv_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
-                               q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
-                               k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, splits, chunk,
-                               workspace, (hipStream_t)stream);
-  return finish_launch();
-}
-
-// ---- lengths on the device: the natural-layout decode path for ragged batches and whole-phase graph capture (awq_devlen.hpp) ----
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-// the shape rules both store entries share (awq_rope_kv_store_natural's, with table_rows in the place of start_pos)
-static bool store_pos_shape_ok(int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
-                               int table_rows, long long qkv_batch_stride, long long qkv_row_stride) {
-  return batch >= 1 && cache_batch >= batch && seqlen >= 1 && nheads >= 1 && nheads_kv >= 1 && (head_dim == 64 || head_dim == 128) &&
-         rot_dim >= 16 && (rot_dim % 16) == 0 && rot_dim <= head_dim && lmax >= 1 && table_rows >= 1 && qkv_batch_stride >= 0 &&
-         qkv_row_stride >= ((long long)nheads + 2ll * nheads_kv) * head_dim && (long long)batch * seqlen * (head_dim / 8) <= 0x3FFFFFFFll * 256;
+static KvView kv_view(const void* k, const void* v, int outer, int rows, long long k_os = 0, long long k_rs = 0, long long v_os = 0,
+                      long long v_rs = 0) {
+  KvView kv;
+  kv.k = k, kv.v = v, kv.outer = outer, kv.rows = rows;
+  kv.k_os = k_os, kv.k_rs = k_rs, kv.v_os = v_os, kv.v_rs = v_rs;
+  return kv;
+}
+static KvView with_scales(KvView kv, const float* k_scale, const float* v_scale, long long ks_os = 0, long long ks_rs = 0, long long vs_os = 0,
+                          long long vs_rs = 0) {
+  kv.k_scale = k_scale, kv.v_scale = v_scale;
+  kv.ks_os = ks_os, kv.ks_rs = ks_rs, kv.vs_os = vs_os, kv.vs_rs = vs_rs;
+  return kv;
+}
+static KvView with_table(KvView kv, const int* block_table, long long table_row_stride, int pages_per_seq) {
+  kv.block_table = block_table, kv.bt_rs = table_row_stride, kv.pages_per_seq = pages_per_seq;
+  return kv;
 }
 
-int awq_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
-                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
-                                  int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs_table || !q_out || !k_cache || !v_cache || !cache_seqlens) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!store_pos_shape_ok(batch, cache_batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride))
+// The view's terms of the null, shape and alignment phases.  strided: the entry gives the caches' strides (every attention entry and the
+// paged stores; the dense stores take contiguous caches).
+static bool kv_has_null(const KvView& kv, int fmt) {
+  return !kv.k || !kv.v || ((fmt & KV_FP8) && (!kv.k_scale || !kv.v_scale)) || ((fmt & KV_PAGED) && !kv.block_table);
+}
+static bool kv_shape_ok(const KvView& kv, int fmt, bool strided, int nheads_kv, int head_dim) {
+  if ((fmt & KV_PAGED) && !(kv.rows >= 64 && (kv.rows % 64) == 0 && kv.outer >= 1 && kv.pages_per_seq >= 1 && kv.bt_rs >= kv.pages_per_seq))
+    return false;
+  if (!strided) return true;
+  const long long row = (long long)nheads_kv * head_dim;
+  if (kv.k_os < 0 || kv.v_os < 0 || kv.k_rs < row || kv.v_rs < row) return false;
+  return !(fmt & KV_FP8) || (kv.ks_os >= 0 && kv.vs_os >= 0 && kv.ks_rs >= nheads_kv && kv.vs_rs >= nheads_kv);
+}
+static bool kv_aligned(const KvView& kv, int fmt, bool strided) {
+  const int unit = (fmt & KV_FP8) ? 16 : 8;  // 16 bytes of T or of codes
+  return aligned16(kv.k) && aligned16(kv.v) && (!(fmt & KV_FP8) || (aligned4(kv.k_scale) && aligned4(kv.v_scale))) &&
+         (!(fmt & KV_PAGED) || aligned4(kv.block_table)) &&
+         (!strided || ((kv.k_os % unit) == 0 && (kv.k_rs % unit) == 0 && (kv.v_os % unit) == 0 && (kv.v_rs % unit) == 0));
+}
+
+static int kv_store(const KvStoreCall& c, int fmt, void* stream) {
+  const KvView& kv = c.kv;
+  const bool paged = fmt & KV_PAGED, devlen = fmt & KV_DEVLEN;
+  if (!c.qkv || !c.freqs || !c.q_out || kv_has_null(kv, fmt) || (devlen && !c.cache_seqlens)) return AWQ_ERR_NULL;
+  if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (c.B < 1 || c.S < 1 || c.H < 1 || c.Hkv < 1 || (c.Dh != 64 && c.Dh != 128) || c.rot < 16 || (c.rot % 16) != 0 || c.rot > c.Dh || c.bs < 0 ||
+      c.rs < ((long long)c.H + 2ll * c.Hkv) * c.Dh || (long long)c.B * c.S * (c.Dh / 8) > 0x3FFFFFFFll * 256 ||
+      (!paged && (kv.outer < c.B || kv.rows < 1)) || !kv_shape_ok(kv, fmt, paged, c.Hkv, c.Dh) ||
+      (devlen ? c.table_rows < 1 : (c.start_pos < 0 || (long long)c.start_pos + c.S > kv.rows)))
     return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) ||
-      !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
+  if (!aligned16(c.qkv) || !aligned16(c.freqs) || !aligned16(c.q_out) || !kv_aligned(kv, fmt, paged) || (devlen && !aligned4(c.cache_seqlens)) ||
+      (c.bs % 8) != 0 || (c.rs % 8) != 0)
     return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_natural_pos(qkv, freqs_table, q_out, k_cache, v_cache, cache_seqlens, batch, seqlen, nheads, nheads_kv, head_dim,
-                                        rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  awq::launch_kv_store(c, (hipStream_t)stream);
   return finish_launch();
 }
 
-int awq_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
-                                      float* v_scale, const int* cache_seqlens, int batch, int cache_batch, int seqlen, int nheads,
-                                      int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
-                                      long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs_table || !q_out || !k_cache || !v_cache || !k_scale || !v_scale || !cache_seqlens) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!store_pos_shape_ok(batch, cache_batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride))
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned4(k_scale) ||
-      !aligned4(v_scale) || !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_natural_pos_fp8(qkv, freqs_table, q_out, k_cache, v_cache, k_scale, v_scale, cache_seqlens, batch, seqlen, nheads,
-                                            nheads_kv, head_dim, rot_dim, lmax, table_rows, qkv_batch_stride, qkv_row_stride, dtype,
-                                            (hipStream_t)stream);
-  return finish_launch();
-}
-
-// the split pair always runs here: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions
+// the split pair always runs under device lengths: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions
 static bool kvcache_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k) {
   return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 && (head_dim == 64 || head_dim == 128) && seqlen_q >= 1 &&
          (long long)seqlen_q * (nheads / nheads_kv) <= 128 && max_seqlen_k >= 1;
@@ -610,79 +506,81 @@ size_t awq_attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, in
   return awq::attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k);
 }
 
-// the checks both cache formats share behind their pointer / stride checks; AWQ_OK: *splits / *chunk hold the plan and the launch may go on
-static int kvcache_check(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, const int* seqlens_k, int seqlen_offset,
-                         int max_seqlen_k, int lmax, const void* workspace, size_t workspace_bytes, int* splits, int* chunk) {
-  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || max_seqlen_k > lmax || seqlen_offset < 0)
+// the four phases every attention entry shares; AWQ_OK: the tail (kv_attn) or the one-pass launch may go on
+static int kv_attn_check(const KvAttnCall& c, int fmt) {
+  const KvView& kv = c.kv;
+  const bool devlen = fmt & KV_DEVLEN;
+  if (!c.q || !c.out || kv_has_null(kv, fmt) || (devlen && !c.seqlens_k)) return AWQ_ERR_NULL;
+  if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  // (host lengths: the T entry keeps the one-pass kernel's head dim 72 for the calls the plan hands to it; the FP8 kernels have 64 / 128)
+  if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k)
+               : ((!(fmt & KV_FP8) || c.Dh == 64 || c.Dh == 128) && prefill_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal))) ||
+      !kv_shape_ok(kv, fmt, true, c.Hkv, c.Dh) || c.q_bs < 0 || c.q_rs < (long long)c.H * c.Dh)
     return AWQ_ERR_SHAPE;
-  if (!aligned4(seqlens_k)) return AWQ_ERR_ALIGN;
-  awq::attn_kvcache_plan(batch, nheads_kv, max_seqlen_k, splits, chunk);
-  if (!workspace || workspace_bytes < awq::attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k))
-    return AWQ_ERR_WORKSPACE;
-  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
-  if ((long long)batch * nheads_kv * *splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
+  if (!aligned16(c.q) || !aligned16(c.out) || !kv_aligned(kv, fmt, true) || (c.q_bs % 8) != 0 || (c.q_rs % 8) != 0) return AWQ_ERR_ALIGN;
   return AWQ_OK;
 }
 
-int awq_attn_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
-                     int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
-                     long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
-                     float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q || !k_cache || !v_cache || !out || !seqlens_k) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || q_batch_stride < 0 || k_batch_stride < 0 ||
-      v_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
-      v_row_stride < (long long)nheads_kv * head_dim)
-    return AWQ_ERR_SHAPE;
-  int splits = 1, chunk = 0;
-  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || (q_batch_stride % 8) != 0 || (k_batch_stride % 8) != 0 ||
-      (v_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, lmax, workspace,
-                               workspace_bytes, &splits, &chunk);
+// check, plan, workspace, launch.  Under a host length a plan of one split is the one-pass launch, bit for bit.
+static int kv_attn(const KvAttnCall& c, int fmt, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView& kv = c.kv;
+  const int rc = kv_attn_check(c, fmt);
   if (rc != AWQ_OK) return rc;
-  awq::launch_attn_kvcache(q, k_cache, v_cache, nullptr, nullptr, out, batch, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv,
-                           head_dim, q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, 0, 0, 0, 0,
-                           softmax_scale, causal, dtype, splits, chunk, workspace, (hipStream_t)stream);
+  int splits = 1, chunk = 0;
+  size_t need = 0;
+  if (fmt & KV_DEVLEN) {
+    if (c.max_seqlen_k > kv.capacity() || c.seqlen_offset < 0) return AWQ_ERR_SHAPE;
+    if (!aligned4(c.seqlens_k)) return AWQ_ERR_ALIGN;
+    awq::attn_kvcache_plan(c.B, c.Hkv, c.max_seqlen_k, &splits, &chunk);
+    need = awq::attn_kvcache_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k);
+  } else {
+    awq::attn_splitkv_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal, &splits, &chunk);
+    if (splits <= 1)
+      return kv.k_scale ? awq_attn_prefill_kv8(c.q, kv.k, kv.v, kv.k_scale, kv.v_scale, c.out, c.B, c.Sq, c.Sk, c.H, c.Hkv, c.Dh, c.q_bs, c.q_rs,
+                                               kv.k_os, kv.k_rs, kv.v_os, kv.v_rs, kv.ks_os, kv.ks_rs, kv.vs_os, kv.vs_rs, c.scale, c.causal,
+                                               c.dtype, stream)
+                        : awq_attn_prefill(c.q, kv.k, kv.v, c.out, c.B, c.Sq, c.Sk, c.H, c.Hkv, c.Dh, c.q_bs, c.q_rs, kv.k_os, kv.k_rs, kv.v_os,
+                                           kv.v_rs, c.scale, c.causal, c.dtype, stream);
+    need = awq::attn_splitkv_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal);
+  }
+  if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
+  if ((long long)c.B * c.Hkv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
+  awq::launch_kv_attn(c, splits, chunk, workspace, (hipStream_t)stream);
   return finish_launch();
 }
 
-int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out, int batch,
-                         int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
-                         int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
-                         long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
-                         long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q || !k_cache || !v_cache || !k_scale || !v_scale || !out || !seqlens_k) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) || q_batch_stride < 0 || k_batch_stride < 0 ||
-      v_batch_stride < 0 || k_scale_batch_stride < 0 || v_scale_batch_stride < 0 || q_row_stride < (long long)nheads * head_dim ||
-      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv ||
-      v_scale_row_stride < nheads_kv)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || !aligned4(k_scale) || !aligned4(v_scale) ||
-      (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_batch_stride % 16) != 0 || (k_row_stride % 16) != 0 ||
-      (v_batch_stride % 16) != 0 || (v_row_stride % 16) != 0)
-    return AWQ_ERR_ALIGN;
-  int splits = 1, chunk = 0;
-  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, lmax, workspace,
-                               workspace_bytes, &splits, &chunk);
-  if (rc != AWQ_OK) return rc;
-  awq::launch_attn_kvcache(q, k_cache, v_cache, k_scale, v_scale, out, batch, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv,
-                           head_dim, q_batch_stride, q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride,
-                           k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, splits,
-                           chunk, workspace, (hipStream_t)stream);
-  return finish_launch();
+int awq_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int batch, int cache_batch,
+                              int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
+                              long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store({qkv, freqs, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), start_pos, nullptr, 0, batch, seqlen, nheads, nheads_kv,
+                   head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype},
+                  0, stream);
 }
 
-// ---- the paged KV cache: the two device-length entries above over a pool of pages and a block table (awq_paged.hpp) ----
-static bool paged_shape_ok(int num_pages, int page_size, int pages_per_seq, long long table_row_stride) {
-  return page_size >= 64 && (page_size % 64) == 0 && num_pages >= 1 && pages_per_seq >= 1 && table_row_stride >= pages_per_seq;
+int awq_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store({qkv, freqs, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale), start_pos, nullptr, 0, batch,
+                   seqlen, nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype},
+                  KV_FP8, stream);
 }
-// keys a table row can name, as an int (positions and lengths are int32)
-static int paged_capacity(int page_size, int pages_per_seq) {
-  const long long cap = (long long)pages_per_seq * page_size;
-  return cap < 0x7FFFFFFFll ? (int)cap : 0x7FFFFFFF;
+
+int awq_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
+                                  int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                  int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store({qkv, freqs_table, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), 0, cache_seqlens, table_rows, batch, seqlen, nheads,
+                   nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype},
+                  KV_DEVLEN, stream);
+}
+
+int awq_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                      float* v_scale, const int* cache_seqlens, int batch, int cache_batch, int seqlen, int nheads,
+                                      int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
+                                      long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store({qkv, freqs_table, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale), 0, cache_seqlens,
+                   table_rows, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype},
+                  KV_FP8 | KV_DEVLEN, stream);
 }
 
 int awq_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
@@ -690,20 +588,11 @@ int awq_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void*
                                 int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
                                 long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
                                 long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs_table || !q_out || !k_pool || !v_pool || !block_table || !cache_seqlens) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!store_pos_shape_ok(batch, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, 1, table_rows, qkv_batch_stride, qkv_row_stride) ||
-      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || k_page_stride < 0 || v_page_stride < 0 ||
-      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned4(block_table) ||
-      !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0 || (k_page_stride % 8) != 0 ||
-      (k_row_stride % 8) != 0 || (v_page_stride % 8) != 0 || (v_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_paged_pos(qkv, freqs_table, q_out, k_pool, v_pool, block_table, table_row_stride, page_size, num_pages, pages_per_seq,
-                                      k_page_stride, k_row_stride, v_page_stride, v_row_stride, cache_seqlens, batch, seqlen, nheads, nheads_kv,
-                                      head_dim, rot_dim, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
-  return finish_launch();
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_store({qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim,
+                   qkv_batch_stride, qkv_row_stride, dtype},
+                  KV_PAGED | KV_DEVLEN, stream);
 }
 
 int awq_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
@@ -713,22 +602,85 @@ int awq_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, v
                                     long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
                                     long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_batch_stride,
                                     long long qkv_row_stride, int dtype, void* stream) {
-  if (!qkv || !freqs_table || !q_out || !k_pool || !v_pool || !k_scale || !v_scale || !block_table || !cache_seqlens) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!store_pos_shape_ok(batch, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, 1, table_rows, qkv_batch_stride, qkv_row_stride) ||
-      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || k_page_stride < 0 || v_page_stride < 0 ||
-      k_scale_page_stride < 0 || v_scale_page_stride < 0 || k_row_stride < (long long)nheads_kv * head_dim ||
-      v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv || v_scale_row_stride < nheads_kv)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(qkv) || !aligned16(freqs_table) || !aligned16(q_out) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned4(k_scale) ||
-      !aligned4(v_scale) || !aligned4(block_table) || !aligned4(cache_seqlens) || (qkv_batch_stride % 8) != 0 || (qkv_row_stride % 8) != 0 ||
-      (k_page_stride % 16) != 0 || (k_row_stride % 16) != 0 || (v_page_stride % 16) != 0 || (v_row_stride % 16) != 0)
-    return AWQ_ERR_ALIGN;
-  awq::launch_rope_kv_store_paged_pos_fp8(qkv, freqs_table, q_out, k_pool, v_pool, k_scale, v_scale, block_table, table_row_stride, page_size,
-                                          num_pages, pages_per_seq, k_page_stride, k_row_stride, v_page_stride, v_row_stride, k_scale_page_stride,
-                                          k_scale_row_stride, v_scale_page_stride, v_scale_row_stride, cache_seqlens, batch, seqlen, nheads,
-                                          nheads_kv, head_dim, rot_dim, table_rows, qkv_batch_stride, qkv_row_stride, dtype, (hipStream_t)stream);
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_store({qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim,
+                   qkv_batch_stride, qkv_row_stride, dtype},
+                  KV_FP8 | KV_PAGED | KV_DEVLEN, stream);
+}
+
+int awq_attn_splitkv(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
+                     int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                     long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  const KvView kv = kv_view(k, v, batch, seqlen_k, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_attn({q, out, kv, seqlen_k, nullptr, 0, 0, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, softmax_scale,
+                  causal, dtype},
+                 0, workspace, workspace_bytes, stream);
+}
+
+// k / v [batch, seqlen_k, Hkv, Dh] of e4m3 codes with their scales, as one descriptor (both host-length FP8 entries)
+static KvAttnCall kv8_attn_call(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                                int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                                long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                                long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                                long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype) {
+  const KvView kv = with_scales(kv_view(k, v, batch, seqlen_k, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale, v_scale,
+                                k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return {q, out, kv, seqlen_k, nullptr, 0, 0, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, softmax_scale, causal,
+          dtype};
+}
+
+int awq_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  const int rc = kv_attn_check(kv8_attn_call(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                                             q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                                             k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype),
+                               KV_FP8);
+  if (rc != AWQ_OK) return rc;
+  awq::launch_attn_prefill_kv8(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride,
+                               q_row_stride, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride,
+                               k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype, (hipStream_t)stream);
   return finish_launch();
+}
+
+int awq_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, int seqlen_k, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                         long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                         long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                         long long v_scale_row_stride, float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  return kv_attn(kv8_attn_call(q, k, v, k_scale, v_scale, out, batch, seqlen_q, seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride,
+                               k_batch_stride, k_row_stride, v_batch_stride, v_row_stride, k_scale_batch_stride, k_scale_row_stride,
+                               v_scale_batch_stride, v_scale_row_stride, softmax_scale, causal, dtype),
+                 KV_FP8, workspace, workspace_bytes, stream);
+}
+
+int awq_attn_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
+                     int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                     long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                     float softmax_scale, int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_attn({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                  q_row_stride, softmax_scale, causal, dtype},
+                 KV_DEVLEN, workspace, workspace_bytes, stream);
+}
+
+int awq_attn_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out, int batch,
+                         int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                         long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                         long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_scales(kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale,
+                                v_scale, k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return kv_attn({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                  q_row_stride, softmax_scale, causal, dtype},
+                 KV_FP8 | KV_DEVLEN, workspace, workspace_bytes, stream);
 }
 
 int awq_attn_kvcache_paged(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch, int seqlen_q,
@@ -736,25 +688,11 @@ int awq_attn_kvcache_paged(const void* q, const void* k_pool, const void* v_pool
                            long long table_row_stride, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
                            long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, float softmax_scale,
                            int causal, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q || !k_pool || !v_pool || !out || !block_table || !seqlens_k) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) ||
-      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || q_batch_stride < 0 || k_page_stride < 0 || v_page_stride < 0 ||
-      q_row_stride < (long long)nheads * head_dim || k_row_stride < (long long)nheads_kv * head_dim ||
-      v_row_stride < (long long)nheads_kv * head_dim)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || !aligned4(block_table) || (q_batch_stride % 8) != 0 ||
-      (k_page_stride % 8) != 0 || (v_page_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_row_stride % 8) != 0 || (v_row_stride % 8) != 0)
-    return AWQ_ERR_ALIGN;
-  int splits = 1, chunk = 0;
-  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k,
-                               paged_capacity(page_size, pages_per_seq), workspace, workspace_bytes, &splits, &chunk);
-  if (rc != AWQ_OK) return rc;
-  awq::launch_attn_kvcache_paged(q, k_pool, v_pool, nullptr, nullptr, out, block_table, table_row_stride, page_size, num_pages, batch, seqlen_q,
-                                 seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_page_stride,
-                                 k_row_stride, v_page_stride, v_row_stride, 0, 0, 0, 0, softmax_scale, causal, dtype, splits, chunk, workspace,
-                                 (hipStream_t)stream);
-  return finish_launch();
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_attn({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                  q_row_stride, softmax_scale, causal, dtype},
+                 KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
 }
 
 int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
@@ -764,27 +702,12 @@ int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_
                                long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
                                long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q || !k_pool || !v_pool || !k_scale || !v_scale || !out || !block_table || !seqlens_k) return AWQ_ERR_NULL;
-  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
-  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) ||
-      !paged_shape_ok(num_pages, page_size, pages_per_seq, table_row_stride) || q_batch_stride < 0 || k_page_stride < 0 || v_page_stride < 0 ||
-      k_scale_page_stride < 0 || v_scale_page_stride < 0 || q_row_stride < (long long)nheads * head_dim ||
-      k_row_stride < (long long)nheads_kv * head_dim || v_row_stride < (long long)nheads_kv * head_dim || k_scale_row_stride < nheads_kv ||
-      v_scale_row_stride < nheads_kv)
-    return AWQ_ERR_SHAPE;
-  if (!aligned16(q) || !aligned16(k_pool) || !aligned16(v_pool) || !aligned16(out) || !aligned4(k_scale) || !aligned4(v_scale) ||
-      !aligned4(block_table) || (q_batch_stride % 8) != 0 || (q_row_stride % 8) != 0 || (k_page_stride % 16) != 0 || (k_row_stride % 16) != 0 ||
-      (v_page_stride % 16) != 0 || (v_row_stride % 16) != 0)
-    return AWQ_ERR_ALIGN;
-  int splits = 1, chunk = 0;
-  const int rc = kvcache_check(batch, nheads, nheads_kv, head_dim, seqlen_q, seqlens_k, seqlen_offset, max_seqlen_k,
-                               paged_capacity(page_size, pages_per_seq), workspace, workspace_bytes, &splits, &chunk);
-  if (rc != AWQ_OK) return rc;
-  awq::launch_attn_kvcache_paged(q, k_pool, v_pool, k_scale, v_scale, out, block_table, table_row_stride, page_size, num_pages, batch, seqlen_q,
-                                 seqlens_k, seqlen_offset, max_seqlen_k, nheads, nheads_kv, head_dim, q_batch_stride, q_row_stride, k_page_stride,
-                                 k_row_stride, v_page_stride, v_row_stride, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride,
-                                 v_scale_row_stride, softmax_scale, causal, dtype, splits, chunk, workspace, (hipStream_t)stream);
-  return finish_launch();
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_attn({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                  q_row_stride, softmax_scale, causal, dtype},
+                 KV_FP8 | KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
 }
 
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {

@@ -11,6 +11,8 @@ namespace awq {
 template <typename DT>
 struct DevLen : DT {};
 template <typename DT>
+using HostLen = DT;  // lengths / positions from the host: the element traits themselves
+template <typename DT>
 struct IsDevLen {
   static constexpr bool value = false;
 };

@@ -184,58 +184,20 @@ int launch_attn_prefill_ftcache(const void* q, const void* k_cache, const void* 
 // prompt-side chunk preparation (awq_attn_chunk_cdna4.hip): rope of q and k, K / V stored into the FT caches, one launch
 int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv, int Dh,
                          int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st);
-int launch_rope_kv_store_natural(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, int B, int S, int H, int Hkv,
-                                 int Dh, int rot, int lmax, int start_pos, long long bs, long long rs, int dtype, hipStream_t st);
 // split-KV attention for few query rows over a long natural-layout history (awq_attn_splitkv_cdna4.hip); arguments validated by the caller
 int attn_splitkv_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* splits, int* chunk);
 size_t attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal);
 int attn_splitkv_tune_set(const char* key, int value);  // "attn_splitkv_chunk": force the chunk, a multiple of 64 (0 = plan)
-int launch_attn_splitkv(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
-                        long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,
-                        int splits, int chunk, void* workspace, hipStream_t st);
+// (the natural-layout store and the split pair themselves: launch_kv_store / launch_kv_attn over the descriptors of awq_kvcache.hpp)
 // FP8 KV cache (awq_kv8.hpp): k / v are e4m3 codes [B, Sk, Hkv, Dh] with strides in bytes, k_scale / v_scale fp32 [B, Sk, Hkv] with strides in
-// floats.  The split form, the one-pass form and the store launch (awq_attn_kv8_cdna4.hip):
-int launch_attn_splitkv_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
-                            int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
-                            long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
-                            int splits, int chunk, void* workspace, hipStream_t st);
+// floats.  The one-pass form (awq_attn_prefill_cdna4.hip):
 int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
                             int Sk, int H, int Hkv, int Dh, long long q_bs, long long q_rs, long long k_bs, long long k_rs, long long v_bs,
                             long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs, long long vs_rs, float scale, int causal, int dtype,
                             hipStream_t st);
-int launch_rope_kv_store_natural_fp8(const void* qkv, const float* freqs, void* q_out, void* k_cache, void* v_cache, float* k_scale,
-                                     float* v_scale, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int start_pos, long long bs,
-                                     long long rs, int dtype, hipStream_t st);
-// lengths on the device (awq_devlen.hpp): the store launch with cache_seqlens [B] and the whole angle table, and the split-KV pair with
-// seqlens_k [B] under a host bound max_seqlen_k (k_scale == nullptr: the T cache); arguments validated by the caller
-int launch_rope_kv_store_natural_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache,
-                                     const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax, int table_rows,
-                                     long long bs, long long rs, int dtype, hipStream_t st);
-int launch_rope_kv_store_natural_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
-                                         float* v_scale, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot, int lmax,
-                                         int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
+// the plan of the device-length form (awq_devlen.hpp): made from the host bound max_seqlen_k alone
 int attn_kvcache_plan(int batch, int nheads_kv, int max_seqlen_k, int* splits, int* chunk);
 size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k);
-int launch_attn_kvcache(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out, int B, int Sq,
-                        const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
-                        long long k_bs, long long k_rs, long long v_bs, long long v_rs, long long ks_bs, long long ks_rs, long long vs_bs,
-                        long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st);
-// the same launches over a pool of pages and a block table (awq_paged.hpp): k / v [num_pages, page_size, Hkv, Dh] with page and row strides
-// (elements, bytes for codes), the scale pools likewise (floats); arguments validated by the caller
-int launch_rope_kv_store_paged_pos(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
-                                   long long table_row_stride, int page_size, int num_pages, int pages_per_seq, long long k_ps, long long k_rs,
-                                   long long v_ps, long long v_rs, const int* cache_seqlens, int B, int S, int H, int Hkv, int Dh, int rot,
-                                   int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
-int launch_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
-                                       float* v_scale, const int* block_table, long long table_row_stride, int page_size, int num_pages,
-                                       int pages_per_seq, long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps,
-                                       long long ks_rs, long long vs_ps, long long vs_rs, const int* cache_seqlens, int B, int S, int H, int Hkv,
-                                       int Dh, int rot, int table_rows, long long bs, long long rs, int dtype, hipStream_t st);
-int launch_attn_kvcache_paged(const void* q, const void* k, const void* v, const float* k_scale, const float* v_scale, void* out,
-                              const int* block_table, long long table_row_stride, int page_size, int num_pages, int B, int Sq,
-                              const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int H, int Hkv, int Dh, long long q_bs, long long q_rs,
-                              long long k_ps, long long k_rs, long long v_ps, long long v_rs, long long ks_ps, long long ks_rs, long long vs_ps,
-                              long long vs_rs, float scale, int causal, int dtype, int splits, int chunk, void* workspace, hipStream_t st);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

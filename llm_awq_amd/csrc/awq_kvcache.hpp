@@ -1,0 +1,80 @@
+// The natural-layout KV cache family, described once (host side only; no device code reads this header's structs).
+//
+// A call of the family is a KvView -- where K / V live: dense caches or a pool of pages, T or FP8 codes with scales -- inside a
+// KvStoreCall (rope + store of a qkv chunk) or a KvAttnCall (split-KV attention of few query rows).  The C entries of awq_capi.hip
+// build one from their positional arguments, check it once per phase and hand it to one of the two launchers below; the launchers pick
+// the kernel traits (HostLen / DevLen / Paged<DevLen>, TCache / Kv8) from what the descriptor holds and fill the kernels' own argument
+// structs.  A new cache variant adds its fields here, its terms to the phase checks and its traits to the two launchers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+namespace awq {
+
+struct KvView {
+  const void* k = nullptr;  // caches [outer, rows, Hkv, Dh] or pools [num_pages, page_size, Hkv, Dh]: T, or e4m3 codes when k_scale is set
+  const void* v = nullptr;
+  const float* k_scale = nullptr;  // [outer, rows, Hkv] fp32 (awq_kv8.hpp); nullptr: the T cache
+  const float* v_scale = nullptr;
+  // outer (batch or page) and row strides: elements of T, bytes of codes, floats of scales.  The dense STORE entries take contiguous
+  // caches and give no strides: theirs stay 0 and the store kernels address [outer, rows, Hkv, Dh] themselves.
+  long long k_os = 0, k_rs = 0, v_os = 0, v_rs = 0, ks_os = 0, ks_rs = 0, vs_os = 0, vs_rs = 0;
+  int outer = 0;                     // cache_batch or num_pages
+  int rows = 0;                      // lmax or page_size
+  const int* block_table = nullptr;  // device int32 [batch, pages_per_seq] (awq_paged.hpp); nullptr: dense caches
+  long long bt_rs = 0;               // its row stride, entries
+  int pages_per_seq = 0;
+  // keys one sequence can hold, as an int (positions and lengths are int32)
+  int capacity() const {
+    const long long cap = block_table ? (long long)pages_per_seq * rows : rows;
+    return cap < 0x7FFFFFFFll ? (int)cap : 0x7FFFFFFF;
+  }
+};
+
+struct KvStoreCall {
+  const void* qkv;     // [B, S, (H + 2 Hkv) Dh], strides bs / rs
+  const float* freqs;  // the call's angles (host start_pos) or the model's whole table [table_rows, rot] (device cache_seqlens)
+  void* q_out;
+  KvView kv;
+  int start_pos;             // host position, used when cache_seqlens == nullptr
+  const int* cache_seqlens;  // device int32 [B] (awq_devlen.hpp), with table_rows
+  int table_rows;
+  int B, S, H, Hkv, Dh, rot;
+  long long bs, rs;
+  int dtype;
+};
+
+struct KvAttnCall {
+  const void* q;  // [B, Sq, H, Dh], strides q_bs / q_rs
+  void* out;
+  KvView kv;
+  int Sk;                // host length, used when seqlens_k == nullptr
+  const int* seqlens_k;  // device int32 [B] (awq_devlen.hpp): length of b = seqlens_k[b] + seqlen_offset <= max_seqlen_k
+  int seqlen_offset, max_seqlen_k;
+  int B, Sq, H, Hkv, Dh;
+  long long q_bs, q_rs;
+  float scale;
+  int causal, dtype;
+};
+
+// Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to
+// awq_attn_kv8_cdna4.hip (each file keeps its own kernel and argument struct).
+int launch_kv_store(const KvStoreCall& c, hipStream_t st);
+int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
+// the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size
+int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
+
+// f(element traits, std::integral_constant<int, DH>) for dtype 0 / 1 (F16 / BF16 of awq_device.hpp) and Dh 128 / 64
+template <typename F16T, typename BF16T, typename F>
+void for_dtype_dh(int dtype, int Dh, F&& f) {
+  if (dtype == 0) {
+    if (Dh == 128) f(F16T{}, std::integral_constant<int, 128>{});
+    else f(F16T{}, std::integral_constant<int, 64>{});
+  } else {
+    if (Dh == 128) f(BF16T{}, std::integral_constant<int, 128>{});
+    else f(BF16T{}, std::integral_constant<int, 64>{});
+  }
+}
+
+}  // namespace awq

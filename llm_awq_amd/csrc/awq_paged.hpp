@@ -22,6 +22,8 @@ namespace awq {
 template <typename DT>
 struct Paged : DT {};
 template <typename DT>
+using PagedDevLen = Paged<DevLen<DT>>;
+template <typename DT>
 struct IsPaged {
   static constexpr bool value = false;
 };

@@ -808,94 +808,273 @@ std::tuple<int64_t, int64_t> attn_splitkv_plan(int64_t batch, int64_t nheads, in
   return {splits, chunk};
 }
 
-// rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos, nheads, nheads_kv) -> q_out: rope_kv_store for the natural-layout caches
-// k_cache / v_cache [Bc, Lmax, Hkv, Dh] of tinychat's long-context path (fused_attn.py:527-537), one launch (csrc/awq_attn_chunk_cdna4.hip).
-torch::Tensor rope_kv_store_natural(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
-                                    int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
-  TORCH_CHECK(qkv.scalar_type() != at::kFloat, "rope_kv_store_natural: float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), "rope_kv_store_natural: tensors must live on the same GPU");
-  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, "rope_kv_store_natural: float16 / bfloat16 only, got ",
-              qkv.scalar_type());
-  TORCH_CHECK(freqs.scalar_type() == at::kFloat, "rope_kv_store_natural: freqs must be float32");
-  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k_cache, &v_cache}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device(), "rope_kv_store_natural: the caches must live on the GPU of the input");
-    TORCH_CHECK(t->scalar_type() == qkv.scalar_type(), "rope_kv_store_natural: the caches must have the dtype of the input");
-    TORCH_CHECK(t->dim() == 4 && t->is_contiguous(), "rope_kv_store_natural: contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] are expected");
-  }
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "rope_kv_store_natural: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
-  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rot = freqs.size(-1);
-  TORCH_CHECK(headdim == 64 || headdim == 128, "rope_kv_store_natural: head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, "rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh]");
-  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
-  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim,
-              "rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
-  TORCH_CHECK(batch <= cache_batch, "rope_kv_store_natural: batch ", batch, " exceeds the cache batch ", cache_batch);
-  TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= lmax, "rope_kv_store_natural: positions ", start_pos, " .. ", start_pos + seqlen,
-              " do not fit the cache of ", lmax);
-  TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot,
-              "rope_kv_store_natural: freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
-  at::Tensor x = qkv;
-  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
-  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
-  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
-  raise_on(awq_rope_kv_store_natural(x.data_ptr(), fr.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), (int)batch,
-                                     (int)cache_batch, (int)seqlen, (int)nheads, (int)nheads_kv, (int)headdim, (int)rot, (int)lmax,
-                                     (int)start_pos, x.stride(0), x.stride(1), dtype_code(x),
-                                     (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
-  return q_out;
-}
-
-// ---- FP8 KV cache on the natural layout (csrc/awq_kv8.hpp): codes [.., L, Hkv, Dh] as float8_e4m3fn or uint8, scales [.., L, Hkv] float32 ----
+// ---- The natural-layout KV cache family (include/awq_cdna4.h): the rope + store bindings and the device-length attention bindings over
+//      dense caches [Bc, Lmax, Hkv, Dh] or pools [num_pages, page_size, Hkv, Dh] with a block table, T or FP8 (csrc/awq_kv8.hpp: codes as
+//      float8_e4m3fn or uint8, scales [.., Hkv] float32).  One description of the caches, one store and one attention implementation. ----
 static bool is_kv8_code(const torch::Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte; }
 
-// rope_kv_store_natural_fp8(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos, nheads, nheads_kv) -> q_out: rope_kv_store_natural
-// with k and v quantised per (token, KV head) on their way into the caches, one launch (csrc/awq_attn_kv8_cdna4.hip).  q_out holds
-// rope_kv_store_natural's bits.
-torch::Tensor rope_kv_store_natural_fp8(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
-                                        torch::Tensor k_scale, torch::Tensor v_scale, int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
-  const char* who = "rope_kv_store_natural_fp8";
+static void check_seqlens(const char* who, const char* name, const torch::Tensor& t, const torch::Tensor& ref, int64_t batch) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), who, ": ", name, " must live on the GPU of the input (it is read by the kernel only)");
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 1 && t.size(0) == batch && t.is_contiguous(), who, ": ", name,
+              " must be a contiguous int32 [B] tensor");
+}
+
+// where K / V of one call live: k_scale set = FP8, block_table set = pools
+struct KvTensors {
+  const torch::Tensor& k;
+  const torch::Tensor& v;
+  const torch::Tensor* k_scale;
+  const torch::Tensor* v_scale;
+  const torch::Tensor* block_table;
+};
+
+// Describe the caches or pools: devices, dtypes (ref's, or codes), one shape with contiguous heads, the scales of that shape, the table
+// [>= batch, pages_per_seq].  contiguous: the dense store entries take no strides.  ref_name: how the messages call the tensor `ref`.
+static void check_kv(const char* who, const KvTensors& kv, const torch::Tensor& ref, const char* ref_name, int64_t batch, bool contiguous) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
+  const char* name[2] = {paged ? "k_pool" : "k_cache", paged ? "v_pool" : "v_cache"};
+  const char* sname[2] = {"k_scale", "v_scale"};
+  const char* layout = paged ? "[num_pages, page_size, Hkv, Dh]" : "[Bc, Lmax, Hkv, Dh]";
+  const torch::Tensor* tensors[2] = {&kv.k, &kv.v};
+  const torch::Tensor* scales[2] = {kv.k_scale, kv.v_scale};
+  for (int i = 0; i < 2; ++i) {
+    const torch::Tensor& t = *tensors[i];
+    TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), who, ": ", name[i], " must live on the GPU of ", ref_name);
+    if (fp8) {
+      TORCH_CHECK(is_kv8_code(t), who, ": ", name[i], " must be float8_e4m3fn or uint8, got ", t.scalar_type());
+    } else {
+      TORCH_CHECK(t.scalar_type() == ref.scalar_type(), who, ": ", name[i], " must have the dtype of ", ref_name, ", got ", t.scalar_type());
+    }
+    TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1 && t.stride(2) == t.size(3) && (!contiguous || t.is_contiguous()), who, ": ", name[i], " must be ",
+                contiguous ? "contiguous " : "", layout, contiguous ? "" : " with contiguous heads (stride(3) == 1, stride(2) == Dh)");
+  }
+  TORCH_CHECK(kv.k.sizes() == kv.v.sizes(), who, ": ", name[0], " and ", name[1], " must have one shape ", layout);
+  if (paged)
+    TORCH_CHECK(kv.k.size(0) >= 1 && kv.k.size(1) >= 64 && kv.k.size(1) % 64 == 0, who, ": page size ", kv.k.size(1),
+                " is not supported (a multiple of 64, at least 64) or the pool is empty");
+  for (int i = 0; fp8 && i < 2; ++i) {
+    const torch::Tensor& s = *scales[i];
+    TORCH_CHECK(s.is_cuda() && s.device() == ref.device(), who, ": ", sname[i], " must live on the GPU of ", ref_name);
+    TORCH_CHECK(s.scalar_type() == at::kFloat, who, ": ", sname[i], " must be float32, got ", s.scalar_type());
+    TORCH_CHECK(s.dim() == 3 && s.size(0) == kv.k.size(0) && s.size(1) == kv.k.size(1) && s.size(2) == kv.k.size(2) && s.stride(2) == 1 &&
+                    (!contiguous || s.is_contiguous()),
+                who, ": ", sname[i], " must be ", contiguous ? "contiguous " : "", paged ? "[num_pages, page_size, Hkv]" : "[Bc, Lmax, Hkv]", " of ",
+                name[i], contiguous ? "" : " with a unit last stride");
+  }
+  if (paged) {
+    const torch::Tensor& bt = *kv.block_table;
+    TORCH_CHECK(bt.is_cuda() && bt.device() == ref.device(), who, ": block_table must live on the GPU of ", ref_name,
+                " (it is read by the kernel only)");
+    TORCH_CHECK(bt.scalar_type() == at::kInt && bt.dim() == 2 && bt.size(0) >= batch && bt.size(1) >= 1 && bt.stride(1) == 1 &&
+                    bt.stride(0) >= bt.size(1),
+                who, ": block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride");
+  }
+}
+
+// The store bindings.  cache_seqlens == nullptr: the host position start_pos, freqs holds the call's B * S * rot_dim angles (copied when
+// misaligned).  Otherwise each sequence's position is read on the device and freqs is the model's whole table [P, rot_dim] (not copied:
+// a misaligned one is refused).  One launch (csrc/awq_attn_chunk_cdna4.hip, csrc/awq_attn_kv8_cdna4.hip).
+static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, const torch::Tensor& freqs, const KvTensors& kv,
+                                     const torch::Tensor* cache_seqlens, int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, devlen = cache_seqlens != nullptr;
   TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
   TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
-  TORCH_CHECK(freqs.scalar_type() == at::kFloat, who, ": freqs must be float32");
-  const char* cname[2] = {"k_cache", "v_cache"};
-  const char* sname[2] = {"k_scale", "v_scale"};
-  const torch::Tensor* caches[2] = {&k_cache, &v_cache};
-  const torch::Tensor* scales[2] = {&k_scale, &v_scale};
-  for (int i = 0; i < 2; ++i) {
-    TORCH_CHECK(caches[i]->is_cuda() && caches[i]->device() == qkv.device(), who, ": ", cname[i], " must live on the GPU of the input");
-    TORCH_CHECK(is_kv8_code(*caches[i]), who, ": ", cname[i], " must be float8_e4m3fn or uint8, got ", caches[i]->scalar_type());
-    TORCH_CHECK(caches[i]->dim() == 4 && caches[i]->is_contiguous(), who, ": ", cname[i], " must be contiguous [Bc, Lmax, Hkv, Dh]");
-    TORCH_CHECK(scales[i]->is_cuda() && scales[i]->device() == qkv.device(), who, ": ", sname[i], " must live on the GPU of the input");
-    TORCH_CHECK(scales[i]->scalar_type() == at::kFloat, who, ": ", sname[i], " must be float32, got ", scales[i]->scalar_type());
-    TORCH_CHECK(scales[i]->dim() == 3 && scales[i]->is_contiguous(), who, ": ", sname[i], " must be contiguous [Bc, Lmax, Hkv]");
+  if (devlen) {
+    TORCH_CHECK(freqs.scalar_type() == at::kFloat && freqs.dim() == 2 && freqs.is_contiguous() &&
+                    (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0,
+                who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
+  } else {
+    TORCH_CHECK(freqs.scalar_type() == at::kFloat, who, ": freqs must be float32");
   }
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who, ": k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
-  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rot = freqs.size(-1);
-  for (int i = 0; i < 2; ++i)
-    TORCH_CHECK(scales[i]->size(0) == cache_batch && scales[i]->size(1) == lmax && scales[i]->size(2) == v_cache.size(2), who, ": ", sname[i],
-                " must be [Bc, Lmax, Hkv] of the caches");
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
   TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
   const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
-  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
-              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
-  TORCH_CHECK(batch <= cache_batch, who, ": batch ", batch, " exceeds the cache batch ", cache_batch);
-  TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= lmax, who, ": positions ", start_pos, " .. ", start_pos + seqlen, " do not fit the cache of ",
-              lmax);
-  TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot, who,
-              ": freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
+  check_kv(who, kv, qkv, "the input", batch, /*contiguous=*/!paged);
+  const torch::Tensor &k = kv.k, &v = kv.v;
+  const int64_t outer = k.size(0), rows = k.size(1), headdim = k.size(3), rot = freqs.size(-1);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
+              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
+  TORCH_CHECK(paged || batch <= outer, who, ": batch ", batch, " exceeds the cache batch ", outer);
+  if (devlen) {
+    TORCH_CHECK(freqs.size(0) >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
+                ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
+    check_seqlens(who, "cache_seqlens", *cache_seqlens, qkv, batch);
+  } else {
+    TORCH_CHECK(start_pos >= 0 && start_pos + seqlen <= rows, who, ": positions ", start_pos, " .. ", start_pos + seqlen,
+                " do not fit the cache of ", rows);
+    TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot, who,
+                ": freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
+  }
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
   at::Tensor x = qkv;
   if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
-  at::Tensor fr = freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0 ? freqs : freqs.contiguous().clone();
+  at::Tensor fr = devlen || (freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0) ? freqs : freqs.contiguous().clone();
   at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
-  raise_on(awq_rope_kv_store_natural_fp8(x.data_ptr(), fr.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                         k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)batch, (int)cache_batch, (int)seqlen,
-                                         (int)nheads, (int)nheads_kv, (int)headdim, (int)rot, (int)lmax, (int)start_pos, x.stride(0), x.stride(1),
-                                         dtype_code(x), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  void *xp = x.data_ptr(), *qp = q_out.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr();
+  const float* fp = fr.data_ptr<float>();
+  float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
+  const int* pos = devlen ? cache_seqlens->data_ptr<int>() : nullptr;
+  const int B = (int)batch, S = (int)seqlen, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot, dt = dtype_code(x);
+  const int64_t bs = x.stride(0), rs = x.stride(1);
+  if (paged) {
+    const torch::Tensor& bt = *kv.block_table;
+    const int P = (int)freqs.size(0), pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+    if (fp8)
+      raise_on(awq_rope_kv_store_paged_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps,
+                                               bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
+                                               kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), bs, rs, dt, st));
+    else
+      raise_on(awq_rope_kv_store_paged_pos(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps, bt.stride(0),
+                                           k.stride(0), k.stride(1), v.stride(0), v.stride(1), bs, rs, dt, st));
+  } else if (devlen) {
+    const int P = (int)freqs.size(0);
+    if (fp8) raise_on(awq_rope_kv_store_natural_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
+    else raise_on(awq_rope_kv_store_natural_pos(xp, fp, qp, kp, vp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
+  } else {
+    if (fp8)
+      raise_on(awq_rope_kv_store_natural_fp8(xp, fp, qp, kp, vp, ksp, vsp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st));
+    else raise_on(awq_rope_kv_store_natural(xp, fp, qp, kp, vp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st));
+  }
   return q_out;
+}
+
+// rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos, nheads, nheads_kv) -> q_out: rope_kv_store for the natural-layout caches
+// k_cache / v_cache [Bc, Lmax, Hkv, Dh] of tinychat's long-context path (fused_attn.py:527-537).
+torch::Tensor rope_kv_store_natural(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
+                                    int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_natural", qkv, freqs, {k_cache, v_cache, nullptr, nullptr, nullptr}, nullptr, start_pos, nheads, nheads_kv);
+}
+
+// ... with k and v quantised per (token, KV head) on their way into the caches.  q_out holds rope_kv_store_natural's bits.
+torch::Tensor rope_kv_store_natural_fp8(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache,
+                                        torch::Tensor k_scale, torch::Tensor v_scale, int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_natural_fp8", qkv, freqs, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, nullptr, start_pos, nheads,
+                         nheads_kv);
+}
+
+// rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural with each
+// sequence's position read on the device (cache_seqlens int32 [B]) and the angles taken from the whole table freqs_table [P, rot_dim].
+torch::Tensor rope_kv_store_natural_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                        const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_natural_pos", qkv, freqs_table, {k_cache, v_cache, nullptr, nullptr, nullptr}, &cache_seqlens, 0, nheads,
+                         nheads_kv);
+}
+
+torch::Tensor rope_kv_store_natural_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                            torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cache_seqlens, int64_t nheads,
+                                            int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_natural_pos_fp8", qkv, freqs_table, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, &cache_seqlens, 0,
+                         nheads, nheads_kv);
+}
+
+// rope_kv_store_paged_pos(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural_pos
+// writing token s of sequence b at logical position cache_seqlens[b] + s of the pages block_table[b] names.
+torch::Tensor rope_kv_store_paged_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                      const torch::Tensor block_table, const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_paged_pos", qkv, freqs_table, {k_pool, v_pool, nullptr, nullptr, &block_table}, &cache_seqlens, 0, nheads,
+                         nheads_kv);
+}
+
+torch::Tensor rope_kv_store_paged_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                          torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table,
+                                          const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
+  return rope_store_impl("rope_kv_store_paged_pos_fp8", qkv, freqs_table, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, &cache_seqlens, 0,
+                         nheads, nheads_kv);
+}
+
+// attn_kvcache[_paged][_kv8](q, caches or pools .., seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: the split-KV pair
+// with Sk_b = seqlens_k[b] + seqlen_offset read on the device, K / V from the caches or fetched from the pools through the table.  The fp32
+// partials live in a buffer of torch's caching allocator, so a graph capture owns them.
+static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& seqlens_k,
+                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
+  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  check_kv(who, kv, q, "q", batch, /*contiguous=*/false);
+  const torch::Tensor &k = kv.k, &v = kv.v;
+  const int64_t outer = k.size(0), rows = k.size(1), nheads_kv = k.size(2), cap = paged ? kv.block_table->size(1) * rows : rows;
+  TORCH_CHECK((paged || outer >= batch) && k.size(3) == headdim, who, ": ", paged ? "k_pool / v_pool must be [num_pages, page_size, Hkv, " : "k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ",
+              headdim, "]");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+              ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
+              " exceeds 128 (the split kernels serve few query rows; ",
+              paged ? "feed a longer prompt in pieces)" : "a prompt goes through the host-length path)");
+  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap,
+              paged ? " (pages_per_seq * page_size)" : " (the cache length)");
+  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
+  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
+  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
+  const int* lens = seqlens_k.data_ptr<int>();
+  const int B = (int)batch, Sq = (int)sq, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, off = (int)seqlen_offset,
+            bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q);
+  const float scale = (float)softmax_scale;
+  if (paged) {
+    const torch::Tensor& bt = *kv.block_table;
+    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+    if (fp8)
+      raise_on(awq_attn_kvcache_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off,
+                                          bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+                                          v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
+                                          kv.v_scale->stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+    else
+      raise_on(awq_attn_kvcache_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off, bound, pages,
+                                      page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
+                                      v.stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+  } else if (fp8) {
+    raise_on(awq_attn_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh,
+                                  q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
+                                  kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+  } else {
+    raise_on(awq_attn_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh, q.stride(0),
+                              q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+  }
+  return out;
+}
+
+torch::Tensor attn_kvcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor seqlens_k,
+                           int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale,
+                           causal);
+}
+
+torch::Tensor attn_kvcache_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                               const torch::Tensor v_scale, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset,
+                               double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal);
+}
+
+torch::Tensor attn_kvcache_paged(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                 const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache_paged", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal);
+}
+
+torch::Tensor attn_kvcache_paged_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                     const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor seqlens_k,
+                                     int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_kvcache_paged_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal);
+}
+
+// (splits, chunk) of awq_attn_kvcache_plan, made from the bound alone.  Host only.
+std::tuple<int64_t, int64_t> attn_kvcache_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t seqlen_q,
+                                               int64_t max_seqlen_k) {
+  int splits = 1, chunk = 0;
+  raise_on(awq_attn_kvcache_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)seqlen_q, (int)max_seqlen_k, &splits, &chunk));
+  return {splits, chunk};
 }
 
 // the checks attn_prefill_kv8 and attn_splitkv_kv8 share: q [B, Sq, H, Dh] of T, k / v codes [B, Sk, Hkv, Dh], k_scale / v_scale [B, Sk, Hkv]
@@ -966,293 +1145,6 @@ torch::Tensor attn_prefill_kv8(const torch::Tensor q, const torch::Tensor k, con
 torch::Tensor attn_splitkv_kv8(const torch::Tensor q, const torch::Tensor k, const torch::Tensor v, const torch::Tensor k_scale,
                                const torch::Tensor v_scale, double softmax_scale, bool causal) {
   return attn_kv8_impl("attn_splitkv_kv8", true, q, k, v, k_scale, v_scale, softmax_scale, causal);
-}
-
-// ---- lengths on the device (include/awq_cdna4.h: awq_rope_kv_store_natural_pos[_fp8], awq_attn_kvcache[_kv8]) ----
-static void check_seqlens(const char* who, const char* name, const torch::Tensor& t, const torch::Tensor& ref, int64_t batch) {
-  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), who, ": ", name, " must live on the GPU of the input (it is read by the kernel only)");
-  TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 1 && t.size(0) == batch && t.is_contiguous(), who, ": ", name,
-              " must be a contiguous int32 [B] tensor");
-}
-
-// the store launch of both cache formats; fp8: the caches hold codes and k_scale / v_scale are defined
-static torch::Tensor rope_store_pos_impl(const char* who, bool fp8, const torch::Tensor& qkv, const torch::Tensor& freqs_table,
-                                         torch::Tensor& k_cache, torch::Tensor& v_cache, torch::Tensor* k_scale, torch::Tensor* v_scale,
-                                         const torch::Tensor& cache_seqlens, int64_t nheads, int64_t nheads_kv) {
-  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(qkv.is_cuda() && freqs_table.is_cuda() && freqs_table.device() == qkv.device(), who, ": tensors must live on the same GPU");
-  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
-  TORCH_CHECK(freqs_table.scalar_type() == at::kFloat && freqs_table.dim() == 2 && freqs_table.is_contiguous() &&
-                  (reinterpret_cast<uintptr_t>(freqs_table.data_ptr()) & 15) == 0,
-              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
-  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k_cache, &v_cache}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device(), who, ": the caches must live on the GPU of the input");
-    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == qkv.scalar_type(), who,
-                fp8 ? ": the caches must be float8_e4m3fn or uint8, got " : ": the caches must have the dtype of the input, got ", t->scalar_type());
-    TORCH_CHECK(t->dim() == 4 && t->is_contiguous(), who, ": contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] are expected");
-  }
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), who, ": k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]");
-  const int64_t cache_batch = v_cache.size(0), lmax = v_cache.size(1), headdim = v_cache.size(3), rows = freqs_table.size(0),
-                rot = freqs_table.size(1);
-  if (fp8)
-    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
-      TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->is_contiguous() &&
-                      t->size(0) == cache_batch && t->size(1) == lmax && t->size(2) == v_cache.size(2),
-                  who, ": k_scale / v_scale must be contiguous float32 [Bc, Lmax, Hkv] tensors on the GPU of the input");
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  TORCH_CHECK(qkv.dim() == 3, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
-  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
-  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_cache.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
-              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the caches' Hkv and Dh");
-  TORCH_CHECK(batch <= cache_batch, who, ": batch ", batch, " exceeds the cache batch ", cache_batch);
-  TORCH_CHECK(rows >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
-              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
-  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
-  at::Tensor x = qkv;
-  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
-  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (fp8)
-    raise_on(awq_rope_kv_store_natural_pos_fp8(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(),
-                                               v_cache.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
-                                               cache_seqlens.data_ptr<int>(), (int)batch, (int)cache_batch, (int)seqlen, (int)nheads,
-                                               (int)nheads_kv, (int)headdim, (int)rot, (int)lmax, (int)rows, x.stride(0), x.stride(1),
-                                               dtype_code(x), st));
-  else
-    raise_on(awq_rope_kv_store_natural_pos(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                           cache_seqlens.data_ptr<int>(), (int)batch, (int)cache_batch, (int)seqlen, (int)nheads, (int)nheads_kv,
-                                           (int)headdim, (int)rot, (int)lmax, (int)rows, x.stride(0), x.stride(1), dtype_code(x), st));
-  return q_out;
-}
-
-// rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural with each
-// sequence's position read on the device (cache_seqlens int32 [B]) and the angles taken from the whole table freqs_table [P, rot_dim].
-torch::Tensor rope_kv_store_natural_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
-                                        const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
-  return rope_store_pos_impl("rope_kv_store_natural_pos", false, qkv, freqs_table, k_cache, v_cache, nullptr, nullptr, cache_seqlens, nheads,
-                             nheads_kv);
-}
-
-torch::Tensor rope_kv_store_natural_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
-                                            torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cache_seqlens, int64_t nheads,
-                                            int64_t nheads_kv) {
-  return rope_store_pos_impl("rope_kv_store_natural_pos_fp8", true, qkv, freqs_table, k_cache, v_cache, &k_scale, &v_scale, cache_seqlens, nheads,
-                             nheads_kv);
-}
-
-// attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: the split-KV pair over the
-// natural-layout caches with Sk_b = seqlens_k[b] + seqlen_offset read on the device.  The fp32 partials live in a buffer of torch's caching
-// allocator, so a graph capture owns them.
-static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
-                                       const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& seqlens_k,
-                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
-  const bool fp8 = k_scale != nullptr;
-  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
-  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, who, ": q [B, Sq, H, Dh], k_cache / v_cache [Bc, Lmax, Hkv, Dh]");
-  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3), lmax = k.size(1), nheads_kv = k.size(2);
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k, &v}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == q.device(), who, ": the caches must live on the GPU of q");
-    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == q.scalar_type(), who,
-                fp8 ? ": the caches must be float8_e4m3fn or uint8, got " : ": the caches must have the dtype of q, got ", t->scalar_type());
-  }
-  TORCH_CHECK(v.sizes() == k.sizes() && k.size(0) >= batch && k.size(3) == headdim, who, ": k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ", headdim,
-              "] of one shape");
-  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
-              ": empty tensors are not supported and H must be a multiple of Hkv");
-  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
-              " exceeds 128 (the split kernels serve few query rows; a prompt goes through the host-length path)");
-  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= lmax, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", lmax, " (the cache length)");
-  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
-  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&q, &k, &v})
-    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == headdim, who, ": the heads of q and of the caches must be contiguous");
-  if (fp8)
-    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
-      TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == k.size(0) &&
-                      t->size(1) == lmax && t->size(2) == nheads_kv && t->stride(2) == 1,
-                  who, ": k_scale / v_scale must be float32 [Bc, Lmax, Hkv] of the caches with a unit last stride");
-  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
-  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
-  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
-  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (fp8)
-    raise_on(awq_attn_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(), out.data_ptr(),
-                                  (int)batch, (int)sq, seqlens_k.data_ptr<int>(), (int)seqlen_offset, (int)max_seqlen_k, (int)lmax, (int)nheads,
-                                  (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                  k_scale->stride(0), k_scale->stride(1), v_scale->stride(0), v_scale->stride(1), (float)softmax_scale,
-                                  causal ? 1 : 0, dtype_code(q), ws.data_ptr(), wsb, st));
-  else
-    raise_on(awq_attn_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), (int)batch, (int)sq, seqlens_k.data_ptr<int>(),
-                              (int)seqlen_offset, (int)max_seqlen_k, (int)lmax, (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1),
-                              k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
-                              ws.data_ptr(), wsb, st));
-  return out;
-}
-
-torch::Tensor attn_kvcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor seqlens_k,
-                           int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
-  return attn_kvcache_impl("attn_kvcache", q, k_cache, v_cache, nullptr, nullptr, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal);
-}
-
-torch::Tensor attn_kvcache_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
-                               const torch::Tensor v_scale, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset,
-                               double softmax_scale, bool causal) {
-  return attn_kvcache_impl("attn_kvcache_kv8", q, k_cache, v_cache, &k_scale, &v_scale, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale,
-                           causal);
-}
-
-// (splits, chunk) of awq_attn_kvcache_plan, made from the bound alone.  Host only.
-std::tuple<int64_t, int64_t> attn_kvcache_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t seqlen_q,
-                                               int64_t max_seqlen_k) {
-  int splits = 1, chunk = 0;
-  raise_on(awq_attn_kvcache_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)seqlen_q, (int)max_seqlen_k, &splits, &chunk));
-  return {splits, chunk};
-}
-
-// ---- the paged KV cache (include/awq_cdna4.h: awq_rope_kv_store_paged_pos[_fp8], awq_attn_kvcache_paged[_kv8]) ----
-// the pools [num_pages, page_size, Hkv, Dh] (and the scale pools [num_pages, page_size, Hkv]) and the table [>= B, pages_per_seq] of one call
-static void check_pools(const char* who, bool fp8, const torch::Tensor& ref, const torch::Tensor& k, const torch::Tensor& v,
-                        const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& block_table, int64_t batch) {
-  for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{&k, &v}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == ref.device(), who, ": the pools must live on the GPU of the input");
-    TORCH_CHECK(fp8 ? is_kv8_code(*t) : t->scalar_type() == ref.scalar_type(), who,
-                fp8 ? ": the pools must be float8_e4m3fn or uint8, got " : ": the pools must have the dtype of the input, got ", t->scalar_type());
-    TORCH_CHECK(t->dim() == 4 && t->stride(3) == 1 && t->stride(2) == t->size(3), who,
-                ": k_pool / v_pool [num_pages, page_size, Hkv, Dh] with contiguous heads are expected");
-  }
-  TORCH_CHECK(k.sizes() == v.sizes(), who, ": k_pool and v_pool must have one shape [num_pages, page_size, Hkv, Dh]");
-  TORCH_CHECK(k.size(0) >= 1 && k.size(1) >= 64 && k.size(1) % 64 == 0, who, ": page size ", k.size(1),
-              " is not supported (a multiple of 64, at least 64) or the pool is empty");
-  if (fp8)
-    for (const torch::Tensor* t : std::initializer_list<const torch::Tensor*>{k_scale, v_scale})
-      TORCH_CHECK(t->is_cuda() && t->device() == ref.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == k.size(0) &&
-                      t->size(1) == k.size(1) && t->size(2) == k.size(2) && t->stride(2) == 1,
-                  who, ": k_scale / v_scale must be float32 [num_pages, page_size, Hkv] of the pools with a unit last stride");
-  TORCH_CHECK(block_table.is_cuda() && block_table.device() == ref.device(), who,
-              ": block_table must live on the GPU of the input (it is read by the kernel only)");
-  TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.dim() == 2 && block_table.size(0) >= batch && block_table.size(1) >= 1 &&
-                  block_table.stride(1) == 1 && block_table.stride(0) >= block_table.size(1),
-              who, ": block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride");
-}
-
-static torch::Tensor rope_store_paged_impl(const char* who, bool fp8, const torch::Tensor& qkv, const torch::Tensor& freqs_table,
-                                           torch::Tensor& k_pool, torch::Tensor& v_pool, torch::Tensor* k_scale, torch::Tensor* v_scale,
-                                           const torch::Tensor& block_table, const torch::Tensor& cache_seqlens, int64_t nheads,
-                                           int64_t nheads_kv) {
-  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(qkv.is_cuda() && freqs_table.is_cuda() && freqs_table.device() == qkv.device(), who, ": tensors must live on the same GPU");
-  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
-  TORCH_CHECK(freqs_table.scalar_type() == at::kFloat && freqs_table.dim() == 2 && freqs_table.is_contiguous() &&
-                  (reinterpret_cast<uintptr_t>(freqs_table.data_ptr()) & 15) == 0,
-              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
-  TORCH_CHECK(qkv.dim() == 3, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
-  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
-  check_pools(who, fp8, qkv, k_pool, v_pool, k_scale, v_scale, block_table, batch);
-  const int64_t headdim = v_pool.size(3), rows = freqs_table.size(0), rot = freqs_table.size(1);
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == v_pool.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
-              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the pools' Hkv and Dh");
-  TORCH_CHECK(rows >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
-              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
-  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
-  at::Tensor x = qkv;
-  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
-  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (fp8)
-    raise_on(awq_rope_kv_store_paged_pos_fp8(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                             k_scale->data_ptr<float>(), v_scale->data_ptr<float>(), block_table.data_ptr<int>(),
-                                             cache_seqlens.data_ptr<int>(), (int)batch, (int)seqlen, (int)nheads, (int)nheads_kv, (int)headdim,
-                                             (int)rot, (int)rows, (int)k_pool.size(0), (int)k_pool.size(1), (int)block_table.size(1),
-                                             block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1),
-                                             k_scale->stride(0), k_scale->stride(1), v_scale->stride(0), v_scale->stride(1), x.stride(0),
-                                             x.stride(1), dtype_code(x), st));
-  else
-    raise_on(awq_rope_kv_store_paged_pos(x.data_ptr(), freqs_table.data_ptr<float>(), q_out.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                         block_table.data_ptr<int>(), cache_seqlens.data_ptr<int>(), (int)batch, (int)seqlen, (int)nheads,
-                                         (int)nheads_kv, (int)headdim, (int)rot, (int)rows, (int)k_pool.size(0), (int)k_pool.size(1),
-                                         (int)block_table.size(1), block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0),
-                                         v_pool.stride(1), x.stride(0), x.stride(1), dtype_code(x), st));
-  return q_out;
-}
-
-// rope_kv_store_paged_pos(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads, nheads_kv) -> q_out: rope_kv_store_natural_pos
-// writing token s of sequence b at logical position cache_seqlens[b] + s of the pages block_table[b] names.
-torch::Tensor rope_kv_store_paged_pos(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
-                                      const torch::Tensor block_table, const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
-  return rope_store_paged_impl("rope_kv_store_paged_pos", false, qkv, freqs_table, k_pool, v_pool, nullptr, nullptr, block_table, cache_seqlens,
-                               nheads, nheads_kv);
-}
-
-torch::Tensor rope_kv_store_paged_pos_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
-                                          torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table,
-                                          const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv) {
-  return rope_store_paged_impl("rope_kv_store_paged_pos_fp8", true, qkv, freqs_table, k_pool, v_pool, &k_scale, &v_scale, block_table,
-                               cache_seqlens, nheads, nheads_kv);
-}
-
-// attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: attn_kvcache with
-// K / V fetched from the pools through the table.  The fp32 partials live in a buffer of torch's caching allocator, so a capture owns them.
-static torch::Tensor attn_kvcache_paged_impl(const char* who, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
-                                             const torch::Tensor* k_scale, const torch::Tensor* v_scale, const torch::Tensor& block_table,
-                                             const torch::Tensor& seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale,
-                                             bool causal) {
-  const bool fp8 = k_scale != nullptr;
-  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
-  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
-  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
-  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  check_pools(who, fp8, q, k, v, k_scale, v_scale, block_table, batch);
-  const int64_t page_size = k.size(1), nheads_kv = k.size(2), pages_per_seq = block_table.size(1);
-  TORCH_CHECK(k.size(3) == headdim, who, ": k_pool / v_pool must be [num_pages, page_size, Hkv, ", headdim, "]");
-  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
-              ": empty tensors are not supported and H must be a multiple of Hkv");
-  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
-              " exceeds 128 (the split kernels serve few query rows; feed a longer prompt in pieces)");
-  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= pages_per_seq * page_size, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ",
-              pages_per_seq * page_size, " (pages_per_seq * page_size)");
-  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
-  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
-  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
-  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
-  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  if (fp8)
-    raise_on(awq_attn_kvcache_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
-                                        out.data_ptr(), block_table.data_ptr<int>(), (int)batch, (int)sq, seqlens_k.data_ptr<int>(),
-                                        (int)seqlen_offset, (int)max_seqlen_k, (int)k.size(0), (int)page_size, (int)pages_per_seq,
-                                        block_table.stride(0), (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1), k.stride(0),
-                                        k.stride(1), v.stride(0), v.stride(1), k_scale->stride(0), k_scale->stride(1), v_scale->stride(0),
-                                        v_scale->stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q), ws.data_ptr(), wsb, st));
-  else
-    raise_on(awq_attn_kvcache_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), block_table.data_ptr<int>(), (int)batch, (int)sq,
-                                    seqlens_k.data_ptr<int>(), (int)seqlen_offset, (int)max_seqlen_k, (int)k.size(0), (int)page_size,
-                                    (int)pages_per_seq, block_table.stride(0), (int)nheads, (int)nheads_kv, (int)headdim, q.stride(0), q.stride(1),
-                                    k.stride(0), k.stride(1), v.stride(0), v.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
-                                    ws.data_ptr(), wsb, st));
-  return out;
-}
-
-torch::Tensor attn_kvcache_paged(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
-                                 const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
-  return attn_kvcache_paged_impl("attn_kvcache_paged", q, k_pool, v_pool, nullptr, nullptr, block_table, seqlens_k, max_seqlen_k, seqlen_offset,
-                                 softmax_scale, causal);
-}
-
-torch::Tensor attn_kvcache_paged_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
-                                     const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor seqlens_k,
-                                     int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
-  return attn_kvcache_paged_impl("attn_kvcache_paged_kv8", q, k_pool, v_pool, &k_scale, &v_scale, block_table, seqlens_k, max_seqlen_k,
-                                 seqlen_offset, softmax_scale, causal);
 }
 
 // flash_attn_varlen_qkvpacked_func's forward (tinychat/models/internvl/internvit.py:45-90) on the gfx950 tower kernel

@@ -643,39 +643,109 @@ def _kv8_codes(who, name, t):
         raise ValueError(f"{who}: {name} must be float8_e4m3fn or uint8, got {t.dtype}")
 
 
+def _on_gpu(*tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+
+
+class _Kv:
+    """Where K / V of one natural-layout call live, once whoever builds it has checked the tensors: dense caches [Bc, Lmax, Hkv, Dh] or,
+    with block_table [>= B, pages_per_seq], pools [num_pages, page_size, Hkv, Dh]; with k_scale / v_scale [.., Hkv] the FP8 format.  The
+    pieces of a C-ABI argument list come out in the order every entry of the family takes them."""
+
+    def __init__(self, k, v, k_scale=None, v_scale=None, block_table=None):
+        self.k, self.v, self.k_scale, self.v_scale, self.block_table = k, v, k_scale, v_scale, block_table
+        self.outer, self.rows, self.Hkv, self.Dh = v.shape  # (cache_batch or num_pages, lmax or page_size, ..)
+        self.fp8, self.paged = k_scale is not None, block_table is not None
+
+    def ptrs(self):
+        return (self.k.data_ptr(), self.v.data_ptr()) + ((self.k_scale.data_ptr(), self.v_scale.data_ptr()) if self.fp8 else ())
+
+    def strides(self):
+        s = (self.k.stride(0), self.k.stride(1), self.v.stride(0), self.v.stride(1))
+        return s + ((self.k_scale.stride(0), self.k_scale.stride(1), self.v_scale.stride(0), self.v_scale.stride(1)) if self.fp8 else ())
+
+    def table(self):  # num_pages, page_size, pages_per_seq, table_row_stride
+        return (self.outer, self.rows, self.block_table.shape[1], self.block_table.stride(0))
+
+
+def _caches(who, qkv, k_cache, v_cache, k_scale, v_scale):
+    """The contiguous caches [Bc, Lmax, Hkv, Dh] of a store call (and their scales [Bc, Lmax, Hkv]), checked against qkv, as a _Kv."""
+    fp8 = k_scale is not None
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if fp8:
+            _kv8_codes(who, name, t)
+        elif t.dtype != qkv.dtype:
+            raise ValueError(f"{who}: the caches must have the dtype of the input")
+        if t.device != qkv.device or t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous [Bc, Lmax, Hkv, Dh] tensor on the GPU of qkv")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"{who}: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]")
+    if fp8:
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.device != qkv.device or t.dtype != torch.float32 or tuple(t.shape) != tuple(v_cache.shape[:3]) or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous float32 [Bc, Lmax, Hkv] tensor on the GPU of qkv")
+    return _Kv(k_cache, v_cache, k_scale, v_scale)
+
+
+def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_seqlens=None):
+    """The six store entries of the C ABI over a described cache.  cache_seqlens None: the host position start_pos and the call's angles;
+    otherwise the positions are read on the device and freqs is the model's whole angle table [P, rot_dim]."""
+    devlen = cache_seqlens is not None
+    if freqs.device != qkv.device or freqs.dtype != torch.float32 or (devlen and freqs.dim() != 2) or not freqs.is_contiguous():
+        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv" if devlen else
+                         f"{who}: contiguous float32 freqs on the GPU of qkv are expected")
+    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != kv.Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * kv.Dh:
+        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with " +
+                         ("the pools' Hkv and Dh" if kv.paged else "a unit last stride and the caches' Hkv and Dh"))
+    B, S = qkv.shape[0], qkv.shape[1]
+    rot = freqs.shape[-1]
+    if devlen:
+        _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
+    elif freqs.numel() < B * S * rot:
+        raise ValueError(f"{who}: freqs holds fewer than B * S * rot_dim angles")
+    q_out = torch.empty(B, S, nheads, kv.Dh, dtype=qkv.dtype, device=qkv.device)
+    head = (qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), *kv.ptrs())
+    shape = (S, int(nheads), int(nheads_kv), kv.Dh, rot)
+    tail = (qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
+    if kv.paged:
+        entry, args = "paged_pos", (*head, kv.block_table.data_ptr(), cache_seqlens.data_ptr(), B, *shape, freqs.shape[0], *kv.table(),
+                                    *kv.strides(), *tail)
+    elif devlen:
+        entry, args = "natural_pos", (*head, cache_seqlens.data_ptr(), B, kv.outer, *shape, kv.rows, freqs.shape[0], *tail)
+    else:
+        entry, args = "natural", (*head, B, kv.outer, *shape, kv.rows, int(start_pos), *tail)
+    with torch.cuda.device(qkv.device):
+        _capi.check(getattr(_capi.lib(), "awq_rope_kv_store_" + entry + ("_fp8" if kv.fp8 else ""))(*args))
+    return q_out
+
+
+def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal):
+    """The four device-length attention entries of the C ABI over a described cache (q and kv checked by the caller)."""
+    B, Sq, H, Dh = q.shape
+    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    L = _capi.lib()
+    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, kv.Hkv, Dh, Sq, int(max_seqlen_k))
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
+    lens = (B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k))
+    where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
+    entry = getattr(L, "awq_attn_kvcache" + ("_paged" if kv.paged else "") + ("_kv8" if kv.fp8 else ""))
+    with torch.cuda.device(q.device):
+        _capi.check(entry(q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), q.stride(1), *kv.strides(), scale,
+                          int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q)))
+    return out
+
+
 def rope_kv_store_natural_fp8(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos: int, nheads: int, nheads_kv: int):
     """C-ABI awq_rope_kv_store_natural_fp8: rope_kv_store_natural with k and v quantised on their way into the FP8 caches (kv8_quant's
     format).  k_cache / v_cache [Bc, Lmax, Hkv, Dh] float8_e4m3fn or uint8, k_scale / v_scale [Bc, Lmax, Hkv] float32.  Writes codes and
     scales at [b, start_pos + s]; returns the rotated q [B, S, H, Dh], rope_kv_store_natural's bits."""
     who = "rope_kv_store_natural_fp8"
-    for t in (qkv, freqs, k_cache, v_cache, k_scale, v_scale):
-        if not t.is_cuda:
-            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        _kv8_codes(who, name, t)
-        if t.device != qkv.device or t.dim() != 4 or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous [Bc, Lmax, Hkv, Dh] tensor on the GPU of qkv")
-    if k_cache.shape != v_cache.shape:
-        raise ValueError(f"{who}: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]")
-    Bc, Lmax, Hkv, Dh = v_cache.shape
-    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
-        if t.device != qkv.device or t.dtype != torch.float32 or tuple(t.shape) != (Bc, Lmax, Hkv) or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous float32 [Bc, Lmax, Hkv] tensor on the GPU of qkv")
-    if freqs.device != qkv.device or freqs.dtype != torch.float32 or not freqs.is_contiguous():
-        raise ValueError(f"{who}: contiguous float32 freqs on the GPU of qkv are expected")
-    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
-        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
-    B, S = qkv.shape[0], qkv.shape[1]
-    rot = freqs.shape[-1]
-    if freqs.numel() < B * S * rot:
-        raise ValueError(f"{who}: freqs holds fewer than B * S * rot_dim angles")
-    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _capi.check(_capi.lib().awq_rope_kv_store_natural_fp8(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
-                                                              v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), B, Bc, S, int(nheads),
-                                                              int(nheads_kv), Dh, rot, Lmax, int(start_pos), qkv.stride(0), qkv.stride(1),
-                                                              _dt(qkv), _stream(qkv)))
-    return q_out
+    _on_gpu(qkv, freqs, k_cache, v_cache, k_scale, v_scale)
+    return _rope_store(who, qkv, freqs, _caches(who, qkv, k_cache, v_cache, k_scale, v_scale), nheads, nheads_kv, start_pos=start_pos)
 
 
 def _check_kv8(who, q, k, v, k_scale, v_scale):
@@ -786,25 +856,7 @@ def attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offse
             raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
         if k_cache.shape != v_cache.shape or k_cache.shape[0] < q.shape[0] or k_cache.shape[3] != q.shape[3]:
             raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_cache / v_cache [Bc >= B, Lmax, Hkv, Dh] are expected")
-    B, Sq, H, Dh = q.shape
-    Lmax, Hkv = k_cache.shape[1], k_cache.shape[2]
-    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
-    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
-    L = _capi.lib()
-    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, Hkv, Dh, Sq, int(max_seqlen_k))
-    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
-    lens = (B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k), Lmax, H, Hkv, Dh)
-    strides = (q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1))
-    tail = (scale, int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q))
-    with torch.cuda.device(q.device):
-        if fp8:
-            _capi.check(L.awq_attn_kvcache_kv8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
-                                               out.data_ptr(), *lens, *strides, k_scale.stride(0), k_scale.stride(1), v_scale.stride(0),
-                                               v_scale.stride(1), *tail))
-        else:
-            _capi.check(L.awq_attn_kvcache(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), *lens, *strides, *tail))
-    return out
+    return _attn_kvcache(who, q, _Kv(k_cache, v_cache, k_scale, v_scale), seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal)
 
 
 def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
@@ -817,52 +869,18 @@ def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens,
     fp8 = k_scale is not None or v_scale is not None
     if fp8 and (k_scale is None or v_scale is None):
         raise ValueError(f"{who}: k_scale and v_scale come together")
-    for t in (qkv, freqs_table, k_cache, v_cache, cache_seqlens) + ((k_scale, v_scale) if fp8 else ()):
-        if not t.is_cuda:
-            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if fp8:
-            _kv8_codes(who, name, t)
-        elif t.dtype != qkv.dtype:
-            raise ValueError(f"{who}: the caches must have the dtype of the input")
-        if t.device != qkv.device or t.dim() != 4 or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous [Bc, Lmax, Hkv, Dh] tensor on the GPU of qkv")
-    if k_cache.shape != v_cache.shape:
-        raise ValueError(f"{who}: k_cache and v_cache must have one shape [Bc, Lmax, Hkv, Dh]")
-    Bc, Lmax, Hkv, Dh = v_cache.shape
-    if fp8:
-        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
-            if t.device != qkv.device or t.dtype != torch.float32 or tuple(t.shape) != (Bc, Lmax, Hkv) or not t.is_contiguous():
-                raise ValueError(f"{who}: {name} must be a contiguous float32 [Bc, Lmax, Hkv] tensor on the GPU of qkv")
-    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
-        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
-    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
-        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
-    B, S = qkv.shape[0], qkv.shape[1]
-    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
-    P, rot = freqs_table.shape
-    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
-    tail = (B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax, P, qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
-    with torch.cuda.device(qkv.device):
-        if fp8:
-            _capi.check(_capi.lib().awq_rope_kv_store_natural_pos_fp8(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
-                                                                      v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
-                                                                      cache_seqlens.data_ptr(), *tail))
-        else:
-            _capi.check(_capi.lib().awq_rope_kv_store_natural_pos(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
-                                                                  v_cache.data_ptr(), cache_seqlens.data_ptr(), *tail))
-    return q_out
+    _on_gpu(qkv, freqs_table, k_cache, v_cache, cache_seqlens, *((k_scale, v_scale) if fp8 else ()))
+    return _rope_store(who, qkv, freqs_table, _caches(who, qkv, k_cache, v_cache, k_scale, v_scale), nheads, nheads_kv,
+                       cache_seqlens=cache_seqlens)
 
 
 # ---- the paged KV cache: the two calls above over a pool of pages and a per-sequence block table ------------------------------------
 def _check_pools(who, ref, k_pool, v_pool, block_table, k_scale, v_scale, batch):
-    """(num_pages, page_size, Hkv, Dh, pages_per_seq) of the pools [num_pages, page_size, Hkv, Dh] and the table [>= B, pages_per_seq]."""
+    """The pools [num_pages, page_size, Hkv, Dh] and the table [>= B, pages_per_seq] of one call, checked against `ref`, as a _Kv."""
     fp8 = k_scale is not None or v_scale is not None
     if fp8 and (k_scale is None or v_scale is None):
         raise ValueError(f"{who}: k_scale and v_scale come together")
-    for t in (ref, k_pool, v_pool, block_table) + ((k_scale, v_scale) if fp8 else ()):
-        if not t.is_cuda:
-            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _on_gpu(ref, k_pool, v_pool, block_table, *((k_scale, v_scale) if fp8 else ()))
     for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
         if fp8:
             _kv8_codes(who, name, t)
@@ -884,7 +902,7 @@ def _check_pools(who, ref, k_pool, v_pool, block_table, k_scale, v_scale, batch)
     if block_table.device != ref.device or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] < batch or \
             block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.stride(0) < block_table.shape[1]:
         raise ValueError(f"{who}: block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride on the GPU of the input")
-    return num_pages, page_size, Hkv, Dh, block_table.shape[1]
+    return _Kv(k_pool, v_pool, k_scale, v_scale, block_table)
 
 
 def attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None,
@@ -896,33 +914,13 @@ def attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: 
     pool.  With k_scale / v_scale [num_pages, page_size, Hkv] float32 the pools are FP8 codes.  The host reads neither the table nor the
     lengths: capturable, and a replay follows what the tensors hold then."""
     who = "attn_kvcache_paged"
-    if not q.is_cuda:
-        raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _on_gpu(q)
     if q.dim() != 4 or q.stride(3) != 1 or q.stride(2) != q.shape[3]:
         raise ValueError(f"{who}: q must be [B, Sq, H, Dh] with contiguous heads")
-    B, Sq, H, Dh = q.shape
-    num_pages, page_size, Hkv, Dhp, pps = _check_pools(who, q, k_pool, v_pool, block_table, k_scale, v_scale, B)
-    if Dhp != Dh:
-        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_pool / v_pool [num_pages, page_size, Hkv, Dh] must share Dh, got {Dh} and {Dhp}")
-    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
-    fp8 = k_scale is not None
-    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
-    L = _capi.lib()
-    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, Hkv, Dh, Sq, int(max_seqlen_k))
-    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
-    lens = (block_table.data_ptr(), B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k), num_pages, page_size, pps,
-            block_table.stride(0), H, Hkv, Dh)
-    strides = (q.stride(0), q.stride(1), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1))
-    tail = (scale, int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q))
-    with torch.cuda.device(q.device):
-        if fp8:
-            _capi.check(L.awq_attn_kvcache_paged_kv8(q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
-                                                     out.data_ptr(), *lens, *strides, k_scale.stride(0), k_scale.stride(1), v_scale.stride(0),
-                                                     v_scale.stride(1), *tail))
-        else:
-            _capi.check(L.awq_attn_kvcache_paged(q.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), out.data_ptr(), *lens, *strides, *tail))
-    return out
+    kv = _check_pools(who, q, k_pool, v_pool, block_table, k_scale, v_scale, q.shape[0])
+    if kv.Dh != q.shape[3]:
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_pool / v_pool [num_pages, page_size, Hkv, Dh] must share Dh, got {q.shape[3]} and {kv.Dh}")
+    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal)
 
 
 def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
@@ -932,34 +930,11 @@ def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seq
     or cache_seqlens[b] + S > min(pages_per_seq * page_size, P) is inactive: nothing of it is stored and its q rows are zeros.  With
     k_scale / v_scale [num_pages, page_size, Hkv] the pools are FP8.  Returns the rotated q [B, S, H, Dh]."""
     who = "rope_kv_store_paged"
-    for t in (qkv, freqs_table, cache_seqlens):
-        if not t.is_cuda:
-            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _on_gpu(qkv, freqs_table, cache_seqlens)
     if qkv.dim() != 3 or qkv.stride(2) != 1:
         raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride")
-    B, S = qkv.shape[0], qkv.shape[1]
-    num_pages, page_size, Hkv, Dh, pps = _check_pools(who, qkv, k_pool, v_pool, block_table, k_scale, v_scale, B)
-    fp8 = k_scale is not None
-    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
-        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
-    if nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
-        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with the pools' Hkv and Dh")
-    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
-    P, rot = freqs_table.shape
-    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
-    head = (block_table.data_ptr(), cache_seqlens.data_ptr(), B, S, int(nheads), int(nheads_kv), Dh, rot, P, num_pages, page_size, pps,
-            block_table.stride(0), k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1))
-    tail = (qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
-    with torch.cuda.device(qkv.device):
-        if fp8:
-            _capi.check(_capi.lib().awq_rope_kv_store_paged_pos_fp8(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_pool.data_ptr(),
-                                                                    v_pool.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), *head,
-                                                                    k_scale.stride(0), k_scale.stride(1), v_scale.stride(0), v_scale.stride(1),
-                                                                    *tail))
-        else:
-            _capi.check(_capi.lib().awq_rope_kv_store_paged_pos(qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), k_pool.data_ptr(),
-                                                                v_pool.data_ptr(), *head, *tail))
-    return q_out
+    kv = _check_pools(who, qkv, k_pool, v_pool, block_table, k_scale, v_scale, qkv.shape[0])
+    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens)
 
 
 def _ft_caches(who, ref, k_cache, v_cache):
@@ -1005,28 +980,12 @@ def rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: 
     """C-ABI awq_rope_kv_store_natural: rope_kv_store for natural-layout caches k_cache / v_cache [Bc, Lmax, Hkv, Dh] (tinychat's
     long-context path).  Writes the rotated k into k_cache[b, start_pos + s] and v into v_cache[b, start_pos + s]; returns the rotated
     q [B, S, H, Dh]."""
-    for t in (qkv, freqs, k_cache, v_cache):
-        if not t.is_cuda:
-            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _on_gpu(qkv, freqs, k_cache, v_cache)
     if k_cache.device != qkv.device or v_cache.device != qkv.device or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
         raise ValueError("rope_kv_store_natural: the caches must have the device and dtype of the input")
     if v_cache.dim() != 4 or k_cache.shape != v_cache.shape or not v_cache.is_contiguous() or not k_cache.is_contiguous():
         raise ValueError("rope_kv_store_natural: contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] of one shape are expected")
-    Bc, Lmax, Hkv, Dh = v_cache.shape
-    if freqs.device != qkv.device or freqs.dtype != torch.float32 or not freqs.is_contiguous():
-        raise ValueError("rope_kv_store_natural: contiguous float32 freqs on the GPU of qkv are expected")
-    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * Dh:
-        raise ValueError("rope_kv_store_natural: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride and the caches' Hkv and Dh")
-    B, S = qkv.shape[0], qkv.shape[1]
-    rot = freqs.shape[-1]
-    if freqs.numel() < B * S * rot:
-        raise ValueError("rope_kv_store_natural: freqs holds fewer than B * S * rot_dim angles")
-    q_out = torch.empty(B, S, nheads, Dh, dtype=qkv.dtype, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _capi.check(_capi.lib().awq_rope_kv_store_natural(qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), k_cache.data_ptr(),
-                                                          v_cache.data_ptr(), B, Bc, S, int(nheads), int(nheads_kv), Dh, rot, Lmax,
-                                                          int(start_pos), qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv)))
-    return q_out
+    return _rope_store("rope_kv_store_natural", qkv, freqs, _Kv(k_cache, v_cache), nheads, nheads_kv, start_pos=start_pos)
 
 
 def attn_prefill_ftcache(q, k_cache, v_cache, kv_start: int, seqlen_k: int, softmax_scale=None, causal: bool = True):
