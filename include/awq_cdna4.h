@@ -562,6 +562,51 @@ int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_
                                long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Prompt chunks of any length on the device-length and paged caches: the ONE-PASS prefill kernel of awq_attn_prefill[_kv8] with every
+ *      sequence's length read on the device, K / V from the dense caches or fetched from the pool through the table.  The arguments are
+ *      those of awq_attn_kvcache[_kv8] / awq_attn_kvcache_paged[_kv8] without the workspace; seqlen_q >= 1 of ANY size (the split pair above
+ *      keeps its seqlen_q * (nheads / nheads_kv) <= 128), head_dim 64 / 128.
+ * Length: Sk_b = seqlens_k[b] + seqlen_offset; sequence b is ACTIVE iff 1 <= Sk_b <= max_seqlen_k.  The causal mask is bottom-right aligned
+ *     per sequence: row i attends keys j <= i + Sk_b - seqlen_q; causal = 0 attends keys 0 .. Sk_b - 1.  A row whose limit is negative
+ *     (Sk_b < seqlen_q) attends nothing and returns zeros; no NaN or Inf is produced from finite attended inputs and nothing divides by 0.
+ * Inactive sequences and unused tiles: a block of an inactive sequence, or one whose q tile attends no key, writes zero rows for its q
+ *     tile and leaves before its first K / V load; a block visits no 64-key tile behind the last key its q tile attends; cache or pool
+ *     rows >= Sk_b are never read (addresses are clamped to row Sk_b - 1).
+ * Grid: from host arguments only -- awq_attn_prefill_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, ..) ignores seqlen_k, so the q
+ *     tile and the block count are the host-length launch's and the knob "attn_prefill_rows" applies.  No workspace, no atomics:
+ *     bit-deterministic and capturable; a replay follows the lengths (and the table) the tensors hold then.
+ * Paged: the pool and table rules above.  Tiles begin at multiples of 64 from key 0, so a tile has one page; its id is a scalar load issued
+ *     a tile ahead of the K / V loads that use it, clamped into [0, num_pages); no entry at or behind ceil(Sk_b / page_size) is read, the
+ *     look-ahead included.  _kv8: codes and scale pools go through the same page id.
+ * Bits: tile walk, masks, LDS images and rounding points are awq_attn_prefill's.  For every active sequence with Sk_b >= seqlen_q, out[b]
+ *     is bit-identical to awq_attn_prefill[_kv8] on that sequence alone (batch 1, seqlen_k = Sk_b, k / v = its cache rows or the gather
+ *     of its pages) under the same q tile.
+ * Returns the codes of awq_attn_kvcache[_kv8] / awq_attn_kvcache_paged[_kv8], all but AWQ_ERR_LAUNCH without a GPU call, with two
+ *     differences: seqlen_q * (nheads / nheads_kv) > 128 is accepted (AWQ_ERR_SHAPE only when batch * nheads * ceil(seqlen_q / 64) exceeds
+ *     2^31 - 1), and AWQ_ERR_WORKSPACE is never returned. */
+int awq_attn_prefill_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
+                             int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                             long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                             long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+int awq_attn_prefill_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                                 int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads,
+                                 int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride,
+                                 long long k_row_stride, long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride,
+                                 long long k_scale_row_stride, long long v_scale_batch_stride, long long v_scale_row_stride,
+                                 float softmax_scale, int causal, int dtype, void* stream);
+int awq_attn_prefill_paged(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch, int seqlen_q,
+                           const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size, int pages_per_seq,
+                           long long table_row_stride, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, float softmax_scale,
+                           int causal, int dtype, void* stream);
+int awq_attn_prefill_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                               const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                               int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                               int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                               long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                               void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

@@ -117,6 +117,13 @@ SIGNATURES = {
                                [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_kvcache_paged_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
                                    [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_prefill_kvcache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 6 + [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_kvcache_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
+                                     [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_paged": (_i, [_vp] * 5 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 6 +
+                               [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_paged_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
+                                   [ctypes.c_float, _i, _i, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

@@ -24,8 +24,11 @@
 //     the tiles the diagonal or the end of K crosses.
 //   * No workspace, no atomics: bit-deterministic.  O is divided by l (IEEE division of 1 / l, once per row) and rounded to T once.
 #include "awq_device.hpp"
+#include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
+#include "awq_kvcache.hpp"
+#include "awq_paged.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -58,6 +61,21 @@ struct PrefillArgs {
   const float* v_scale;
   long long ks_bs, ks_rs, vs_bs, vs_rs;
 };
+// DevLen / Paged only (awq_devlen.hpp, awq_paged.hpp): what awq_attn_prefill_kvcache / awq_attn_prefill_paged add to a launch.  A struct
+// of its own, passed NEXT to PrefillArgs as a second kernel argument: the host-length kernels keep their PrefillArgs block, their
+// register assignment and their code (DESIGN.md "Prompt chunks on the device-length caches").
+struct PrefillLenArgs {
+  const int* seqlens_k;  // device int32 [B]: the length of sequence b is seqlens_k[b] + seqlen_offset
+  int seqlen_offset;
+  int max_seqlen_k;      // the host's bound: a sequence beyond it is inactive
+  PageArgs pg;           // Paged: a.k / a.v are then the pools and a.k_bs / a.v_bs (a.ks_bs / a.vs_bs) their PAGE strides
+};
+
+struct NoLenArgs {};
+template <typename DT>
+using LenArgsOf = typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type;
+__device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}}; }
+__device__ __forceinline__ PrefillLenArgs len_args(const PrefillLenArgs& x) { return x; }
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
 //   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
@@ -96,10 +114,34 @@ struct IsFtCache<FtCache<DT>> {
   static constexpr bool value = true;
 };
 
+//
+// DevLen<..> (awq_attn_prefill_kvcache[_kv8]): Sk_b = seqlens_k[b] + seqlen_offset stands wherever a.Sk stands in the host-length form.  The
+// length is one scalar load at the head of the block, issued next to the Q loads, which do not depend on it.  A block whose sequence is
+// inactive (Sk_b < 1 or Sk_b > max_seqlen_k) or whose q tile attends no key (causal, Sk_b < Sq: every row's limit is negative) writes zero
+// rows and leaves before its first K / V load; the test is uniform over the block and no barrier precedes it.  A row of a live block may
+// still attend nothing (its limit is negative while a later row's is not): its running max stays -inf, so 0 is subtracted in its place
+// (every weight is exp2(-inf) = 0, alpha = 0 multiplies an O and an l that are still 0: no Inf - Inf), and it is written as zeros without
+// the division by l = 0.  With a finite max both guards select the host-length kernel's expressions: same bits.
+//
+// Paged<DevLen<..>> (awq_attn_prefill_paged[_kv8]): key g of the sequence is row g % page_size of page table[b][g / page_size].  Tiles
+// begin at multiples of 64 from key 0 and page_size % 64 == 0, so a tile (and the clamp to Sk_b - 1, which stays inside it) has ONE page,
+// uniform over the block: a scalar load.  The ids run a tile ahead of the loads that use them, as in the split kernel
+// (awq_attn_splitkv_cdna4.hip): tile t + 1's K / V loads of iteration t take an id requested in iteration t - 1, the first two at the head
+// of the block behind the length.  (pg_i, pg_ro) advance by 64 rows: no division in the loop.  Only tiles j < nt are looked up; their
+// first key lies below kv_end <= Sk_b, so no entry at or behind ceil(Sk_b / page_size) is read.
+//
+// The device-length forms take their PrefillLenArgs as a SECOND kernel argument.  For the host-length forms that argument is the empty
+// NoLenArgs -- one padded byte behind PrefillArgs that no instruction reads: their PrefillArgs, their registers and their instruction
+// stream are those of the one-argument kernel.
 template <typename DT, int DH, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
+__global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, LenArgsOf<DT> xs) {
+  const PrefillLenArgs x = len_args(xs);
   constexpr bool FT = IsFtCache<DT>::value;
   constexpr bool KV8 = IsKv8<DT>::value;
+  constexpr bool DEVLEN = IsDevLen<DT>::value;
+  constexpr bool PAGED = IsPaged<DT>::value;
+  static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
+  static_assert(!FT || !DEVLEN, "the FT caches take a host length");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = NW * 64;
@@ -121,17 +163,25 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
   const int tile = a.causal ? a.ntiles - 1 - rank : rank;
   const int kvh = h / a.G;
   const int q0 = tile * (NW * kMfmaRows);
-  const int shift = a.Sk - a.Sq;
+  int Sk = a.Sk;
+  bool live = true;
+  (void)live;
+  if constexpr (DEVLEN) {  // one scalar load; the Q loads below do not depend on it and are issued beside it
+    const long long len = (long long)x.seqlens_k[b] + x.seqlen_offset;  // 64 bits: no entry can wrap into an active length
+    Sk = (int)len;
+    live = len >= 1 && len <= x.max_seqlen_k;
+  }
+  const int shift = Sk - a.Sq;
   const int q_last = min(q0 + NW * kMfmaRows, a.Sq) - 1;
-  const int kv_end = a.causal ? min(a.Sk, q_last + shift + 1) : a.Sk;  // keys [0, kv_end) matter to this block
+  const int kv_end = a.causal ? min(Sk, q_last + shift + 1) : Sk;  // keys [0, kv_end) matter to this block
   const int nt = (kv_end + kKV - 1) / kKV;
 
   const int wq0 = q0 + wave * kMfmaRows;
   const bool wave_on = wq0 < a.Sq;                 // (a wave past the last row still stages K / V and meets the barriers)
   const int qi = min(wq0 + r, a.Sq - 1);           // rows >= Sq compute row Sq - 1 again and are not stored
-  const int lim = a.causal ? qi + shift : a.Sk - 1;                                 // last key this lane's row attends
-  const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, a.Sq - 1) + shift : a.Sk - 1;  // .. any row of the wave
-  const int wave_min = a.causal ? wq0 + shift : a.Sk - 1;                           // every row of the wave attends keys <= this
+  const int lim = a.causal ? qi + shift : Sk - 1;                                 // last key this lane's row attends
+  const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, a.Sq - 1) + shift : Sk - 1;  // .. any row of the wave
+  const int wave_min = a.causal ? wq0 + shift : Sk - 1;                           // every row of the wave attends keys <= this
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   vec8 qf[KS];
@@ -141,28 +191,52 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
   }
 
-  const uint16_t* kb = a.k + (long long)b * a.k_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
-  const uint16_t* vb = a.v + (long long)b * a.v_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
+  if constexpr (DEVLEN) {
+    if (!live || kv_end < 1) {  // inactive, or no row of the q tile attends a key: zero rows, no K / V load
+      if (wq0 + r < a.Sq) {
+        uint16_t* op = a.out + (((long long)b * a.Sq + qi) * a.H + h) * DH + 4 * hh;
+#pragma unroll
+        for (int c = 0; c < DH / 8; ++c) *reinterpret_cast<u32x2*>(op + 8 * c) = u32x2{0u, 0u};
+      }
+      return;
+    }
+  }
+
+  const long long pool_b = PAGED ? 0 : b;  // Paged: the pools have no batch dimension, the page offset is added per tile
+  const uint16_t* kb = a.k + pool_b * a.k_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
+  const uint16_t* vb = a.v + pool_b * a.v_bs + (FT ? (long long)kvh * a.k_rs * CPR : (long long)kvh * DH);
   using stage_t = typename std::conditional<KV8, u32x2, u32x4>::type;
   stage_t kr[LOADS], vr[LOADS];
   float ksc[KV8 ? LOADS : 1], vsc[KV8 ? LOADS : 1];  // Kv8: the scale of the chunk's row
-  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + (long long)b * a.k_bs + (long long)kvh * DH;
-  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + (long long)b * a.v_bs + (long long)kvh * DH;
-  const float* ksb = KV8 ? a.k_scale + (long long)b * a.ks_bs + kvh : nullptr;
-  const float* vsb = KV8 ? a.v_scale + (long long)b * a.vs_bs + kvh : nullptr;
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + pool_b * a.k_bs + (long long)kvh * DH;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + pool_b * a.v_bs + (long long)kvh * DH;
+  const float* ksb = KV8 ? a.k_scale + pool_b * a.ks_bs + kvh : nullptr;
+  const float* vsb = KV8 ? a.v_scale + pool_b * a.vs_bs + kvh : nullptr;
   // FT: the K chunks of a tile go to the threads with the KEY fastest (NT is a multiple of 64, so a wave reads 64 consecutive positions
   // of one chunk index: 1 KiB contiguous in the cache) and land in the same LDS image; V rows are DH contiguous elements in the cache
   // too, so V keeps the chunk-fastest mapping.  Keys >= Sk are clamped to Sk - 1 like rows: no position outside the Sk keys is read.
-  auto stage_load = [&](int t0) {
+  // Paged: page = the (clamped) id of the tile's page, ro = the tile's first row inside it; unused otherwise
+  auto stage_load = [&](int t0, int page, int ro) {
 #pragma unroll
     for (int i = 0; i < LOADS; ++i) {
       const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-      const long long g = min(t0 + row, a.Sk - 1);
+      const long long g = min(t0 + row, Sk - 1);
       if constexpr (FT) {
         const int krow = c % kKV, kch = c / kKV;
-        const long long kg = min(t0 + krow, a.Sk - 1);
+        const long long kg = min(t0 + krow, Sk - 1);
         kr[i] = *reinterpret_cast<const u32x4*>(kb + kch * a.k_rs + kg * 8);
         vr[i] = *reinterpret_cast<const u32x4*>(vb + g * DH + ch * 8);
+      } else if constexpr (PAGED) {
+        const long long prow = ro + (g - t0);  // row of the page: < page_size, the tile does not straddle
+        if constexpr (KV8) {
+          kr[i] = *reinterpret_cast<const u32x2*>(kb8 + page * a.k_bs + prow * a.k_rs + ch * 8);
+          vr[i] = *reinterpret_cast<const u32x2*>(vb8 + page * a.v_bs + prow * a.v_rs + ch * 8);
+          ksc[i] = ksb[page * a.ks_bs + prow * a.ks_rs];
+          vsc[i] = vsb[page * a.vs_bs + prow * a.vs_rs];
+        } else {
+          kr[i] = *reinterpret_cast<const u32x4*>(kb + page * a.k_bs + prow * a.k_rs + ch * 8);
+          vr[i] = *reinterpret_cast<const u32x4*>(vb + page * a.v_bs + prow * a.v_rs + ch * 8);
+        }
       } else if constexpr (KV8) {
         kr[i] = *reinterpret_cast<const u32x2*>(kb8 + g * a.k_rs + ch * 8);
         vr[i] = *reinterpret_cast<const u32x2*>(vb8 + g * a.v_rs + ch * 8);
@@ -201,7 +275,31 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
   // transposed-read addressing: lane 4 qq + p of a 16-lane group supplies row qq, columns 4 p .. 4 p + 3 of the group's 4 x 16 block
   const int tr_q = (lane & 15) >> 2, tr_p = lane & 3, tr_g = (lane >> 4) & 1;
 
-  stage_load(0);
+  // Paged: the ids of tiles 0 and 1, both requested before the first K / V load is issued.  The table is read through the constant
+  // address space: nothing writes it while the kernel runs, and only so does the load inside the loop stay a SCALAR load -- behind a
+  // barrier the compiler otherwise takes memory for clobbered and reads the entry with a vector load and a full wait at the head of
+  // every tile.  An entry is REQUESTED at the head of an iteration and clamped (page_id) behind the barrier that ends it, where the
+  // wait the barrier needs anyway has covered it.
+  typedef const int __attribute__((address_space(4))) * const_table_t;
+  const const_table_t table = PAGED ? reinterpret_cast<const_table_t>(reinterpret_cast<uintptr_t>(x.pg.block_table + (long long)b * x.pg.bt_rs)) : nullptr;
+  int pg_i = 0, pg_ro = 0, pg_cur = 0, pg_nxt = 0, ro_nxt = 0;
+  auto next_entry = [&]() {  // (pg_i, pg_ro) -> the tile 64 keys on; returns its table entry, not yet clamped
+    pg_ro += kKV;
+    if (pg_ro == x.pg.page_size) {
+      pg_ro = 0;
+      ++pg_i;
+    }
+    return table[pg_i];
+  };
+  if constexpr (PAGED) {
+    pg_cur = page_id(table[0], x.pg.num_pages);
+    if (nt > 1) {
+      pg_nxt = page_id(next_entry(), x.pg.num_pages);
+      ro_nxt = pg_ro;
+    }
+  }
+
+  stage_load(0, pg_cur, 0);
   stage_write(0);
   // Q has arrived before the loop starts: a wait for it inside the loop would be a vmcnt(0) behind the loads the loop has just
   // issued (the counter retires in order), which is exactly the overlap the staging exists for
@@ -212,7 +310,14 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
   for (int t = 0; t < nt; ++t) {
     const int buf = t & 1, t0 = t * kKV;
     const bool more = t + 1 < nt;
-    if (more) stage_load(t0 + kKV);
+    int pg_n2 = pg_nxt, ro_n2 = ro_nxt;
+    if constexpr (PAGED) {
+      if (t + 2 < nt) {  // the entry tile t + 2 will load with in the next iteration: a whole tile ahead of its use
+        pg_n2 = next_entry();
+        ro_n2 = pg_ro;
+      }
+    }
+    if (more) stage_load(t0 + kKV, pg_nxt, ro_nxt);
 
     if (wave_on && t0 <= wave_max) {
       // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, query row r ----
@@ -243,8 +348,10 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
           mx = fmaxf(mx, x);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float m_new = fmaxf(m_run, mx);  // finite from the first tile on: key 0 is attended by every row
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      const float m_new = fmaxf(m_run, mx);  // host length: finite from the first tile on, key 0 is attended by every row
+      float m_sub = m_new;
+      if constexpr (DEVLEN) m_sub = m_new == -INFINITY ? 0.f : m_new;  // a row that has attended nothing so far
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_sub);
       m_run = m_new;
       vec8 pf[4];
       float sum = 0.f;
@@ -252,7 +359,7 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
       for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const elem pt = (elem)__builtin_amdgcn_exp2f(s[kb2][e] - m_new);  // the ONE rounding of a weight
+          const elem pt = (elem)__builtin_amdgcn_exp2f(s[kb2][e] - m_sub);  // the ONE rounding of a weight
           pf[2 * kb2 + (e >> 3)][e & 7] = pt;
           sum += (float)pt;
         }
@@ -279,12 +386,17 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
 
     if (more) stage_write(buf ^ 1);  // the other buffer: its readers finished before the barrier that ended tile t - 1
     __syncthreads();
+    if constexpr (PAGED) {
+      pg_nxt = page_id(pg_n2, x.pg.num_pages);  // (clamping an id twice changes nothing)
+      ro_nxt = ro_n2;
+    }
   }
 
   // ---- O / l, rounded to T once; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   if (wq0 + r < a.Sq) {
-    const float inv = 1.0f / l_tot;
+    float inv = 1.0f / l_tot;
+    if constexpr (DEVLEN) inv = l_tot > 0.f ? inv : 0.f;  // a row that attended nothing: zeros (o is 0), never 0 * Inf
     uint16_t* op = a.out + (((long long)b * a.Sq + qi) * a.H + h) * DH + 4 * hh;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
@@ -300,9 +412,9 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a) {
 template <typename DT, int DH>
 void launch_nw(const PrefillArgs& a, int nw, int blocks, hipStream_t st) {
   switch (nw) {
-    case 8: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 8>), dim3(blocks), dim3(512), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 4>), dim3(blocks), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 2>), dim3(blocks), dim3(128), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 8>), dim3(blocks), dim3(512), 0, st, a, NoLenArgs{}); break;
+    case 4: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 4>), dim3(blocks), dim3(256), 0, st, a, NoLenArgs{}); break;
+    default: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 2>), dim3(blocks), dim3(128), 0, st, a, NoLenArgs{}); break;
   }
 }
 
@@ -552,6 +664,65 @@ int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const f
   } else {
     if (Dh == 128) launch_nw<Kv8<BF16>, 128>(a, nw, blocks, st);
     else launch_nw<Kv8<BF16>, 64>(a, nw, blocks, st);
+  }
+  return 0;
+}
+
+namespace {
+
+// L<K<DT>>: K is the cache's traits (DT, or Kv8<DT> for codes with scales), L the lengths' (DevLen, or PagedDevLen over a pool)
+template <template <typename> class K, template <typename> class L>
+void launch_kv_prefill_as(const PrefillArgs& a, const PrefillLenArgs& x, int Dh, int dtype, int nw, int blocks, hipStream_t st) {
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    using DT = L<K<decltype(dt)>>;
+    constexpr int DH = decltype(dh)::value;
+    switch (nw) {
+      case 8: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 8>), dim3(blocks), dim3(512), 0, st, a, x); break;
+      case 4: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 4>), dim3(blocks), dim3(256), 0, st, a, x); break;
+      default: hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 2>), dim3(blocks), dim3(128), 0, st, a, x); break;
+    }
+  });
+}
+template <typename DT>
+using TCache = DT;  // the T cache: the element traits themselves
+
+}  // namespace
+
+// The one-pass kernel over a view with every sequence's length read on the device (awq_attn_prefill_kvcache[_kv8], awq_attn_prefill_paged
+// [_kv8]): dense caches or a pool of pages, T or FP8, selected by what the descriptor holds.  The plan is asked with the bound in the place
+// of seqlen_k -- it ignores both -- so the q tile and the block count are the host-length launch's for the same (B, H, Dh, Sq), and the
+// knob attn_prefill_rows applies.  The caller has validated the arguments: max_seqlen_k <= the capacity of the view, so the clamp to
+// Sk_b - 1 stays inside a sequence's rows and every table index inside a table row.
+int launch_kv_prefill(const KvAttnCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  PrefillArgs a;
+  a.q = (const uint16_t*)c.q;
+  a.k = (const uint16_t*)kv.k;
+  a.v = (const uint16_t*)kv.v;
+  a.out = (uint16_t*)c.out;
+  a.q_bs = c.q_bs, a.q_rs = c.q_rs;
+  a.k_bs = kv.k_os, a.k_rs = kv.k_rs, a.v_bs = kv.v_os, a.v_rs = kv.v_rs;
+  a.B = c.B;
+  a.Sq = c.Sq;
+  a.Sk = c.max_seqlen_k;
+  a.H = c.H;
+  a.G = c.H / c.Hkv;
+  a.causal = c.causal ? 1 : 0;
+  a.scale_log2e = c.scale * 1.4426950408889634f;
+  a.k_scale = kv.k_scale;
+  a.v_scale = kv.v_scale;
+  a.ks_bs = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_bs = kv.vs_os, a.vs_rs = kv.vs_rs;
+  const PrefillLenArgs x{c.seqlens_k, c.seqlen_offset, c.max_seqlen_k, PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer}};
+  int rows = 0, blocks = 0;
+  attn_prefill_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, c.causal, &rows, &blocks);
+  a.ntiles = (c.Sq + rows - 1) / rows;
+  const int nw = rows / kMfmaRows;
+  if (kv.block_table) {
+    if (kv.k_scale) launch_kv_prefill_as<Kv8, PagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+    else launch_kv_prefill_as<TCache, PagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+  } else {
+    if (kv.k_scale) launch_kv_prefill_as<Kv8, DevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+    else launch_kv_prefill_as<TCache, DevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
   }
   return 0;
 }

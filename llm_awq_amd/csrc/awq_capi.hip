@@ -430,7 +430,8 @@ size_t awq_attn_splitkv_workspace_bytes(int batch, int nheads, int nheads_kv, in
 using awq::KvAttnCall;
 using awq::KvStoreCall;
 using awq::KvView;
-enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4 };  // what an entry requires of its descriptor
+// what an entry requires of its descriptor; KV_ONEPASS: the one-pass prefill kernel serves, any seqlen_q (no seqlen_q * G <= 128 term)
+enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8 };
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
@@ -489,10 +490,12 @@ static int kv_store(const KvStoreCall& c, int fmt, void* stream) {
   return finish_launch();
 }
 
-// the split pair always runs under device lengths: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions
-static bool kvcache_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k) {
+// the split pair always runs under device lengths: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions.  one_pass
+// (awq_attn_prefill_kvcache and its siblings): any seqlen_q whose grid of 64-row q tiles fits an int, as in prefill_shape_ok
+static bool kvcache_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k, bool one_pass = false) {
   return batch >= 1 && nheads >= 1 && nheads_kv >= 1 && (nheads % nheads_kv) == 0 && (head_dim == 64 || head_dim == 128) && seqlen_q >= 1 &&
-         (long long)seqlen_q * (nheads / nheads_kv) <= 128 && max_seqlen_k >= 1;
+         (one_pass ? (long long)batch * nheads * ((seqlen_q + 63) / 64) <= 0x7FFFFFFFll : (long long)seqlen_q * (nheads / nheads_kv) <= 128) &&
+         max_seqlen_k >= 1;
 }
 
 int awq_attn_kvcache_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k, int* splits, int* chunk) {
@@ -513,7 +516,7 @@ static int kv_attn_check(const KvAttnCall& c, int fmt) {
   if (!c.q || !c.out || kv_has_null(kv, fmt) || (devlen && !c.seqlens_k)) return AWQ_ERR_NULL;
   if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
   // (host lengths: the T entry keeps the one-pass kernel's head dim 72 for the calls the plan hands to it; the FP8 kernels have 64 / 128)
-  if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k)
+  if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, fmt & KV_ONEPASS)
                : ((!(fmt & KV_FP8) || c.Dh == 64 || c.Dh == 128) && prefill_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal))) ||
       !kv_shape_ok(kv, fmt, true, c.Hkv, c.Dh) || c.q_bs < 0 || c.q_rs < (long long)c.H * c.Dh)
     return AWQ_ERR_SHAPE;
@@ -547,6 +550,17 @@ static int kv_attn(const KvAttnCall& c, int fmt, void* workspace, size_t workspa
   if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
   if ((long long)c.B * c.Hkv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
   awq::launch_kv_attn(c, splits, chunk, workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
+// The one-pass prefill kernel under device lengths (awq_attn_prefill_kvcache[_kv8], awq_attn_prefill_paged[_kv8]): the same four phases
+// with the seqlen_q * G <= 128 term lifted, the tail of the device-length entries, no plan and no workspace.
+static int kv_prefill(const KvAttnCall& c, int fmt, void* stream) {
+  const int rc = kv_attn_check(c, fmt | KV_ONEPASS);
+  if (rc != AWQ_OK) return rc;
+  if (c.max_seqlen_k > c.kv.capacity() || c.seqlen_offset < 0) return AWQ_ERR_SHAPE;
+  if (!aligned4(c.seqlens_k)) return AWQ_ERR_ALIGN;
+  awq::launch_kv_prefill(c, (hipStream_t)stream);
   return finish_launch();
 }
 
@@ -708,6 +722,56 @@ int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_
   return kv_attn({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
                   q_row_stride, softmax_scale, causal, dtype},
                  KV_FP8 | KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
+}
+
+int awq_attn_prefill_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
+                             int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
+                             long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                             long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  const KvView kv = kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_prefill({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                     q_row_stride, softmax_scale, causal, dtype},
+                    KV_DEVLEN, stream);
+}
+
+int awq_attn_prefill_kvcache_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                                 int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int lmax, int nheads,
+                                 int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride, long long k_batch_stride,
+                                 long long k_row_stride, long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride,
+                                 long long k_scale_row_stride, long long v_scale_batch_stride, long long v_scale_row_stride,
+                                 float softmax_scale, int causal, int dtype, void* stream) {
+  const KvView kv = with_scales(kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale,
+                                v_scale, k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return kv_prefill({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                     q_row_stride, softmax_scale, causal, dtype},
+                    KV_FP8 | KV_DEVLEN, stream);
+}
+
+int awq_attn_prefill_paged(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch, int seqlen_q,
+                           const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size, int pages_per_seq,
+                           long long table_row_stride, int nheads, int nheads_kv, int head_dim, long long q_batch_stride, long long q_row_stride,
+                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, float softmax_scale,
+                           int causal, int dtype, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_prefill({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                     q_row_stride, softmax_scale, causal, dtype},
+                    KV_PAGED | KV_DEVLEN, stream);
+}
+
+int awq_attn_prefill_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                               const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                               int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                               int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                               long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                               void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_prefill({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                     q_row_stride, softmax_scale, causal, dtype},
+                    KV_FP8 | KV_PAGED | KV_DEVLEN, stream);
 }
 
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {

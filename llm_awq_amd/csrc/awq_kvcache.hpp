@@ -64,6 +64,8 @@ int launch_kv_store(const KvStoreCall& c, hipStream_t st);
 int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
 // the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
+// the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace
+int launch_kv_prefill(const KvAttnCall& c, hipStream_t st);
 
 // f(element traits, std::integral_constant<int, DH>) for dtype 0 / 1 (F16 / BF16 of awq_device.hpp) and Dh 128 / 64
 template <typename F16T, typename BF16T, typename F>

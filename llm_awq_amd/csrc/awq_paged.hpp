@@ -49,5 +49,7 @@ struct PageArgs {
 
 // entry idx of a sequence's table row, clamped into the pool.  idx is uniform over the block in the attention kernel (a scalar load).
 __device__ __forceinline__ int page_id(const int* table_row, int idx, int num_pages) { return min(max(table_row[idx], 0), num_pages - 1); }
+// the same clamp for an entry that was loaded earlier (the one-pass prefill kernel requests an entry a tile ahead and clamps it at its use)
+__device__ __forceinline__ int page_id(int entry, int num_pages) { return min(max(entry, 0), num_pages - 1); }
 
 }  // namespace awq

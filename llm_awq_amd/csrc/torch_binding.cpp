@@ -986,9 +986,10 @@ torch::Tensor rope_kv_store_paged_pos_fp8(const torch::Tensor qkv, const torch::
 
 // attn_kvcache[_paged][_kv8](q, caches or pools .., seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: the split-KV pair
 // with Sk_b = seqlens_k[b] + seqlen_offset read on the device, K / V from the caches or fetched from the pools through the table.  The fp32
-// partials live in a buffer of torch's caching allocator, so a graph capture owns them.
+// partials live in a buffer of torch's caching allocator, so a graph capture owns them.  one_pass: attn_prefill_kvcache[_kv8] /
+// attn_prefill_paged[_kv8], the one-pass prefill kernel under the same lengths -- any seqlen_q, no workspace.
 static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& seqlens_k,
-                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal, bool one_pass = false) {
   const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
   TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
@@ -1003,7 +1004,7 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
               headdim, "]");
   TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
               ": empty tensors are not supported and H must be a multiple of Hkv");
-  TORCH_CHECK(sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
+  TORCH_CHECK(one_pass || sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
               " exceeds 128 (the split kernels serve few query rows; ",
               paged ? "feed a longer prompt in pieces)" : "a prompt goes through the host-length path)");
   TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap,
@@ -1012,7 +1013,7 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
-  const size_t wsb = awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
+  const size_t wsb = one_pass ? 0 : awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
   at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
   void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
@@ -1020,6 +1021,30 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   const int B = (int)batch, Sq = (int)sq, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, off = (int)seqlen_offset,
             bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q);
   const float scale = (float)softmax_scale;
+  if (one_pass) {
+    if (paged) {
+      const torch::Tensor& bt = *kv.block_table;
+      const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+      if (fp8)
+        raise_on(awq_attn_prefill_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off,
+                                            bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+                                            v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
+                                            kv.v_scale->stride(1), scale, cz, dt, st));
+      else
+        raise_on(awq_attn_prefill_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off, bound, pages,
+                                        page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
+                                        v.stride(1), scale, cz, dt, st));
+    } else if (fp8) {
+      raise_on(awq_attn_prefill_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H,
+                                            Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                                            kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz,
+                                            dt, st));
+    } else {
+      raise_on(awq_attn_prefill_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh,
+                                        q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, st));
+    }
+    return out;
+  }
   if (paged) {
     const torch::Tensor& bt = *kv.block_table;
     const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
@@ -1067,6 +1092,34 @@ torch::Tensor attn_kvcache_paged_kv8(const torch::Tensor q, const torch::Tensor 
                                      int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
   return attn_kvcache_impl("attn_kvcache_paged_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, seqlen_offset,
                            softmax_scale, causal);
+}
+
+// attn_prefill_kvcache[_kv8] / attn_prefill_paged[_kv8]: the arguments of their attn_kvcache* neighbours, served by the one-pass prefill
+// kernel (csrc/awq_attn_prefill_cdna4.hip) for a prompt chunk of any length.
+torch::Tensor attn_prefill_kvcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor seqlens_k,
+                                   int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_prefill_kvcache", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal, true);
+}
+
+torch::Tensor attn_prefill_kvcache_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                                       const torch::Tensor v_scale, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset,
+                                       double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_prefill_kvcache_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal, true);
+}
+
+torch::Tensor attn_prefill_paged(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                 const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_prefill_paged", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal, true);
+}
+
+torch::Tensor attn_prefill_paged_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                     const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor seqlens_k,
+                                     int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  return attn_kvcache_impl("attn_prefill_paged_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, seqlen_offset,
+                           softmax_scale, causal, true);
 }
 
 // (splits, chunk) of awq_attn_kvcache_plan, made from the bound alone.  Host only.
@@ -1484,6 +1537,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_kvcache_paged_kv8", &attn_kvcache_paged_kv8, "attn_kvcache_paged on FP8 pools with per-(key, KV head) fp32 scale pools",
         py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_prefill_kvcache", &attn_prefill_kvcache,
+        "The one-pass prefill kernel over natural-layout caches with per-sequence lengths read on the device: a prompt chunk of any length",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("seqlen_offset"),
+        py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_prefill_kvcache_kv8", &attn_prefill_kvcache_kv8, "attn_prefill_kvcache on the FP8 cache", py::arg("q"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("seqlen_offset"),
+        py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_prefill_paged", &attn_prefill_paged,
+        "attn_prefill_kvcache over a paged KV cache: K / V fetched from pools [num_pages, page_size, Hkv, Dh] through block_table [B, pages_per_seq]",
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_prefill_paged_kv8", &attn_prefill_paged_kv8, "attn_prefill_paged on FP8 pools with per-(key, KV head) fp32 scale pools", py::arg("q"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
         py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",

@@ -17,7 +17,8 @@ window, no ALiBi.  Anything else that is asked for raises NotImplementedError na
 
 `flash_attn_with_kvcache` is what a decode engine with continuous batching or a captured decode graph asks of flash-attn: per-sequence
 lengths in a device tensor.  It is served for an already updated cache (`k` / `v` None) by the split-KV kernels with device-side lengths
-(`attn_kvcache`, csrc/awq_attn_splitkv_cdna4.hip).
+(`attn_kvcache`, csrc/awq_attn_splitkv_cdna4.hip) and, for more than 128 query rows per KV head -- a prompt chunk --, by the one-pass prefill
+kernel under the same lengths (`attn_prefill_kvcache`, csrc/awq_attn_prefill_cdna4.hip).
 """
 from __future__ import annotations
 
@@ -63,8 +64,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
                             rotary_interleaved=True, alibi_slopes=None, num_splits=0, return_softmax_lse=False):
     """flash_attn.flash_attn_with_kvcache's forward for a cache that is already up to date: q [B, Sq, H, Dh], k_cache / v_cache
     [Bc >= B, Lmax, Hkv, Dh], cache_seqlens the TOTAL length of every sequence as an int32 tensor [B] on the GPU (read by the kernels only:
-    no host copy, no sync, capturable) or an int -> [B, Sq, H, Dh].  Served by `attn_kvcache` with max_seqlen_k = Lmax: Sq * (H / Hkv) <= 128,
-    Dh 64 or 128.  A sequence whose length is < 1 or > Lmax returns zeros.  `cache_seqlens=None` attends the whole cache
+    no host copy, no sync, capturable) or an int -> [B, Sq, H, Dh].  Served with max_seqlen_k = Lmax by `attn_kvcache` while
+    Sq * (H / Hkv) <= 128 and by `attn_prefill_kvcache` (the one-pass prefill kernel, any Sq) beyond; Dh 64 or 128.  A sequence whose length is < 1 or > Lmax returns zeros.  `cache_seqlens=None` attends the whole cache
     (`flash_attn_func`).  Appending k / v, rotary_cos / rotary_sin, block_table, cache_batch_idx, cache_leftpad, a window, softcap, ALiBi
     and the softmax LSE are not implemented and raise NotImplementedError naming the argument (`rotary_interleaved` and `num_splits`
     have nothing to act on and are ignored: there is no rotation here, and the split count is the plan's)."""
@@ -87,7 +88,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
     scale = float(q.shape[-1]) ** -0.5 if softmax_scale is None else float(softmax_scale)
-    return load_engine().attn_kvcache(q, k_cache, v_cache, cache_seqlens, int(k_cache.shape[1]), 0, scale, bool(causal))
+    eng = load_engine()
+    prompt = q.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and q.shape[1] * (q.shape[2] // k_cache.shape[2]) > 128
+    attn = eng.attn_prefill_kvcache if prompt else eng.attn_kvcache
+    return attn(q, k_cache, v_cache, cache_seqlens, int(k_cache.shape[1]), 0, scale, bool(causal))
 
 
 def _plan_splits(eng, q, k, causal) -> bool:

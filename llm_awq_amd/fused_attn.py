@@ -35,6 +35,11 @@ With `block_table=` and `page_size=` (and a tensor `start_pos`) the module's cac
 max_batch_size * kv_max_seq_len / page_size pages -- a view, nothing is copied or allocated -- through the per-sequence block table
 (`rope_kv_store_paged_pos[_fp8]`, `attn_kvcache_paged[_kv8]`; `llm_awq_amd.paged_kv.PageTable` hands the pages out): a sequence holds the
 pages its tokens need, not kv_max_seq_len rows, and one sequence may grow past kv_max_seq_len while others are short.
+
+Under a tensor `start_pos` a chunk of ANY length is served, with and without pages, T and FP8: up to seqlen * (H / Hkv) = 128 query rows per
+KV head the attention is the split-KV pair above; a longer chunk -- a prompt -- goes to the one-pass prefill kernel under the same device
+lengths (`attn_prefill_kvcache[_kv8]`, `attn_prefill_paged[_kv8]`, csrc/awq_attn_prefill_cdna4.hip).  A server prefills into the pool
+with one `forward` per chunk; a chunked prefill is one captured graph, replayed while `start_pos += chunk` runs on the device.
 """
 from __future__ import annotations
 
@@ -105,7 +110,8 @@ class QuantLlamaAttentionFused(nn.Module):
         """`mask` is accepted and ignored, as in the reference's short_forward: the attention is causal.
 
         With `kv_layout="natural"`, `start_pos` may be an int32 tensor [bsz] on the GPU: the tokens already in each sequence's cache, read
-        by the kernels only (a ragged batch in one call; a captured graph replays any position).  `freqs` is then the model's whole angle
+        by the kernels only (a ragged batch in one call; a captured graph replays any position; any seqlen -- a chunk with
+        seqlen * (H / Hkv) > 128 takes the one-pass prefill kernel, a shorter one the split-KV pair).  `freqs` is then the model's whole angle
         table [P, rot_dim] and `decode_max_seqlen` (default `kv_max_seq_len`) the host bound on start_pos + seqlen that sizes the attention
         launch.  A sequence with start_pos[b] < 0 is a finished slot: nothing is stored for it and its attention rows are zeros.
 
@@ -174,7 +180,9 @@ class QuantLlamaAttentionFused(nn.Module):
 
     def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None):
         """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host.  With a
-        block table: rope_kv_store_paged_pos[_fp8] followed by attn_kvcache_paged[_kv8] on the caches viewed as pages."""
+        block table: rope_kv_store_paged_pos[_fp8] followed by attn_kvcache_paged[_kv8] on the caches viewed as pages.  A chunk with
+        seqlen * num_key_value_groups > 128 is beyond the split pair: attn_prefill_kvcache[_kv8] / attn_prefill_paged[_kv8] take its place
+        with the same arguments (the one-pass prefill kernel under the same lengths)."""
         if self.kv_layout != "natural":
             raise ValueError("QuantLlamaAttentionFused: a tensor start_pos needs kv_layout 'natural' (the FT-layout path takes start_pos as "
                              "an int; its decode kernel reads per-sequence lengths through single_query_attention's length_per_sample)")
@@ -182,6 +190,7 @@ class QuantLlamaAttentionFused(nn.Module):
         bound = self.kv_max_seq_len if decode_max_seqlen is None else int(decode_max_seqlen)
         xqkv = self.qkv_proj(x).reshape(bsz, seqlen, -1)
         scale = self.head_dim ** -0.5
+        prompt = seqlen * self.num_key_value_groups > 128  # more query rows per KV head than the split pair serves
         if self.kv_dtype == "fp8":
             if self.cache_k.device != xqkv.device:
                 for name in ("cache_k", "cache_v", "cache_k_scale", "cache_v_scale"):
@@ -197,20 +206,23 @@ class QuantLlamaAttentionFused(nn.Module):
             if self.kv_dtype == "fp8":
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool), self.cache_k_scale.view(pool[:3]), self.cache_v_scale.view(pool[:3]))
                 xq = eng.rope_kv_store_paged_pos_fp8(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
-                output = eng.attn_kvcache_paged_kv8(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+                attn = eng.attn_prefill_paged_kv8 if prompt else eng.attn_kvcache_paged_kv8
+                output = attn(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
             else:
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool))
                 xq = eng.rope_kv_store_paged_pos(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
-                output = eng.attn_kvcache_paged(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+                attn = eng.attn_prefill_paged if prompt else eng.attn_kvcache_paged
+                output = attn(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if self.kv_dtype == "fp8":
             xq = eng.rope_kv_store_natural_pos_fp8(xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos,
                                                    self.n_local_heads, self.num_key_value_heads)
-            output = eng.attn_kvcache_kv8(xq, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos, bound, seqlen,
-                                          scale, True)
+            attn = eng.attn_prefill_kvcache_kv8 if prompt else eng.attn_kvcache_kv8
+            output = attn(xq, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos, bound, seqlen, scale, True)
         else:
             xq = eng.rope_kv_store_natural_pos(xqkv, freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads, self.num_key_value_heads)
-            output = eng.attn_kvcache(xq, self.cache_k, self.cache_v, start_pos, bound, seqlen, scale, True)
+            attn = eng.attn_prefill_kvcache if prompt else eng.attn_kvcache
+            output = attn(xq, self.cache_k, self.cache_v, start_pos, bound, seqlen, scale, True)
         return self.o_proj(output.view(bsz, seqlen, -1))
 
 

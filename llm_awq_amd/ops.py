@@ -721,21 +721,28 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
     return q_out
 
 
-def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal):
-    """The four device-length attention entries of the C ABI over a described cache (q and kv checked by the caller)."""
+def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False):
+    """The device-length attention entries of the C ABI over a described cache (q and kv checked by the caller): the four of the split
+    pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace)."""
     B, Sq, H, Dh = q.shape
     _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
     scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
     L = _capi.lib()
-    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, kv.Hkv, Dh, Sq, int(max_seqlen_k))
     out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
     lens = (B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k))
     where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
+    head = (q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), q.stride(1), *kv.strides(), scale, int(bool(causal)),
+            _dt(q))
+    if one_pass:
+        entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_kv8" if kv.fp8 else ""))
+        with torch.cuda.device(q.device):
+            _capi.check(entry(*head, _stream(q)))
+        return out
+    wsb = L.awq_attn_kvcache_workspace_bytes(B, H, kv.Hkv, Dh, Sq, int(max_seqlen_k))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
     entry = getattr(L, "awq_attn_kvcache" + ("_paged" if kv.paged else "") + ("_kv8" if kv.fp8 else ""))
     with torch.cuda.device(q.device):
-        _capi.check(entry(q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), q.stride(1), *kv.strides(), scale,
-                          int(bool(causal)), _dt(q), ws.data_ptr(), wsb, _stream(q)))
+        _capi.check(entry(*head, ws.data_ptr(), wsb, _stream(q)))
     return out
 
 
@@ -839,7 +846,11 @@ def attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offse
     zeros.  Causal rows attend keys j <= i + Sk_b - Sq.  Sq * (H / Hkv) <= 128, Dh 64 or 128.  With k_scale / v_scale [Bc, Lmax, Hkv]
     float32 the caches are FP8 codes (kv8_quant's format).  The host never reads seqlens_k: the call is capturable and a replay follows the
     lengths the tensor holds then."""
-    who = "attn_kvcache"
+    return _attn_dense("attn_kvcache", False, q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale, v_scale)
+
+
+def _attn_dense(who, one_pass, q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale, v_scale):
+    """attn_kvcache / attn_prefill_kvcache: the tensor checks of the dense caches, then the entry."""
     fp8 = k_scale is not None or v_scale is not None
     if fp8:
         if k_scale is None or v_scale is None:
@@ -856,7 +867,19 @@ def attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offse
             raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
         if k_cache.shape != v_cache.shape or k_cache.shape[0] < q.shape[0] or k_cache.shape[3] != q.shape[3]:
             raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_cache / v_cache [Bc >= B, Lmax, Hkv, Dh] are expected")
-    return _attn_kvcache(who, q, _Kv(k_cache, v_cache, k_scale, v_scale), seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal)
+    return _attn_kvcache(who, q, _Kv(k_cache, v_cache, k_scale, v_scale), seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass)
+
+
+def attn_prefill_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None, causal: bool = True,
+                         k_scale=None, v_scale=None):
+    """C-ABI awq_attn_prefill_kvcache[_kv8]: `attn_kvcache`'s arguments and lengths served by the ONE-PASS prefill kernel, for a prompt
+    chunk of any length: q [B, Sq, H, Dh] with Sq >= 1 of any size, Dh 64 or 128, no workspace.  Sk_b = seqlens_k[b] + seqlen_offset; a
+    sequence with Sk_b < 1 or Sk_b > max_seqlen_k returns zeros and none of its cache rows is read; a row whose causal limit
+    i + Sk_b - Sq is negative returns zeros.  For every active sequence with Sk_b >= Sq the result is bit-identical to `flash_attn_func`
+    (`attn_prefill_kv8`) on (q[b:b+1], cache[b:b+1, :Sk_b]) under the same q tile.  Capturable: a replay follows the lengths the tensor
+    holds then."""
+    return _attn_dense("attn_prefill_kvcache", True, q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale,
+                       v_scale)
 
 
 def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
@@ -913,14 +936,29 @@ def attn_kvcache_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: 
     `attn_kvcache` on the dense gather of its pages.  Entries behind a sequence's live range are never read; a page id is clamped into the
     pool.  With k_scale / v_scale [num_pages, page_size, Hkv] float32 the pools are FP8 codes.  The host reads neither the table nor the
     lengths: capturable, and a replay follows what the tensors hold then."""
-    who = "attn_kvcache_paged"
+    return _attn_paged("attn_kvcache_paged", False, q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal,
+                       k_scale, v_scale)
+
+
+def _attn_paged(who, one_pass, q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale, v_scale):
+    """attn_kvcache_paged / attn_prefill_paged: the tensor checks of the pools and the table, then the entry."""
     _on_gpu(q)
     if q.dim() != 4 or q.stride(3) != 1 or q.stride(2) != q.shape[3]:
         raise ValueError(f"{who}: q must be [B, Sq, H, Dh] with contiguous heads")
     kv = _check_pools(who, q, k_pool, v_pool, block_table, k_scale, v_scale, q.shape[0])
     if kv.Dh != q.shape[3]:
         raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_pool / v_pool [num_pages, page_size, Hkv, Dh] must share Dh, got {q.shape[3]} and {kv.Dh}")
-    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal)
+    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass)
+
+
+def attn_prefill_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None,
+                       causal: bool = True, k_scale=None, v_scale=None):
+    """C-ABI awq_attn_prefill_paged[_kv8]: `attn_prefill_kvcache` over a paged KV cache (`attn_kvcache_paged`'s pools, table and bound): a
+    prompt chunk of any length attends the pages its sequence holds.  For every active sequence the result is bit-identical to
+    `attn_prefill_kvcache` on the dense gather of its pages.  Entries behind a sequence's live range are never read; a page id is clamped
+    into the pool."""
+    return _attn_paged("attn_prefill_paged", True, q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal,
+                       k_scale, v_scale)
 
 
 def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
