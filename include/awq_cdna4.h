@@ -255,6 +255,28 @@ int awq_w4a16_moe_mlp_gate_up_cdna4_szh(const void* x_sorted, const void* qweigh
                                         size_t scratch_bytes, int total_tokens, int num_experts, int n2, int k, int gpad, int group_size, int dtype,
                                         void* stream);
 
+/* ---- MoE routing on the device: what surrounds the grouped launches above in a Mixtral-style block (new capability: the reference has no MoE
+ * path).  One launch each, no workspace, no atomics, no host read; every size that shapes a grid is an argument.  Limits (AWQ_ERR_SHAPE
+ * otherwise, before anything is launched): 1 <= num_experts <= 64, 1 <= top_k <= min(num_experts, 8), tokens >= 1, tokens * top_k <= 2^20.
+ * Pointers: AWQ_ERR_NULL / AWQ_ERR_ALIGN (activations 16 bytes, int32 / fp32 arrays 4 bytes, logits their element size). ---- */
+#define AWQ_F32 2 /* router logits only */
+/* router_logits [tokens, num_experts] (logits_dtype AWQ_F16 / AWQ_BF16 / AWQ_F32; AWQ_ERR_DTYPE otherwise), contiguous ->
+ *   topk_ids int32 [tokens, top_k]  the top_k largest logits of the row in descending order; among equal logits the lower index wins (compared
+ *                                   through the monotone float -> unsigned key, a total order whatever the bits)
+ *   topk_w   fp32  [tokens, top_k]  exp(l_j - l_0) / sum_{i < top_k} exp(l_i - l_0) (renormalize != 0: softmax -> topk -> w / w.sum()), or
+ *                                   exp(l_j - l_0) / sum_{e < num_experts} exp(l_e - l_0) (renormalize == 0: plain softmax weights)
+ *   order    int32 [tokens top_k]   the flat slots s = t top_k + j sorted by expert, stable;  inv [tokens top_k]: inv[order[r]] = r
+ *   offsets  int32 [num_experts+1]  first sorted row of every expert, offsets[num_experts] = tokens top_k (the grouped launches' expert_offsets)
+ * A row that holds a NaN, or whose largest logit is infinite, has unspecified weights; its ids are still top_k distinct experts and the three index
+ * arrays a valid sort. */
+int awq_moe_route(const void* router_logits, int logits_dtype, int tokens, int num_experts, int top_k, int renormalize, void* topk_ids,
+                  void* topk_w, void* order, void* inv, void* offsets, void* stream);
+/* xs[r] = x[order[r] / top_k]: x T [tokens, hidden] -> xs T [tokens top_k, hidden]; hidden % 8 == 0 (16-byte loads and stores) */
+int awq_moe_gather(const void* x, const void* order, void* xs, int tokens, int top_k, int hidden, int dtype, void* stream);
+/* out[t] = T( sum_j f32( T( f32(ys[inv[t top_k + j]]) * f32(T(topk_w[t, j])) ) ) ): the sum in fp32, j ascending from +0, one final rounding; writes
+ * every element of out T [tokens, hidden] (no zero-fill, no scatter).  ys T [tokens top_k, hidden], hidden % 8 == 0. */
+int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, void* stream);
+
 /* ---- W3A16 ("w3c" tiles): BASELINE.json's INT3 configuration.  The reference has NO packed 3-bit format
  * (awq/quantize/qmodule.py:82-83 raises for w_bit != 4; INT3 exists only as pseudo-quantisation,
  * awq/quantize/quantizer.py:61-103 with n_bit = 3), so the format is this repository's: per 16-row x 128-k tile

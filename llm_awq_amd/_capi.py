@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWQ_CDNA4_LIB") or os.path.join(_HERE, "lib", "libawq_cdna4.so")
 
 AWQ_F16, AWQ_BF16 = 0, 1
+AWQ_F32 = 2  # router logits of awq_moe_route only
 AWQ_ERR_WORKSPACE = -7  # include/awq_cdna4.h
 _lib = None
 
@@ -59,6 +60,9 @@ SIGNATURES = {
     "awq_silu_mul": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     "awq_w4a16_moe_mlp_gate_up_cdna4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "awq_w4a16_moe_mlp_gate_up_cdna4_szh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "awq_moe_route": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "awq_moe_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "awq_moe_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_pack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_unpack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_dequant_w3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1083,6 +1083,46 @@ int awq_w4a16_moe_mlp_gate_up_cdna4_szh(const void* x_sorted, const void* qweigh
   return finish_launch();
 }
 
+// ---- MoE routing on the device (awq_moe_route_cdna4.hip) ----
+static int check_moe_sizes(int tokens, int num_experts, int top_k) {
+  if (num_experts < 1 || num_experts > 64 || top_k < 1 || top_k > 8 || top_k > num_experts || tokens < 1 || (long long)tokens * top_k > (1ll << 20))
+    return AWQ_ERR_SHAPE;
+  return AWQ_OK;
+}
+static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int awq_moe_route(const void* router_logits, int logits_dtype, int tokens, int num_experts, int top_k, int renormalize, void* topk_ids,
+                  void* topk_w, void* order, void* inv, void* offsets, void* stream) {
+  if (!router_logits || !topk_ids || !topk_w || !order || !inv || !offsets) return AWQ_ERR_NULL;
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (check_moe_sizes(tokens, num_experts, top_k)) return AWQ_ERR_SHAPE;
+  if (!aligned_to(router_logits, logits_dtype == AWQ_F32 ? 4 : 2) || !aligned_to(topk_ids, 4) || !aligned_to(topk_w, 4) || !aligned_to(order, 4) ||
+      !aligned_to(inv, 4) || !aligned_to(offsets, 4))
+    return AWQ_ERR_ALIGN;
+  if (awq::launch_moe_route(router_logits, logits_dtype, tokens, num_experts, top_k, renormalize, topk_ids, topk_w, order, inv, offsets,
+                            (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_moe_gather(const void* x, const void* order, void* xs, int tokens, int top_k, int hidden, int dtype, void* stream) {
+  if (!x || !order || !xs) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (check_moe_sizes(tokens, 64, top_k) || hidden < 8 || (hidden % 8) != 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(xs) || !aligned_to(order, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_moe_gather(x, order, xs, tokens, top_k, hidden, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, void* stream) {
+  if (!ys || !inv || !topk_w || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (check_moe_sizes(tokens, 64, top_k) || hidden < 8 || (hidden % 8) != 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(ys) || !aligned16(out) || !aligned_to(inv, 4) || !aligned_to(topk_w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_moe_combine(ys, inv, topk_w, out, tokens, top_k, hidden, dtype, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- W3 ("w3c") : the repository's 3-bit format (bf16 only; no reference counterpart) ----
 static int check_w3_shape(int n, int k) { return (n < 16 || (n % 16) != 0 || k < 128 || (k % 128) != 0) ? AWQ_ERR_SHAPE : AWQ_OK; }
 

@@ -147,6 +147,12 @@ int launch_moe_gemm_cdna4_v6(const void* x, const void* qw, const void* szp, con
 int launch_silu_mul_interleaved(const void* in, void* out, int m, int n2, int dtype, hipStream_t st);
 int launch_silu_mul(const void* gate, const void* up, void* out, size_t count, int dtype, hipStream_t st);  // out = T(T(silu(gate)) * up), count % 8 == 0
 bool moe_v6_enabled();  // knob moe_v6 (default on)
+// MoE routing on the device (awq_moe_route_cdna4.hip); -1 if the sizes are outside the documented limits, pointers validated by the caller
+// logits [tokens, experts] (logits_dtype 0 fp16, 1 bf16, 2 fp32) -> topk_ids int32 / topk_w fp32 [tokens, top_k], order / inv int32 [tokens top_k], offsets int32 [experts + 1]
+int launch_moe_route(const void* logits, int logits_dtype, int tokens, int experts, int top_k, int renormalize, void* topk_ids, void* topk_w,
+                     void* order, void* inv, void* offsets, hipStream_t st);
+int launch_moe_gather(const void* x, const void* order, void* xs, int tokens, int top_k, int hidden, hipStream_t st);  // xs[r] = x[order[r] / top_k]
+int launch_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, hipStream_t st);
 // awq_gemm_v6.hip: 256 x 256 blocks of four software-pipelined waves (256 x 64 per wave, weights in registers, x through ds_write)
 void launch_gemm_cdna4_v6(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int n_begin,
                           int n_end, int dtype, hipStream_t st, int bits = 4, int epi = 0, int szfmt = 0, int tile_n = 256);

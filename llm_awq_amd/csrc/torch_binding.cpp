@@ -512,6 +512,49 @@ torch::Tensor moe_forward_cdna4(torch::Tensor x_sorted, torch::Tensor kernel, to
   return out;
 }
 
+// ---- MoE routing on the device: top-k gate + stable sort by expert, row gather, weighted combine (one launch each) ----
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> moe_route(torch::Tensor router_logits, int64_t top_k,
+                                                                                                bool renormalize) {
+  TORCH_CHECK(router_logits.is_cuda() && router_logits.is_contiguous() && router_logits.dim() == 2,
+              "awq_inference_engine: router_logits must be a contiguous [T, E] GPU tensor");
+  const auto st = router_logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "moe_route: float32 / bfloat16 / float16 logits");
+  const int code = st == at::kFloat ? AWQ_F32 : dtype_code(router_logits);
+  const int64_t t = router_logits.size(0), e = router_logits.size(1);
+  TORCH_CHECK(top_k >= 1 && top_k <= 8 && t >= 1 && t * top_k <= (1 << 20), "moe_route: 1 <= top_k <= 8, 1 <= T, T * top_k <= 2^20");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(router_logits.device());
+  const auto iopt = router_logits.options().dtype(at::kInt);
+  at::Tensor ids = torch::empty({t, top_k}, iopt), w = torch::empty({t, top_k}, router_logits.options().dtype(at::kFloat));
+  at::Tensor order = torch::empty({t * top_k}, iopt), inv = torch::empty({t * top_k}, iopt), offsets = torch::empty({e + 1}, iopt);
+  raise_on(awq_moe_route(router_logits.data_ptr(), code, (int)t, (int)e, (int)top_k, renormalize ? 1 : 0, ids.data_ptr(), w.data_ptr(), order.data_ptr(),
+                         inv.data_ptr(), offsets.data_ptr(), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {ids, w, order, inv, offsets};
+}
+
+torch::Tensor moe_gather(torch::Tensor x, torch::Tensor order, int64_t top_k) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 && order.is_cuda() && order.is_contiguous() && order.scalar_type() == at::kInt,
+              "awq_inference_engine: x must be a contiguous [T, H] GPU tensor and order int32 on the GPU");
+  TORCH_CHECK(top_k >= 1 && order.numel() == x.size(0) * top_k, "moe_gather: order must hold T * top_k slots");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor xs = torch::empty({order.numel(), x.size(1)}, x.options());
+  raise_on(awq_moe_gather(x.data_ptr(), order.data_ptr(), xs.data_ptr(), (int)x.size(0), (int)top_k, (int)x.size(1), dtype_code(x),
+                          (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return xs;
+}
+
+torch::Tensor moe_combine(torch::Tensor ys, torch::Tensor inv, torch::Tensor topk_w) {
+  TORCH_CHECK(ys.is_cuda() && ys.is_contiguous() && ys.dim() == 2 && inv.is_cuda() && inv.is_contiguous() && inv.scalar_type() == at::kInt &&
+                  topk_w.is_cuda() && topk_w.is_contiguous() && topk_w.dim() == 2 && topk_w.scalar_type() == at::kFloat,
+              "awq_inference_engine: ys [T * k, H], inv int32 [T * k] and topk_w float32 [T, k] must be contiguous GPU tensors");
+  const int64_t t = topk_w.size(0), k = topk_w.size(1);
+  TORCH_CHECK(inv.numel() == t * k && ys.size(0) == t * k, "moe_combine: ys / inv must hold T * k rows");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(ys.device());
+  at::Tensor out = torch::empty({t, ys.size(1)}, ys.options());
+  raise_on(awq_moe_combine(ys.data_ptr(), inv.data_ptr(), topk_w.data_ptr(), out.data_ptr(), (int)t, (int)k, (int)ys.size(1), dtype_code(ys),
+                           (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
 // ---- W3 ("w3c" tiles, bf16): pack from logical integers, and WQLinear.forward for w_bit = 3 ----
 torch::Tensor pack_w3(torch::Tensor q_u8) {
   TORCH_CHECK(q_u8.is_cuda() && q_u8.is_contiguous() && q_u8.scalar_type() == at::kByte && q_u8.dim() == 2);
@@ -1615,6 +1658,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemm_forward", &moe_gemm_forward, "grouped per-expert W4A16 GEMM (tokens sorted by expert)", py::arg("x_sorted"),
         py::arg("kernel"), py::arg("scales"), py::arg("zeros"), py::arg("expert_offsets"), py::arg("cdna4") = false);
   m.def("moe_forward_cdna4", &moe_forward_cdna4, "grouped per-expert forward on cdna4 buffers (GEMV for <= 8 rows, GEMM otherwise)");
+  m.def("moe_route", &moe_route, "router logits [T, E] -> (topk_ids, topk_w, order, inv, offsets): top-k gate + stable sort by expert, one launch",
+        py::arg("router_logits"), py::arg("top_k"), py::arg("renormalize") = true);
+  m.def("moe_gather", &moe_gather, "xs[r] = x[order[r] / top_k]", py::arg("x"), py::arg("order"), py::arg("top_k"));
+  m.def("moe_combine", &moe_combine, "out[t] = sum_j ys[inv[t k + j]] * w[t, j] (fp32 sum of T-rounded products, one final rounding)", py::arg("ys"),
+        py::arg("inv"), py::arg("topk_w"));
   m.def("pack_w3", &pack_w3, "logical uint8 [N, K] (0..7) -> w3c tiles int16 [N/4, 3K/4]");
   m.def("forward_w3", &forward_w3, "WQLinear forward for w_bit = 3 (w3c tiles)", py::arg("in_feats"), py::arg("kernel"),
         py::arg("scales"), py::arg("zeros"), py::arg("sz_packed"), py::arg("bias") = py::none());

@@ -3,9 +3,10 @@
 The reference has no MoE path, so this is new capability built from the same contract:
 every expert is a `WQLinear` whose buffers are stacked along a leading expert dimension
     qweight int16 [E, N/4, K]   scales / scaled_zeros T [E, Gpad, N]
-and one launch runs all experts over tokens sorted by expert (`awq_w4a16_moe_gemm`).  Routing (top-k, sort,
-un-sort, weighting) is ordinary torch glue around the path; it never synchronises the host: the per-expert row
-ranges go to the kernel as a device int32 [E + 1] offsets array.
+and one launch runs all experts over tokens sorted by expert (`awq_w4a16_moe_gemm`).  The per-expert row ranges go to
+the kernel as a device int32 [E + 1] offsets array.  Routing (top-k, sort, un-sort, weighting) around the path is either
+ordinary torch glue (`routing="torch"`, the default; its `torch.bincount` reads the bin count back to the host) or three HIP
+launches (`routing="device"`: `ops.moe_route` / `moe_gather` / `moe_combine`, no host read, capturable into a hipGraph).
 """
 from __future__ import annotations
 
@@ -150,16 +151,20 @@ class GroupedGateUp(_LayoutMarker, nn.Module):
 class SparseMoeMLP(nn.Module):
     """Mixtral-style block: y = sum_k p_k * w2_e( silu(w1_e x) * w3_e x ) over each token's top-k experts."""
 
-    def __init__(self, w1, w3, w2: GroupedWQLinear, top_k: int = 2, gate_up: Optional[GroupedGateUp] = None):
+    def __init__(self, w1, w3, w2: GroupedWQLinear, top_k: int = 2, gate_up: Optional[GroupedGateUp] = None, routing: str = "torch"):
         """w1 / w3: GroupedWQLinear modules (two grouped launches + the SiLU * mul tail as a third), or None with `gate_up` = a
-        GroupedGateUp built from the same experts (ONE grouped launch for h: `SparseMoeMLP.fused(w1_experts, w3_experts, w2, top_k)`)."""
+        GroupedGateUp built from the same experts (ONE grouped launch for h: `SparseMoeMLP.fused(w1_experts, w3_experts, w2, top_k)`).
+        routing: "torch" = the torch glue of `forward` (the default; `torch.bincount` reads back to the host, so it cannot be captured), "device" =
+        `ops.moe_route` -> `ops.moe_gather` -> the grouped launches -> `ops.moe_combine`: nothing but HIP launches, no host read, GPU tensors only."""
         super().__init__()
-        self.w1, self.w3, self.w2, self.top_k, self.gate_up = w1, w3, w2, top_k, gate_up
+        if routing not in ("torch", "device"):
+            raise ValueError(f"SparseMoeMLP: routing must be 'torch' or 'device', got {routing!r}")
+        self.w1, self.w3, self.w2, self.top_k, self.gate_up, self.routing = w1, w3, w2, top_k, gate_up, routing
         assert gate_up is not None or (w1 is not None and w3 is not None)
 
     @classmethod
-    def fused(cls, w1_experts: Sequence[WQLinear], w3_experts: Sequence[WQLinear], w2: GroupedWQLinear, top_k: int = 2):
-        return cls(None, None, w2, top_k, GroupedGateUp(w1_experts, w3_experts))
+    def fused(cls, w1_experts: Sequence[WQLinear], w3_experts: Sequence[WQLinear], w2: GroupedWQLinear, top_k: int = 2, routing: str = "torch"):
+        return cls(None, None, w2, top_k, GroupedGateUp(w1_experts, w3_experts), routing)
 
     def _h(self, xs, offsets):
         if self.gate_up is not None:
@@ -174,6 +179,11 @@ class SparseMoeMLP(nn.Module):
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, router_logits: torch.Tensor) -> torch.Tensor:
+        if self.routing == "device":
+            from . import ops
+            _ids, w, order, inv, offsets = ops.moe_route(router_logits.contiguous(), self.top_k, renormalize=True)
+            xs = ops.moe_gather(x.contiguous(), order, self.top_k)
+            return ops.moe_combine(self.w2(self._h(xs, offsets), offsets), inv, w)
         T = x.shape[0]
         probs = torch.softmax(router_logits.float(), dim=-1)
         w, ids = torch.topk(probs, self.top_k, dim=-1)

@@ -482,6 +482,61 @@ def silu_mul(gate, up):
     return out
 
 
+# ---- MoE routing on the device (awq_moe_route_cdna4.hip): one launch each, nothing read back to the host ----
+
+def moe_route(router_logits, top_k: int, renormalize: bool = True):
+    """C-ABI awq_moe_route.  router_logits [T, E] (fp32 / bf16 / fp16) -> (topk_ids int32 [T, k], topk_w fp32 [T, k], order int32 [T k],
+    inv int32 [T k], offsets int32 [E + 1]): the k largest logits of a row in descending order (ties: the lower index), their softmax weights
+    (renormalize: over the k picked, Mixtral; else over all E), and the stable sort of the flat slots t k + j by expert -- `order` is
+    moe.sort_by_expert's, `inv` its inverse, `offsets` the grouped launches' expert_offsets."""
+    _need_gpu(router_logits)
+    if router_logits.dim() != 2:
+        raise ValueError("moe_route: router_logits must be [T, E]")
+    code = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}.get(router_logits.dtype)
+    if code is None:
+        raise TypeError(f"moe_route: expected float32/bfloat16/float16 logits, got {router_logits.dtype}")
+    t, e = router_logits.shape
+    k, dev = int(top_k), router_logits.device
+    if k < 1:
+        raise ValueError("moe_route: top_k must be at least 1")
+    ids = torch.empty(t, k, dtype=torch.int32, device=dev)
+    w = torch.empty(t, k, dtype=torch.float32, device=dev)
+    order = torch.empty(t * k, dtype=torch.int32, device=dev)
+    inv = torch.empty_like(order)
+    offsets = torch.empty(e + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().awq_moe_route(router_logits.data_ptr(), code, t, e, k, 1 if renormalize else 0, ids.data_ptr(), w.data_ptr(),
+                                              order.data_ptr(), inv.data_ptr(), offsets.data_ptr(), _stream(router_logits)))
+    return ids, w, order, inv, offsets
+
+
+def moe_gather(x, order, top_k: int):
+    """C-ABI awq_moe_gather: xs[r] = x[order[r] // top_k]; x [T, H] bf16 / fp16 with H % 8 == 0, order int32 [T top_k] -> xs [T top_k, H]."""
+    _need_gpu(x, order)
+    if x.dim() != 2 or order.dtype != torch.int32 or order.numel() != x.shape[0] * int(top_k):
+        raise ValueError("moe_gather: x must be [T, H] and order int32 [T * top_k]")
+    t, h = x.shape
+    xs = torch.empty(order.numel(), h, dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_moe_gather(x.data_ptr(), order.data_ptr(), xs.data_ptr(), t, int(top_k), h, _dt(x), _stream(x)))
+    return xs
+
+
+def moe_combine(ys, inv, topk_w):
+    """C-ABI awq_moe_combine: out[t] = T(sum_j f32(T(f32(ys[inv[t k + j]]) * f32(T(topk_w[t, j]))))), summed in fp32 with j ascending, rounded
+    once; ys [T k, H] bf16 / fp16 with H % 8 == 0, inv int32 [T k], topk_w fp32 [T, k] -> out [T, H] (every element written)."""
+    _need_gpu(ys, inv, topk_w)
+    if ys.dim() != 2 or topk_w.dim() != 2 or topk_w.dtype != torch.float32 or inv.dtype != torch.int32 or \
+            inv.numel() != topk_w.numel() or ys.shape[0] != topk_w.numel():
+        raise ValueError("moe_combine: ys must be [T * k, H], inv int32 [T * k] and topk_w float32 [T, k]")
+    t, k = topk_w.shape
+    h = ys.shape[1]
+    out = torch.empty(t, h, dtype=ys.dtype, device=ys.device)
+    with torch.cuda.device(ys.device):
+        _capi.check(_capi.lib().awq_moe_combine(ys.data_ptr(), inv.data_ptr(), topk_w.data_ptr(), out.data_ptr(), t, k, h, _dt(ys), _stream(ys)))
+    return out
+
+
 def pair_lost_count(device=None) -> int:
     """C-ABI awq_w4a16_gemm_cdna4_pair_lost: blocks of the block-pair K split (down_proj-shaped prefill launches) of `device` that gave up waiting
     for their partner since the library was loaded -- their outputs are NaN.  0 on a healthy run; synchronises with the device.  A serving loop
