@@ -277,6 +277,25 @@ int awq_moe_gather(const void* x, const void* order, void* xs, int tokens, int t
  * every element of out T [tokens, hidden] (no zero-fill, no scatter).  ys T [tokens top_k, hidden], hidden % 8 == 0. */
 int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, void* stream);
 
+/* ---- Next-token sampling on the device: what tinychat/stream_generators/stream_gen.py:19-32,120-134 does between two decode steps
+ * (temperature -> repetition penalty -> top-p -> top-k -> softmax -> multinomial -> int()), as ONE launch without a host read.  logits
+ * [batch, vocab] (AWQ_F16 / AWQ_BF16 / AWQ_F32, contiguous, aligned to its element) -> tokens int32 [batch].  Every parameter is a per-row device array
+ * and may be NULL, which switches that step off: u fp32 [batch] in [0, 1) (required), temperature / top_p / repetition_penalty fp32 [batch],
+ * top_k int32 [batch] (<= 0 or >= vocab: off), history int32 [batch, max_history] with hist_len int32 [batch] (both or neither), seqlens int32
+ * [batch] (a negative entry = an inactive slot: tokens[b] = -1 and nothing else is read or written for the row), stop_ids int32 [num_stop],
+ * finished int32 [batch].  DESIGN.md "Sampling" states the result by values (fp32 arithmetic, IEEE division by the temperature, whole tie groups
+ * kept, fixed-point masses so that the launch is bit-stable from run to run).  flags: AWQ_SAMPLE_APPEND writes the token to
+ * history[b, hist_len[b]] (if it fits) and adds one to hist_len[b]; AWQ_SAMPLE_ADVANCE sets seqlens[b] to -1 if the token is a stop id or
+ * seqlens[b] + 1 >= max_len, else to seqlens[b] + 1; a token in stop_ids sets finished[b] = 1 whenever both arrays are given.  A row that holds a
+ * NaN or +inf returns an unspecified token in [0, vocab) and does not disturb the other rows; history ids outside [0, vocab) are ignored.
+ * Limits: 1 <= vocab <= 2^20, batch >= 1 (AWQ_ERR_SHAPE), checked with the pointers (AWQ_ERR_NULL / AWQ_ERR_DTYPE / AWQ_ERR_ALIGN) before anything
+ * is launched.  No workspace, no global atomics; capturable. ---- */
+#define AWQ_SAMPLE_APPEND 1
+#define AWQ_SAMPLE_ADVANCE 2
+int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
+                      const void* top_p, const void* repetition_penalty, void* history, void* hist_len, int max_history, void* seqlens,
+                      const void* stop_ids, int num_stop, void* finished, int max_len, int flags, void* tokens, void* stream);
+
 /* ---- W3A16 ("w3c" tiles): BASELINE.json's INT3 configuration.  The reference has NO packed 3-bit format
  * (awq/quantize/qmodule.py:82-83 raises for w_bit != 4; INT3 exists only as pseudo-quantisation,
  * awq/quantize/quantizer.py:61-103 with n_bit = 3), so the format is this repository's: per 16-row x 128-k tile

@@ -1123,6 +1123,27 @@ int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* o
   return finish_launch();
 }
 
+// ---- next-token sampling on the device (awq_sample_cdna4.hip) ----
+int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
+                      const void* top_p, const void* repetition_penalty, void* history, void* hist_len, int max_history, void* seqlens,
+                      const void* stop_ids, int num_stop, void* finished, int max_len, int flags, void* tokens, void* stream) {
+  if (!logits || !u || !tokens) return AWQ_ERR_NULL;
+  if ((history != nullptr) != (hist_len != nullptr)) return AWQ_ERR_NULL;  // a history comes with its lengths
+  if ((flags & AWQ_SAMPLE_APPEND) && !history) return AWQ_ERR_NULL;
+  if ((flags & AWQ_SAMPLE_ADVANCE) && !seqlens) return AWQ_ERR_NULL;
+  if (num_stop > 0 && !stop_ids) return AWQ_ERR_NULL;
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (batch < 1 || vocab < 1 || vocab > (1 << 20) || (history && max_history < 1) || num_stop < 0 || (flags & ~3)) return AWQ_ERR_SHAPE;
+  if (!aligned_to(logits, logits_dtype == AWQ_F32 ? 4 : 2)) return AWQ_ERR_ALIGN;  // rows are walked from the 16-byte boundary below them
+  const void* words[] = {u, temperature, top_k, top_p, repetition_penalty, history, hist_len, seqlens, stop_ids, finished, tokens};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_sample_logits(logits, logits_dtype, batch, vocab, u, temperature, top_k, top_p, repetition_penalty, history, hist_len, max_history,
+                                seqlens, stop_ids, num_stop, finished, max_len, flags, tokens, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- W3 ("w3c") : the repository's 3-bit format (bf16 only; no reference counterpart) ----
 static int check_w3_shape(int n, int k) { return (n < 16 || (n % 16) != 0 || k < 128 || (k % 128) != 0) ? AWQ_ERR_SHAPE : AWQ_OK; }
 

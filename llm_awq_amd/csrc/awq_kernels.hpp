@@ -153,6 +153,11 @@ int launch_moe_route(const void* logits, int logits_dtype, int tokens, int exper
                      void* order, void* inv, void* offsets, hipStream_t st);
 int launch_moe_gather(const void* x, const void* order, void* xs, int tokens, int top_k, int hidden, hipStream_t st);  // xs[r] = x[order[r] / top_k]
 int launch_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, hipStream_t st);
+// next-token sampling on the device (awq_sample_cdna4.hip): one block per row of logits [batch, vocab]; -1 if the sizes are outside the documented
+// limits, pointers validated by the caller (every pointer but logits / u / tokens may be null = that step is off); flags: 1 append, 2 advance
+int launch_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
+                         const void* top_p, const void* penalty, void* history, void* hist_len, int max_history, void* seqlens, const void* stop_ids,
+                         int num_stop, void* finished, int max_len, int flags, void* tokens, hipStream_t st);
 // awq_gemm_v6.hip: 256 x 256 blocks of four software-pipelined waves (256 x 64 per wave, weights in registers, x through ds_write)
 void launch_gemm_cdna4_v6(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int n_begin,
                           int n_end, int dtype, hipStream_t st, int bits = 4, int epi = 0, int szfmt = 0, int tile_n = 256);

@@ -555,6 +555,53 @@ torch::Tensor moe_combine(torch::Tensor ys, torch::Tensor inv, torch::Tensor top
   return out;
 }
 
+// ---- next-token sampling on the device: logits [B, V] -> tokens int32 [B], one launch, every parameter an optional per-row GPU tensor ----
+torch::Tensor sample_logits(torch::Tensor logits, torch::Tensor u, c10::optional<torch::Tensor> temperature, c10::optional<torch::Tensor> top_k,
+                            c10::optional<torch::Tensor> top_p, c10::optional<torch::Tensor> repetition_penalty,
+                            c10::optional<torch::Tensor> history, c10::optional<torch::Tensor> hist_len, c10::optional<torch::Tensor> seqlens,
+                            c10::optional<torch::Tensor> stop_ids, c10::optional<torch::Tensor> finished, int64_t max_len, bool append, bool advance) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "awq_inference_engine: logits must be a contiguous [B, V] GPU tensor");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "sample_logits: float32 / bfloat16 / float16 logits");
+  const int code = st == at::kFloat ? AWQ_F32 : dtype_code(logits);
+  const int64_t b = logits.size(0), v = logits.size(1);
+  auto row = [&](const c10::optional<torch::Tensor>& t, at::ScalarType want, const char* name) -> void* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == want && t->numel() == b && t->device() == logits.device(),
+                "sample_logits: ", name, " must be a contiguous [B] GPU tensor of its dtype");
+    return t->data_ptr();
+  };
+  TORCH_CHECK(u.is_cuda() && u.is_contiguous() && u.scalar_type() == at::kFloat && u.numel() == b, "sample_logits: u must be float32 [B] on the GPU");
+  TORCH_CHECK(history.has_value() == hist_len.has_value(), "sample_logits: history and hist_len come together");
+  void* hist = nullptr;
+  int64_t lh = 0;
+  if (history.has_value()) {
+    TORCH_CHECK(history->is_cuda() && history->is_contiguous() && history->scalar_type() == at::kInt && history->dim() == 2 &&
+                    history->size(0) == b && history->size(1) >= 1,
+                "sample_logits: history must be a contiguous int32 [B, Lh] GPU tensor");
+    hist = history->data_ptr();
+    lh = history->size(1);
+  }
+  void* stops = nullptr;
+  int64_t ns = 0;
+  if (stop_ids.has_value()) {
+    TORCH_CHECK(stop_ids->is_cuda() && stop_ids->is_contiguous() && stop_ids->scalar_type() == at::kInt && stop_ids->dim() == 1,
+                "sample_logits: stop_ids must be a contiguous int32 [S] GPU tensor");
+    stops = stop_ids->data_ptr();
+    ns = stop_ids->numel();
+  }
+  TORCH_CHECK(!append || hist, "sample_logits: append needs history and hist_len");
+  TORCH_CHECK(!advance || seqlens.has_value(), "sample_logits: advance needs seqlens");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  at::Tensor tokens = torch::empty({b}, logits.options().dtype(at::kInt));
+  raise_on(awq_sample_logits(logits.data_ptr(), code, (int)b, (int)v, u.data_ptr(), row(temperature, at::kFloat, "temperature"),
+                             row(top_k, at::kInt, "top_k"), row(top_p, at::kFloat, "top_p"), row(repetition_penalty, at::kFloat, "repetition_penalty"),
+                             hist, row(hist_len, at::kInt, "hist_len"), (int)lh, row(seqlens, at::kInt, "seqlens"), stops, (int)ns,
+                             row(finished, at::kInt, "finished"), (int)max_len, (append ? AWQ_SAMPLE_APPEND : 0) | (advance ? AWQ_SAMPLE_ADVANCE : 0),
+                             tokens.data_ptr(), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return tokens;
+}
+
 // ---- W3 ("w3c" tiles, bf16): pack from logical integers, and WQLinear.forward for w_bit = 3 ----
 torch::Tensor pack_w3(torch::Tensor q_u8) {
   TORCH_CHECK(q_u8.is_cuda() && q_u8.is_contiguous() && q_u8.scalar_type() == at::kByte && q_u8.dim() == 2);
@@ -1663,6 +1710,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gather", &moe_gather, "xs[r] = x[order[r] / top_k]", py::arg("x"), py::arg("order"), py::arg("top_k"));
   m.def("moe_combine", &moe_combine, "out[t] = sum_j ys[inv[t k + j]] * w[t, j] (fp32 sum of T-rounded products, one final rounding)", py::arg("ys"),
         py::arg("inv"), py::arg("topk_w"));
+  m.def("sample_logits", &sample_logits, "logits [B, V], u [B] -> next tokens int32 [B]: temperature, repetition penalty, top-p, top-k and the draw, one launch",
+        py::arg("logits"), py::arg("u"), py::kw_only(), py::arg("temperature") = py::none(), py::arg("top_k") = py::none(),
+        py::arg("top_p") = py::none(), py::arg("repetition_penalty") = py::none(), py::arg("history") = py::none(),
+        py::arg("hist_len") = py::none(), py::arg("seqlens") = py::none(), py::arg("stop_ids") = py::none(), py::arg("finished") = py::none(),
+        py::arg("max_len") = 0, py::arg("append") = false, py::arg("advance") = false);
   m.def("pack_w3", &pack_w3, "logical uint8 [N, K] (0..7) -> w3c tiles int16 [N/4, 3K/4]");
   m.def("forward_w3", &forward_w3, "WQLinear forward for w_bit = 3 (w3c tiles)", py::arg("in_feats"), py::arg("kernel"),
         py::arg("scales"), py::arg("zeros"), py::arg("sz_packed"), py::arg("bias") = py::none());

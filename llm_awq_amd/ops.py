@@ -537,6 +537,53 @@ def moe_combine(ys, inv, topk_w):
     return out
 
 
+# ---- next-token sampling on the device (awq_sample_cdna4.hip): one launch, nothing read back to the host ----
+
+def sample_logits(logits, u, *, temperature=None, top_k=None, top_p=None, repetition_penalty=None, history=None, hist_len=None, seqlens=None,
+                  stop_ids=None, finished=None, max_len=0, append=False, advance=False):
+    """C-ABI awq_sample_logits.  logits [B, V] (fp32 / bf16 / fp16) and u fp32 [B] in [0, 1) -> tokens int32 [B]: temperature -> repetition penalty
+    -> top-p -> top-k -> the first kept token whose running mass passes u times the kept mass (DESIGN.md "Sampling").  Every other argument is a
+    per-row GPU tensor or None (= that step is off): temperature / top_p / repetition_penalty fp32 [B], top_k int32 [B], history int32 [B, Lh] with
+    hist_len int32 [B], seqlens int32 [B] (negative = inactive slot, token -1), stop_ids int32 [S], finished int32 [B].  append / advance: the
+    launch also writes the token into the history and moves seqlens on (-1 after a stop id or at max_len)."""
+    params = (u, temperature, top_k, top_p, repetition_penalty, history, hist_len, seqlens, stop_ids, finished)
+    _need_gpu(logits, *params)
+    if logits.dim() != 2:
+        raise ValueError("sample_logits: logits must be [B, V]")
+    code = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}.get(logits.dtype)
+    if code is None:
+        raise TypeError(f"sample_logits: expected float32/bfloat16/float16 logits, got {logits.dtype}")
+    b, v = logits.shape
+    for name, t, dt in (("u", u, torch.float32), ("temperature", temperature, torch.float32), ("top_p", top_p, torch.float32),
+                        ("repetition_penalty", repetition_penalty, torch.float32), ("top_k", top_k, torch.int32),
+                        ("hist_len", hist_len, torch.int32), ("seqlens", seqlens, torch.int32), ("finished", finished, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != b or t.device != logits.device):
+            raise ValueError(f"sample_logits: {name} must be {dt} [B] on the logits' device")
+    if u is None:
+        raise ValueError("sample_logits: u is required")
+    if (history is None) != (hist_len is None):
+        raise ValueError("sample_logits: history and hist_len come together")
+    if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != b or history.shape[1] < 1 or
+                                history.device != logits.device):
+        raise ValueError("sample_logits: history must be int32 [B, Lh] with Lh >= 1 on the logits' device")
+    if stop_ids is not None and (stop_ids.dtype != torch.int32 or stop_ids.dim() != 1 or stop_ids.device != logits.device):
+        raise ValueError("sample_logits: stop_ids must be int32 [S] on the logits' device")
+    if append and history is None:
+        raise ValueError("sample_logits: append needs history and hist_len")
+    if advance and seqlens is None:
+        raise ValueError("sample_logits: advance needs seqlens")
+    tokens = torch.empty(b, dtype=torch.int32, device=logits.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    flags = (_capi.AWQ_SAMPLE_APPEND if append else 0) | (_capi.AWQ_SAMPLE_ADVANCE if advance else 0)
+    with torch.cuda.device(logits.device):
+        _capi.check(_capi.lib().awq_sample_logits(logits.data_ptr(), code, b, v, u.data_ptr(), ptr(temperature), ptr(top_k), ptr(top_p),
+                                                  ptr(repetition_penalty), ptr(history), ptr(hist_len),
+                                                  0 if history is None else history.shape[1], ptr(seqlens), ptr(stop_ids),
+                                                  0 if stop_ids is None else stop_ids.numel(), ptr(finished), int(max_len), flags,
+                                                  tokens.data_ptr(), _stream(logits)))
+    return tokens
+
+
 def pair_lost_count(device=None) -> int:
     """C-ABI awq_w4a16_gemm_cdna4_pair_lost: blocks of the block-pair K split (down_proj-shaped prefill launches) of `device` that gave up waiting
     for their partner since the library was loaded -- their outputs are NaN.  0 on a healthy run; synchronises with the device.  A serving loop
