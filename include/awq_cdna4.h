@@ -296,6 +296,26 @@ int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab
                       const void* top_p, const void* repetition_penalty, void* history, void* hist_len, int max_history, void* seqlens,
                       const void* stop_ids, int num_stop, void* finished, int max_len, int flags, void* tokens, void* stream);
 
+/* ---- LM head for decode: the reference's `self.norm` + `lm_head` (tinychat/models/llama.py:395,412: an RMSNorm and an unquantised
+ * nn.Linear(hidden, vocab)) as ONE launch that reads the weight matrix once whatever m is.  DESIGN.md "LM head" states the result by values:
+ *   x       T [m, k], row stride ldx elements (ldx % 8 == 0, ldx >= k): a prompt's last rows are selected by ldx, nothing is copied
+ *   gamma   T [k] or NULL: xn = T((f32(x) * rsqrtf(sum x^2 / k + eps)) * f32(gamma)), awq_rmsnorm's arithmetic bit for bit; NULL: xn = x
+ *   weight  T [v, k] row-major contiguous (nn.Linear.weight as it is loaded, no repack); bias T [v] or NULL, added in fp32 after the k sum
+ *   seqlens int32 [m] or NULL: a row with seqlens[b] < 0 is inactive -- out[b, :] is left untouched and whatever x[b, :] holds changes no other
+ *           row; if every row is inactive nothing is read
+ *   out     [m, v] contiguous, out_dtype AWQ_F32 (the fp32 sum: what awq_sample_logits should be fed) or dtype (rounded once, nearest-even)
+ * The fp32 sum is taken in an order that depends on k alone (not on m, gamma or max_blocks), so a row's logits do not depend on its batch.
+ * Limits: 1 <= m <= 64 (AWQ_ERR_BATCH), v >= 1, k >= 8 and k % 8 == 0, ldx as above (AWQ_ERR_SHAPE), out_dtype AWQ_F32 or dtype (AWQ_ERR_DTYPE),
+ * x / weight / out / gamma / bias 16-byte aligned, seqlens 4-byte aligned (AWQ_ERR_ALIGN); checked before anything is launched.  max_blocks: 0 =
+ * the plan's grid, otherwise a cap on it (tests).  No workspace, no atomics, bit-stable from run to run; capturable.
+ * awq_lm_head_plan (host only, no device call): out[4] = {blocks, vocabulary rows per tile, waves per block, k split}. ---- */
+int awq_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                int out_dtype, int m, int v, int k, int dtype, int max_blocks, void* stream);
+int awq_lm_head_plan(int m, int v, int k, int out[4]);
+/* out T [n, k] = table T [v, k] rows named by tokens int32 [n]; ZEROS for an id outside [0, v) (-1 = the sampler's finished slot), which never
+ * causes a read outside the table.  n >= 1, v >= 1, k >= 8, k % 8 == 0 (AWQ_ERR_SHAPE); table / out 16-byte, tokens 4-byte aligned. */
+int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, int dtype, void* stream);
+
 /* ---- W3A16 ("w3c" tiles): BASELINE.json's INT3 configuration.  The reference has NO packed 3-bit format
  * (awq/quantize/qmodule.py:82-83 raises for w_bit != 4; INT3 exists only as pseudo-quantisation,
  * awq/quantize/quantizer.py:61-103 with n_bit = 3), so the format is this repository's: per 16-row x 128-k tile

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWQ_CDNA4_LIB") or os.path.join(_HERE, "lib", "libawq_cdna4.so")
 
 AWQ_F16, AWQ_BF16 = 0, 1
-AWQ_F32 = 2  # router logits of awq_moe_route and logits of awq_sample_logits only
+AWQ_F32 = 2  # router logits of awq_moe_route, logits of awq_sample_logits and the fp32 output of awq_lm_head only
 AWQ_SAMPLE_APPEND, AWQ_SAMPLE_ADVANCE = 1, 2  # flags of awq_sample_logits
 AWQ_ERR_WORKSPACE = -7  # include/awq_cdna4.h
 _lib = None
@@ -65,6 +65,9 @@ SIGNATURES = {
     "awq_moe_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_moe_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_sample_logits": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "awq_lm_head": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "awq_lm_head_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "awq_embed_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_pack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_unpack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_dequant_w3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1144,6 +1144,36 @@ int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab
   return finish_launch();
 }
 
+// ---- LM head for decode and the token embedding gather (awq_lm_head_cdna4.hip) ----
+int awq_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                int out_dtype, int m, int v, int k, int dtype, int max_blocks, void* stream) {
+  if (!x || !weight || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (out_dtype != AWQ_F32 && out_dtype != dtype) return AWQ_ERR_DTYPE;
+  if (m < 1 || m > 64) return AWQ_ERR_BATCH;
+  if (v < 1 || k < 8 || (k % 8) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || !aligned16(gamma) || !aligned16(bias) || !aligned_to(seqlens, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_lm_head(x, ldx, gamma, eps, weight, bias, seqlens, out, out_dtype == AWQ_F32 ? 1 : 0, m, v, k, dtype, max_blocks,
+                          (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_lm_head_plan(int m, int v, int k, int out[4]) {
+  if (!out) return AWQ_ERR_NULL;
+  if (m < 1 || m > 64) return AWQ_ERR_BATCH;
+  return awq::lm_head_plan(m, v, k, out) != 0 ? AWQ_ERR_SHAPE : AWQ_OK;
+}
+
+int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, int dtype, void* stream) {
+  if (!tokens || !table || !out) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (n < 1 || v < 1 || k < 8 || (k % 8) != 0) return AWQ_ERR_SHAPE;
+  if (!aligned16(table) || !aligned16(out) || !aligned_to(tokens, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_embed_tokens(tokens, table, out, n, v, k, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- W3 ("w3c") : the repository's 3-bit format (bf16 only; no reference counterpart) ----
 static int check_w3_shape(int n, int k) { return (n < 16 || (n % 16) != 0 || k < 128 || (k % 128) != 0) ? AWQ_ERR_SHAPE : AWQ_OK; }
 

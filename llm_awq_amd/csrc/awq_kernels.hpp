@@ -158,6 +158,12 @@ int launch_moe_combine(const void* ys, const void* inv, const void* topk_w, void
 int launch_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
                          const void* top_p, const void* penalty, void* history, void* hist_len, int max_history, void* seqlens, const void* stop_ids,
                          int num_stop, void* finished, int max_len, int flags, void* tokens, hipStream_t st);
+// LM head for decode (awq_lm_head_cdna4.hip): out[m, v] = rmsnorm(x)[m, k] W[v, k]^T (+ bias) in one launch, rows with seqlens[b] < 0 left untouched;
+// the plan is {blocks, vocabulary rows per tile, waves, k split}; -1 if the sizes are outside the documented limits, pointers validated by the caller
+int lm_head_plan(int m, int v, int k, int out[4]);
+int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                   int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st);
+int launch_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, hipStream_t st);  // zeros for an id outside [0, v)
 // awq_gemm_v6.hip: 256 x 256 blocks of four software-pipelined waves (256 x 64 per wave, weights in registers, x through ds_write)
 void launch_gemm_cdna4_v6(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int n_begin,
                           int n_end, int dtype, hipStream_t st, int bits = 4, int epi = 0, int szfmt = 0, int tile_n = 256);

@@ -602,6 +602,53 @@ torch::Tensor sample_logits(torch::Tensor logits, torch::Tensor u, c10::optional
   return tokens;
 }
 
+// ---- LM head for decode (final RMSNorm + vocabulary GEMV, one launch) and the token embedding gather that takes the sampler's -1 ----
+torch::Tensor lm_head(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
+                      c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out, at::ScalarType out_dtype, int64_t max_blocks) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && (x.stride(1) == 1 || x.size(1) <= 1), "awq_inference_engine: lm_head: x must be a [M, K] GPU tensor with a contiguous last dimension");
+  TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() && weight.dim() == 2 && weight.size(1) == x.size(1) && weight.scalar_type() == x.scalar_type(),
+              "lm_head: weight must be a contiguous [V, K] GPU tensor of x's dtype");
+  const int code = dtype_code(x);
+  const int64_t m = x.size(0), k = x.size(1), v = weight.size(0);
+  auto vec = [&](const c10::optional<torch::Tensor>& t, at::ScalarType want, int64_t n, const char* name) -> void* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == want && t->numel() == n && t->device() == x.device(), "lm_head: ", name,
+                " must be a contiguous GPU tensor of its size and dtype");
+    return t->data_ptr();
+  };
+  TORCH_CHECK(out_dtype == at::kFloat || out_dtype == x.scalar_type(), "lm_head: out_dtype must be float32 or x's dtype");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  at::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    TORCH_CHECK(o.is_cuda() && o.is_contiguous() && o.dim() == 2 && o.size(0) == m && o.size(1) == v && o.scalar_type() == out_dtype &&
+                    o.device() == x.device(),
+                "lm_head: out must be a contiguous [M, V] tensor of out_dtype on x's device");
+  } else {
+    o = seqlens.has_value() ? torch::zeros({m, v}, x.options().dtype(out_dtype)) : torch::empty({m, v}, x.options().dtype(out_dtype));
+  }
+  const int64_t ldx = m > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), k) / 8 * 8;
+  raise_on(awq_lm_head(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
+                       vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(seqlens, at::kInt, m, "seqlens"), o.data_ptr(),
+                       out_dtype == at::kFloat ? AWQ_F32 : code, (int)m, (int)v, (int)k, code, (int)max_blocks,
+                       (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return o;
+}
+
+torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
+  TORCH_CHECK(tokens.is_cuda() && tokens.is_contiguous() && tokens.scalar_type() == at::kInt, "awq_inference_engine: embed_tokens: tokens must be a contiguous int32 GPU tensor");
+  TORCH_CHECK(table.is_cuda() && table.is_contiguous() && table.dim() == 2 && table.device() == tokens.device(),
+              "embed_tokens: table must be a contiguous [V, K] GPU tensor on the tokens' device");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(table.device());
+  auto shape = tokens.sizes().vec();
+  shape.push_back(table.size(1));
+  at::Tensor out = torch::empty(shape, table.options());
+  if (tokens.numel() == 0) return out;
+  raise_on(awq_embed_tokens((const int*)tokens.data_ptr(), table.data_ptr(), out.data_ptr(), (int)tokens.numel(), (int)table.size(0), (int)table.size(1),
+                            dtype_code(table), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
 // ---- W3 ("w3c" tiles, bf16): pack from logical integers, and WQLinear.forward for w_bit = 3 ----
 torch::Tensor pack_w3(torch::Tensor q_u8) {
   TORCH_CHECK(q_u8.is_cuda() && q_u8.is_contiguous() && q_u8.scalar_type() == at::kByte && q_u8.dim() == 2);
@@ -1715,6 +1762,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("top_p") = py::none(), py::arg("repetition_penalty") = py::none(), py::arg("history") = py::none(),
         py::arg("hist_len") = py::none(), py::arg("seqlens") = py::none(), py::arg("stop_ids") = py::none(), py::arg("finished") = py::none(),
         py::arg("max_len") = 0, py::arg("append") = false, py::arg("advance") = false);
+  m.def("lm_head", &lm_head, "logits [M, V] = rmsnorm(x) @ weight^T (+ bias): final RMSNorm and vocabulary GEMV in one launch, inactive rows (seqlens < 0) untouched",
+        py::arg("x"), py::arg("weight"), py::arg("gamma") = py::none(), py::arg("eps") = 0.0, py::arg("bias") = py::none(),
+        py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
+  m.def("embed_tokens", &embed_tokens, "out[i] = table[tokens[i]], zeros for an id outside the table (-1 = a finished slot)", py::arg("tokens"),
+        py::arg("table"));
   m.def("pack_w3", &pack_w3, "logical uint8 [N, K] (0..7) -> w3c tiles int16 [N/4, 3K/4]");
   m.def("forward_w3", &forward_w3, "WQLinear forward for w_bit = 3 (w3c tiles)", py::arg("in_feats"), py::arg("kernel"),
         py::arg("scales"), py::arg("zeros"), py::arg("sz_packed"), py::arg("bias") = py::none());

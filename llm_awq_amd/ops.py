@@ -584,6 +584,69 @@ def sample_logits(logits, u, *, temperature=None, top_k=None, top_p=None, repeti
     return tokens
 
 
+# ---- LM head for decode and the token embedding gather (awq_lm_head_cdna4.hip) ----
+
+def lm_head_plan(m: int, v: int, k: int) -> dict:
+    """C-ABI awq_lm_head_plan (host only): the launch shape awq_lm_head takes for [m, k] x [v, k]."""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    _capi.check(_capi.lib().awq_lm_head_plan(int(m), int(v), int(k), out))
+    return {"blocks": out[0], "tile_rows": out[1], "waves": out[2], "k_split": out[3]}
+
+
+def lm_head(x, weight, gamma=None, eps=0.0, bias=None, seqlens=None, out=None, out_dtype=torch.float32, max_blocks=0):
+    """C-ABI awq_lm_head: logits [M, V] = rmsnorm(x)[M, K] @ weight[V, K]^T (+ bias) in one launch that reads the weights once for 1 <= M <= 64.
+    x: [M, K] or a strided view with a contiguous last dimension (h[:, -1, :]): the row stride is passed on, nothing is copied.  gamma [K] (None:
+    no norm), bias [V], weight as nn.Linear holds it.  seqlens int32 [M]: rows with a negative entry are left untouched in `out` (a fresh `out`
+    is then allocated zeroed).  out_dtype: torch.float32 (what sample_logits should be fed) or x.dtype."""
+    if x.dim() != 2 or weight.dim() != 2:
+        raise ValueError("lm_head: x must be [M, K] and weight [V, K]")
+    for t in (x, weight, gamma, bias, seqlens, out):
+        if t is not None and not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _need_gpu(weight, gamma, bias, seqlens, out)
+    m, k = x.shape
+    v = weight.shape[0]
+    if x.stride(1) != 1 and k > 1:
+        raise ValueError("lm_head: the last dimension of x must be contiguous")
+    if weight.shape[1] != k or weight.dtype != x.dtype:
+        raise ValueError("lm_head: weight must be [V, K] of x's dtype")
+    for name, t, n in (("gamma", gamma, k), ("bias", bias, v)):
+        if t is not None and (t.dtype != x.dtype or t.numel() != n or t.device != x.device):
+            raise ValueError(f"lm_head: {name} must hold {n} values of x's dtype on x's device")
+    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.numel() != m or seqlens.device != x.device):
+        raise ValueError("lm_head: seqlens must be int32 [M] on x's device")
+    if out_dtype not in (torch.float32, x.dtype):
+        raise TypeError(f"lm_head: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}")
+    if out is None:
+        out = (torch.zeros if seqlens is not None else torch.empty)((m, v), dtype=out_dtype, device=x.device)
+    elif out.shape != (m, v) or out.dtype != out_dtype or out.device != x.device:
+        raise ValueError("lm_head: out must be a contiguous [M, V] tensor of out_dtype on x's device")
+    ldx = x.stride(0) if m > 1 else max(x.stride(0), k) // 8 * 8  # (a single row's stride is never used)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_lm_head(x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(seqlens), out.data_ptr(),
+                                            _capi.AWQ_F32 if out_dtype == torch.float32 else _dt(x), m, v, k, _dt(x), int(max_blocks),
+                                            _stream(x)))
+    return out
+
+
+def embed_tokens(tokens, table):
+    """C-ABI awq_embed_tokens: out[i] = table[tokens[i]] for tokens int32 [...] and table [V, K]; ZEROS for an id outside [0, V) (-1 is the sampler's
+    finished slot).  Returns [..., K]."""
+    _need_gpu(tokens, table)
+    if tokens.dtype != torch.int32 or table.dim() != 2 or tokens.device != table.device:
+        raise ValueError("embed_tokens: tokens must be int32 and table [V, K], on one device")
+    v, k = table.shape
+    out = torch.empty(*tokens.shape, k, dtype=table.dtype, device=table.device)
+    if tokens.numel() == 0:
+        return out
+    with torch.cuda.device(table.device):
+        _capi.check(_capi.lib().awq_embed_tokens(tokens.data_ptr(), table.data_ptr(), out.data_ptr(), tokens.numel(), v, k, _dt(table),
+                                                 _stream(table)))
+    return out
+
+
 def pair_lost_count(device=None) -> int:
     """C-ABI awq_w4a16_gemm_cdna4_pair_lost: blocks of the block-pair K split (down_proj-shaped prefill launches) of `device` that gave up waiting
     for their partner since the library was loaded -- their outputs are NaN.  0 on a healthy run; synchronises with the device.  A serving loop
