@@ -316,6 +316,47 @@ int awq_lm_head_plan(int m, int v, int k, int out[4]);
  * causes a read outside the table.  n >= 1, v >= 1, k >= 8, k % 8 == 0 (AWQ_ERR_SHAPE); table / out 16-byte, tokens 4-byte aligned. */
 int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, int dtype, void* stream);
 
+/* ---- AWQ quantisation: the asymmetric per-group grid of the reference's pseudo_quantize_tensor(zero_point=True)
+ * (awq/quantize/quantizer.py:61-103) evaluated as torch evaluates it on T tensors -- every operation in fp32 on T values and rounded to T
+ * (nearest-even, fp16 subnormals kept) before the next one, IEEE division, no fused multiply-add across two of torch's roundings.  DESIGN.md
+ * "AWQ quantisation" holds the contract.  Group size 128 only (AWQ_ERR_GROUP), n_bit 3 or 4 (AWQ_ERR_BITS), k % 128 == 0, n >= 1.  Inputs must be
+ * finite and every group's hi - lo finite in T: nothing checks it.  Row limit (one grid dimension holds the row tiles): n <= 1 048 560 for
+ * awq_quantize_group, n <= 2 097 120 for awq_clip_search (AWQ_ERR_SHAPE above).  No workspace, no atomics, no host read: both calls can be captured.
+ *
+ * awq_quantize_group: one launch per weight matrix.  Per group of 128 along k:  v = round_T(w * col_scale) (col_scale given),
+ * v = clamp(v, -clip_max, clip_max) (clip_max given), then the grid.  Every output is optional (NULL = not wanted, left untouched); every
+ * element of a requested output is written:
+ *   w        T [n, k], row stride ldw elements (ldw >= k, ldw % 8 == 0);  col_scale T [k] or NULL;  clip_max T [n, k/128] or NULL
+ *   w_fake   T [n, k] contiguous: the fake-quantised v, divided by col_scale again (round_T(fake / col_scale)) when col_scale is given --
+ *            with col_scale one evaluation of the scale search's w_quantize_func(w * s) / s (auto_scale.py:128-148)
+ *   scales, scaled_zeros   T [gpad, n], gpad = calculate_zeros_width(k) * 8, pad rows written as zeros; scaled_zeros = -(T(scale) * float(int(zero)))
+ *            rounded to T: WQLinear.from_linear's buffers (qmodule.py:155-197)
+ *   zeros    T [n, k/128]
+ *   qweight  int16 [n/4, k], layout 0 = v2 (n % 8 == 0), 1 = cdna4 (n % 16 == 0; equals awq_repack_v2_to_cdna4 of the v2 output); n_bit 4 only
+ *            (a packed 3-bit output is AWQ_ERR_BITS).  The integers are the ones from_linear recovers, round((fake + zero * scale) / scale) in T,
+ *            not clamped, low four bits kept.
+ * w / col_scale / w_fake / qweight 16-byte aligned, the others 2-byte (AWQ_ERR_ALIGN).
+ *
+ * awq_clip_search: the reference's auto_clip_layer (awq/quantize/auto_clip.py:11-63) for one weight matrix in one launch.  Per (row, group):
+ * m = amax|w|, candidates mv_i = round_T(m * float(1 - i / n_grid)) for i < n_steps (the factor in double, as Python computes it, rounded to fp32;
+ * the product in fp32), q_i = the grid on clamp(w, -mv_i, mv_i), err_i = (1/s) sum_t (x_t . q_i - x_t . w)^2 with the products of T values on the
+ * matrix cores and everything else in fp32 (the reference sums in T: DESIGN.md says why this differs).  The result is the first i whose err_i is
+ * strictly below 1e9 and every earlier one (i = 0 if there is none).  A cell's sum order depends on s alone, not on n or the launch shape.
+ *   w  T [n, k], row stride ldw;  x  T [s, k], row stride ldx (a token subsample is a strided view);  ld* >= k, ld* % 8 == 0;  any n >= 1 up to the row limit, s >= 1
+ *   best_max_val T [n, k/128] (the bits of mv_i*), best_idx int32 [n, k/128], err fp32 [n, k/128, n_steps] or NULL
+ *   1 <= n_steps <= 16, n_grid >= 1 (AWQ_ERR_SHAPE). ---- */
+#define AWQ_QWEIGHT_V2 0
+#define AWQ_QWEIGHT_CDNA4 1
+int awq_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                       void* zeros, void* qweight, int qweight_layout, int n, int k, int group_size, int n_bit, int dtype, void* stream);
+/* awq_quantize_group's arithmetic on the HOST, for host memory and without a device: the same source text (csrc/awq_quant_grid.hpp) compiled for the
+ * CPU, so the grid can be held to the torch composition where there is no GPU.  Same inputs and outputs (a)-(c); instead of a packed qweight,
+ * intweight uint8 [n, k] receives the recovered integers' low four bits.  A reference, not a fast path. */
+int awq_quantize_group_host(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                            void* zeros, void* intweight, int n, int k, int group_size, int n_bit, int dtype);
+int awq_clip_search(const void* w, long ldw, const void* x, long ldx, void* best_max_val, int* best_idx, float* err, int n, int k, int s,
+                    int group_size, int n_bit, int n_grid, int n_steps, int dtype, void* stream);
+
 /* ---- W3A16 ("w3c" tiles): BASELINE.json's INT3 configuration.  The reference has NO packed 3-bit format
  * (awq/quantize/qmodule.py:82-83 raises for w_bit != 4; INT3 exists only as pseudo-quantisation,
  * awq/quantize/quantizer.py:61-103 with n_bit = 3), so the format is this repository's: per 16-row x 128-k tile

@@ -68,6 +68,9 @@ SIGNATURES = {
     "awq_lm_head": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awq_lm_head_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_embed_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "awq_quantize_group": (_i, [_vp, ctypes.c_long] + [_vp] * 7 + [_i] * 6 + [_vp]),
+    "awq_quantize_group_host": (_i, [_vp, ctypes.c_long] + [_vp] * 7 + [_i] * 5),
+    "awq_clip_search": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp] + [_i] * 8 + [_vp]),
     "awq_pack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_unpack_w3": (_i, [_vp, _vp, _i, _i, _vp]),
     "awq_dequant_w3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1174,6 +1174,54 @@ int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int
   return finish_launch();
 }
 
+// ---- AWQ quantisation: group quantiser + packer, clip search (awq_quant_cdna4.hip) ----
+int awq_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                       void* zeros, void* qweight, int qweight_layout, int n, int k, int group_size, int n_bit, int dtype, void* stream) {
+  if (!w) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (group_size != 128) return AWQ_ERR_GROUP;
+  if (n_bit != 3 && n_bit != 4) return AWQ_ERR_BITS;
+  if (n < 1 || k < 128 || (k % 128) != 0 || ldw < k || (ldw % 8) != 0) return AWQ_ERR_SHAPE;
+  if (qweight) {
+    if (n_bit != 4) return AWQ_ERR_BITS;  // a packed 3-bit (w3c) output is not produced here
+    if (qweight_layout != AWQ_QWEIGHT_V2 && qweight_layout != AWQ_QWEIGHT_CDNA4) return AWQ_ERR_SHAPE;
+    if ((n % (qweight_layout == AWQ_QWEIGHT_CDNA4 ? 16 : 8)) != 0) return AWQ_ERR_SHAPE;
+  }
+  if (!aligned16(w) || !aligned16(col_scale) || !aligned16(w_fake) || !aligned16(qweight) || !aligned_to(clip_max, 2) || !aligned_to(scales, 2) ||
+      !aligned_to(scaled_zeros, 2) || !aligned_to(zeros, 2))
+    return AWQ_ERR_ALIGN;
+  if (awq::launch_quantize_group(w, ldw, col_scale, clip_max, w_fake, scales, scaled_zeros, zeros, qweight, qweight_layout, n, k, n_bit, dtype,
+                                 (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_quantize_group_host(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                            void* zeros, void* intweight, int n, int k, int group_size, int n_bit, int dtype) {
+  if (!w) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (group_size != 128) return AWQ_ERR_GROUP;
+  if (n_bit != 3 && n_bit != 4) return AWQ_ERR_BITS;
+  if (n < 1 || k < 128 || (k % 128) != 0 || ldw < k) return AWQ_ERR_SHAPE;
+  awq::quantize_group_host(w, ldw, col_scale, clip_max, w_fake, scales, scaled_zeros, zeros, intweight, n, k, n_bit, dtype);
+  return AWQ_OK;
+}
+
+int awq_clip_search(const void* w, long ldw, const void* x, long ldx, void* best_max_val, int* best_idx, float* err, int n, int k, int s,
+                    int group_size, int n_bit, int n_grid, int n_steps, int dtype, void* stream) {
+  if (!w || !x || !best_max_val || !best_idx) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  if (group_size != 128) return AWQ_ERR_GROUP;
+  if (n_bit != 3 && n_bit != 4) return AWQ_ERR_BITS;
+  if (n < 1 || s < 1 || k < 128 || (k % 128) != 0 || ldw < k || (ldw % 8) != 0 || ldx < k || (ldx % 8) != 0 || n_grid < 1 || n_steps < 1 ||
+      n_steps > 16)
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(w) || !aligned16(x) || !aligned_to(best_max_val, 2) || !aligned_to(best_idx, 4) || !aligned_to(err, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_clip_search(w, ldw, x, ldx, best_max_val, best_idx, err, n, k, s, n_bit, n_grid, n_steps, dtype, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- W3 ("w3c") : the repository's 3-bit format (bf16 only; no reference counterpart) ----
 static int check_w3_shape(int n, int k) { return (n < 16 || (n % 16) != 0 || k < 128 || (k % 128) != 0) ? AWQ_ERR_SHAPE : AWQ_OK; }
 

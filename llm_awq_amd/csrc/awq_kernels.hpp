@@ -164,6 +164,16 @@ int lm_head_plan(int m, int v, int k, int out[4]);
 int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                    int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st);
 int launch_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, hipStream_t st);  // zeros for an id outside [0, v)
+// AWQ quantisation (awq_quant_cdna4.hip): the group quantiser + packer (layout 0 = v2, 1 = cdna4; every output optional) and the clip search;
+// -1 if the sizes are outside the documented limits, pointers / alignment validated by the caller
+int launch_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                          void* zeros, void* qweight, int layout, int n, int k, int n_bit, int dtype, hipStream_t st);
+// host twin of launch_quantize_group for host memory (the same awq_quant_grid.hpp text compiled for the CPU); intweight: uint8 [n, k], the recovered
+// integers' low four bits, instead of a packed qweight
+void quantize_group_host(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
+                         void* zeros, void* intweight, int n, int k, int n_bit, int dtype);
+int launch_clip_search(const void* w, long ldw, const void* x, long ldx, void* best_max_val, int* best_idx, float* err, int n, int k, int s,
+                       int n_bit, int n_grid, int n_steps, int dtype, hipStream_t st);
 // awq_gemm_v6.hip: 256 x 256 blocks of four software-pipelined waves (256 x 64 per wave, weights in registers, x through ds_write)
 void launch_gemm_cdna4_v6(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int n_begin,
                           int n_end, int dtype, hipStream_t st, int bits = 4, int epi = 0, int szfmt = 0, int tile_n = 256);

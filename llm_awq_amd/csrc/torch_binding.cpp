@@ -649,6 +649,62 @@ torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
   return out;
 }
 
+// ---- AWQ quantisation: group quantiser + packer and clip search, one launch each ----
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>>
+quantize_pack(torch::Tensor w, c10::optional<torch::Tensor> col_scale, c10::optional<torch::Tensor> clip_max, int64_t n_bit, std::string layout,
+              bool want_fake, bool want_scales, bool want_zeros, bool want_qweight) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && (w.stride(1) == 1 || w.size(1) <= 1),
+              "awq_inference_engine: quantize_pack: w must be a [N, K] GPU tensor with a contiguous last dimension");
+  TORCH_CHECK(layout == "cdna4" || layout == "v2", "quantize_pack: layout must be \"cdna4\" or \"v2\"");
+  const int code = dtype_code(w);
+  const int64_t n = w.size(0), k = w.size(1);
+  TORCH_CHECK(k >= 128 && k % 128 == 0, "quantize_pack: in_features must be a multiple of 128");
+  const int64_t g = k / 128, gpad = (g + 7) / 8 * 8;
+  auto in = [&](const c10::optional<torch::Tensor>& t, int64_t numel, const char* name) -> void* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == w.scalar_type() && t->numel() == numel && t->device() == w.device(),
+                "quantize_pack: ", name, " must be a contiguous GPU tensor of w's dtype and its documented size");
+    return t->data_ptr();
+  };
+  void* cs = in(col_scale, k, "col_scale");
+  void* cm = in(clip_max, n * g, "clip_max");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(w.device());
+  c10::optional<torch::Tensor> fake, scales, szeros, zeros, qweight;
+  if (want_fake) fake = torch::empty({n, k}, w.options());
+  if (want_scales) scales = torch::empty({gpad, n}, w.options()), szeros = torch::empty({gpad, n}, w.options());
+  if (want_zeros) zeros = torch::empty({n, g}, w.options());
+  if (want_qweight) {
+    TORCH_CHECK(n % 4 == 0, "quantize_pack: a packed output needs out_features % 8 == 0 (v2) or % 16 == 0 (cdna4)");
+    qweight = torch::empty({n / 4, k}, w.options().dtype(at::kShort));
+  }
+  auto ptr = [](const c10::optional<torch::Tensor>& t) -> void* { return t.has_value() ? t->data_ptr() : nullptr; };
+  const int64_t ldw = n > 1 ? w.stride(0) : k;
+  raise_on(awq_quantize_group(w.data_ptr(), (long)ldw, cs, cm, ptr(fake), ptr(scales), ptr(szeros), ptr(zeros), ptr(qweight),
+                              layout == "cdna4" ? AWQ_QWEIGHT_CDNA4 : AWQ_QWEIGHT_V2, (int)n, (int)k, 128, (int)n_bit, code,
+                              (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return std::make_tuple(fake, scales, szeros, zeros, qweight);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>> clip_search(torch::Tensor w, torch::Tensor x, int64_t n_bit, int64_t n_grid,
+                                                                                  int64_t n_steps, bool return_err) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && (w.stride(1) == 1 || w.size(1) <= 1) && x.is_cuda() && x.dim() == 2 &&
+                  (x.stride(1) == 1 || x.size(1) <= 1) && x.size(1) == w.size(1) && x.scalar_type() == w.scalar_type() && x.device() == w.device(),
+              "awq_inference_engine: clip_search: w [N, K] and x [S, K] must be GPU tensors of one dtype and device with contiguous last dimensions");
+  const int code = dtype_code(w);
+  const int64_t n = w.size(0), k = w.size(1), s = x.size(0);
+  TORCH_CHECK(k >= 128 && k % 128 == 0 && s >= 1 && n >= 1, "clip_search: in_features must be a multiple of 128 and there must be rows and tokens");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(w.device());
+  torch::Tensor best = torch::empty({n, k / 128}, w.options());
+  torch::Tensor idx = torch::empty({n, k / 128}, w.options().dtype(at::kInt));
+  c10::optional<torch::Tensor> err;
+  if (return_err) err = torch::empty({n, k / 128, n_steps}, w.options().dtype(at::kFloat));
+  raise_on(awq_clip_search(w.data_ptr(), (long)(n > 1 ? w.stride(0) : k), x.data_ptr(), (long)(s > 1 ? x.stride(0) : k), best.data_ptr(),
+                           (int*)idx.data_ptr(), err.has_value() ? (float*)err->data_ptr() : nullptr, (int)n, (int)k, (int)s, 128, (int)n_bit,
+                           (int)n_grid, (int)n_steps, code, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return std::make_tuple(best, idx, err);
+}
+
 // ---- W3 ("w3c" tiles, bf16): pack from logical integers, and WQLinear.forward for w_bit = 3 ----
 torch::Tensor pack_w3(torch::Tensor q_u8) {
   TORCH_CHECK(q_u8.is_cuda() && q_u8.is_contiguous() && q_u8.scalar_type() == at::kByte && q_u8.dim() == 2);
@@ -1767,6 +1823,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
   m.def("embed_tokens", &embed_tokens, "out[i] = table[tokens[i]], zeros for an id outside the table (-1 = a finished slot)", py::arg("tokens"),
         py::arg("table"));
+  m.def("quantize_pack", &quantize_pack,
+        "AWQ group quantiser + packer, one launch: (w_fake, scales, scaled_zeros, zeros, qweight), None where not wanted", py::arg("w"),
+        py::arg("col_scale") = py::none(), py::arg("clip_max") = py::none(), py::arg("n_bit") = 4, py::arg("layout") = "cdna4",
+        py::arg("want_fake") = false, py::arg("want_scales") = true, py::arg("want_zeros") = false, py::arg("want_qweight") = true);
+  m.def("clip_search", &clip_search, "AWQ clip search, one launch: (best_max_val [N, K/128], best_idx int32, err fp32 [N, K/128, n_steps] or None)",
+        py::arg("w"), py::arg("x"), py::arg("n_bit") = 4, py::arg("n_grid") = 20, py::arg("n_steps") = 10, py::arg("return_err") = false);
   m.def("pack_w3", &pack_w3, "logical uint8 [N, K] (0..7) -> w3c tiles int16 [N/4, 3K/4]");
   m.def("forward_w3", &forward_w3, "WQLinear forward for w_bit = 3 (w3c tiles)", py::arg("in_feats"), py::arg("kernel"),
         py::arg("scales"), py::arg("zeros"), py::arg("sz_packed"), py::arg("bias") = py::none());

@@ -647,6 +647,80 @@ def embed_tokens(tokens, table):
     return out
 
 
+# ---- AWQ quantisation: group quantiser + packer and clip search (awq_quant_cdna4.hip) ----
+
+def _quant_weight(who, w):
+    if w.dim() != 2:
+        raise ValueError(f"{who}: w must be [N, K]")
+    if not w.is_cuda:
+        raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    _dt(w)
+    n, k = w.shape
+    if k < 128 or k % 128:
+        raise ValueError(f"{who}: in_features must be a multiple of 128 (group size 128 only)")
+    if w.stride(1) != 1 or (n > 1 and (w.stride(0) < k or w.stride(0) % 8)):
+        raise ValueError(f"{who}: rows must be contiguous with a stride that is a multiple of 8 elements")
+    return n, k
+
+
+def quantize_pack(w, col_scale=None, clip_max=None, n_bit: int = 4, layout: str = "cdna4", *, w_fake=False, scales=True, scaled_zeros=True,
+                  zeros=False, qweight=True) -> dict:
+    """C-ABI awq_quantize_group: the per-group grid of pseudo_quantize_tensor(zero_point=True), group size 128, on w T [N, K] (rows may be
+    strided) in one launch, bit-identical to the torch composition on T tensors.  col_scale T [K]: v = w * col_scale first, and w_fake is divided
+    by it again; clip_max T [N, K/128] (or [N, K/128, 1]): v is clamped to +-clip_max.  Each output is False / None (not wanted), True (allocated)
+    or a tensor to write into: w_fake T [N, K], scales / scaled_zeros T [gpad, N] (WQLinear's buffers), zeros T [N, K/128], qweight int16
+    [N/4, K] in `layout` "cdna4" or "v2" (n_bit 4 only).  Returns {name: tensor} of the requested outputs."""
+    n, k = _quant_weight("quantize_pack", w)
+    if layout not in ("cdna4", "v2"):
+        raise ValueError('quantize_pack: layout must be "cdna4" or "v2"')
+    g = k // 128
+    gpad = -(-g // 8) * 8
+    if clip_max is not None and clip_max.dim() == 3:
+        clip_max = clip_max.reshape(n, g)
+    for name, t, numel in (("col_scale", col_scale, k), ("clip_max", clip_max, n * g)):
+        if t is not None and (not t.is_cuda or t.dtype != w.dtype or t.numel() != numel or t.device != w.device or not t.is_contiguous()):
+            raise ValueError(f"quantize_pack: {name} must hold {numel} contiguous values of w's dtype on w's device")
+    spec = {"w_fake": (w_fake, (n, k), w.dtype), "scales": (scales, (gpad, n), w.dtype), "scaled_zeros": (scaled_zeros, (gpad, n), w.dtype),
+            "zeros": (zeros, (n, g), w.dtype), "qweight": (qweight, (n // 4, k), torch.int16)}
+    out = {}
+    for name, (want, shape, dtype) in spec.items():
+        if want is None or want is False:
+            continue
+        if want is True:
+            out[name] = torch.empty(shape, dtype=dtype, device=w.device)
+        elif tuple(want.shape) != shape or want.dtype != dtype or want.device != w.device or not want.is_contiguous():
+            raise ValueError(f"quantize_pack: {name} must be a contiguous {shape} tensor of {dtype} on w's device")
+        else:
+            out[name] = want
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(w.device):
+        _capi.check(_capi.lib().awq_quantize_group(w.data_ptr(), w.stride(0) if n > 1 else k, ptr(col_scale), ptr(clip_max), ptr(out.get("w_fake")),
+                                                   ptr(out.get("scales")), ptr(out.get("scaled_zeros")), ptr(out.get("zeros")),
+                                                   ptr(out.get("qweight")), 1 if layout == "cdna4" else 0, n, k, 128, int(n_bit), _dt(w),
+                                                   _stream(w)))
+    return out
+
+
+def clip_search(w, x, n_bit: int = 4, n_grid: int = 20, n_steps: int = 10, return_err: bool = False):
+    """C-ABI awq_clip_search: auto_clip_layer's search for w T [N, K] against tokens x T [S, K] (rows of either may be strided) in one launch.
+    Returns (best_max_val T [N, K/128], best_idx int32 [N, K/128]) and, with return_err, the table err fp32 [N, K/128, n_steps]."""
+    n, k = _quant_weight("clip_search", w)
+    if x.dim() != 2 or not x.is_cuda or x.dtype != w.dtype or x.device != w.device or x.shape[1] != k or x.shape[0] < 1:
+        raise ValueError("clip_search: x must be a [S, K] GPU tensor of w's dtype on w's device, S >= 1")
+    s = x.shape[0]
+    if x.stride(1) != 1 or (s > 1 and (x.stride(0) < k or x.stride(0) % 8)):
+        raise ValueError("clip_search: the rows of x must be contiguous with a stride that is a multiple of 8 elements")
+    g = k // 128
+    best = torch.empty((n, g), dtype=w.dtype, device=w.device)
+    idx = torch.empty((n, g), dtype=torch.int32, device=w.device)
+    err = torch.empty((n, g, int(n_steps)), dtype=torch.float32, device=w.device) if return_err else None
+    with torch.cuda.device(w.device):
+        _capi.check(_capi.lib().awq_clip_search(w.data_ptr(), w.stride(0) if n > 1 else k, x.data_ptr(), x.stride(0) if s > 1 else k,
+                                                best.data_ptr(), idx.data_ptr(), None if err is None else err.data_ptr(), n, k, s, 128,
+                                                int(n_bit), int(n_grid), int(n_steps), _dt(w), _stream(w)))
+    return (best, idx, err) if return_err else (best, idx)
+
+
 def pair_lost_count(device=None) -> int:
     """C-ABI awq_w4a16_gemm_cdna4_pair_lost: blocks of the block-pair K split (down_proj-shaped prefill launches) of `device` that gave up waiting
     for their partner since the library was loaded -- their outputs are NaN.  0 on a healthy run; synchronises with the device.  A serving loop

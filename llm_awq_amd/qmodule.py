@@ -176,6 +176,35 @@ class WQLinear(nn.Module):
         q.scaled_zeros = sz.transpose(1, 0).contiguous()
         return q
 
+    @classmethod
+    @torch.no_grad()
+    def quantize_linear(cls, linear, w_bit=4, group_size=128, clip_max=None, layout="cdna4"):
+        """An UNQUANTISED nn.Linear (fp16 / bf16 weight on the GPU) -> a ready module through one launch of the group quantiser
+        (ops.quantize_pack) plus the side-buffer builders: buffers bit-identical to `from_linear(fake-quantised linear, scales, zeros)` followed,
+        for layout "cdna4", by `.to_cdna4()`.  clip_max T [N, K/128] (or [N, K/128, 1], what auto_clip_layer returns): the weight is clamped to
+        +-clip_max per group first (apply_clip).  4 bit, group size 128 only: the packed 3-bit form is still made by from_linear."""
+        from . import ops
+        if w_bit != 4:
+            raise NotImplementedError("quantize_linear packs 4-bit weights only (w3c tiles: fake-quantise with n_bit 3, then from_linear)")
+        if group_size != 128:
+            raise NotImplementedError("quantize_linear implements group_size 128 only")
+        if layout not in ("cdna4", "v2"):
+            raise ValueError('layout must be "cdna4" or "v2"')
+        w = linear.weight.data
+        # (built on the meta device: the launch's outputs become the buffers, nothing is allocated and zeroed to be thrown away)
+        q = cls(w_bit, group_size, linear.in_features, linear.out_features, linear.bias is not None, "meta", dtype=w.dtype)
+        r = ops.quantize_pack(w, clip_max=clip_max, n_bit=w_bit, layout=layout)
+        q.qweight, q.scales, q.scaled_zeros = r["qweight"], r["scales"], r["scaled_zeros"]
+        if linear.bias is not None:
+            q.bias = linear.bias.clone().to(w.dtype)
+        if layout == "cdna4":  # what to_cdna4() does after its repack
+            eng = load_engine()
+            q.sz_cdna4 = eng.pack_sz_cdna4(q.scales, q.scaled_zeros, q.in_features)
+            q._sz_key = q._side_key()
+            q._build_szh(eng)
+            q.layout = "cdna4"
+        return q
+
     def engine_converted(self) -> bool:
         """True while the engine's cache holds THIS qweight converted in place (AWQ_CDNA4_INPLACE=1: the reference entry points permuted the
         bytes where they lie; `layout` still says "v2").  Format tools -- to_cdna4, tensor-parallel sharding, QuantLlamaMLP's stacking,
