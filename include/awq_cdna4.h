@@ -709,6 +709,101 @@ int awq_attn_prefill_paged_kv8(const void* q, const void* k_pool, const void* v_
                                long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                                void* stream);
 
+/* ---- Continuous batching ("varq"): per-sequence numbers of NEW tokens on the KV-cache path.  The tokens of a step are PACKED: one flat run
+ *      of rows in which sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1.  One store launch and one attention launch serve any
+ *      mix -- decodes of one token, prompt chunks, the tail of a prompt -- and one captured graph replays every step of a fixed token budget.
+ * The packed step (all eight entries):
+ *     cu_seqlens_q  device int32 [batch + 1], 4-byte aligned, non-decreasing, cu[0] = 0 (taken for granted).  The host never reads it.
+ *     Sq_b          cu[b + 1] - cu[b].  0 is legal -- a slot with nothing to do: nothing of that sequence is read or written.
+ *     total_q       (host) rows of the packed tensors, cu[batch] <= total_q.  Rows >= cu[batch] are the padding of a fixed token budget and
+ *                   belong to nobody: neither launch reads or writes them.
+ *     max_seqlen_q  (host) bounds every Sq_b and sizes the attention grid.  batch <= 65535.
+ *     Every row index formed from cu_seqlens_q is clamped into [0, total_q - 1] before it forms an address and every write is guarded by
+ *     row < min(cu[b + 1], total_q): a corrupt array gives unspecified results, never an address outside the tensors (awq_attn_varlen's rule).
+ *
+ * awq_attn_prefill_kvcache_varq[_kv8] / awq_attn_prefill_paged_varq[_kv8]: awq_attn_prefill_kvcache[_kv8] / awq_attn_prefill_paged[_kv8] with
+ *     q [total_q, nheads, head_dim] under a row stride (elements; heads contiguous) and out [total_q, nheads, head_dim] contiguous;
+ *     (batch, seqlen_q) replaced by (batch, cu_seqlens_q, max_seqlen_q, total_q); seqlen_offset replaced by the flag lens_before_step.
+ * Length: lens_before_step != 0: Sk_b = seqlens_k[b] + Sq_b -- seqlens_k is then the cache_seqlens the store launch took; 0: Sk_b =
+ *     seqlens_k[b], total lengths.  The sum is formed in 64 bits.  Sequence b is ACTIVE iff 0 <= Sq_b <= max_seqlen_q and
+ *     1 <= Sk_b <= max_seqlen_k.
+ * Mask: causal: row s of sequence b attends keys j <= s + Sk_b - Sq_b; a row with a negative limit returns zeros.  causal = 0 attends keys
+ *     0 .. Sk_b - 1.
+ * Inactive sequences: rows s < min(Sq_b, max_seqlen_q) are written as zeros, further rows are not written, nothing of the sequence's cache
+ *     or pages is read.
+ * Grid: ceil(max_seqlen_q / rows) * batch * nheads blocks from host arguments only, rows from awq_attn_varq_plan (64 or 128; the knob
+ *     "attn_prefill_rows" forces either, a forced 256 leaves the plan's choice).  A block reads cu[b] and cu[b + 1] (two scalar loads); one
+ *     whose rank is at or beyond ceil(Sq_b / rows) returns before any vector load -- a loose max_seqlen_q costs empty blocks, nothing else.
+ *     No workspace, no atomics: bit-deterministic and capturable; a replay follows whatever cu_seqlens_q, the lengths and the table hold then.
+ * Bits: tile walk, masks, LDS images and rounding points are the rectangular kernel's.  For every active sequence with Sk_b >= Sq_b its out
+ *     rows are bit-identical to awq_attn_prefill_kvcache[_kv8] / awq_attn_prefill_paged[_kv8] on that sequence alone (batch 1, seqlen_q =
+ *     Sq_b, its own length and its own table row) under the same q tile.
+ * Returns the codes of the rectangular entries, all but AWQ_ERR_LAUNCH without a GPU call, and: cu_seqlens_q NULL AWQ_ERR_NULL; not 4-byte
+ *     aligned AWQ_ERR_ALIGN; max_seqlen_q < 1, total_q < 1, batch > 65535 or batch * nheads * ceil(max_seqlen_q / 64) > 2^31 - 1
+ *     AWQ_ERR_SHAPE.
+ *
+ * awq_attn_varq_plan: *q_tile_rows = 64 when max_seqlen_q <= 64, otherwise awq_attn_prefill_plan's choice for seqlen_q = max_seqlen_q capped
+ *     at 128; *blocks = the grid above.  A PROVISIONAL rule, not a measurement.  Host only.
+ *
+ * awq_rope_kv_store_natural_varq[_fp8] / awq_rope_kv_store_paged_varq[_fp8]: awq_rope_kv_store_natural_pos[_fp8] /
+ *     awq_rope_kv_store_paged_pos[_fp8] with qkv [total_q, (nheads + 2 nheads_kv) head_dim] under a row stride, q_out [total_q, nheads,
+ *     head_dim] contiguous, and (batch, seqlen) replaced by (batch, cu_seqlens_q, max_seqlen_q, total_q).
+ * Owner: token t < cu[batch] belongs to the sequence b with cu[b] <= t < cu[b + 1] -- a binary search over cu_seqlens_q per thread, at most
+ *     17 cached loads; a tie at zero-length sequences resolves to the owner.  It is token s = t - cu[b] of b: written at position
+ *     cache_seqlens[b] + s with the angles of that table row; the paged form looks the page up per token.
+ * Sequence b is ACTIVE iff 0 <= cache_seqlens[b], Sq_b <= max_seqlen_q and cache_seqlens[b] + Sq_b <= min(capacity, table_rows).  An inactive
+ *     sequence gets zero q_out rows and nothing else.
+ * Bits: for every active sequence the q_out rows, the cache / pool rows and the scales are those the _pos entry leaves for that sequence
+ *     alone; no other byte of the caches, pools or scale pools is written.
+ * Grid: ceil(total_q * head_dim / 8 / 256) blocks, from host arguments only.
+ * Returns the codes of the _pos entries with the packed-step codes above (the grid term: total_q * head_dim / 8 beyond 2^38). */
+int awq_attn_varq_plan(int batch, int nheads, int nheads_kv, int head_dim, int max_seqlen_q, int* q_tile_rows, int* blocks);
+int awq_attn_prefill_kvcache_varq(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q,
+                                  int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax,
+                                  int nheads, int nheads_kv, int head_dim, long long q_row_stride, long long k_batch_stride,
+                                  long long k_row_stride, long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal,
+                                  int dtype, void* stream);
+int awq_attn_prefill_kvcache_varq_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
+                                      void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k,
+                                      int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim,
+                                      long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                                      long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                                      long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                      void* stream);
+int awq_attn_prefill_paged_varq(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                                const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                                int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                                int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                                long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream);
+int awq_attn_prefill_paged_varq_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                    const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                    const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                    int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                    long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                    long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                    long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                    void* stream);
+int awq_rope_kv_store_natural_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
+                                   int batch, int cache_batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                   int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype,
+                                   void* stream);
+int awq_rope_kv_store_natural_varq_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                       float* v_scale, const int* cache_seqlens, int batch, int cache_batch, const int* cu_seqlens_q,
+                                       int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                       int table_rows, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_paged_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                 const int* cache_seqlens, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                 int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                 long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                 long long v_row_stride, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_paged_varq_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                     float* v_scale, const int* block_table, const int* cache_seqlens, int batch, const int* cu_seqlens_q,
+                                     int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim, int table_rows,
+                                     int num_pages, int page_size, int pages_per_seq, long long table_row_stride, long long k_page_stride,
+                                     long long k_row_stride, long long v_page_stride, long long v_row_stride, long long k_scale_page_stride,
+                                     long long k_scale_row_stride, long long v_scale_page_stride, long long v_scale_row_stride,
+                                     long long qkv_row_stride, int dtype, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

@@ -136,6 +136,19 @@ SIGNATURES = {
                                [ctypes.c_float, _i, _i, _vp]),
     "awq_attn_prefill_paged_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
                                    [ctypes.c_float, _i, _i, _vp]),
+    # packed steps (per-sequence query lengths): cu_seqlens_q, max_seqlen_q, total_q in the place of one seqlen
+    "awq_attn_varq_plan": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_attn_prefill_kvcache_varq": (_i, [_vp] * 4 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_kvcache_varq_kv8": (_i, [_vp] * 6 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 9 +
+                                          [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_paged_varq": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                    [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i, _vp]),
+    "awq_attn_prefill_paged_varq_kv8": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                        [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i, _vp]),
+    "awq_rope_kv_store_natural_varq": (_i, [_vp] * 6 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
+    "awq_rope_kv_store_natural_varq_fp8": (_i, [_vp] * 8 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
+    "awq_rope_kv_store_paged_varq": (_i, [_vp] * 7 + [_i, _vp] + [_i] * 10 + [ctypes.c_longlong] * 6 + [_i, _vp]),
+    "awq_rope_kv_store_paged_varq_fp8": (_i, [_vp] * 9 + [_i, _vp] + [_i] * 10 + [ctypes.c_longlong] * 10 + [_i, _vp]),
     "awq_attn_varlen_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "awq_attn_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _i, _i, ctypes.c_longlong, ctypes.c_longlong,
                              ctypes.c_longlong, ctypes.c_float, _i, _i, _vp]),

@@ -21,6 +21,7 @@
 #include "awq_kernels.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_varq.hpp"
 
 #include <math.h>
 
@@ -39,6 +40,7 @@ struct RopeStoreArgs {
   // Paged only (awq_paged.hpp): k_cache / v_cache are the pools, page and row strides in elements; lmax = min(pages_per_seq * page_size, INT_MAX)
   PageArgs pg;
   long long k_ps, k_rs, v_ps, v_rs;
+  VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
 
 template <typename DT>
@@ -130,25 +132,45 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
 // Paged<DevLen<..>> (awq_paged.hpp, awq_rope_kv_store_paged_pos): token s of an active sequence goes to row p % page_size of page
 // table[b][p / page_size], p = pos_b + s -- looked up per TOKEN, a chunk may cross page edges.  p < pages_per_seq * page_size for an active
 // sequence, so the table index lies inside the row; the id is clamped into the pool.
+//
+// VarQ<..> over the two device forms (awq_varq.hpp, awq_rope_kv_store_natural_varq / awq_rope_kv_store_paged_varq): one thread = 8 columns
+// of one PACKED token t < total_q.  Its sequence b is looked up in cu_seqlens_q (varq_owner), s = t - cu[b], and from there on the thread
+// is the rectangular form's thread (b, s) of a chunk of Sq_b tokens: same position, same angles, same bits.  A sequence with
+// Sq_b > max_seqlen_q is inactive as well.  Rows >= cu[B] leave before they read anything.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArgs a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
+  constexpr bool VARQ = IsVarQ<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its positions on the device");
+  static_assert(!VARQ || DEVLEN, "packed tokens read their positions on the device");
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (long long)a.B * a.S * CPR) return;
-  const int ch = (int)(id % CPR);
-  const int s = (int)((id / CPR) % a.S);
-  const int b = (int)(id / ((long long)a.S * CPR));
+  int ch, s, b;
+  long long S = a.S;      // the tokens the sequence brings: a.S, or Sq_b of a packed step
+  long long tok_row = 0;  // VarQ: the token's packed row, < total_q by the grid guard and < cu[b + 1] by the lookup
+  (void)tok_row;
+  if constexpr (VARQ) {
+    if (id >= (long long)a.vq.total_q * CPR) return;
+    ch = (int)(id % CPR);
+    tok_row = id / CPR;
+    long long s64;
+    if (!varq_owner(as_const_i32(a.vq.cu_seqlens_q), a.B, (int)tok_row, b, s64, S)) return;  // a padding row: nobody's
+    s = (int)s64;  // (beyond int only under an inactive S, which leaves below before s is used)
+  } else {
+    if (id >= (long long)a.B * a.S * CPR) return;
+    ch = (int)(id % CPR);
+    s = (int)((id / CPR) % a.S);
+    b = (int)(id / ((long long)a.S * CPR));
+  }
   const int c0 = ch * 8, half = a.rot >> 1;
-  const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
+  const uint16_t* row = a.qkv + (VARQ ? tok_row * a.rs : b * a.bs + s * a.rs);
   const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
-  uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
+  uint16_t* qd = a.q_out + (VARQ ? tok_row : (long long)b * a.S + s) * a.H * DH + c0;
   int start = a.start;
   if constexpr (DEVLEN) {
     start = a.seqlens[b];
-    if (start < 0 || (long long)start + a.S > (long long)min(a.lmax, a.start)) {
+    if (start < 0 || (VARQ && S > a.vq.max_seqlen_q) || (long long)start + S > (long long)min(a.lmax, a.start)) {
       for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = u32x4{0u, 0u, 0u, 0u};
       return;
     }
@@ -230,6 +252,25 @@ int launch_kv_store(const KvStoreCall& c, hipStream_t st) {
     launch_store<DevLen>(a, c.dtype, c.Dh, st);
   } else {
     launch_store<HostLen>(a, c.dtype, c.Dh, st);
+  }
+  return 0;
+}
+
+// The packed-token store (awq_varq.hpp): the grid covers the total_q rows of the call, ceil(total_q * Dh / 8 / 256) blocks from host
+// arguments only; a.S is the host's bound max_seqlen_q.
+int launch_kv_store_varq(const KvStoreCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  if (kv.k_scale) return launch_kv_store_varq_fp8(c, st);
+  const int nb = (int)(((long long)c.total_q * (c.Dh / 8) + 255) / 256);
+  RopeStoreArgs a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint16_t*)kv.k, (uint16_t*)kv.v, 0, c.rs, c.B, c.max_seqlen_q, c.H, c.Hkv,
+                  c.rot, kv.capacity(), c.table_rows, nb, c.cache_seqlens};
+  a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  if (kv.block_table) {
+    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
+    launch_store<VarQPagedDevLen>(a, c.dtype, c.Dh, st);
+  } else {
+    launch_store<VarQDevLen>(a, c.dtype, c.Dh, st);
   }
   return 0;
 }

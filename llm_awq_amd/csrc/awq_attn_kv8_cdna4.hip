@@ -23,6 +23,7 @@
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_varq.hpp"
 
 #include <math.h>
 
@@ -44,6 +45,7 @@ struct RopeStoreFp8Args {
   // min(pages_per_seq * page_size, INT_MAX)
   PageArgs pg;
   long long k_ps, k_rs, v_ps, v_rs, ks_ps, ks_rs, vs_ps, vs_rs;
+  VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
 
 template <typename DT>
@@ -71,26 +73,45 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
 //
 // Paged<DevLen<..>> (awq_paged.hpp, awq_rope_kv_store_paged_pos_fp8): rope_kv_store_natural_kernel's paged form -- the token's page is looked
 // up in the table, codes and scales go to row p % page_size of that page in their pools.
+//
+// VarQ<..> over the two device forms (awq_varq.hpp, awq_rope_kv_store_natural_varq_fp8 / awq_rope_kv_store_paged_varq_fp8):
+// rope_kv_store_natural_kernel's packed tokens -- the owner of packed row t is looked up in cu_seqlens_q, and the thread goes on as thread
+// (b, t - cu[b]) of the rectangular form.  The CPR lanes of a token share t, so the lookup keeps them together.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStoreFp8Args a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
+  constexpr bool VARQ = IsVarQ<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its positions on the device");
+  static_assert(!VARQ || DEVLEN, "packed tokens read their positions on the device");
   constexpr int CPR = DH / 8;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (long long)a.B * a.S * CPR) return;  // (the CPR lanes of a (b, s) leave or stay together)
-  const int ch = (int)(id % CPR);
-  const int s = (int)((id / CPR) % a.S);
-  const int b = (int)(id / ((long long)a.S * CPR));
+  int ch, s, b;
+  long long S = a.S;      // the tokens the sequence brings: a.S, or Sq_b of a packed step
+  long long tok_row = 0;  // VarQ: the token's packed row, < total_q by the grid guard and < cu[b + 1] by the lookup
+  (void)tok_row;
+  if constexpr (VARQ) {
+    if (id >= (long long)a.vq.total_q * CPR) return;  // (the CPR lanes of a token share every test below: they leave or stay together)
+    ch = (int)(id % CPR);
+    tok_row = id / CPR;
+    long long s64;
+    if (!varq_owner(as_const_i32(a.vq.cu_seqlens_q), a.B, (int)tok_row, b, s64, S)) return;  // a padding row: nobody's
+    s = (int)s64;  // (beyond int only under an inactive S, which leaves below before s is used)
+  } else {
+    if (id >= (long long)a.B * a.S * CPR) return;  // (the CPR lanes of a (b, s) leave or stay together)
+    ch = (int)(id % CPR);
+    s = (int)((id / CPR) % a.S);
+    b = (int)(id / ((long long)a.S * CPR));
+  }
   const int c0 = ch * 8, half = a.rot >> 1;
-  const uint16_t* row = a.qkv + b * a.bs + s * a.rs;
+  const uint16_t* row = a.qkv + (VARQ ? tok_row * a.rs : b * a.bs + s * a.rs);
   const uint16_t* ks = row + (long long)a.H * DH;  // the K heads follow the H query heads
   const uint16_t* vs = row + (long long)(a.H + a.Hkv) * DH;
-  uint16_t* qd = a.q_out + ((long long)b * a.S + s) * a.H * DH + c0;
+  uint16_t* qd = a.q_out + (VARQ ? tok_row : (long long)b * a.S + s) * a.H * DH + c0;
   int start = a.start;
   if constexpr (DEVLEN) {
     start = a.seqlens[b];
-    if (start < 0 || (long long)start + a.S > (long long)min(a.lmax, a.start)) {
+    if (start < 0 || (VARQ && S > a.vq.max_seqlen_q) || (long long)start + S > (long long)min(a.lmax, a.start)) {
       for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = u32x4{0u, 0u, 0u, 0u};
       return;
     }
@@ -156,7 +177,8 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
 
 template <template <typename> class L>
 void launch_store(const RopeStoreFp8Args& a, int dtype, int Dh, hipStream_t st) {
-  const dim3 grid((unsigned)(((long long)a.B * a.S * (Dh / 8) + 255) / 256));
+  const long long tokens = a.vq.cu_seqlens_q ? (long long)a.vq.total_q : (long long)a.B * a.S;
+  const dim3 grid((unsigned)((tokens * (Dh / 8) + 255) / 256));
   for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
     hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<L<decltype(dt)>, decltype(dh)::value>), grid, dim3(256), 0, st, a);
   });
@@ -178,6 +200,23 @@ int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st) {
     launch_store<DevLen>(a, c.dtype, c.Dh, st);
   } else {
     launch_store<HostLen>(a, c.dtype, c.Dh, st);
+  }
+  return 0;
+}
+
+// launch_kv_store_varq's FP8 half
+int launch_kv_store_varq_fp8(const KvStoreCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  RopeStoreFp8Args a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint8_t*)kv.k, (uint8_t*)kv.v, (float*)kv.k_scale, (float*)kv.v_scale,
+                     0, c.rs, c.B, c.max_seqlen_q, c.H, c.Hkv, c.rot, kv.capacity(), c.table_rows, c.cache_seqlens};
+  a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  if (kv.block_table) {
+    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
+    a.ks_ps = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_ps = kv.vs_os, a.vs_rs = kv.vs_rs;
+    launch_store<VarQPagedDevLen>(a, c.dtype, c.Dh, st);
+  } else {
+    launch_store<VarQDevLen>(a, c.dtype, c.Dh, st);
   }
   return 0;
 }

@@ -29,6 +29,7 @@
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_varq.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -69,12 +70,13 @@ struct PrefillLenArgs {
   int seqlen_offset;
   int max_seqlen_k;      // the host's bound: a sequence beyond it is inactive
   PageArgs pg;           // Paged: a.k / a.v are then the pools and a.k_bs / a.v_bs (a.ks_bs / a.vs_bs) their PAGE strides
+  VarQArgs vq;           // VarQ (awq_varq.hpp): a.q / a.out are then the packed rows, a.Sq the host's bound max_seqlen_q; no other form reads it
 };
 
 struct NoLenArgs {};
 template <typename DT>
 using LenArgsOf = typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type;
-__device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}}; }
+__device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}, VarQArgs{nullptr, 0, 0, 0}}; }
 __device__ __forceinline__ PrefillLenArgs len_args(const PrefillLenArgs& x) { return x; }
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
@@ -130,6 +132,15 @@ struct IsFtCache<FtCache<DT>> {
 // of the block behind the length.  (pg_i, pg_ro) advance by 64 rows: no division in the loop.  Only tiles j < nt are looked up; their
 // first key lies below kv_end <= Sk_b, so no entry at or behind ceil(Sk_b / page_size) is read.
 //
+// VarQ<..> over the four forms above (awq_varq.hpp, awq_attn_prefill_kvcache_varq[_kv8], awq_attn_prefill_paged_varq[_kv8]): q / out are
+// packed rows and Sq_b = cu[b + 1] - cu[b] stands wherever a.Sq stands -- shift, q_last, qi, wave_on and the store guard -- so an active
+// sequence's rows carry the bits of the rectangular launch on that sequence alone.  cu[b] and cu[b + 1] are two scalar loads through the
+// constant address space at the very head of the block, in front of the length: the q row (cu[b] + qi) depends on them, so unlike the
+// rectangular forms the Q loads wait for one scalar round trip.  The grid is sized by the host's bound, ceil(max_seqlen_q / rows) ranks;
+// a block whose rank is at or beyond ntiles_b = ceil(Sq_b / rows) returns before any vector load, and the tile reversal counts from
+// ntiles_b, so rank 0 is every sequence's longest tile.  Sq_b outside [0, max_seqlen_q] makes the sequence inactive: rows
+// s < min(Sq_b, max_seqlen_q) are written as zeros.  With lens_before_step the length is seqlens_k[b] + Sq_b, formed in 64 bits.
+//
 // The device-length forms take their PrefillLenArgs as a SECOND kernel argument.  For the host-length forms that argument is the empty
 // NoLenArgs -- one padded byte behind PrefillArgs that no instruction reads: their PrefillArgs, their registers and their instruction
 // stream are those of the one-argument kernel.
@@ -140,8 +151,10 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   constexpr bool KV8 = IsKv8<DT>::value;
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
+  constexpr bool VARQ = IsVarQ<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!FT || !DEVLEN, "the FT caches take a host length");
+  static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = NW * 64;
@@ -160,41 +173,65 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   bi /= a.H;
   const int b = bi % a.B;
   const int rank = bi / a.B;
-  const int tile = a.causal ? a.ntiles - 1 - rank : rank;
+  int Sq = a.Sq, ntiles = a.ntiles;
+  long long row0 = 0, row_end = 0, sq_b = 0;  // VarQ: the sequence's first packed row, the end of its rows, Sq_b before the clamp
+  (void)row0, (void)row_end, (void)sq_b;
+  if constexpr (VARQ) {  // two scalar loads; everything below depends on them
+    const const_i32_t cu = as_const_i32(x.vq.cu_seqlens_q);
+    const int c0 = cu[b], c1 = cu[b + 1];
+    row0 = c0;
+    row_end = min((long long)c1, (long long)x.vq.total_q);
+    sq_b = (long long)c1 - c0;
+    Sq = (int)min(max(sq_b, 0ll), (long long)x.vq.max_seqlen_q);
+    ntiles = (Sq + NW * kMfmaRows - 1) / (NW * kMfmaRows);
+    if (rank >= ntiles) return;  // a rank the host's bound paid for and this sequence does not need; Sq_b = 0: every block
+  }
+  const int tile = a.causal ? ntiles - 1 - rank : rank;
   const int kvh = h / a.G;
   const int q0 = tile * (NW * kMfmaRows);
   int Sk = a.Sk;
   bool live = true;
   (void)live;
   if constexpr (DEVLEN) {  // one scalar load; the Q loads below do not depend on it and are issued beside it
-    const long long len = (long long)x.seqlens_k[b] + x.seqlen_offset;  // 64 bits: no entry can wrap into an active length
+    // 64 bits: no entry can wrap into an active length
+    const long long len = (long long)x.seqlens_k[b] + (VARQ ? (x.vq.lens_before_step ? sq_b : 0ll) : (long long)x.seqlen_offset);
     Sk = (int)len;
     live = len >= 1 && len <= x.max_seqlen_k;
+    if constexpr (VARQ) {
+      live = live && sq_b == Sq;  // Sq_b < 0 never gets here (ntiles = 0); Sq_b > max_seqlen_q: inactive
+      Sk = live ? Sk : 1;         // (an inactive sequence forms no address from its length; keep the arithmetic below inside int)
+    }
   }
-  const int shift = Sk - a.Sq;
-  const int q_last = min(q0 + NW * kMfmaRows, a.Sq) - 1;
+  const int shift = Sk - Sq;
+  const int q_last = min(q0 + NW * kMfmaRows, Sq) - 1;
   const int kv_end = a.causal ? min(Sk, q_last + shift + 1) : Sk;  // keys [0, kv_end) matter to this block
   const int nt = (kv_end + kKV - 1) / kKV;
 
   const int wq0 = q0 + wave * kMfmaRows;
-  const bool wave_on = wq0 < a.Sq;                 // (a wave past the last row still stages K / V and meets the barriers)
-  const int qi = min(wq0 + r, a.Sq - 1);           // rows >= Sq compute row Sq - 1 again and are not stored
+  const bool wave_on = wq0 < Sq;                   // (a wave past the last row still stages K / V and meets the barriers)
+  const int qi = min(wq0 + r, Sq - 1);             // rows >= Sq compute row Sq - 1 again and are not stored
   const int lim = a.causal ? qi + shift : Sk - 1;                                 // last key this lane's row attends
-  const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, a.Sq - 1) + shift : Sk - 1;  // .. any row of the wave
+  const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, Sq - 1) + shift : Sk - 1;  // .. any row of the wave
   const int wave_min = a.causal ? wq0 + shift : Sk - 1;                           // every row of the wave attends keys <= this
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
+  // VarQ: the packed row of (b, qi), clamped into the tensors before it forms an address; a store is guarded by row < min(cu[b + 1], total_q)
+  const long long qrow = VARQ ? min(max(row0 + qi, 0ll), (long long)x.vq.total_q - 1) : 0ll;
+  const bool row_ok = VARQ ? row0 + qi < row_end : true;
+  (void)qrow, (void)row_ok;
   vec8 qf[KS];
   {
     const uint16_t* qp = a.q + (long long)b * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
+    if constexpr (VARQ) qp = a.q + qrow * a.q_rs + (long long)h * DH + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
   }
 
   if constexpr (DEVLEN) {
     if (!live || kv_end < 1) {  // inactive, or no row of the q tile attends a key: zero rows, no K / V load
-      if (wq0 + r < a.Sq) {
+      if (wq0 + r < Sq && row_ok) {
         uint16_t* op = a.out + (((long long)b * a.Sq + qi) * a.H + h) * DH + 4 * hh;
+        if constexpr (VARQ) op = a.out + (qrow * a.H + h) * DH + 4 * hh;
 #pragma unroll
         for (int c = 0; c < DH / 8; ++c) *reinterpret_cast<u32x2*>(op + 8 * c) = u32x2{0u, 0u};
       }
@@ -394,10 +431,11 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
 
   // ---- O / l, rounded to T once; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  if (wq0 + r < a.Sq) {
+  if (wq0 + r < Sq && row_ok) {
     float inv = 1.0f / l_tot;
     if constexpr (DEVLEN) inv = l_tot > 0.f ? inv : 0.f;  // a row that attended nothing: zeros (o is 0), never 0 * Inf
     uint16_t* op = a.out + (((long long)b * a.Sq + qi) * a.H + h) * DH + 4 * hh;
+    if constexpr (VARQ) op = a.out + (qrow * a.H + h) * DH + 4 * hh;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -543,6 +581,22 @@ int attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int se
   return 0;
 }
 
+// Host plan of a packed-query launch (awq_varq.hpp).  PROVISIONAL, not a measurement: 64 rows while no sequence can fill more
+// (max_seqlen_q <= 64), otherwise what attn_prefill_plan gives for a rectangle of max_seqlen_q rows, capped at 128 -- only the 64- and
+// 128-row kernels exist for packed queries.  The knob attn_prefill_rows forces 64 or 128; a forced 256 leaves this plan's own choice in
+// place.  *blocks is the grid: ceil(max_seqlen_q / rows) ranks for every (sequence, head), whatever the sequences turn out to hold.
+int attn_varq_plan(int batch, int nheads, int nheads_kv, int head_dim, int max_seqlen_q, int* q_tile_rows, int* blocks) {
+  (void)nheads_kv;
+  const long long bh = (long long)batch * nheads;
+  auto nblocks = [&](int rows) { return bh * ((max_seqlen_q + rows - 1) / rows); };
+  int rows = 128;
+  if (max_seqlen_q <= 64 || (head_dim == 64 && nblocks(128) < 2 * kCUs)) rows = 64;
+  if (g_force_rows == 64 || g_force_rows == 128) rows = g_force_rows;
+  *q_tile_rows = rows;
+  *blocks = (int)nblocks(rows);
+  return 0;
+}
+
 int attn_prefill_tune_set(const char* key, int value) {
   if (strcmp(key, "attn_prefill_rows") != 0 || (value != 0 && value != 64 && value != 128 && value != 256)) return -1;
   g_force_rows = value;
@@ -683,6 +737,16 @@ void launch_kv_prefill_as(const PrefillArgs& a, const PrefillLenArgs& x, int Dh,
     }
   });
 }
+// the packed-query forms: q tiles of 128 and 64 rows only (attn_varq_plan)
+template <template <typename> class K, template <typename> class L>
+void launch_kv_prefill_varq_as(const PrefillArgs& a, const PrefillLenArgs& x, int Dh, int dtype, int nw, int blocks, hipStream_t st) {
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    using DT = L<K<decltype(dt)>>;
+    constexpr int DH = decltype(dh)::value;
+    if (nw == 4) hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 4>), dim3(blocks), dim3(256), 0, st, a, x);
+    else hipLaunchKernelGGL((attn_prefill_kernel<DT, DH, 2>), dim3(blocks), dim3(128), 0, st, a, x);
+  });
+}
 template <typename DT>
 using TCache = DT;  // the T cache: the element traits themselves
 
@@ -712,8 +776,24 @@ int launch_kv_prefill(const KvAttnCall& c, hipStream_t st) {
   a.k_scale = kv.k_scale;
   a.v_scale = kv.v_scale;
   a.ks_bs = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_bs = kv.vs_os, a.vs_rs = kv.vs_rs;
-  const PrefillLenArgs x{c.seqlens_k, c.seqlen_offset, c.max_seqlen_k, PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer}};
   int rows = 0, blocks = 0;
+  if (c.cu_seqlens_q) {  // packed queries: c.Sq is max_seqlen_q, c.seqlen_offset the flag lens_before_step; the kernel forms a.ntiles per sequence
+    const PrefillLenArgs x{c.seqlens_k, 0, c.max_seqlen_k, PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer},
+                           VarQArgs{c.cu_seqlens_q, c.total_q, c.Sq, c.seqlen_offset ? 1 : 0}};
+    attn_varq_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, &rows, &blocks);
+    a.ntiles = (c.Sq + rows - 1) / rows;
+    const int nw = rows / kMfmaRows;
+    if (kv.block_table) {
+      if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, VarQPagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+      else launch_kv_prefill_varq_as<TCache, VarQPagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+    } else {
+      if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, VarQDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+      else launch_kv_prefill_varq_as<TCache, VarQDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
+    }
+    return 0;
+  }
+  const PrefillLenArgs x{c.seqlens_k, c.seqlen_offset, c.max_seqlen_k, PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer},
+                         VarQArgs{nullptr, 0, 0, 0}};
   attn_prefill_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, c.causal, &rows, &blocks);
   a.ntiles = (c.Sq + rows - 1) / rows;
   const int nw = rows / kMfmaRows;

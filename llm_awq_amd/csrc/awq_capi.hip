@@ -431,7 +431,8 @@ using awq::KvAttnCall;
 using awq::KvStoreCall;
 using awq::KvView;
 // what an entry requires of its descriptor; KV_ONEPASS: the one-pass prefill kernel serves, any seqlen_q (no seqlen_q * G <= 128 term)
-enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8 };
+// KV_VARQ: packed tokens / queries (awq_varq.hpp) -- cu_seqlens_q, max_seqlen_q and total_q in the place of one seqlen for the batch
+enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8, KV_VARQ = 16 };
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
@@ -473,21 +474,37 @@ static bool kv_aligned(const KvView& kv, int fmt, bool strided) {
          (!strided || ((kv.k_os % unit) == 0 && (kv.k_rs % unit) == 0 && (kv.v_os % unit) == 0 && (kv.v_rs % unit) == 0));
 }
 
+// the packed step's own terms of the null, shape and alignment phases (KV_VARQ); the grid term is the caller's
+static bool varq_shape_ok(int batch, int max_seqlen_q, int total_q) { return batch <= 65535 && max_seqlen_q >= 1 && total_q >= 1; }
+
 static int kv_store(const KvStoreCall& c, int fmt, void* stream) {
   const KvView& kv = c.kv;
-  const bool paged = fmt & KV_PAGED, devlen = fmt & KV_DEVLEN;
-  if (!c.qkv || !c.freqs || !c.q_out || kv_has_null(kv, fmt) || (devlen && !c.cache_seqlens)) return AWQ_ERR_NULL;
+  const bool paged = fmt & KV_PAGED, devlen = fmt & KV_DEVLEN, varq = fmt & KV_VARQ;
+  if (!c.qkv || !c.freqs || !c.q_out || kv_has_null(kv, fmt) || (devlen && !c.cache_seqlens) || (varq && !c.cu_seqlens_q)) return AWQ_ERR_NULL;
   if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  // tokens of the call: the rectangle, or the packed rows (c.S is then max_seqlen_q)
+  const long long tokens = varq ? (long long)c.total_q : (long long)c.B * c.S;
   if (c.B < 1 || c.S < 1 || c.H < 1 || c.Hkv < 1 || (c.Dh != 64 && c.Dh != 128) || c.rot < 16 || (c.rot % 16) != 0 || c.rot > c.Dh || c.bs < 0 ||
-      c.rs < ((long long)c.H + 2ll * c.Hkv) * c.Dh || (long long)c.B * c.S * (c.Dh / 8) > 0x3FFFFFFFll * 256 ||
-      (!paged && (kv.outer < c.B || kv.rows < 1)) || !kv_shape_ok(kv, fmt, paged, c.Hkv, c.Dh) ||
+      c.rs < ((long long)c.H + 2ll * c.Hkv) * c.Dh || (varq && !varq_shape_ok(c.B, c.max_seqlen_q, c.total_q)) ||
+      tokens * (c.Dh / 8) > 0x3FFFFFFFll * 256 || (!paged && (kv.outer < c.B || kv.rows < 1)) || !kv_shape_ok(kv, fmt, paged, c.Hkv, c.Dh) ||
       (devlen ? c.table_rows < 1 : (c.start_pos < 0 || (long long)c.start_pos + c.S > kv.rows)))
     return AWQ_ERR_SHAPE;
   if (!aligned16(c.qkv) || !aligned16(c.freqs) || !aligned16(c.q_out) || !kv_aligned(kv, fmt, paged) || (devlen && !aligned4(c.cache_seqlens)) ||
-      (c.bs % 8) != 0 || (c.rs % 8) != 0)
+      (varq && !aligned4(c.cu_seqlens_q)) || (c.bs % 8) != 0 || (c.rs % 8) != 0)
     return AWQ_ERR_ALIGN;
-  awq::launch_kv_store(c, (hipStream_t)stream);
+  if (varq) awq::launch_kv_store_varq(c, (hipStream_t)stream);
+  else awq::launch_kv_store(c, (hipStream_t)stream);
   return finish_launch();
+}
+
+// a packed-token store call: the device-position descriptor with the packed step's three fields; S carries max_seqlen_q
+static KvStoreCall varq_store_call(const void* qkv, const float* freqs_table, void* q_out, const KvView& kv, const int* cache_seqlens, int table_rows,
+                                   int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim,
+                                   int rot_dim, long long qkv_row_stride, int dtype) {
+  KvStoreCall c{qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, max_seqlen_q, nheads, nheads_kv, head_dim, rot_dim, 0,
+                qkv_row_stride, dtype};
+  c.cu_seqlens_q = cu_seqlens_q, c.max_seqlen_q = max_seqlen_q, c.total_q = total_q;
+  return c;
 }
 
 // the split pair always runs under device lengths: Sq * G <= 128 and Dh 64 / 128 are requirements, not routing conditions.  one_pass
@@ -512,15 +529,19 @@ size_t awq_attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, in
 // the four phases every attention entry shares; AWQ_OK: the tail (kv_attn) or the one-pass launch may go on
 static int kv_attn_check(const KvAttnCall& c, int fmt) {
   const KvView& kv = c.kv;
-  const bool devlen = fmt & KV_DEVLEN;
-  if (!c.q || !c.out || kv_has_null(kv, fmt) || (devlen && !c.seqlens_k)) return AWQ_ERR_NULL;
+  const bool devlen = fmt & KV_DEVLEN, varq = fmt & KV_VARQ;
+  if (!c.q || !c.out || kv_has_null(kv, fmt) || (devlen && !c.seqlens_k) || (varq && !c.cu_seqlens_q)) return AWQ_ERR_NULL;
   if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  // (packed queries: c.Sq is max_seqlen_q, so the one-pass grid term bounds ceil(max_seqlen_q / 64) * batch * nheads)
+  if (varq && !varq_shape_ok(c.B, c.max_seqlen_q, c.total_q)) return AWQ_ERR_SHAPE;
   // (host lengths: the T entry keeps the one-pass kernel's head dim 72 for the calls the plan hands to it; the FP8 kernels have 64 / 128)
   if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, fmt & KV_ONEPASS)
                : ((!(fmt & KV_FP8) || c.Dh == 64 || c.Dh == 128) && prefill_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal))) ||
       !kv_shape_ok(kv, fmt, true, c.Hkv, c.Dh) || c.q_bs < 0 || c.q_rs < (long long)c.H * c.Dh)
     return AWQ_ERR_SHAPE;
-  if (!aligned16(c.q) || !aligned16(c.out) || !kv_aligned(kv, fmt, true) || (c.q_bs % 8) != 0 || (c.q_rs % 8) != 0) return AWQ_ERR_ALIGN;
+  if (!aligned16(c.q) || !aligned16(c.out) || !kv_aligned(kv, fmt, true) || (c.q_bs % 8) != 0 || (c.q_rs % 8) != 0 ||
+      (varq && !aligned4(c.cu_seqlens_q)))
+    return AWQ_ERR_ALIGN;
   return AWQ_OK;
 }
 
@@ -772,6 +793,123 @@ int awq_attn_prefill_paged_kv8(const void* q, const void* k_pool, const void* v_
   return kv_prefill({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
                      q_row_stride, softmax_scale, causal, dtype},
                     KV_FP8 | KV_PAGED | KV_DEVLEN, stream);
+}
+
+// ---- packed queries (awq_varq.hpp): one store launch and one attention launch for any mix of new-token counts
+int awq_attn_varq_plan(int batch, int nheads, int nheads_kv, int head_dim, int max_seqlen_q, int* q_tile_rows, int* blocks) {
+  if (!q_tile_rows || !blocks) return AWQ_ERR_NULL;
+  if (!kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, max_seqlen_q, 1, true) || batch > 65535) return AWQ_ERR_SHAPE;
+  return awq::attn_varq_plan(batch, nheads, nheads_kv, head_dim, max_seqlen_q, q_tile_rows, blocks);
+}
+
+// a packed-query attention call: the device-length descriptor with the packed step's three fields; Sq carries max_seqlen_q and
+// seqlen_offset the flag
+static KvAttnCall varq_attn_call(const void* q, void* out, const KvView& kv, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                 const int* seqlens_k, int lens_before_step, int max_seqlen_k, int nheads, int nheads_kv, int head_dim,
+                                 long long q_row_stride, float softmax_scale, int causal, int dtype) {
+  KvAttnCall c{q, out, kv, 0, seqlens_k, lens_before_step ? 1 : 0, max_seqlen_k, batch, max_seqlen_q, nheads, nheads_kv, head_dim, 0, q_row_stride,
+               softmax_scale, causal, dtype};
+  c.cu_seqlens_q = cu_seqlens_q, c.max_seqlen_q = max_seqlen_q, c.total_q = total_q;
+  return c;
+}
+
+int awq_attn_prefill_kvcache_varq(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q,
+                                  int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax,
+                                  int nheads, int nheads_kv, int head_dim, long long q_row_stride, long long k_batch_stride,
+                                  long long k_row_stride, long long v_batch_stride, long long v_row_stride, float softmax_scale, int causal,
+                                  int dtype, void* stream) {
+  const KvView kv = kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_prefill(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                   nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                    KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_attn_prefill_kvcache_varq_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale,
+                                      void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k,
+                                      int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim,
+                                      long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                                      long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                                      long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                      void* stream) {
+  const KvView kv = with_scales(kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale,
+                                v_scale, k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return kv_prefill(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                   nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                    KV_FP8 | KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_attn_prefill_paged_varq(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                                const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                                int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                                int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                                long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_prefill(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                   nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                    KV_PAGED | KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_attn_prefill_paged_varq_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                    const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                    const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                    int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                    long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                    long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                    long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                    void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_prefill(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                   nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                    KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_rope_kv_store_natural_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
+                                   int batch, int cache_batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                   int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype,
+                                   void* stream) {
+  return kv_store(varq_store_call(qkv, freqs_table, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), cache_seqlens, table_rows, batch,
+                                  cu_seqlens_q, max_seqlen_q, total_q, nheads, nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype),
+                  KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_rope_kv_store_natural_varq_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, float* k_scale,
+                                       float* v_scale, const int* cache_seqlens, int batch, int cache_batch, const int* cu_seqlens_q,
+                                       int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                       int table_rows, long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store(varq_store_call(qkv, freqs_table, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale),
+                                  cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q, nheads, nheads_kv, head_dim, rot_dim,
+                                  qkv_row_stride, dtype),
+                  KV_FP8 | KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_rope_kv_store_paged_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, const int* block_table,
+                                 const int* cache_seqlens, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                 int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                 long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                 long long v_row_stride, long long qkv_row_stride, int dtype, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_store(varq_store_call(qkv, freqs_table, q_out, kv, cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q, nheads,
+                                  nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype),
+                  KV_PAGED | KV_DEVLEN | KV_VARQ, stream);
+}
+
+int awq_rope_kv_store_paged_varq_fp8(const void* qkv, const float* freqs_table, void* q_out, void* k_pool, void* v_pool, float* k_scale,
+                                     float* v_scale, const int* block_table, const int* cache_seqlens, int batch, const int* cu_seqlens_q,
+                                     int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim, int table_rows,
+                                     int num_pages, int page_size, int pages_per_seq, long long table_row_stride, long long k_page_stride,
+                                     long long k_row_stride, long long v_page_stride, long long v_row_stride, long long k_scale_page_stride,
+                                     long long k_scale_row_stride, long long v_scale_page_stride, long long v_scale_row_stride,
+                                     long long qkv_row_stride, int dtype, void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_store(varq_store_call(qkv, freqs_table, q_out, kv, cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q, nheads,
+                                  nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype),
+                  KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, stream);
 }
 
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {

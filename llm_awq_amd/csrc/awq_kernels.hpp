@@ -201,6 +201,8 @@ int launch_attn_decode(const void* q, const void* k, const void* v, void* k_cach
 // prefill attention and the prompt-side rotary embeddings (awq_attn_prefill_cdna4.hip); arguments validated by the caller
 int attn_prefill_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int seqlen_k, int causal, int* q_tile_rows,
                       int* blocks);
+// the q tile and the grid of a packed-query launch (awq_varq.hpp): 64 or 128 rows, a provisional rule
+int attn_varq_plan(int batch, int nheads, int nheads_kv, int head_dim, int max_seqlen_q, int* q_tile_rows, int* blocks);
 int attn_prefill_tune_set(const char* key, int value);  // "attn_prefill_rows": force the q tile (0 = plan)
 int launch_attn_prefill(const void* q, const void* k, const void* v, void* out, int B, int Sq, int Sk, int H, int Hkv, int Dh, long long q_bs,
                         long long q_rs, long long k_bs, long long k_rs, long long v_bs, long long v_rs, float scale, int causal, int dtype,

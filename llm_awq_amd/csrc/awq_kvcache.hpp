@@ -43,6 +43,10 @@ struct KvStoreCall {
   int B, S, H, Hkv, Dh, rot;
   long long bs, rs;
   int dtype;
+  // packed tokens (awq_varq.hpp): qkv [total_q, (H + 2 Hkv) Dh] with row stride rs, sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1;
+  // S is then the host's bound max_seqlen_q and bs unused.  nullptr: the rectangle [B, S]
+  const int* cu_seqlens_q = nullptr;
+  int max_seqlen_q = 0, total_q = 0;
 };
 
 struct KvAttnCall {
@@ -56,15 +60,23 @@ struct KvAttnCall {
   long long q_bs, q_rs;
   float scale;
   int causal, dtype;
+  // packed queries (awq_varq.hpp): q / out [total_q, H, Dh], row stride q_rs; Sq is then the host's bound max_seqlen_q, q_bs unused and
+  // seqlen_offset the flag lens_before_step (length of b = seqlens_k[b] + Sq_b when set, seqlens_k[b] when clear).  nullptr: the rectangle
+  const int* cu_seqlens_q = nullptr;
+  int max_seqlen_q = 0, total_q = 0;
 };
 
 // Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to
 // awq_attn_kv8_cdna4.hip (each file keeps its own kernel and argument struct).
 int launch_kv_store(const KvStoreCall& c, hipStream_t st);
 int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
+// the packed-token stores (awq_varq.hpp): device positions, dense or paged; the same split between the two files
+int launch_kv_store_varq(const KvStoreCall& c, hipStream_t st);
+int launch_kv_store_varq_fp8(const KvStoreCall& c, hipStream_t st);
 // the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
-// the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace
+// the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace; with
+// cu_seqlens_q set, its packed-query form
 int launch_kv_prefill(const KvAttnCall& c, hipStream_t st);
 
 // f(element traits, std::integral_constant<int, DH>) for dtype 0 / 1 (F16 / BF16 of awq_device.hpp) and Dh 128 / 64

@@ -1315,6 +1315,203 @@ torch::Tensor attn_prefill_paged_kv8(const torch::Tensor q, const torch::Tensor 
                            softmax_scale, causal, true);
 }
 
+// ---- Packed steps (continuous batching, include/awq_cdna4.h "varq"): the tokens of a call are one flat run of rows, sequence b owns rows
+//      cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1, read on the device.  out / q_out may be handed in (a buffer of a fixed token budget
+//      whose padding rows the launches leave alone); otherwise they are allocated and rows >= cu[B] hold whatever the allocator left.
+static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
+  TORCH_CHECK(cu.is_cuda() && cu.device() == ref.device(), who, ": cu_seqlens_q must live on the GPU of the input (it is read by the kernel only)");
+  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.size(0) >= 2 && cu.is_contiguous(), who,
+              ": cu_seqlens_q must be a contiguous int32 [B + 1] tensor");
+  TORCH_CHECK(cu.size(0) - 1 <= 65535, who, ": batch ", cu.size(0) - 1, " exceeds 65535");
+  TORCH_CHECK(max_seqlen_q >= 1, who, ": max_seqlen_q must be at least 1");
+}
+
+static at::Tensor packed_out(const char* who, const char* name, const c10::optional<torch::Tensor>& given, const torch::Tensor& ref, int64_t total,
+                             int64_t nheads, int64_t headdim) {
+  if (!given.has_value()) return torch::empty({total, nheads, headdim}, ref.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  const torch::Tensor& o = *given;
+  TORCH_CHECK(o.is_cuda() && o.device() == ref.device() && o.scalar_type() == ref.scalar_type() && o.dim() == 3 && o.size(0) == total &&
+                  o.size(1) == nheads && o.size(2) == headdim && o.is_contiguous(),
+              who, ": ", name, " must be a contiguous [total_q, H, Dh] tensor of the input's dtype on its GPU");
+  return o;
+}
+
+static torch::Tensor rope_store_varq_impl(const char* who, const torch::Tensor& qkv, const torch::Tensor& freqs, const KvTensors& kv,
+                                          const torch::Tensor& cu, int64_t max_seqlen_q, const torch::Tensor& cache_seqlens, int64_t nheads,
+                                          int64_t nheads_kv, const c10::optional<torch::Tensor>& q_out_given) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
+  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
+  TORCH_CHECK(freqs.scalar_type() == at::kFloat && freqs.dim() == 2 && freqs.is_contiguous() &&
+                  (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0,
+              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
+  TORCH_CHECK(qkv.dim() == 2, who, ": qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh]");
+  check_cu_seqlens(who, cu, qkv, max_seqlen_q);
+  const int64_t batch = cu.size(0) - 1, total = qkv.size(0);
+  check_kv(who, kv, qkv, "the input", batch, /*contiguous=*/!paged);
+  const torch::Tensor &k = kv.k, &v = kv.v;
+  const int64_t outer = k.size(0), rows = k.size(1), headdim = k.size(3), rot = freqs.size(1);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  TORCH_CHECK(total >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(1) == (nheads + 2 * nheads_kv) * headdim, who,
+              ": qkv must be [total_q, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
+  TORCH_CHECK(paged || batch <= outer, who, ": batch ", batch, " exceeds the cache batch ", outer);
+  TORCH_CHECK(freqs.size(0) >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
+              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
+  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor x = qkv;
+  if (x.stride(1) != 1 || x.stride(0) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor q_out = packed_out(who, "q_out", q_out_given, qkv, total, nheads, headdim);
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  void *xp = x.data_ptr(), *qp = q_out.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr();
+  const float* fp = freqs.data_ptr<float>();
+  float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
+  const int *pos = cache_seqlens.data_ptr<int>(), *cup = cu.data_ptr<int>();
+  const int B = (int)batch, M = (int)max_seqlen_q, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot,
+            P = (int)freqs.size(0), dt = dtype_code(x);
+  const int64_t rs = x.stride(0);
+  if (paged) {
+    const torch::Tensor& bt = *kv.block_table;
+    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+    if (fp8)
+      raise_on(awq_rope_kv_store_paged_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, cup, M, T, H, Hkv, Dh, R, P, pages, page,
+                                                pps, bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
+                                                kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), rs, dt, st));
+    else
+      raise_on(awq_rope_kv_store_paged_varq(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, cup, M, T, H, Hkv, Dh, R, P, pages, page, pps,
+                                            bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), rs, dt, st));
+  } else if (fp8) {
+    raise_on(awq_rope_kv_store_natural_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, cup, M, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
+  } else {
+    raise_on(awq_rope_kv_store_natural_varq(xp, fp, qp, kp, vp, pos, B, (int)outer, cup, M, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
+  }
+  return q_out;
+}
+
+// rope_kv_store_natural_varq[_fp8] / rope_kv_store_paged_varq[_fp8](qkv [total_q, (H + 2 Hkv) Dh], freqs_table, caches or pools ..,
+// cu_seqlens_q, max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out = None) -> q_out [total_q, H, Dh]
+torch::Tensor rope_kv_store_natural_varq(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                         const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens, int64_t nheads,
+                                         int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
+  return rope_store_varq_impl("rope_kv_store_natural_varq", qkv, freqs_table, {k_cache, v_cache, nullptr, nullptr, nullptr}, cu_seqlens_q,
+                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+}
+
+torch::Tensor rope_kv_store_natural_varq_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
+                                             torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
+                                             const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv,
+                                             c10::optional<torch::Tensor> q_out) {
+  return rope_store_varq_impl("rope_kv_store_natural_varq_fp8", qkv, freqs_table, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, cu_seqlens_q,
+                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+}
+
+torch::Tensor rope_kv_store_paged_varq(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                       const torch::Tensor block_table, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
+                                       const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
+  return rope_store_varq_impl("rope_kv_store_paged_varq", qkv, freqs_table, {k_pool, v_pool, nullptr, nullptr, &block_table}, cu_seqlens_q,
+                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+}
+
+torch::Tensor rope_kv_store_paged_varq_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
+                                           torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table,
+                                           const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
+                                           int64_t nheads, int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
+  return rope_store_varq_impl("rope_kv_store_paged_varq_fp8", qkv, freqs_table, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, cu_seqlens_q,
+                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+}
+
+static torch::Tensor attn_varq_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& cu, int64_t max_seqlen_q,
+                                    const torch::Tensor& seqlens_k, int64_t max_seqlen_k, bool lens_before_step, double softmax_scale, bool causal,
+                                    const c10::optional<torch::Tensor>& out_given) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
+  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 3 && q.stride(2) == 1 && q.stride(1) == q.size(2), who, ": q [total_q, H, Dh] (packed rows) with contiguous heads is expected");
+  check_cu_seqlens(who, cu, q, max_seqlen_q);
+  const int64_t batch = cu.size(0) - 1, total = q.size(0), nheads = q.size(1), headdim = q.size(2);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  check_kv(who, kv, q, "q", batch, /*contiguous=*/false);
+  const torch::Tensor &k = kv.k, &v = kv.v;
+  const int64_t outer = k.size(0), rows = k.size(1), nheads_kv = k.size(2), cap = paged ? kv.block_table->size(1) * rows : rows;
+  TORCH_CHECK((paged || outer >= batch) && k.size(3) == headdim, who, ": ", paged ? "k_pool / v_pool must be [num_pages, page_size, Hkv, " : "k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ",
+              headdim, "]");
+  TORCH_CHECK(total >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who, ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap,
+              paged ? " (pages_per_seq * page_size)" : " (the cache length)");
+  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = packed_out(who, "out", out_given, q, total, nheads, headdim);
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
+  const int *lens = seqlens_k.data_ptr<int>(), *cup = cu.data_ptr<int>();
+  const int B = (int)batch, M = (int)max_seqlen_q, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim,
+            before = lens_before_step ? 1 : 0, bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q);
+  const float scale = (float)softmax_scale;
+  if (paged) {
+    const torch::Tensor& bt = *kv.block_table;
+    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+    if (fp8)
+      raise_on(awq_attn_prefill_paged_varq_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, cup, M, T,
+                                               lens, before, bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1),
+                                               v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
+                                               kv.v_scale->stride(1), scale, cz, dt, st));
+    else
+      raise_on(awq_attn_prefill_paged_varq(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, cup, M, T, lens, before,
+                                           bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0),
+                                           v.stride(1), scale, cz, dt, st));
+  } else if (fp8) {
+    raise_on(awq_attn_prefill_kvcache_varq_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, cup, M, T, lens, before, bound,
+                                               (int)rows, H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                                               kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz,
+                                               dt, st));
+  } else {
+    raise_on(awq_attn_prefill_kvcache_varq(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, cup, M, T, lens, before, bound, (int)rows, H,
+                                           Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, st));
+  }
+  return out;
+}
+
+// attn_prefill_varq[_kv8] / attn_prefill_paged_varq[_kv8](q [total_q, H, Dh], caches or pools .., cu_seqlens_q, max_seqlen_q, seqlens_k,
+// max_seqlen_k, lens_before_step, softmax_scale, causal, out = None) -> out [total_q, H, Dh]: the one-pass prefill kernel over packed queries
+torch::Tensor attn_prefill_varq(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor cu_seqlens_q,
+                                int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step,
+                                double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  return attn_varq_impl("attn_prefill_varq", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k,
+                        lens_before_step, softmax_scale, causal, out);
+}
+
+torch::Tensor attn_prefill_varq_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                                    const torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
+                                    const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step, double softmax_scale, bool causal,
+                                    c10::optional<torch::Tensor> out) {
+  return attn_varq_impl("attn_prefill_varq_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, cu_seqlens_q, max_seqlen_q, seqlens_k,
+                        max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+}
+
+torch::Tensor attn_prefill_paged_varq(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                      const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k,
+                                      bool lens_before_step, double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  return attn_varq_impl("attn_prefill_paged_varq", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, cu_seqlens_q, max_seqlen_q, seqlens_k,
+                        max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+}
+
+torch::Tensor attn_prefill_paged_varq_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                          const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q,
+                                          int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step,
+                                          double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  return attn_varq_impl("attn_prefill_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, cu_seqlens_q, max_seqlen_q,
+                        seqlens_k, max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+}
+
+// (q_tile_rows, blocks) of awq_attn_varq_plan.  Host only.
+std::tuple<int64_t, int64_t> attn_varq_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t max_seqlen_q) {
+  int rows = 0, blocks = 0;
+  raise_on(awq_attn_varq_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)max_seqlen_q, &rows, &blocks));
+  return {rows, blocks};
+}
+
 // (splits, chunk) of awq_attn_kvcache_plan, made from the bound alone.  Host only.
 std::tuple<int64_t, int64_t> attn_kvcache_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t seqlen_q,
                                                int64_t max_seqlen_k) {
@@ -1745,6 +1942,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_prefill_paged_kv8", &attn_prefill_paged_kv8, "attn_prefill_paged on FP8 pools with per-(key, KV head) fp32 scale pools", py::arg("q"),
         py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
         py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("rope_kv_store_natural_varq", &rope_kv_store_natural_varq,
+        "rope_kv_store_natural_pos over PACKED tokens: qkv [total_q, (H + 2 Hkv) Dh], sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
+        py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_natural_varq_fp8", &rope_kv_store_natural_varq_fp8, "rope_kv_store_natural_varq on the FP8 cache", py::arg("qkv"),
+        py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cu_seqlens_q"),
+        py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_paged_varq", &rope_kv_store_paged_varq, "rope_kv_store_natural_varq over a paged KV cache", py::arg("qkv"),
+        py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
+        py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_paged_varq_fp8", &rope_kv_store_paged_varq_fp8, "rope_kv_store_paged_varq on FP8 pools", py::arg("qkv"),
+        py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
+        py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"),
+        py::arg("q_out") = py::none());
+  m.def("attn_prefill_varq", &attn_prefill_varq,
+        "The one-pass prefill kernel over PACKED queries q [total_q, H, Dh] with per-sequence query lengths (cu_seqlens_q) and key lengths on the device",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_prefill_varq_kv8", &attn_prefill_varq_kv8, "attn_prefill_varq on the FP8 cache", py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_prefill_paged_varq", &attn_prefill_paged_varq, "attn_prefill_varq over a paged KV cache", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_prefill_paged_varq_kv8", &attn_prefill_paged_varq_kv8, "attn_prefill_paged_varq on FP8 pools", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
+        py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"),
+        py::arg("out") = py::none());
+  m.def("attn_varq_plan", &attn_varq_plan, "(q_tile_rows, blocks) of a packed-query launch: a provisional host rule", py::arg("batch"),
+        py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("max_seqlen_q"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,
         "Encoder attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward): qkv [nnz, 3, H, Dh], cu_seqlens int32 [nseq + 1]",
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("softmax_scale"), py::arg("causal"));

@@ -19,6 +19,10 @@ window, no ALiBi.  Anything else that is asked for raises NotImplementedError na
 lengths in a device tensor.  It is served for an already updated cache (`k` / `v` None) by the split-KV kernels with device-side lengths
 (`attn_kvcache`, csrc/awq_attn_splitkv_cdna4.hip) and, for more than 128 query rows per KV head -- a prompt chunk --, by the one-pass prefill
 kernel under the same lengths (`attn_prefill_kvcache`, csrc/awq_attn_prefill_cdna4.hip).
+
+`flash_attn_varlen_func` is the step of a continuous-batching scheduler: packed queries with per-sequence query lengths (`cu_seqlens_q`)
+over a paged cache (`block_table`).  It is served by the packed-query form of the one-pass prefill kernel (`attn_prefill_paged_varq`);
+packed K / V without a cache are not implemented.
 """
 from __future__ import annotations
 
@@ -123,6 +127,34 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
     return load_engine().attn_varlen_qkvpacked(qkv, cu_seqlens, int(max_seqlen), scale, False)
 
 
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0, softmax_scale=None, causal=False,
+                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, block_table=None,
+                           **kw):
+    """flash_attn.flash_attn_varlen_func's forward over a PAGED KV cache (the continuous-batching step): q [total_q, H, Dh] packed rows,
+    cu_seqlens_q int32 [B + 1] on the GPU, k / v the pools [num_pages, page_size, Hkv, Dh] with block_table int32 [B, pages_per_seq],
+    cu_seqlens_k int32 [B + 1] whose differences are the TOTAL key lengths (formed on the device: no host read, capturable)
+    -> [total_q, H, Dh].  Served by `attn_prefill_paged_varq` (the one-pass prefill kernel over packed queries; Dh 64 or 128, page_size a
+    multiple of 64).  Packed K / V without a cache (block_table=None), dropout, a window, softcap, ALiBi and the attention probabilities
+    are not implemented and raise NotImplementedError naming the argument."""
+    if dropout_p:
+        raise NotImplementedError("flash_attn_varlen_func on MI355X: dropout_p != 0 is not implemented (inference only)")
+    asked = dict(kw, window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, return_attn_probs=return_attn_probs)
+    for name, value in asked.items():
+        if not _is_off(name, value):
+            shown = f"tensor{tuple(value.shape)}" if hasattr(value, "shape") else repr(value)
+            raise NotImplementedError(f"flash_attn_varlen_func on MI355X: keyword {name}={shown} is not implemented")
+    if block_table is None:
+        raise NotImplementedError("flash_attn_varlen_func on MI355X: block_table=None is not implemented (packed k / v without a cache; "
+                                  "k / v must be the pools [num_pages, page_size, Hkv, Dh] of a paged KV cache that already holds the new "
+                                  "tokens -- an encoder's packed qkv is served by flash_attn_varlen_qkvpacked_func)")
+    from . import load_engine
+
+    scale = float(q.shape[-1]) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    seqlens_k = (cu_seqlens_k[1:] - cu_seqlens_k[:-1]).contiguous()  # total lengths, on the device
+    return load_engine().attn_prefill_paged_varq(q, k, v, block_table, cu_seqlens_q, int(max_seqlen_q), seqlens_k, int(max_seqlen_k), False, scale,
+                                                 bool(causal))
+
+
 # ---- flash_attn.bert_padding: plain torch, any device ----
 def index_first_axis(input, indices):
     """input [n, ...] -> input[indices] (flash_attn.bert_padding.index_first_axis's forward)."""
@@ -160,8 +192,8 @@ def _namespace(name, **members):
 
 flash_attn_interface = _namespace("flash_attn_interface", flash_attn_func=flash_attn_func,
                                   flash_attn_varlen_qkvpacked_func=flash_attn_varlen_qkvpacked_func,
-                                  flash_attn_with_kvcache=flash_attn_with_kvcache)
+                                  flash_attn_varlen_func=flash_attn_varlen_func, flash_attn_with_kvcache=flash_attn_with_kvcache)
 bert_padding = _namespace("bert_padding", unpad_input=unpad_input, pad_input=pad_input, index_first_axis=index_first_axis)
 SUBMODULES = {"flash_attn_interface": flash_attn_interface, "bert_padding": bert_padding}
 
-__all__ = ["flash_attn_func", "flash_attn_varlen_qkvpacked_func", "flash_attn_with_kvcache", "flash_attn_interface", "bert_padding"]
+__all__ = ["flash_attn_func", "flash_attn_varlen_qkvpacked_func", "flash_attn_varlen_func", "flash_attn_with_kvcache", "flash_attn_interface", "bert_padding"]

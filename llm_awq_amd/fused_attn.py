@@ -40,6 +40,11 @@ Under a tensor `start_pos` a chunk of ANY length is served, with and without pag
 KV head the attention is the split-KV pair above; a longer chunk -- a prompt -- goes to the one-pass prefill kernel under the same device
 lengths (`attn_prefill_kvcache[_kv8]`, `attn_prefill_paged[_kv8]`, csrc/awq_attn_prefill_cdna4.hip).  A server prefills into the pool
 with one `forward` per chunk; a chunked prefill is one captured graph, replayed while `start_pos += chunk` runs on the device.
+
+`forward_packed(x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, ...)` is a PACKED step of continuous batching: `x` is [1, T, hidden], the new tokens of all
+sequences in one run of rows with per-sequence counts read on the device (`rope_kv_store_{natural,paged}_varq[_fp8]`,
+`attn_prefill[_paged]_varq[_kv8]`, csrc/awq_varq.hpp) -- decodes, prompt chunks and idle slots in one store launch and one attention
+launch, and one captured graph for every step of a fixed token budget.
 """
 from __future__ import annotations
 
@@ -118,7 +123,9 @@ class QuantLlamaAttentionFused(nn.Module):
         `block_table` (int32 [>= bsz, pages_per_seq] on the GPU) and `page_size` (a multiple of 64 that divides `kv_max_seq_len`) come
         together and with a tensor `start_pos`: the caches are then a pool of max_batch_size * kv_max_seq_len / page_size pages and token
         p of sequence b lives in row p % page_size of page block_table[b, p // page_size].  `decode_max_seqlen` defaults to
-        pages_per_seq * page_size."""
+        pages_per_seq * page_size.
+
+        A PACKED step of continuous batching (per-sequence numbers of new tokens) is `forward_packed`."""
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
         eng = load_engine()
@@ -177,6 +184,71 @@ class QuantLlamaAttentionFused(nn.Module):
         page_size = int(page_size)
         if page_size < 64 or page_size % 64 or self.kv_max_seq_len % page_size:
             raise ValueError(f"{who}: page_size {page_size} must be a multiple of 64 that divides kv_max_seq_len {self.kv_max_seq_len}")
+
+    def _check_packed(self, x, start_pos, cu_seqlens_q, max_seqlen_q):
+        """The packed call's conditions, before any work."""
+        who = "QuantLlamaAttentionFused"
+        if cu_seqlens_q is None or max_seqlen_q is None:
+            raise ValueError(f"{who}: cu_seqlens_q and max_seqlen_q come together")
+        if self.kv_layout != "natural":
+            raise ValueError(f"{who}: cu_seqlens_q needs kv_layout 'natural' (the FT-layout cache takes one seqlen for the batch)")
+        if not isinstance(start_pos, torch.Tensor):
+            raise ValueError(f"{who}: cu_seqlens_q needs start_pos as an int32 tensor [B] on the GPU (the packed kernels read every "
+                             "sequence's position on the device)")
+        if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or \
+                cu_seqlens_q.shape[0] != start_pos.shape[0] + 1:
+            raise ValueError(f"{who}: cu_seqlens_q must be an int32 tensor [B + 1] on the GPU for start_pos [B]")
+        if x.dim() != 3 or x.shape[0] != 1:
+            raise ValueError(f"{who}: cu_seqlens_q needs x as the packed tokens [1, T, hidden], got {tuple(x.shape)}")
+        if int(max_seqlen_q) < 1:
+            raise ValueError(f"{who}: max_seqlen_q {int(max_seqlen_q)} must be at least 1")
+
+    @torch.no_grad()
+    def forward_packed(self, x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen=None, block_table=None, page_size=None):
+        """A PACKED step of continuous batching.  `x` is [1, T, hidden], the new tokens of all B sequences in one run of rows; sequence b
+        owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (`cu_seqlens_q` int32 [B + 1] on the GPU; any mix of counts, 0 included;
+        rows >= cu_seqlens_q[B] are the padding of a fixed token budget) and `max_seqlen_q` is the host bound of every count.  `start_pos`
+        is the int32 tensor [B], `freqs` the whole angle table, `kv_layout` "natural" -- dense or with `block_table` / `page_size`, T or
+        FP8; `decode_max_seqlen` as in `forward`.  A method of its own and not two more keywords of `forward`, whose parameter list is the
+        reference's plus the paged pair.
+
+        rope_kv_store_natural_varq[_fp8] / rope_kv_store_paged_varq[_fp8] followed by attn_prefill_varq[_kv8] / attn_prefill_paged_varq
+        [_kv8] with lens_before_step: start_pos is what both launches take, and no length or token count reaches the host.  Returns
+        [1, T, hidden].  The rows of the sequences' last tokens (what the LM head needs) are out[:, cu_seqlens_q[1:] - 1], a device gather
+        that a graph captures.  Errors are raised before any work."""
+        self._check_packed(x, start_pos, cu_seqlens_q, max_seqlen_q)
+        if block_table is not None or page_size is not None:
+            self._check_paged(start_pos, block_table, page_size)
+        eng = load_engine()
+        max_seqlen_q = int(max_seqlen_q)
+        total = x.shape[1]
+        bound = self.kv_max_seq_len if decode_max_seqlen is None else int(decode_max_seqlen)
+        xqkv = self.qkv_proj(x).reshape(total, -1)
+        scale = self.head_dim ** -0.5
+        fp8 = self.kv_dtype == "fp8"
+        names = ("cache_k", "cache_v") + (("cache_k_scale", "cache_v_scale") if fp8 else ())
+        if fp8:
+            if self.cache_k.device != xqkv.device:
+                for name in names:
+                    setattr(self, name, getattr(self, name).to(xqkv.device))
+        elif self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:
+            self.cache_k = self.cache_k.to(xqkv)
+            self.cache_v = self.cache_v.to(xqkv)
+        kv = tuple(getattr(self, name) for name in names)
+        table = ()
+        if block_table is not None:
+            ps = int(page_size)
+            pool = (-1, ps, self.num_key_value_heads, self.head_dim)
+            if decode_max_seqlen is None:
+                bound = block_table.shape[1] * ps
+            kv = tuple(t.view(pool if t.dim() == 4 else pool[:3]) for t in kv)
+            table = (block_table,)
+        where = ("paged" if table else "natural", "_paged" if table else "")
+        store = getattr(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""))
+        attn = getattr(eng, "attn_prefill" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
+        xq = store(xqkv, freqs, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
+        output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, True, scale, True)
+        return self.o_proj(output.view(1, total, -1))
 
     def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None):
         """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host.  With a

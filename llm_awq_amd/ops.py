@@ -1214,6 +1214,135 @@ def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seq
     return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens)
 
 
+# ---- packed steps (continuous batching): per-sequence numbers of new tokens, read on the device ---------------------------------------
+def attn_varq_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, max_seqlen_q: int):
+    """Host-side awq_attn_varq_plan: (q_tile_rows, blocks) of a packed-query launch (no GPU needed).  64 rows when max_seqlen_q <= 64,
+    otherwise `attn_prefill_plan`'s choice for seqlen_q = max_seqlen_q capped at 128; blocks = ceil(max_seqlen_q / rows) * batch * nheads.
+    The rule is provisional, not a measurement.  The knob attn_prefill_rows forces 64 or 128; a forced 256 leaves the plan's own choice."""
+    import ctypes
+
+    r, b = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_varq_plan(batch, nheads, nheads_kv, head_dim, max_seqlen_q, ctypes.byref(r), ctypes.byref(b)))
+    return r.value, b.value
+
+
+def _check_packed(who, name, t, cu_seqlens_q, max_seqlen_q):
+    """The packed rows `t` [total_q, ..] and their cu_seqlens_q int32 [B + 1]; returns B."""
+    _on_gpu(t, cu_seqlens_q)
+    if cu_seqlens_q.device != t.device or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 2 or \
+            not cu_seqlens_q.is_contiguous():
+        raise ValueError(f"{who}: cu_seqlens_q must be a contiguous int32 [B + 1] tensor on the GPU of {name}")
+    if cu_seqlens_q.shape[0] - 1 > 65535:
+        raise ValueError(f"{who}: batch {cu_seqlens_q.shape[0] - 1} exceeds 65535")
+    if int(max_seqlen_q) < 1 or t.shape[0] < 1:
+        raise ValueError(f"{who}: max_seqlen_q >= 1 and at least one packed row are expected")
+    return cu_seqlens_q.shape[0] - 1
+
+
+def _packed_out(who, name, given, ref, H, Dh):
+    if given is None:
+        return torch.empty(ref.shape[0], H, Dh, dtype=ref.dtype, device=ref.device)
+    if given.device != ref.device or given.dtype != ref.dtype or tuple(given.shape) != (ref.shape[0], H, Dh) or not given.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous [total_q, H, Dh] tensor of the input's dtype on its GPU")
+    return given
+
+
+def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, nheads: int, nheads_kv: int, block_table=None,
+                       k_scale=None, v_scale=None, q_out=None):
+    """C-ABI awq_rope_kv_store_natural_varq[_fp8] / awq_rope_kv_store_paged_varq[_fp8]: `rope_kv_store_natural_pos` / `rope_kv_store_paged`
+    over PACKED tokens.  qkv [total_q, (H + 2 Hkv) * Dh] with a unit last stride; sequence b owns rows cu_seqlens_q[b] ..
+    cu_seqlens_q[b + 1] - 1 (int32 [B + 1] on the GPU, non-decreasing, cu[0] = 0; the host never reads it).  Token s = t - cu[b] of
+    sequence b is rotated by row cache_seqlens[b] + s of freqs_table [P, rot_dim] and stored at that position of k / v -- the contiguous
+    caches [Bc >= B, Lmax, Hkv, Dh], or with block_table [>= B, pages_per_seq] the pools [num_pages, page_size, Hkv, Dh]; with k_scale /
+    v_scale the FP8 format.  Sq_b = 0 is a slot with nothing to do.  A sequence with cache_seqlens[b] < 0, Sq_b > max_seqlen_q or
+    cache_seqlens[b] + Sq_b > min(capacity, P) is inactive: nothing of it is stored and its q rows are zeros.  Rows >= cu[B] (the padding
+    of a fixed token budget) are neither read nor written: hand q_out in to keep what they hold.  For every active sequence the rows,
+    the cache bytes and the scales are those of the rectangular call on that sequence alone.  Returns the rotated q [total_q, H, Dh]."""
+    who = "rope_kv_store_varq"
+    fp8 = k_scale is not None or v_scale is not None
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError(f"{who}: k_scale and v_scale come together")
+    _on_gpu(qkv, freqs_table, cache_seqlens)
+    if qkv.dim() != 2 or qkv.stride(1) != 1:
+        raise ValueError(f"{who}: qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh] with a unit last stride")
+    B = _check_packed(who, "qkv", qkv, cu_seqlens_q, max_seqlen_q)
+    if block_table is not None:
+        kv = _check_pools(who, qkv, k, v, block_table, k_scale, v_scale, B)
+    else:
+        _on_gpu(k, v, *((k_scale, v_scale) if fp8 else ()))
+        kv = _caches(who, qkv, k, v, k_scale, v_scale)
+        if kv.outer < B:
+            raise ValueError(f"{who}: batch {B} exceeds the cache batch {kv.outer}")
+    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
+        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
+    if nheads_kv != kv.Hkv or qkv.shape[1] != (nheads + 2 * nheads_kv) * kv.Dh:
+        raise ValueError(f"{who}: qkv must be [total_q, (H + 2 Hkv) * Dh] with the " + ("pools'" if kv.paged else "caches'") + " Hkv and Dh")
+    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
+    q_out = _packed_out(who, "q_out", q_out, qkv, int(nheads), kv.Dh)
+    head = (qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), *kv.ptrs())
+    packed = (cu_seqlens_q.data_ptr(), int(max_seqlen_q), qkv.shape[0])
+    shape = (int(nheads), int(nheads_kv), kv.Dh, freqs_table.shape[1])
+    tail = (qkv.stride(0), _dt(qkv), _stream(qkv))
+    if kv.paged:
+        entry, args = "paged_varq", (*head, kv.block_table.data_ptr(), cache_seqlens.data_ptr(), B, *packed, *shape, freqs_table.shape[0],
+                                     *kv.table(), *kv.strides(), *tail)
+    else:
+        entry, args = "natural_varq", (*head, cache_seqlens.data_ptr(), B, kv.outer, *packed, *shape, kv.rows, freqs_table.shape[0], *tail)
+    with torch.cuda.device(qkv.device):
+        _capi.check(getattr(_capi.lib(), "awq_rope_kv_store_" + entry + ("_fp8" if kv.fp8 else ""))(*args))
+    return q_out
+
+
+def attn_prefill_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, lens_before_step: bool = True, block_table=None,
+                      softmax_scale=None, causal: bool = True, k_scale=None, v_scale=None, out=None):
+    """C-ABI awq_attn_prefill_kvcache_varq[_kv8] / awq_attn_prefill_paged_varq[_kv8]: `attn_prefill_kvcache` / `attn_prefill_paged` over
+    PACKED queries.  q [total_q, H, Dh] with contiguous heads; sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 and brings
+    Sq_b = cu[b + 1] - cu[b] <= max_seqlen_q rows (0 is legal).  k / v are the caches [Bc >= B, Lmax, Hkv, Dh] or, with block_table, the
+    pools; with k_scale / v_scale FP8 codes.  lens_before_step: Sk_b = seqlens_k[b] + Sq_b -- seqlens_k is then the cache_seqlens that
+    `rope_kv_store_varq` took; otherwise Sk_b = seqlens_k[b].  Row s of sequence b attends keys j <= s + Sk_b - Sq_b (causal; a negative
+    limit returns zeros) or keys 0 .. Sk_b - 1.  A sequence with Sq_b > max_seqlen_q, Sk_b < 1 or Sk_b > max_seqlen_k is inactive: its
+    first min(Sq_b, max_seqlen_q) rows are zeros, nothing else of it is written and none of its keys is read.  Rows >= cu[B] are neither
+    read nor written: hand `out` in to keep what they hold.  For every active sequence with Sk_b >= Sq_b the rows are bit-identical to the
+    rectangular call on that sequence alone under the same q tile (`attn_varq_plan`).  max_seqlen_q sizes the grid: a loose bound costs
+    empty blocks.  Capturable: a replay follows what cu_seqlens_q, the lengths and the table hold then.  Returns out [total_q, H, Dh]."""
+    who = "attn_prefill_varq"
+    _on_gpu(q)
+    if q.dim() != 3 or q.stride(2) != 1 or q.stride(1) != q.shape[2]:
+        raise ValueError(f"{who}: q must be the packed rows [total_q, H, Dh] with contiguous heads")
+    B = _check_packed(who, "q", q, cu_seqlens_q, max_seqlen_q)
+    T, H, Dh = q.shape
+    fp8 = k_scale is not None or v_scale is not None
+    if block_table is not None:
+        kv = _check_pools(who, q, k, v, block_table, k_scale, v_scale, B)
+    else:
+        if fp8:
+            if k_scale is None or v_scale is None:
+                raise ValueError(f"{who}: k_scale and v_scale come together")
+            _check_kv8(who, q.unsqueeze(0), k[:1], v[:1], k_scale[:1], v_scale[:1])  # (the checks of the host-length FP8 entries, on one cache row)
+        else:
+            for t in (k, v):
+                _on_gpu(t)
+                if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+                    raise ValueError(f"{who}: k / v must be [Bc, Lmax, Hkv, Dh] with contiguous heads")
+            if k.device != q.device or v.device != q.device or k.dtype != q.dtype or v.dtype != q.dtype:
+                raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
+        if k.shape != v.shape or k.shape[0] < B:
+            raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [Bc >= B, Lmax, Hkv, Dh] are expected")
+        kv = _Kv(k, v, k_scale, v_scale)
+    if kv.Dh != Dh:
+        raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [.., Hkv, Dh] must share Dh, got {Dh} and {kv.Dh}")
+    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    out = _packed_out(who, "out", out, q, H, Dh)
+    lens = (B, cu_seqlens_q.data_ptr(), int(max_seqlen_q), T, seqlens_k.data_ptr(), int(bool(lens_before_step)), int(max_seqlen_k))
+    where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
+    entry = getattr(_capi.lib(), "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + "_varq" + ("_kv8" if kv.fp8 else ""))
+    with torch.cuda.device(q.device):
+        _capi.check(entry(q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), *kv.strides(), scale, int(bool(causal)),
+                          _dt(q), _stream(q)))
+    return out
+
+
 def _ft_caches(who, ref, k_cache, v_cache):
     """(Bc, Hkv, Lmax, Dh) of the FT caches k_cache [Bc, Hkv, Dh/8, Lmax, 8] / v_cache [Bc, Hkv, Lmax, Dh], checked against `ref`."""
     for t in (ref, k_cache, v_cache):
