@@ -20,10 +20,10 @@
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kvcache.hpp"
+#include "awq_kvstore.hpp"
 #include "awq_paged.hpp"
+#include "awq_rope.hpp"
 #include "awq_varq.hpp"
-
-#include <math.h>
 
 namespace awq {
 namespace {
@@ -42,23 +42,6 @@ struct RopeStoreArgs {
   long long k_ps, k_rs, v_ps, v_rs;
   VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
-
-template <typename DT>
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
-  const u32 ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
-    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
-  }
-}
-template <typename DT>
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  u32 ws[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
-  return u32x4{ws[0], ws[1], ws[2], ws[3]};
-}
 
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
@@ -226,52 +209,27 @@ int launch_rope_kv_store(const void* qkv, const float* freqs, void* q_out, void*
   return 0;
 }
 
-namespace {
-template <template <typename> class L>
-void launch_store(const RopeStoreArgs& a, int dtype, int Dh, hipStream_t st) {
-  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
-    hipLaunchKernelGGL((rope_kv_store_natural_kernel<L<decltype(dt)>, decltype(dh)::value>), dim3((unsigned)a.qv_blocks), dim3(256), 0, st, a);
-  });
-}
-}  // namespace
-
-// The natural-layout store on the T cache (a view with scales goes to awq_attn_kv8_cdna4.hip).  Device positions: cache_seqlens in the
-// place of start_pos and the whole angle table [table_rows, rot] in the place of the call's angles.  Paged: the pools and their table in
-// the place of the caches, lmax = the capacity of a table row.
+// The natural-layout store on the T cache (a view with scales goes to awq_attn_kv8_cdna4.hip): the rectangle or a packed step, host or
+// device positions, dense caches or pools -- the form is what the descriptor holds (for_kv_store_form, awq_kvstore.hpp).  Device positions:
+// cache_seqlens in the place of start_pos and the whole angle table [table_rows, rot] in the place of the call's angles.  Paged: the pools
+// and their table in the place of the caches, lmax = the capacity of a table row.  A packed call carries S = max_seqlen_q and bs = 0 in
+// the descriptor already; its grid covers the total_q rows.
 int launch_kv_store(const KvStoreCall& c, hipStream_t st) {
   const KvView& kv = c.kv;
   if (kv.k_scale) return launch_kv_store_fp8(c, st);
-  const int nb = (int)(((long long)c.B * c.S * (c.Dh / 8) + 255) / 256);
   RopeStoreArgs a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint16_t*)kv.k, (uint16_t*)kv.v, c.bs, c.rs, c.B, c.S, c.H, c.Hkv,
-                  c.rot, kv.capacity(), c.cache_seqlens ? c.table_rows : c.start_pos, nb, c.cache_seqlens};
+                  c.rot, kv.capacity(), c.cache_seqlens ? c.table_rows : c.start_pos, (int)kv_store_blocks(c), c.cache_seqlens};
   if (kv.block_table) {
     a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
     a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
-    launch_store<PagedDevLen>(a, c.dtype, c.Dh, st);
-  } else if (c.cache_seqlens) {
-    launch_store<DevLen>(a, c.dtype, c.Dh, st);
-  } else {
-    launch_store<HostLen>(a, c.dtype, c.Dh, st);
   }
-  return 0;
-}
-
-// The packed-token store (awq_varq.hpp): the grid covers the total_q rows of the call, ceil(total_q * Dh / 8 / 256) blocks from host
-// arguments only; a.S is the host's bound max_seqlen_q.
-int launch_kv_store_varq(const KvStoreCall& c, hipStream_t st) {
-  const KvView& kv = c.kv;
-  if (kv.k_scale) return launch_kv_store_varq_fp8(c, st);
-  const int nb = (int)(((long long)c.total_q * (c.Dh / 8) + 255) / 256);
-  RopeStoreArgs a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint16_t*)kv.k, (uint16_t*)kv.v, 0, c.rs, c.B, c.max_seqlen_q, c.H, c.Hkv,
-                  c.rot, kv.capacity(), c.table_rows, nb, c.cache_seqlens};
-  a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
-  if (kv.block_table) {
-    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
-    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
-    launch_store<VarQPagedDevLen>(a, c.dtype, c.Dh, st);
-  } else {
-    launch_store<VarQDevLen>(a, c.dtype, c.Dh, st);
-  }
+  if (c.cu_seqlens_q) a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  for_kv_store_form(c, [&](auto form) {
+    for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
+      using DT = typename decltype(form)::template of<decltype(dt)>;
+      hipLaunchKernelGGL((rope_kv_store_natural_kernel<DT, decltype(dh)::value>), dim3((unsigned)a.qv_blocks), dim3(256), 0, st, a);
+    });
+  });
   return 0;
 }
 

@@ -22,10 +22,10 @@
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
+#include "awq_kvstore.hpp"
 #include "awq_paged.hpp"
+#include "awq_rope.hpp"
 #include "awq_varq.hpp"
-
-#include <math.h>
 
 namespace awq {
 namespace {
@@ -48,24 +48,6 @@ struct RopeStoreFp8Args {
   VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
 
-template <typename DT>
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
-  const u32 ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
-    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
-  }
-}
-template <typename DT>
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  u32 ws[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
-  return u32x4{ws[0], ws[1], ws[2], ws[3]};
-}
-
-//
 // DevLen<..> (awq_devlen.hpp, awq_rope_kv_store_natural_pos_fp8): rope_kv_store_natural_kernel's device positions.  a.freqs is the whole
 // angle table [a.start rows, rot], pos_b = a.seqlens[b]; an inactive sequence (pos_b < 0 or pos_b + S > min(lmax, table rows)) gets a zero
 // q_out and nothing else.  The CPR lanes of a (b, s) share b, so they leave or stay together and the butterflies below never meet a lane
@@ -175,18 +157,10 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
   for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), vc, vsc, hd);
 }
 
-template <template <typename> class L>
-void launch_store(const RopeStoreFp8Args& a, int dtype, int Dh, hipStream_t st) {
-  const long long tokens = a.vq.cu_seqlens_q ? (long long)a.vq.total_q : (long long)a.B * a.S;
-  const dim3 grid((unsigned)((tokens * (Dh / 8) + 255) / 256));
-  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
-    hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<L<decltype(dt)>, decltype(dh)::value>), grid, dim3(256), 0, st, a);
-  });
-}
-
 }  // namespace
 
-// launch_kv_store's FP8 half: the same three forms (host position, device positions, device positions over pools) with codes and scales
+// launch_kv_store's FP8 half: the same forms (the rectangle or a packed step; host position, device positions, device positions over
+// pools) with codes and scales
 int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st) {
   const KvView& kv = c.kv;
   RopeStoreFp8Args a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint8_t*)kv.k, (uint8_t*)kv.v, (float*)kv.k_scale, (float*)kv.v_scale,
@@ -195,29 +169,14 @@ int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st) {
     a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
     a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
     a.ks_ps = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_ps = kv.vs_os, a.vs_rs = kv.vs_rs;
-    launch_store<PagedDevLen>(a, c.dtype, c.Dh, st);
-  } else if (c.cache_seqlens) {
-    launch_store<DevLen>(a, c.dtype, c.Dh, st);
-  } else {
-    launch_store<HostLen>(a, c.dtype, c.Dh, st);
   }
-  return 0;
-}
-
-// launch_kv_store_varq's FP8 half
-int launch_kv_store_varq_fp8(const KvStoreCall& c, hipStream_t st) {
-  const KvView& kv = c.kv;
-  RopeStoreFp8Args a{(const uint16_t*)c.qkv, c.freqs, (uint16_t*)c.q_out, (uint8_t*)kv.k, (uint8_t*)kv.v, (float*)kv.k_scale, (float*)kv.v_scale,
-                     0, c.rs, c.B, c.max_seqlen_q, c.H, c.Hkv, c.rot, kv.capacity(), c.table_rows, c.cache_seqlens};
-  a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
-  if (kv.block_table) {
-    a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
-    a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
-    a.ks_ps = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_ps = kv.vs_os, a.vs_rs = kv.vs_rs;
-    launch_store<VarQPagedDevLen>(a, c.dtype, c.Dh, st);
-  } else {
-    launch_store<VarQDevLen>(a, c.dtype, c.Dh, st);
-  }
+  if (c.cu_seqlens_q) a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  for_kv_store_form(c, [&](auto form) {
+    for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
+      using DT = typename decltype(form)::template of<decltype(dt)>;
+      hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DT, decltype(dh)::value>), dim3(kv_store_blocks(c)), dim3(256), 0, st, a);
+    });
+  });
   return 0;
 }
 

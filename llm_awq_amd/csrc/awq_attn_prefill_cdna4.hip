@@ -29,6 +29,7 @@
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_rope.hpp"
 #include "awq_varq.hpp"
 
 #include <math.h>
@@ -472,23 +473,6 @@ struct RopePosArgs {
 };
 
 template <typename DT>
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&f)[8]) {
-  const u32 ws[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[2 * e] = DT::to_float((uint16_t)(ws[e] & 0xFFFFu));
-    f[2 * e + 1] = DT::to_float((uint16_t)(ws[e] >> 16));
-  }
-}
-template <typename DT>
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-  u32 ws[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(f[2 * e]) | ((u32)DT::from_float(f[2 * e + 1]) << 16);
-  return u32x4{ws[0], ws[1], ws[2], ws[3]};
-}
-
-template <typename DT>
 __global__ __launch_bounds__(256) void rope_with_pos_kernel(RopePosArgs a) {
   const int cpr = a.d >> 3;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -496,7 +480,7 @@ __global__ __launch_bounds__(256) void rope_with_pos_kernel(RopePosArgs a) {
   const int ch = (int)(id % cpr);
   const long long pos = id / cpr;
   const int i1 = (int)(pos % a.n1), i0 = (int)(pos / a.n1);
-  const int c0 = ch * 8, half = a.d2 >> 1;
+  const int c0 = ch * 8;
   const uint16_t* src = a.in + i0 * a.s0 + i1 * a.s1;
   uint16_t* dst = a.out + i0 * a.o0 + i1 * a.o1;
   if (c0 >= a.d2) {
@@ -504,23 +488,8 @@ __global__ __launch_bounds__(256) void rope_with_pos_kernel(RopePosArgs a) {
       *reinterpret_cast<u32x4*>(dst + hd * a.oh + c0) = *reinterpret_cast<const u32x4*>(src + hd * a.sh + c0);
     return;
   }
-  const float* fr = a.freqs + ((long long)i1 * a.n0 + i0) * a.d2 + c0;
-  const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
-  const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
-  float cs[8], sn[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
-  const bool first = c0 + half < a.d2;
-  const int pc = first ? c0 + half : c0 - half;
-  const float sign = first ? -1.f : 1.f;
-  for (int hd = 0; hd < a.h; ++hd) {
-    float x[8], y[8], res[8];
-    unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * a.sh + c0), x);
-    unpack8<DT>(*reinterpret_cast<const u32x4*>(src + hd * a.sh + pc), y);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) res[e] = __builtin_fmaf(x[e], cs[e], (sign * y[e]) * sn[e]);
-    *reinterpret_cast<u32x4*>(dst + hd * a.oh + c0) = pack8<DT>(res);
-  }
+  const RopeLane rope(a.freqs + ((long long)i1 * a.n0 + i0) * a.d2 + c0, c0, a.d2);  // awq_rope.hpp
+  for (int hd = 0; hd < a.h; ++hd) *reinterpret_cast<u32x4*>(dst + hd * a.oh + c0) = rope.rotate<DT>(src + hd * a.sh, c0);
 }
 
 // rotary_embedding_neox (awq/kernels/csrc/position_embedding/pos_encoding_kernels.cu:12-87): in place on query and key

@@ -492,8 +492,7 @@ static int kv_store(const KvStoreCall& c, int fmt, void* stream) {
   if (!aligned16(c.qkv) || !aligned16(c.freqs) || !aligned16(c.q_out) || !kv_aligned(kv, fmt, paged) || (devlen && !aligned4(c.cache_seqlens)) ||
       (varq && !aligned4(c.cu_seqlens_q)) || (c.bs % 8) != 0 || (c.rs % 8) != 0)
     return AWQ_ERR_ALIGN;
-  if (varq) awq::launch_kv_store_varq(c, (hipStream_t)stream);
-  else awq::launch_kv_store(c, (hipStream_t)stream);
+  awq::launch_kv_store(c, (hipStream_t)stream);
   return finish_launch();
 }
 

@@ -67,12 +67,10 @@ struct KvAttnCall {
 };
 
 // Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to
-// awq_attn_kv8_cdna4.hip (each file keeps its own kernel and argument struct).
+// awq_attn_kv8_cdna4.hip: each file keeps its own kernel and argument struct; the form and the grid come from awq_kvstore.hpp.  With
+// cu_seqlens_q set, the packed-token store (awq_varq.hpp): device positions, dense or paged.
 int launch_kv_store(const KvStoreCall& c, hipStream_t st);
 int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
-// the packed-token stores (awq_varq.hpp): device positions, dense or paged; the same split between the two files
-int launch_kv_store_varq(const KvStoreCall& c, hipStream_t st);
-int launch_kv_store_varq_fp8(const KvStoreCall& c, hipStream_t st);
 // the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
 // the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace; with

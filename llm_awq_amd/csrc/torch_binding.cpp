@@ -1064,12 +1064,43 @@ static void check_kv(const char* who, const KvTensors& kv, const torch::Tensor& 
   }
 }
 
+// A packed step (continuous batching, include/awq_cdna4.h "varq"), the optional part of a call's description: the tokens are one flat run
+// of rows, sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1, read on the device.  out / q_out may be handed in (a buffer of
+// a fixed token budget whose padding rows the launches leave alone); otherwise they are allocated and rows >= cu[B] hold whatever the
+// allocator left.  cu == nullptr: the rectangle [B, S].
+struct PackedStep {
+  const torch::Tensor* cu = nullptr;
+  int64_t max_seqlen_q = 0;
+  const c10::optional<torch::Tensor>* out = nullptr;
+  bool lens_before_step = false;  // attention only
+};
+
+static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
+  TORCH_CHECK(cu.is_cuda() && cu.device() == ref.device(), who, ": cu_seqlens_q must live on the GPU of the input (it is read by the kernel only)");
+  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.size(0) >= 2 && cu.is_contiguous(), who,
+              ": cu_seqlens_q must be a contiguous int32 [B + 1] tensor");
+  TORCH_CHECK(cu.size(0) - 1 <= 65535, who, ": batch ", cu.size(0) - 1, " exceeds 65535");
+  TORCH_CHECK(max_seqlen_q >= 1, who, ": max_seqlen_q must be at least 1");
+}
+
+static at::Tensor packed_out(const char* who, const char* name, const c10::optional<torch::Tensor>& given, const torch::Tensor& ref, int64_t total,
+                             int64_t nheads, int64_t headdim) {
+  if (!given.has_value()) return torch::empty({total, nheads, headdim}, ref.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  const torch::Tensor& o = *given;
+  TORCH_CHECK(o.is_cuda() && o.device() == ref.device() && o.scalar_type() == ref.scalar_type() && o.dim() == 3 && o.size(0) == total &&
+                  o.size(1) == nheads && o.size(2) == headdim && o.is_contiguous(),
+              who, ": ", name, " must be a contiguous [total_q, H, Dh] tensor of the input's dtype on its GPU");
+  return o;
+}
+
 // The store bindings.  cache_seqlens == nullptr: the host position start_pos, freqs holds the call's B * S * rot_dim angles (copied when
 // misaligned).  Otherwise each sequence's position is read on the device and freqs is the model's whole table [P, rot_dim] (not copied:
-// a misaligned one is refused).  One launch (csrc/awq_attn_chunk_cdna4.hip, csrc/awq_attn_kv8_cdna4.hip).
+// a misaligned one is refused).  step: qkv is the packed tokens [total_q, ..] (device positions only).  One launch
+// (csrc/awq_attn_chunk_cdna4.hip, csrc/awq_attn_kv8_cdna4.hip).
 static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, const torch::Tensor& freqs, const KvTensors& kv,
-                                     const torch::Tensor* cache_seqlens, int64_t start_pos, int64_t nheads, int64_t nheads_kv) {
-  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, devlen = cache_seqlens != nullptr;
+                                     const torch::Tensor* cache_seqlens, int64_t start_pos, int64_t nheads, int64_t nheads_kv,
+                                     const PackedStep& step = {}) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, devlen = cache_seqlens != nullptr, packed = step.cu != nullptr;
   TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
   TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
@@ -1080,14 +1111,25 @@ static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, 
   } else {
     TORCH_CHECK(freqs.scalar_type() == at::kFloat, who, ": freqs must be float32");
   }
-  TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
-  const int64_t batch = qkv.size(0), seqlen = qkv.size(1);
+  if (packed) {
+    TORCH_CHECK(qkv.dim() == 2, who, ": qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh]");
+    check_cu_seqlens(who, *step.cu, qkv, step.max_seqlen_q);
+  } else {
+    TORCH_CHECK(qkv.dim() == 3 && freqs.dim() >= 1, who, ": qkv must be [B, S, (H + 2 Hkv) * Dh]");
+  }
+  // the rectangle [batch, seqlen], or total packed rows of batch sequences that bring at most seqlen each
+  const int64_t batch = packed ? step.cu->size(0) - 1 : qkv.size(0), seqlen = packed ? step.max_seqlen_q : qkv.size(1), total = qkv.size(0);
   check_kv(who, kv, qkv, "the input", batch, /*contiguous=*/!paged);
   const torch::Tensor &k = kv.k, &v = kv.v;
   const int64_t outer = k.size(0), rows = k.size(1), headdim = k.size(3), rot = freqs.size(-1);
   TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
-              ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
+  if (packed) {
+    TORCH_CHECK(total >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(1) == (nheads + 2 * nheads_kv) * headdim, who,
+                ": qkv must be [total_q, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
+  } else {
+    TORCH_CHECK(batch >= 1 && seqlen >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(2) == (nheads + 2 * nheads_kv) * headdim, who,
+                ": qkv must be [B, S, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
+  }
   TORCH_CHECK(paged || batch <= outer, who, ": batch ", batch, " exceeds the cache batch ", outer);
   if (devlen) {
     TORCH_CHECK(freqs.size(0) >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
@@ -1100,29 +1142,43 @@ static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, 
                 ": freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
   }
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
-  at::Tensor x = qkv;
-  if (x.stride(2) != 1 || x.stride(0) % 8 || x.stride(1) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
+  at::Tensor x = qkv;  // rows of a unit stride, every other stride a multiple of 16 bytes
+  if (x.stride(-1) != 1 || x.stride(0) % 8 || x.stride(-2) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
   at::Tensor fr = devlen || (freqs.is_contiguous() && (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0) ? freqs : freqs.contiguous().clone();
-  at::Tensor q_out = torch::empty({batch, seqlen, nheads, headdim}, qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
+  at::Tensor q_out = packed ? packed_out(who, "q_out", *step.out, qkv, total, nheads, headdim)
+                            : torch::empty({batch, seqlen, nheads, headdim},
+                                           qkv.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
   void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   void *xp = x.data_ptr(), *qp = q_out.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr();
   const float* fp = fr.data_ptr<float>();
   float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
-  const int* pos = devlen ? cache_seqlens->data_ptr<int>() : nullptr;
-  const int B = (int)batch, S = (int)seqlen, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot, dt = dtype_code(x);
-  const int64_t bs = x.stride(0), rs = x.stride(1);
+  const int *pos = devlen ? cache_seqlens->data_ptr<int>() : nullptr, *cup = packed ? step.cu->data_ptr<int>() : nullptr;
+  // S: the rectangle's seqlen, or the packed step's bound max_seqlen_q; T: the packed rows
+  const int B = (int)batch, S = (int)seqlen, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot,
+            P = devlen ? (int)freqs.size(0) : 0, dt = dtype_code(x);
+  const int64_t bs = x.stride(0), rs = x.stride(-2);
   if (paged) {
     const torch::Tensor& bt = *kv.block_table;
-    const int P = (int)freqs.size(0), pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
-    if (fp8)
+    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
+    const int64_t kps = k.stride(0), krs = k.stride(1), vps = v.stride(0), vrs = v.stride(1);
+    if (packed && fp8)
+      raise_on(awq_rope_kv_store_paged_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page,
+                                                pps, bt.stride(0), kps, krs, vps, vrs, kv.k_scale->stride(0), kv.k_scale->stride(1),
+                                                kv.v_scale->stride(0), kv.v_scale->stride(1), rs, dt, st));
+    else if (packed)
+      raise_on(awq_rope_kv_store_paged_varq(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page, pps,
+                                            bt.stride(0), kps, krs, vps, vrs, rs, dt, st));
+    else if (fp8)
       raise_on(awq_rope_kv_store_paged_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps,
-                                               bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
-                                               kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), bs, rs, dt, st));
+                                               bt.stride(0), kps, krs, vps, vrs, kv.k_scale->stride(0), kv.k_scale->stride(1),
+                                               kv.v_scale->stride(0), kv.v_scale->stride(1), bs, rs, dt, st));
     else
       raise_on(awq_rope_kv_store_paged_pos(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps, bt.stride(0),
-                                           k.stride(0), k.stride(1), v.stride(0), v.stride(1), bs, rs, dt, st));
+                                           kps, krs, vps, vrs, bs, rs, dt, st));
+  } else if (packed) {
+    if (fp8) raise_on(awq_rope_kv_store_natural_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
+    else raise_on(awq_rope_kv_store_natural_varq(xp, fp, qp, kp, vp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
   } else if (devlen) {
-    const int P = (int)freqs.size(0);
     if (fp8) raise_on(awq_rope_kv_store_natural_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
     else raise_on(awq_rope_kv_store_natural_pos(xp, fp, qp, kp, vp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
   } else {
@@ -1180,22 +1236,32 @@ torch::Tensor rope_kv_store_paged_pos_fp8(const torch::Tensor qkv, const torch::
 // attn_kvcache[_paged][_kv8](q, caches or pools .., seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal) -> out: the split-KV pair
 // with Sk_b = seqlens_k[b] + seqlen_offset read on the device, K / V from the caches or fetched from the pools through the table.  The fp32
 // partials live in a buffer of torch's caching allocator, so a graph capture owns them.  one_pass: attn_prefill_kvcache[_kv8] /
-// attn_prefill_paged[_kv8], the one-pass prefill kernel under the same lengths -- any seqlen_q, no workspace.
+// attn_prefill_paged[_kv8], the one-pass prefill kernel under the same lengths -- any seqlen_q, no workspace.  step (one_pass only): q is
+// the packed rows [total_q, H, Dh], and the flag lens_before_step stands in the place of seqlen_offset.
 static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& seqlens_k,
-                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal, bool one_pass = false) {
-  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
+                                       int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal, bool one_pass = false,
+                                       const PackedStep& step = {}) {
+  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, packed = step.cu != nullptr;
   TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
   TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
-  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
-  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
+  if (packed) {
+    TORCH_CHECK(q.dim() == 3 && q.stride(2) == 1 && q.stride(1) == q.size(2), who, ": q [total_q, H, Dh] (packed rows) with contiguous heads is expected");
+    check_cu_seqlens(who, *step.cu, q, step.max_seqlen_q);
+  } else {
+    TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
+  }
+  // the rectangle [batch, sq], or total packed rows of batch sequences that bring at most sq each
+  const int64_t batch = packed ? step.cu->size(0) - 1 : q.size(0), sq = packed ? step.max_seqlen_q : q.size(1), total = q.size(0),
+                nheads = q.size(-2), headdim = q.size(-1);
+  if (packed) seqlen_offset = step.lens_before_step ? 1 : 0;
   TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
   check_kv(who, kv, q, "q", batch, /*contiguous=*/false);
   const torch::Tensor &k = kv.k, &v = kv.v;
   const int64_t outer = k.size(0), rows = k.size(1), nheads_kv = k.size(2), cap = paged ? kv.block_table->size(1) * rows : rows;
   TORCH_CHECK((paged || outer >= batch) && k.size(3) == headdim, who, ": ", paged ? "k_pool / v_pool must be [num_pages, page_size, Hkv, " : "k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ",
               headdim, "]");
-  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+  TORCH_CHECK((packed ? total >= 1 : batch >= 1 && sq >= 1) && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
               ": empty tensors are not supported and H must be a multiple of Hkv");
   TORCH_CHECK(one_pass || sq * (nheads / nheads_kv) <= 128, who, ": seqlen_q * (H / Hkv) = ", sq * (nheads / nheads_kv),
               " exceeds 128 (the split kernels serve few query rows; ",
@@ -1205,58 +1271,59 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
   check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
-  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  at::Tensor out = packed ? packed_out(who, "out", *step.out, q, total, nheads, headdim)
+                          : torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
   const size_t wsb = one_pass ? 0 : awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
   at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
   void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  void *qp = q.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr(), *op = out.data_ptr();
   const float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
-  const int* lens = seqlens_k.data_ptr<int>();
-  const int B = (int)batch, Sq = (int)sq, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, off = (int)seqlen_offset,
-            bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q);
+  const int *lens = seqlens_k.data_ptr<int>(), *cup = packed ? step.cu->data_ptr<int>() : nullptr;
+  // Sq: the rectangle's seqlen_q, or the packed step's bound max_seqlen_q; T: the packed rows; off: seqlen_offset, or the flag
+  const int B = (int)batch, Sq = (int)sq, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, off = (int)seqlen_offset,
+            bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q), L = (int)rows;
   const float scale = (float)softmax_scale;
-  if (one_pass) {
-    if (paged) {
-      const torch::Tensor& bt = *kv.block_table;
-      const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
-      if (fp8)
-        raise_on(awq_attn_prefill_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off,
-                                            bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                                            v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
-                                            kv.v_scale->stride(1), scale, cz, dt, st));
-      else
-        raise_on(awq_attn_prefill_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off, bound, pages,
-                                        page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
-                                        v.stride(1), scale, cz, dt, st));
-    } else if (fp8) {
-      raise_on(awq_attn_prefill_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H,
-                                            Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                            kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz,
-                                            dt, st));
-    } else {
-      raise_on(awq_attn_prefill_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh,
-                                        q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, st));
-    }
-    return out;
-  }
-  if (paged) {
-    const torch::Tensor& bt = *kv.block_table;
-    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
-    if (fp8)
-      raise_on(awq_attn_kvcache_paged_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off,
-                                          bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                                          v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
-                                          kv.v_scale->stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+  const int64_t qbs = q.stride(0), qrs = q.stride(-3), kbs = k.stride(0), krs = k.stride(1), vbs = v.stride(0), vrs = v.stride(1),
+                ksbs = fp8 ? kv.k_scale->stride(0) : 0, ksrs = fp8 ? kv.k_scale->stride(1) : 0, vsbs = fp8 ? kv.v_scale->stride(0) : 0,
+                vsrs = fp8 ? kv.v_scale->stride(1) : 0;
+  const int* btp = paged ? kv.block_table->data_ptr<int>() : nullptr;
+  const int pages = (int)outer, page = (int)rows, pps = paged ? (int)kv.block_table->size(1) : 0;
+  const int64_t btrs = paged ? kv.block_table->stride(0) : 0;
+  if (packed) {
+    if (paged && fp8)
+      raise_on(awq_attn_prefill_paged_varq_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs,
+                                               kbs, krs, vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, st));
+    else if (paged)
+      raise_on(awq_attn_prefill_paged_varq(qp, kp, vp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs, vbs,
+                                           vrs, scale, cz, dt, st));
+    else if (fp8)
+      raise_on(awq_attn_prefill_kvcache_varq_kv8(qp, kp, vp, ksp, vsp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, ksbs,
+                                                 ksrs, vsbs, vsrs, scale, cz, dt, st));
     else
-      raise_on(awq_attn_kvcache_paged(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, Sq, lens, off, bound, pages,
-                                      page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
-                                      v.stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
-  } else if (fp8) {
-    raise_on(awq_attn_kvcache_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh,
-                                  q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
-                                  kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+      raise_on(awq_attn_prefill_kvcache_varq(qp, kp, vp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, scale, cz, dt, st));
+  } else if (one_pass) {
+    if (paged && fp8)
+      raise_on(awq_attn_prefill_paged_kv8(qp, kp, vp, ksp, vsp, op, btp, B, Sq, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qbs, qrs, kbs, krs,
+                                          vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, st));
+    else if (paged)
+      raise_on(awq_attn_prefill_paged(qp, kp, vp, op, btp, B, Sq, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs,
+                                      scale, cz, dt, st));
+    else if (fp8)
+      raise_on(awq_attn_prefill_kvcache_kv8(qp, kp, vp, ksp, vsp, op, B, Sq, lens, off, bound, L, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs, ksbs, ksrs,
+                                            vsbs, vsrs, scale, cz, dt, st));
+    else raise_on(awq_attn_prefill_kvcache(qp, kp, vp, op, B, Sq, lens, off, bound, L, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs, scale, cz, dt, st));
   } else {
-    raise_on(awq_attn_kvcache(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Sq, lens, off, bound, (int)rows, H, Hkv, Dh, q.stride(0),
-                              q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, ws.data_ptr(), wsb, st));
+    if (paged && fp8)
+      raise_on(awq_attn_kvcache_paged_kv8(qp, kp, vp, ksp, vsp, op, btp, B, Sq, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qbs, qrs, kbs, krs,
+                                          vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ws.data_ptr(), wsb, st));
+    else if (paged)
+      raise_on(awq_attn_kvcache_paged(qp, kp, vp, op, btp, B, Sq, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs,
+                                      scale, cz, dt, ws.data_ptr(), wsb, st));
+    else if (fp8)
+      raise_on(awq_attn_kvcache_kv8(qp, kp, vp, ksp, vsp, op, B, Sq, lens, off, bound, L, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs, ksbs, ksrs, vsbs,
+                                    vsrs, scale, cz, dt, ws.data_ptr(), wsb, st));
+    else
+      raise_on(awq_attn_kvcache(qp, kp, vp, op, B, Sq, lens, off, bound, L, H, Hkv, Dh, qbs, qrs, kbs, krs, vbs, vrs, scale, cz, dt, ws.data_ptr(), wsb, st));
   }
   return out;
 }
@@ -1315,162 +1382,36 @@ torch::Tensor attn_prefill_paged_kv8(const torch::Tensor q, const torch::Tensor 
                            softmax_scale, causal, true);
 }
 
-// ---- Packed steps (continuous batching, include/awq_cdna4.h "varq"): the tokens of a call are one flat run of rows, sequence b owns rows
-//      cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1, read on the device.  out / q_out may be handed in (a buffer of a fixed token budget
-//      whose padding rows the launches leave alone); otherwise they are allocated and rows >= cu[B] hold whatever the allocator left.
-static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
-  TORCH_CHECK(cu.is_cuda() && cu.device() == ref.device(), who, ": cu_seqlens_q must live on the GPU of the input (it is read by the kernel only)");
-  TORCH_CHECK(cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.size(0) >= 2 && cu.is_contiguous(), who,
-              ": cu_seqlens_q must be a contiguous int32 [B + 1] tensor");
-  TORCH_CHECK(cu.size(0) - 1 <= 65535, who, ": batch ", cu.size(0) - 1, " exceeds 65535");
-  TORCH_CHECK(max_seqlen_q >= 1, who, ": max_seqlen_q must be at least 1");
-}
-
-static at::Tensor packed_out(const char* who, const char* name, const c10::optional<torch::Tensor>& given, const torch::Tensor& ref, int64_t total,
-                             int64_t nheads, int64_t headdim) {
-  if (!given.has_value()) return torch::empty({total, nheads, headdim}, ref.options().requires_grad(false).memory_format(at::MemoryFormat::Contiguous));
-  const torch::Tensor& o = *given;
-  TORCH_CHECK(o.is_cuda() && o.device() == ref.device() && o.scalar_type() == ref.scalar_type() && o.dim() == 3 && o.size(0) == total &&
-                  o.size(1) == nheads && o.size(2) == headdim && o.is_contiguous(),
-              who, ": ", name, " must be a contiguous [total_q, H, Dh] tensor of the input's dtype on its GPU");
-  return o;
-}
-
-static torch::Tensor rope_store_varq_impl(const char* who, const torch::Tensor& qkv, const torch::Tensor& freqs, const KvTensors& kv,
-                                          const torch::Tensor& cu, int64_t max_seqlen_q, const torch::Tensor& cache_seqlens, int64_t nheads,
-                                          int64_t nheads_kv, const c10::optional<torch::Tensor>& q_out_given) {
-  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
-  TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
-  TORCH_CHECK(qkv.scalar_type() == at::kHalf || qkv.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", qkv.scalar_type());
-  TORCH_CHECK(freqs.scalar_type() == at::kFloat && freqs.dim() == 2 && freqs.is_contiguous() &&
-                  (reinterpret_cast<uintptr_t>(freqs.data_ptr()) & 15) == 0,
-              who, ": freqs_table must be a contiguous, 16-byte aligned float32 [P, rot_dim] tensor (the whole angle table; it is not copied)");
-  TORCH_CHECK(qkv.dim() == 2, who, ": qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh]");
-  check_cu_seqlens(who, cu, qkv, max_seqlen_q);
-  const int64_t batch = cu.size(0) - 1, total = qkv.size(0);
-  check_kv(who, kv, qkv, "the input", batch, /*contiguous=*/!paged);
-  const torch::Tensor &k = kv.k, &v = kv.v;
-  const int64_t outer = k.size(0), rows = k.size(1), headdim = k.size(3), rot = freqs.size(1);
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  TORCH_CHECK(total >= 1 && nheads >= 1 && nheads_kv == k.size(2) && qkv.size(1) == (nheads + 2 * nheads_kv) * headdim, who,
-              ": qkv must be [total_q, (H + 2 Hkv) * Dh] with the ", paged ? "pools'" : "caches'", " Hkv and Dh");
-  TORCH_CHECK(paged || batch <= outer, who, ": batch ", batch, " exceeds the cache batch ", outer);
-  TORCH_CHECK(freqs.size(0) >= 1 && rot >= 16 && rot % 16 == 0 && rot <= headdim, who,
-              ": freqs_table must be [P >= 1, rot_dim] with rot_dim % 16 == 0 and rot_dim <= head dim");
-  check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
-  at::Tensor x = qkv;
-  if (x.stride(1) != 1 || x.stride(0) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
-  at::Tensor q_out = packed_out(who, "q_out", q_out_given, qkv, total, nheads, headdim);
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  void *xp = x.data_ptr(), *qp = q_out.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr();
-  const float* fp = freqs.data_ptr<float>();
-  float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
-  const int *pos = cache_seqlens.data_ptr<int>(), *cup = cu.data_ptr<int>();
-  const int B = (int)batch, M = (int)max_seqlen_q, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot,
-            P = (int)freqs.size(0), dt = dtype_code(x);
-  const int64_t rs = x.stride(0);
-  if (paged) {
-    const torch::Tensor& bt = *kv.block_table;
-    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
-    if (fp8)
-      raise_on(awq_rope_kv_store_paged_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, cup, M, T, H, Hkv, Dh, R, P, pages, page,
-                                                pps, bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0),
-                                                kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), rs, dt, st));
-    else
-      raise_on(awq_rope_kv_store_paged_varq(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, cup, M, T, H, Hkv, Dh, R, P, pages, page, pps,
-                                            bt.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), rs, dt, st));
-  } else if (fp8) {
-    raise_on(awq_rope_kv_store_natural_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, cup, M, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
-  } else {
-    raise_on(awq_rope_kv_store_natural_varq(xp, fp, qp, kp, vp, pos, B, (int)outer, cup, M, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
-  }
-  return q_out;
-}
-
 // rope_kv_store_natural_varq[_fp8] / rope_kv_store_paged_varq[_fp8](qkv [total_q, (H + 2 Hkv) Dh], freqs_table, caches or pools ..,
 // cu_seqlens_q, max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out = None) -> q_out [total_q, H, Dh]
 torch::Tensor rope_kv_store_natural_varq(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
                                          const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens, int64_t nheads,
                                          int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
-  return rope_store_varq_impl("rope_kv_store_natural_varq", qkv, freqs_table, {k_cache, v_cache, nullptr, nullptr, nullptr}, cu_seqlens_q,
-                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+  return rope_store_impl("rope_kv_store_natural_varq", qkv, freqs_table, {k_cache, v_cache, nullptr, nullptr, nullptr}, &cache_seqlens, 0, nheads,
+                         nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out});
 }
 
 torch::Tensor rope_kv_store_natural_varq_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_cache, torch::Tensor v_cache,
                                              torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
                                              const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv,
                                              c10::optional<torch::Tensor> q_out) {
-  return rope_store_varq_impl("rope_kv_store_natural_varq_fp8", qkv, freqs_table, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, cu_seqlens_q,
-                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+  return rope_store_impl("rope_kv_store_natural_varq_fp8", qkv, freqs_table, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, &cache_seqlens, 0,
+                         nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out});
 }
 
 torch::Tensor rope_kv_store_paged_varq(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
                                        const torch::Tensor block_table, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
                                        const torch::Tensor cache_seqlens, int64_t nheads, int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
-  return rope_store_varq_impl("rope_kv_store_paged_varq", qkv, freqs_table, {k_pool, v_pool, nullptr, nullptr, &block_table}, cu_seqlens_q,
-                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
+  return rope_store_impl("rope_kv_store_paged_varq", qkv, freqs_table, {k_pool, v_pool, nullptr, nullptr, &block_table}, &cache_seqlens, 0, nheads,
+                         nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out});
 }
 
 torch::Tensor rope_kv_store_paged_varq_fp8(const torch::Tensor qkv, const torch::Tensor freqs_table, torch::Tensor k_pool, torch::Tensor v_pool,
                                            torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table,
                                            const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
                                            int64_t nheads, int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
-  return rope_store_varq_impl("rope_kv_store_paged_varq_fp8", qkv, freqs_table, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, cu_seqlens_q,
-                              max_seqlen_q, cache_seqlens, nheads, nheads_kv, q_out);
-}
-
-static torch::Tensor attn_varq_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& cu, int64_t max_seqlen_q,
-                                    const torch::Tensor& seqlens_k, int64_t max_seqlen_k, bool lens_before_step, double softmax_scale, bool causal,
-                                    const c10::optional<torch::Tensor>& out_given) {
-  const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr;
-  TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
-  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
-  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
-  TORCH_CHECK(q.dim() == 3 && q.stride(2) == 1 && q.stride(1) == q.size(2), who, ": q [total_q, H, Dh] (packed rows) with contiguous heads is expected");
-  check_cu_seqlens(who, cu, q, max_seqlen_q);
-  const int64_t batch = cu.size(0) - 1, total = q.size(0), nheads = q.size(1), headdim = q.size(2);
-  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
-  check_kv(who, kv, q, "q", batch, /*contiguous=*/false);
-  const torch::Tensor &k = kv.k, &v = kv.v;
-  const int64_t outer = k.size(0), rows = k.size(1), nheads_kv = k.size(2), cap = paged ? kv.block_table->size(1) * rows : rows;
-  TORCH_CHECK((paged || outer >= batch) && k.size(3) == headdim, who, ": ", paged ? "k_pool / v_pool must be [num_pages, page_size, Hkv, " : "k_cache / v_cache must be [Bc >= B, Lmax, Hkv, ",
-              headdim, "]");
-  TORCH_CHECK(total >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who, ": empty tensors are not supported and H must be a multiple of Hkv");
-  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap,
-              paged ? " (pages_per_seq * page_size)" : " (the cache length)");
-  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
-  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
-  at::Tensor out = packed_out(who, "out", out_given, q, total, nheads, headdim);
-  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  const float *ksp = fp8 ? kv.k_scale->data_ptr<float>() : nullptr, *vsp = fp8 ? kv.v_scale->data_ptr<float>() : nullptr;
-  const int *lens = seqlens_k.data_ptr<int>(), *cup = cu.data_ptr<int>();
-  const int B = (int)batch, M = (int)max_seqlen_q, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim,
-            before = lens_before_step ? 1 : 0, bound = (int)max_seqlen_k, cz = causal ? 1 : 0, dt = dtype_code(q);
-  const float scale = (float)softmax_scale;
-  if (paged) {
-    const torch::Tensor& bt = *kv.block_table;
-    const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
-    if (fp8)
-      raise_on(awq_attn_prefill_paged_varq_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), bt.data_ptr<int>(), B, cup, M, T,
-                                               lens, before, bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1),
-                                               v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0),
-                                               kv.v_scale->stride(1), scale, cz, dt, st));
-    else
-      raise_on(awq_attn_prefill_paged_varq(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, cup, M, T, lens, before,
-                                           bound, pages, page, pps, bt.stride(0), H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0),
-                                           v.stride(1), scale, cz, dt, st));
-  } else if (fp8) {
-    raise_on(awq_attn_prefill_kvcache_varq_kv8(q.data_ptr(), k.data_ptr(), v.data_ptr(), ksp, vsp, out.data_ptr(), B, cup, M, T, lens, before, bound,
-                                               (int)rows, H, Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                               kv.k_scale->stride(0), kv.k_scale->stride(1), kv.v_scale->stride(0), kv.v_scale->stride(1), scale, cz,
-                                               dt, st));
-  } else {
-    raise_on(awq_attn_prefill_kvcache_varq(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, cup, M, T, lens, before, bound, (int)rows, H,
-                                           Hkv, Dh, q.stride(0), k.stride(0), k.stride(1), v.stride(0), v.stride(1), scale, cz, dt, st));
-  }
-  return out;
+  return rope_store_impl("rope_kv_store_paged_varq_fp8", qkv, freqs_table, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, &cache_seqlens, 0,
+                         nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out});
 }
 
 // attn_prefill_varq[_kv8] / attn_prefill_paged_varq[_kv8](q [total_q, H, Dh], caches or pools .., cu_seqlens_q, max_seqlen_q, seqlens_k,
@@ -1478,31 +1419,31 @@ static torch::Tensor attn_varq_impl(const char* who, const torch::Tensor& q, con
 torch::Tensor attn_prefill_varq(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor cu_seqlens_q,
                                 int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step,
                                 double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
-  return attn_varq_impl("attn_prefill_varq", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k,
-                        lens_before_step, softmax_scale, causal, out);
+  return attn_kvcache_impl("attn_prefill_varq", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal, true,
+                           {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step});
 }
 
 torch::Tensor attn_prefill_varq_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
                                     const torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
                                     const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step, double softmax_scale, bool causal,
                                     c10::optional<torch::Tensor> out) {
-  return attn_varq_impl("attn_prefill_varq_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, cu_seqlens_q, max_seqlen_q, seqlens_k,
-                        max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+  return attn_kvcache_impl("attn_prefill_varq_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal,
+                           true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step});
 }
 
 torch::Tensor attn_prefill_paged_varq(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
                                       const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k,
                                       bool lens_before_step, double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
-  return attn_varq_impl("attn_prefill_paged_varq", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, cu_seqlens_q, max_seqlen_q, seqlens_k,
-                        max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+  return attn_kvcache_impl("attn_prefill_paged_varq", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step});
 }
 
 torch::Tensor attn_prefill_paged_varq_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
                                           const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q,
                                           int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, bool lens_before_step,
                                           double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
-  return attn_varq_impl("attn_prefill_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, cu_seqlens_q, max_seqlen_q,
-                        seqlens_k, max_seqlen_k, lens_before_step, softmax_scale, causal, out);
+  return attn_kvcache_impl("attn_prefill_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0,
+                           softmax_scale, causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step});
 }
 
 // (q_tile_rows, blocks) of awq_attn_varq_plan.  Host only.

@@ -909,9 +909,18 @@ class _Kv:
         return (self.outer, self.rows, self.block_table.shape[1], self.block_table.stride(0))
 
 
+def _fp8_pair(who, k_scale, v_scale):
+    """Whether the call brings the scales of the FP8 format; one without the other is refused."""
+    fp8 = k_scale is not None or v_scale is not None
+    if fp8 and (k_scale is None or v_scale is None):
+        raise ValueError(f"{who}: k_scale and v_scale come together")
+    return fp8
+
+
 def _caches(who, qkv, k_cache, v_cache, k_scale, v_scale):
     """The contiguous caches [Bc, Lmax, Hkv, Dh] of a store call (and their scales [Bc, Lmax, Hkv]), checked against qkv, as a _Kv."""
-    fp8 = k_scale is not None
+    fp8 = _fp8_pair(who, k_scale, v_scale)
+    _on_gpu(k_cache, v_cache, *((k_scale, v_scale) if fp8 else ()))
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if fp8:
             _kv8_codes(who, name, t)
@@ -928,31 +937,40 @@ def _caches(who, qkv, k_cache, v_cache, k_scale, v_scale):
     return _Kv(k_cache, v_cache, k_scale, v_scale)
 
 
-def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_seqlens=None):
-    """The six store entries of the C ABI over a described cache.  cache_seqlens None: the host position start_pos and the call's angles;
-    otherwise the positions are read on the device and freqs is the model's whole angle table [P, rot_dim]."""
+def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_seqlens=None, packed=None):
+    """The ten store entries of the C ABI over a described cache.  cache_seqlens None: the host position start_pos and the call's angles;
+    otherwise the positions are read on the device and freqs is the model's whole angle table [P, rot_dim].  packed = (cu_seqlens_q,
+    max_seqlen_q, q_out or None), checked by the caller: qkv is the packed tokens [total_q, ..] of a step (device positions only)."""
     devlen = cache_seqlens is not None
     if freqs.device != qkv.device or freqs.dtype != torch.float32 or (devlen and freqs.dim() != 2) or not freqs.is_contiguous():
         raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv" if devlen else
                          f"{who}: contiguous float32 freqs on the GPU of qkv are expected")
-    if qkv.dim() != 3 or qkv.stride(2) != 1 or nheads_kv != kv.Hkv or qkv.shape[2] != (nheads + 2 * nheads_kv) * kv.Dh:
-        raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with " +
-                         ("the pools' Hkv and Dh" if kv.paged else "a unit last stride and the caches' Hkv and Dh"))
-    B, S = qkv.shape[0], qkv.shape[1]
+    if (packed is None and (qkv.dim() != 3 or qkv.stride(2) != 1)) or nheads_kv != kv.Hkv or qkv.shape[-1] != (nheads + 2 * nheads_kv) * kv.Dh:
+        raise ValueError(f"{who}: qkv must be " + ("[total_q, (H + 2 Hkv) * Dh] with the " + ("pools'" if kv.paged else "caches'") + " Hkv and Dh"
+                                                   if packed else "[B, S, (H + 2 Hkv) * Dh] with " +
+                                                   ("the pools' Hkv and Dh" if kv.paged else "a unit last stride and the caches' Hkv and Dh")))
+    if packed:
+        cu, S, q_out = packed
+        B, tokens = cu.shape[0] - 1, (cu.data_ptr(), int(S), qkv.shape[0])
+    else:
+        B, S = qkv.shape[0], qkv.shape[1]
+        tokens = (S,)
     rot = freqs.shape[-1]
     if devlen:
         _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
     elif freqs.numel() < B * S * rot:
         raise ValueError(f"{who}: freqs holds fewer than B * S * rot_dim angles")
-    q_out = torch.empty(B, S, nheads, kv.Dh, dtype=qkv.dtype, device=qkv.device)
+    q_out = _packed_out(who, "q_out", q_out, qkv, int(nheads), kv.Dh) if packed else \
+        torch.empty(B, S, nheads, kv.Dh, dtype=qkv.dtype, device=qkv.device)
     head = (qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), *kv.ptrs())
-    shape = (S, int(nheads), int(nheads_kv), kv.Dh, rot)
-    tail = (qkv.stride(0), qkv.stride(1), _dt(qkv), _stream(qkv))
+    shape = (*tokens, int(nheads), int(nheads_kv), kv.Dh, rot)
+    tail = (*qkv.stride()[:-1], _dt(qkv), _stream(qkv))  # the batch stride (a rectangle's only) and the row stride
+    form = "_varq" if packed else "_pos"
     if kv.paged:
-        entry, args = "paged_pos", (*head, kv.block_table.data_ptr(), cache_seqlens.data_ptr(), B, *shape, freqs.shape[0], *kv.table(),
-                                    *kv.strides(), *tail)
+        entry, args = "paged" + form, (*head, kv.block_table.data_ptr(), cache_seqlens.data_ptr(), B, *shape, freqs.shape[0], *kv.table(),
+                                       *kv.strides(), *tail)
     elif devlen:
-        entry, args = "natural_pos", (*head, cache_seqlens.data_ptr(), B, kv.outer, *shape, kv.rows, freqs.shape[0], *tail)
+        entry, args = "natural" + form, (*head, cache_seqlens.data_ptr(), B, kv.outer, *shape, kv.rows, freqs.shape[0], *tail)
     else:
         entry, args = "natural", (*head, B, kv.outer, *shape, kv.rows, int(start_pos), *tail)
     with torch.cuda.device(qkv.device):
@@ -960,20 +978,28 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
     return q_out
 
 
-def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False):
+def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None):
     """The device-length attention entries of the C ABI over a described cache (q and kv checked by the caller): the four of the split
-    pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace)."""
-    B, Sq, H, Dh = q.shape
+    pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace).  packed = (cu_seqlens_q, max_seqlen_q, out or
+    None), checked by the caller (one_pass only): q is the packed rows [total_q, H, Dh] of a step, the four varq entries serve and
+    seqlen_offset carries the flag lens_before_step."""
+    if packed:
+        cu, Sq, out = packed
+        (T, H, Dh), B = q.shape, cu.shape[0] - 1
+        rows = (cu.data_ptr(), int(Sq), T)
+    else:
+        B, Sq, H, Dh = q.shape
+        rows = (Sq,)
     _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
     scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
     L = _capi.lib()
-    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
-    lens = (B, Sq, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k))
+    out = _packed_out(who, "out", out, q, H, Dh) if packed else torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    lens = (B, *rows, seqlens_k.data_ptr(), int(seqlen_offset), int(max_seqlen_k))
     where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
-    head = (q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), q.stride(1), *kv.strides(), scale, int(bool(causal)),
-            _dt(q))
+    # q's strides: the batch stride (a rectangle's only) and the row stride
+    head = (q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, *q.stride()[:-2], *kv.strides(), scale, int(bool(causal)), _dt(q))
     if one_pass:
-        entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_kv8" if kv.fp8 else ""))
+        entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_varq" if packed else "") + ("_kv8" if kv.fp8 else ""))
         with torch.cuda.device(q.device):
             _capi.check(entry(*head, _stream(q)))
         return out
@@ -1088,25 +1114,34 @@ def attn_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offse
     return _attn_dense("attn_kvcache", False, q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale, v_scale)
 
 
+def _check_caches(who, q, k, v, k_scale, v_scale, packed_batch=None):
+    """The dense caches [Bc >= B, Lmax, Hkv, Dh] of an attention call (T, or FP8 codes with their scales), checked against q [B, Sq, H, Dh]
+    -- or, with packed_batch = the B of a packed step, against the rows [total_q, H, Dh] the caller has checked -- as a _Kv."""
+    packed = packed_batch is not None
+    fp8 = _fp8_pair(who, k_scale, v_scale)
+    if fp8:  # (the checks of the host-length FP8 entries, on the batch rows this call reads; packed rows stand as one batch row)
+        nb = 1 if packed else q.shape[0]
+        _check_kv8(who, q.unsqueeze(0) if packed else q, k[:nb], v[:nb], k_scale[:nb], v_scale[:nb])
+    else:
+        for t in ((k, v) if packed else (q, k, v)):
+            _on_gpu(t)
+            if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+                raise ValueError(f"{who}: k / v must be [Bc, Lmax, Hkv, Dh] with contiguous heads" if packed else
+                                 f"{who}: q / k_cache / v_cache must be [B, S, heads, Dh] with contiguous heads")
+        if k.device != q.device or v.device != q.device or k.dtype != q.dtype or v.dtype != q.dtype:
+            raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
+    if packed:
+        if k.shape != v.shape or k.shape[0] < packed_batch:
+            raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [Bc >= B, Lmax, Hkv, Dh] are expected")
+    elif not fp8 and (k.shape != v.shape or k.shape[0] < q.shape[0] or k.shape[3] != q.shape[3]):
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_cache / v_cache [Bc >= B, Lmax, Hkv, Dh] are expected")
+    return _Kv(k, v, k_scale, v_scale)
+
+
 def _attn_dense(who, one_pass, q, k_cache, v_cache, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, k_scale, v_scale):
     """attn_kvcache / attn_prefill_kvcache: the tensor checks of the dense caches, then the entry."""
-    fp8 = k_scale is not None or v_scale is not None
-    if fp8:
-        if k_scale is None or v_scale is None:
-            raise ValueError(f"{who}: k_scale and v_scale come together")
-        nb = q.shape[0]  # (the checks of the host-length FP8 entries, on the batch rows this call reads)
-        _check_kv8(who, q, k_cache[:nb], v_cache[:nb], k_scale[:nb], v_scale[:nb])
-    else:
-        for t in (q, k_cache, v_cache):
-            if not t.is_cuda:
-                raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
-            if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
-                raise ValueError(f"{who}: q / k_cache / v_cache must be [B, S, heads, Dh] with contiguous heads")
-        if k_cache.device != q.device or v_cache.device != q.device or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-            raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
-        if k_cache.shape != v_cache.shape or k_cache.shape[0] < q.shape[0] or k_cache.shape[3] != q.shape[3]:
-            raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_cache / v_cache [Bc >= B, Lmax, Hkv, Dh] are expected")
-    return _attn_kvcache(who, q, _Kv(k_cache, v_cache, k_scale, v_scale), seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass)
+    kv = _check_caches(who, q, k_cache, v_cache, k_scale, v_scale)
+    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass)
 
 
 def attn_prefill_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None, causal: bool = True,
@@ -1128,10 +1163,7 @@ def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens,
     sequence with cache_seqlens[b] < 0 or cache_seqlens[b] + S > min(Lmax, P) is inactive: nothing of it is stored and its q rows are
     zeros.  With k_scale / v_scale the caches are FP8 (rope_kv_store_natural_fp8's arguments).  Returns the rotated q [B, S, H, Dh]."""
     who = "rope_kv_store_natural_pos"
-    fp8 = k_scale is not None or v_scale is not None
-    if fp8 and (k_scale is None or v_scale is None):
-        raise ValueError(f"{who}: k_scale and v_scale come together")
-    _on_gpu(qkv, freqs_table, k_cache, v_cache, cache_seqlens, *((k_scale, v_scale) if fp8 else ()))
+    _on_gpu(qkv, freqs_table, cache_seqlens)
     return _rope_store(who, qkv, freqs_table, _caches(who, qkv, k_cache, v_cache, k_scale, v_scale), nheads, nheads_kv,
                        cache_seqlens=cache_seqlens)
 
@@ -1139,9 +1171,7 @@ def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens,
 # ---- the paged KV cache: the two calls above over a pool of pages and a per-sequence block table ------------------------------------
 def _check_pools(who, ref, k_pool, v_pool, block_table, k_scale, v_scale, batch):
     """The pools [num_pages, page_size, Hkv, Dh] and the table [>= B, pages_per_seq] of one call, checked against `ref`, as a _Kv."""
-    fp8 = k_scale is not None or v_scale is not None
-    if fp8 and (k_scale is None or v_scale is None):
-        raise ValueError(f"{who}: k_scale and v_scale come together")
+    fp8 = _fp8_pair(who, k_scale, v_scale)
     _on_gpu(ref, k_pool, v_pool, block_table, *((k_scale, v_scale) if fp8 else ()))
     for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
         if fp8:
@@ -1259,9 +1289,6 @@ def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, 
     of a fixed token budget) are neither read nor written: hand q_out in to keep what they hold.  For every active sequence the rows,
     the cache bytes and the scales are those of the rectangular call on that sequence alone.  Returns the rotated q [total_q, H, Dh]."""
     who = "rope_kv_store_varq"
-    fp8 = k_scale is not None or v_scale is not None
-    if fp8 and (k_scale is None or v_scale is None):
-        raise ValueError(f"{who}: k_scale and v_scale come together")
     _on_gpu(qkv, freqs_table, cache_seqlens)
     if qkv.dim() != 2 or qkv.stride(1) != 1:
         raise ValueError(f"{who}: qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh] with a unit last stride")
@@ -1269,28 +1296,10 @@ def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, 
     if block_table is not None:
         kv = _check_pools(who, qkv, k, v, block_table, k_scale, v_scale, B)
     else:
-        _on_gpu(k, v, *((k_scale, v_scale) if fp8 else ()))
         kv = _caches(who, qkv, k, v, k_scale, v_scale)
         if kv.outer < B:
             raise ValueError(f"{who}: batch {B} exceeds the cache batch {kv.outer}")
-    if freqs_table.device != qkv.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or not freqs_table.is_contiguous():
-        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, rot_dim] tensor on the GPU of qkv")
-    if nheads_kv != kv.Hkv or qkv.shape[1] != (nheads + 2 * nheads_kv) * kv.Dh:
-        raise ValueError(f"{who}: qkv must be [total_q, (H + 2 Hkv) * Dh] with the " + ("pools'" if kv.paged else "caches'") + " Hkv and Dh")
-    _check_seqlens(who, "cache_seqlens", cache_seqlens, qkv, B)
-    q_out = _packed_out(who, "q_out", q_out, qkv, int(nheads), kv.Dh)
-    head = (qkv.data_ptr(), freqs_table.data_ptr(), q_out.data_ptr(), *kv.ptrs())
-    packed = (cu_seqlens_q.data_ptr(), int(max_seqlen_q), qkv.shape[0])
-    shape = (int(nheads), int(nheads_kv), kv.Dh, freqs_table.shape[1])
-    tail = (qkv.stride(0), _dt(qkv), _stream(qkv))
-    if kv.paged:
-        entry, args = "paged_varq", (*head, kv.block_table.data_ptr(), cache_seqlens.data_ptr(), B, *packed, *shape, freqs_table.shape[0],
-                                     *kv.table(), *kv.strides(), *tail)
-    else:
-        entry, args = "natural_varq", (*head, cache_seqlens.data_ptr(), B, kv.outer, *packed, *shape, kv.rows, freqs_table.shape[0], *tail)
-    with torch.cuda.device(qkv.device):
-        _capi.check(getattr(_capi.lib(), "awq_rope_kv_store_" + entry + ("_fp8" if kv.fp8 else ""))(*args))
-    return q_out
+    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens, packed=(cu_seqlens_q, max_seqlen_q, q_out))
 
 
 def attn_prefill_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, lens_before_step: bool = True, block_table=None,
@@ -1310,37 +1319,14 @@ def attn_prefill_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_s
     if q.dim() != 3 or q.stride(2) != 1 or q.stride(1) != q.shape[2]:
         raise ValueError(f"{who}: q must be the packed rows [total_q, H, Dh] with contiguous heads")
     B = _check_packed(who, "q", q, cu_seqlens_q, max_seqlen_q)
-    T, H, Dh = q.shape
-    fp8 = k_scale is not None or v_scale is not None
     if block_table is not None:
         kv = _check_pools(who, q, k, v, block_table, k_scale, v_scale, B)
     else:
-        if fp8:
-            if k_scale is None or v_scale is None:
-                raise ValueError(f"{who}: k_scale and v_scale come together")
-            _check_kv8(who, q.unsqueeze(0), k[:1], v[:1], k_scale[:1], v_scale[:1])  # (the checks of the host-length FP8 entries, on one cache row)
-        else:
-            for t in (k, v):
-                _on_gpu(t)
-                if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
-                    raise ValueError(f"{who}: k / v must be [Bc, Lmax, Hkv, Dh] with contiguous heads")
-            if k.device != q.device or v.device != q.device or k.dtype != q.dtype or v.dtype != q.dtype:
-                raise ValueError(f"{who}: q and the caches must share one GPU and one dtype")
-        if k.shape != v.shape or k.shape[0] < B:
-            raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [Bc >= B, Lmax, Hkv, Dh] are expected")
-        kv = _Kv(k, v, k_scale, v_scale)
-    if kv.Dh != Dh:
-        raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [.., Hkv, Dh] must share Dh, got {Dh} and {kv.Dh}")
-    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
-    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
-    out = _packed_out(who, "out", out, q, H, Dh)
-    lens = (B, cu_seqlens_q.data_ptr(), int(max_seqlen_q), T, seqlens_k.data_ptr(), int(bool(lens_before_step)), int(max_seqlen_k))
-    where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
-    entry = getattr(_capi.lib(), "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + "_varq" + ("_kv8" if kv.fp8 else ""))
-    with torch.cuda.device(q.device):
-        _capi.check(entry(q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, q.stride(0), *kv.strides(), scale, int(bool(causal)),
-                          _dt(q), _stream(q)))
-    return out
+        kv = _check_caches(who, q, k, v, k_scale, v_scale, packed_batch=B)
+    if kv.Dh != q.shape[2]:
+        raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [.., Hkv, Dh] must share Dh, got {q.shape[2]} and {kv.Dh}")
+    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, bool(lens_before_step), softmax_scale, causal, one_pass=True,
+                         packed=(cu_seqlens_q, max_seqlen_q, out))
 
 
 def _ft_caches(who, ref, k_cache, v_cache):
