@@ -804,6 +804,54 @@ int awq_rope_kv_store_paged_varq_fp8(const void* qkv, const float* freqs_table, 
                                      long long k_scale_row_stride, long long v_scale_page_stride, long long v_scale_row_stride,
                                      long long qkv_row_stride, int dtype, void* stream);
 
+/* ---- A MIXED packed step: who serves a sequence.  awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8] take the arguments of
+ *      awq_attn_prefill_kvcache_varq[_kv8] / awq_attn_prefill_paged_varq[_kv8] and, behind dtype, split_seqlen_q, split_min_keys, workspace and
+ *      workspace_bytes.  Three launches in one stream -- the packed one-pass kernel, the packed split-KV kernel, its combine -- whose set
+ *      and grids depend on host arguments only; each sequence is served by exactly one of the two kernels, chosen ON THE DEVICE:
+ *          the split pair takes sequence b  iff  b is active with 1 <= Sq_b (above), Sq_b <= split_seqlen_q and Sk_b >= split_min_keys;
+ *          everything else -- prompt chunks, short histories, Sq_b = 0, inactive sequences (zero rows) -- is the one-pass kernel's, exactly
+ *          as in awq_attn_prefill_*_varq.
+ *      A one-token sequence over a long history then shares the K / V fetch among the heads of a KV group and spreads over the chip, inside
+ *      the same call (and the same captured graph) that serves the prompt chunks.
+ * split_seqlen_q >= 0 with split_seqlen_q * (nheads / nheads_kv) <= 128; 0: nothing is split -- the call IS awq_attn_prefill_*_varq, one
+ *     launch, workspace unused (NULL is fine).  split_min_keys >= 1.
+ * Plan: awq_attn_varq_split_plan returns awq_attn_kvcache_plan's (splits, chunk) for the bound max_seqlen_k (the knob "attn_splitkv_chunk"
+ *     applies); split grid batch * nheads_kv * splits, combine grid ceil(batch * nheads * split_seqlen_q * head_dim / 8 / 256).
+ * Workspace: awq_attn_varq_split_workspace_bytes = batch * nheads * split_seqlen_q * splits * (head_dim + 2) * 4 bytes, 16-byte aligned;
+ *     entry ((b * nheads_kv + kvh) * split_seqlen_q * G + row) * splits + s.  Rows of sequences the pair does not take are never touched.
+ * Bits: a taken sequence's rows are those of awq_attn_kvcache[_kv8] / awq_attn_kvcache_paged[_kv8] on that sequence alone (batch 1,
+ *     seqlen_q = Sq_b, seqlen_offset = Sq_b under lens_before_step, else 0; same max_seqlen_k and chunk); every other row below
+ *     cu[batch] is awq_attn_prefill_*_varq's; rows >= cu[batch] are not written.  No atomics: bit-deterministic and capturable.
+ * Returns the codes of awq_attn_prefill_*_varq, and: split_seqlen_q < 0, split_min_keys < 1 or split_seqlen_q * G > 128 AWQ_ERR_SHAPE;
+ *     with split_seqlen_q > 0 a NULL or short workspace AWQ_ERR_WORKSPACE, a misaligned one AWQ_ERR_ALIGN.  Every check precedes the first
+ *     launch.  The plan refuses head dims other than 64 / 128 and split_seqlen_q * G > 128 with AWQ_ERR_SHAPE; the byte count is then 0. */
+int awq_attn_varq_split_plan(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int* splits, int* chunk);
+size_t awq_attn_varq_split_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k);
+int awq_attn_varq(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q,
+                  int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim,
+                  long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                  float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int awq_attn_varq_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out, int batch,
+                      const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k,
+                      int lmax, int nheads, int nheads_kv, int head_dim, long long q_row_stride, long long k_batch_stride, long long k_row_stride,
+                      long long v_batch_stride, long long v_row_stride, long long k_scale_batch_stride, long long k_scale_row_stride,
+                      long long v_scale_batch_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                      int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                        const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k,
+                        int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                        long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                        float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                            const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k,
+                            int lens_before_step, int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                            int nheads, int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                            long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                            long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                            int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

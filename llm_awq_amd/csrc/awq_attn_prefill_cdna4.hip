@@ -74,11 +74,21 @@ struct PrefillLenArgs {
   VarQArgs vq;           // VarQ (awq_varq.hpp): a.q / a.out are then the packed rows, a.Sq the host's bound max_seqlen_q; no other form reads it
 };
 
+// VarQMix only (awq_varq.hpp, a mixed step): the two thresholds of the rule behind the length arguments.  A struct of its own, so that the
+// plain VarQ kernels keep their PrefillLenArgs block
+struct PrefillMixArgs : PrefillLenArgs {
+  VarQSplitArgs sp;
+};
+
 struct NoLenArgs {};
 template <typename DT>
-using LenArgsOf = typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type;
+using LenArgsOf = typename std::conditional<IsVarQMix<DT>::value, PrefillMixArgs,
+                                            typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type>::type;
 __device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}, VarQArgs{nullptr, 0, 0, 0}}; }
 __device__ __forceinline__ PrefillLenArgs len_args(const PrefillLenArgs& x) { return x; }
+__device__ __forceinline__ VarQSplitArgs split_args(const NoLenArgs&) { return VarQSplitArgs{0, 0}; }
+__device__ __forceinline__ VarQSplitArgs split_args(const PrefillLenArgs&) { return VarQSplitArgs{0, 0}; }
+__device__ __forceinline__ VarQSplitArgs split_args(const PrefillMixArgs& x) { return x.sp; }
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
 //   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
@@ -142,6 +152,10 @@ struct IsFtCache<FtCache<DT>> {
 // ntiles_b, so rank 0 is every sequence's longest tile.  Sq_b outside [0, max_seqlen_q] makes the sequence inactive: rows
 // s < min(Sq_b, max_seqlen_q) are written as zeros.  With lens_before_step the length is seqlens_k[b] + Sq_b, formed in 64 bits.
 //
+// VarQMix<..> (awq_attn_varq[_kv8], awq_attn_paged_varq[_kv8]): the VarQ form of a mixed step.  Behind the length load the block evaluates
+// varq_split_takes (awq_varq.hpp) on its sequence; a sequence the split pair takes is not this kernel's: the block returns before any
+// vector load and writes nothing.  The test is uniform over the block and no barrier precedes it.  Every other sequence runs the VarQ code.
+//
 // The device-length forms take their PrefillLenArgs as a SECOND kernel argument.  For the host-length forms that argument is the empty
 // NoLenArgs -- one padded byte behind PrefillArgs that no instruction reads: their PrefillArgs, their registers and their instruction
 // stream are those of the one-argument kernel.
@@ -196,6 +210,9 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   if constexpr (DEVLEN) {  // one scalar load; the Q loads below do not depend on it and are issued beside it
     // 64 bits: no entry can wrap into an active length
     const long long len = (long long)x.seqlens_k[b] + (VARQ ? (x.vq.lens_before_step ? sq_b : 0ll) : (long long)x.seqlen_offset);
+    if constexpr (IsVarQMix<DT>::value) {  // the split pair's sequence: nothing of it is read or written here
+      if (varq_split_takes(sq_b, len, x.vq.max_seqlen_q, x.max_seqlen_k, split_args(xs))) return;
+    }
     Sk = (int)len;
     live = len >= 1 && len <= x.max_seqlen_k;
     if constexpr (VARQ) {
@@ -707,8 +724,8 @@ void launch_kv_prefill_as(const PrefillArgs& a, const PrefillLenArgs& x, int Dh,
   });
 }
 // the packed-query forms: q tiles of 128 and 64 rows only (attn_varq_plan)
-template <template <typename> class K, template <typename> class L>
-void launch_kv_prefill_varq_as(const PrefillArgs& a, const PrefillLenArgs& x, int Dh, int dtype, int nw, int blocks, hipStream_t st) {
+template <template <typename> class K, template <typename> class L, typename X>
+void launch_kv_prefill_varq_as(const PrefillArgs& a, const X& x, int Dh, int dtype, int nw, int blocks, hipStream_t st) {
   for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
     using DT = L<K<decltype(dt)>>;
     constexpr int DH = decltype(dh)::value;
@@ -752,6 +769,19 @@ int launch_kv_prefill(const KvAttnCall& c, hipStream_t st) {
     attn_varq_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, &rows, &blocks);
     a.ntiles = (c.Sq + rows - 1) / rows;
     const int nw = rows / kMfmaRows;
+    if (c.split_seqlen_q > 0) {  // a mixed step: the same launch, with the sequences of the split pair left alone
+      PrefillMixArgs m;
+      static_cast<PrefillLenArgs&>(m) = x;
+      m.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
+      if (kv.block_table) {
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, VarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, VarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+      } else {
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, VarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, VarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+      }
+      return 0;
+    }
     if (kv.block_table) {
       if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, VarQPagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);
       else launch_kv_prefill_varq_as<TCache, VarQPagedDevLen>(a, x, c.Dh, c.dtype, nw, blocks, st);

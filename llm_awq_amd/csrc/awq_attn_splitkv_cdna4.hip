@@ -38,12 +38,17 @@
 //
 // awq_attn_kvcache_paged[_kv8] is that pair again with K / V (and the scales) fetched from a pool of pages through a block table
 // (Paged<DevLen<..>> instantiations of the split kernel, awq_paged.hpp; the combine launch is the dense form's).
+//
+// awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8] run the pair inside a PACKED step (VarQ<..> instantiations of both kernels, awq_varq.hpp):
+// q / out are packed rows, sequence b brings Sq_b = cu[b + 1] - cu[b] of them, and the pair serves only the sequences varq_split_takes
+// hands to it -- few new tokens over a long history.  Every other sequence belongs to the one-pass launch of the same call.
 #include "awq_device.hpp"
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_varq.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -92,8 +97,21 @@ struct SplitArgs {
 struct PagedSplitArgs : SplitArgs {
   PageArgs pg;
 };
+// VarQ only (awq_varq.hpp): q / out are the packed rows, Sq the host's split_seqlen_q and R = split_seqlen_q * G the workspace rows per
+// (sequence, KV head); the dense form carries an unused pg.  A struct of its own again, for both kernels of the pair.
+struct VarQSplitKArgs : PagedSplitArgs {
+  VarQArgs vq;
+  VarQSplitArgs sp;
+};
 template <typename DT>
-using SplitArgsOf = typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type;
+using SplitArgsOf = typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
+                                              typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type;
+template <typename DT>
+using CombineArgsOf = typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs, SplitArgs>::type;
+__device__ __forceinline__ VarQArgs varq_args(const SplitArgs&) { return VarQArgs{nullptr, 0, 0, 0}; }
+__device__ __forceinline__ VarQArgs varq_args(const VarQSplitKArgs& a) { return a.vq; }
+__device__ __forceinline__ VarQSplitArgs split_args(const SplitArgs&) { return VarQSplitArgs{0, 0}; }
+__device__ __forceinline__ VarQSplitArgs split_args(const VarQSplitKArgs& a) { return a.sp; }
 __device__ __forceinline__ PageArgs page_args(const SplitArgs&) { return PageArgs{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ PageArgs page_args(const PagedSplitArgs& a) { return a.pg; }
 
@@ -125,12 +143,21 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // load stands between a barrier and the K / V loads behind it.  (pg_i, pg_ro) = (table index, first row inside the page) of the tile last
 // looked up; they advance by 64 rows, so the one division is the block's first.  Only tiles j < nt are looked up: their first key lies
 // below Sk_b, so no entry at or behind ceil(Sk_b / page_size) is read.  Everything behind the staging loads is the dense kernel.
+//
+// VarQ<DevLen<..>> / VarQ<Paged<DevLen<..>>> (awq_varq.hpp, a mixed step): the head of the block loads cu[b] and cu[b + 1] through the
+// constant address space, then the length, and evaluates varq_split_takes.  Not taken: the block returns before any vector load and writes
+// nothing, not even to the workspace.  Taken with k_begin >= Sk_b: m = -inf, l = 0 for its R_b rows, as the DevLen form.  Otherwise the
+// DevLen / Paged kernel with Sq = Sq_b and R = R_b = Sq_b * G (block-uniform) and the q row cu[b] + qi, clamped into [0, total_q - 1].
+// Every early exit is uniform over the block and stands in front of the first barrier.  The workspace keeps a.R = split_seqlen_q * G rows
+// per (sequence, KV head); rows >= R_b are neither written nor read.
 template <typename DT, int DH>
 __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> a) {
   constexpr bool KV8 = IsKv8<DT>::value;
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
+  constexpr bool VARQ = IsVarQ<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
+  static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -151,7 +178,29 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   const int b = bi / a.Hkv;
   const int k_begin = split * a.chunk;                  // < Sk: (splits - 1) * chunk < Sk (DevLen: or the block is empty)
   int Sk = a.Sk;
-  if constexpr (DEVLEN) {
+  int Sq = a.Sq, R = a.R;  // VarQ: Sq_b and R_b = Sq_b * G, block-uniform; a.R stays the workspace's row count
+  long long row0 = 0;      // VarQ: the sequence's first packed row
+  (void)row0;
+  if constexpr (VARQ) {
+    const VarQArgs vq = varq_args(a);
+    const const_i32_t cu = as_const_i32(vq.cu_seqlens_q);
+    const int c0 = cu[b], c1 = cu[b + 1];
+    const long long sq_b = (long long)c1 - c0;
+    const long long len = (long long)a.seqlens_k[b] + (vq.lens_before_step ? sq_b : 0ll);  // 64 bits, as the one-pass kernel forms it
+    if (!varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a))) return;  // the one-pass kernel's sequence
+    Sq = (int)sq_b;  // 1 .. split_seqlen_q
+    R = Sq * a.G;    // <= a.R <= 128
+    row0 = c0;
+    Sk = (int)len;   // 1 .. a.Sk
+    if (k_begin >= Sk) {  // empty
+      if (tid < R) {
+        const long long e = (((long long)b * a.Hkv + kvh) * a.R + tid) * a.splits + split;
+        a.ws_m[e] = -INFINITY;
+        a.ws_l[e] = 0.f;
+      }
+      return;
+    }
+  } else if constexpr (DEVLEN) {
     const long long len = (long long)a.seqlens_k[b] + a.seqlen_offset;  // 64 bits: no entry can wrap into an active length
     Sk = (int)len;
     if (len < 1 || len > a.Sk || k_begin >= Sk) {  // empty
@@ -163,22 +212,24 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
       return;
     }
   }
-  const int shift = Sk - a.Sq;
+  const int shift = Sk - Sq;
   const int k_end = min(Sk, k_begin + a.chunk);         // keys [k_begin, k_end) are this block's
   const int nt = (k_end - k_begin + kKV - 1) / kKV;
 
   const int wr0 = wave * kMfmaRows;                     // first packed row of the wave
-  const bool wave_on = wr0 < a.R;                       // (a wave without rows still stages K / V and meets the barriers)
-  const int pr = min(wr0 + r, a.R - 1);                 // rows >= R compute row R - 1 again and are not stored
+  const bool wave_on = wr0 < R;                         // (a wave without rows still stages K / V and meets the barriers)
+  const int pr = min(wr0 + r, R - 1);                   // rows >= R compute row R - 1 again and are not stored
   const int qi = pr / a.G, h = kvh * a.G + pr % a.G;    // packed row = i * G + g
   const int lim = a.causal ? qi + shift : Sk - 1;                                     // last key this lane's row attends
-  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, a.R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
+  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
   const int wave_min = a.causal ? wr0 / a.G + shift : Sk - 1;                         // every row of the wave attends keys <= this
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   vec8 qf[KS];
   {
     const uint16_t* qp = a.q + (long long)b * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
+    if constexpr (VARQ)  // the packed row of (b, qi), clamped into the tensor before it forms an address
+      qp = a.q + min(max(row0 + qi, 0ll), (long long)varq_args(a).total_q - 1) * a.q_rs + (long long)h * DH + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = __builtin_bit_cast(vec8, *reinterpret_cast<const u32x4*>(qp + 16 * ks));
   }
@@ -360,7 +411,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 
   // ---- the unnormalised partial; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  if (wr0 + r < a.R) {
+  if (wr0 + r < R) {
     const long long e = (((long long)b * a.Hkv + kvh) * a.R + pr) * a.splits + split;
     float* op = a.ws_o + e * DH + 4 * hh;
 #pragma unroll
@@ -377,9 +428,14 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 
 // DevLen<..>: a row may have attended nothing at all (its sequence is inactive, or Sk_b < Sq and the row's causal limit is negative); then
 // every m_s is -inf, M = -inf and L = 0, and the row is written as zeros without the division.
+//
+// VarQ<DevLen<..>> (a mixed step): one thread = 8 columns of one (b, kvh, row < a.R = split_seqlen_q * G).  It evaluates varq_split_takes
+// on its sequence and leaves if the split kernel did not take it or row >= R_b: such a workspace row was never written.  The result goes
+// to packed row cu[b] + row / G, guarded by row < min(cu[b + 1], total_q).
 template <typename DT, int DH>
-__global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) {
+__global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(CombineArgsOf<DT> a) {
   constexpr int CPR = DH / 8;
+  constexpr bool VARQ = IsVarQ<DT>::value;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.Hkv * a.R * CPR) return;
   const int ch = (int)(id % CPR);
@@ -388,6 +444,17 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) 
   const long long bk = row / a.R;
   const int kvh = (int)(bk % a.Hkv);
   const long long b = bk / a.Hkv;
+  long long out_row = b * a.Sq + pr / a.G;  // VarQ: the packed row
+  if constexpr (VARQ) {
+    const VarQArgs vq = varq_args(a);
+    const const_i32_t cu = as_const_i32(vq.cu_seqlens_q);
+    const int c0 = cu[b], c1 = cu[b + 1];
+    const long long sq_b = (long long)c1 - c0;
+    const long long len = (long long)a.seqlens_k[b] + (vq.lens_before_step ? sq_b : 0ll);
+    if (!varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a)) || pr >= sq_b * a.G) return;
+    out_row = (long long)c0 + pr / a.G;
+    if (out_row < 0 || out_row >= min((long long)c1, (long long)vq.total_q)) return;  // (a corrupt array: no address outside the tensor)
+  }
   const float* pm = a.ws_m + row * a.splits;
   const float* pl = a.ws_l + row * a.splits;
   const float* po = a.ws_o + row * a.splits * DH + ch * 8;
@@ -409,7 +476,7 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) 
   }
   if constexpr (IsDevLen<DT>::value) {
     if (M == -INFINITY) {  // nothing attended: zeros, never 0 / 0
-      *reinterpret_cast<u32x4*>(a.out + ((b * a.Sq + pr / a.G) * a.H + kvh * a.G + pr % a.G) * DH + ch * 8) = u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(a.out + (out_row * a.H + kvh * a.G + pr % a.G) * DH + ch * 8) = u32x4{0u, 0u, 0u, 0u};
       return;
     }
   }
@@ -417,8 +484,8 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(SplitArgs a) 
   u32 ws[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) ws[e] = (u32)DT::from_float(acc[2 * e] * inv) | ((u32)DT::from_float(acc[2 * e + 1] * inv) << 16);
-  const int qi = pr / a.G, h = kvh * a.G + pr % a.G;
-  *reinterpret_cast<u32x4*>(a.out + ((b * a.Sq + qi) * a.H + h) * DH + ch * 8) = u32x4{ws[0], ws[1], ws[2], ws[3]};
+  const int h = kvh * a.G + pr % a.G;
+  *reinterpret_cast<u32x4*>(a.out + (out_row * a.H + h) * DH + ch * 8) = u32x4{ws[0], ws[1], ws[2], ws[3]};
 }
 
 }  // namespace
@@ -511,7 +578,7 @@ void launch_pair(const A& a, int Dh, int dtype, hipStream_t st) {
     using DT = decltype(dt);
     constexpr int DH = decltype(dh)::value;
     hipLaunchKernelGGL((attn_splitkv_kernel<L<K<DT>>, DH>), grid, dim3(kNW * 64), 0, st, a);
-    hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<DT>, DH>), cgrid, dim3(256), 0, st, (const SplitArgs&)a);
+    hipLaunchKernelGGL((attn_splitkv_combine_kernel<C<DT>, DH>), cgrid, dim3(256), 0, st, (const CombineArgsOf<C<DT>>&)a);
   });
 }
 template <typename DT>
@@ -532,7 +599,8 @@ void launch_for_cache(const A& a, int Dh, int dtype, hipStream_t st) {
 // (splits > 1 for a host length) and a workspace of its size.
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st) {
   const KvView& kv = c.kv;
-  PagedSplitArgs a;
+  const bool mixed = c.cu_seqlens_q && c.split_seqlen_q > 0;  // the packed pair: c.Sq is max_seqlen_q, c.seqlen_offset the flag
+  VarQSplitKArgs a;
   a.q = (const uint16_t*)c.q;
   a.k = (const uint16_t*)kv.k;
   a.v = (const uint16_t*)kv.v;
@@ -540,12 +608,12 @@ int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, 
   a.q_bs = c.q_bs, a.q_rs = c.q_rs;
   a.k_bs = kv.k_os, a.k_rs = kv.k_rs, a.v_bs = kv.v_os, a.v_rs = kv.v_rs;
   a.B = c.B;
-  a.Sq = c.Sq;
+  a.Sq = mixed ? c.split_seqlen_q : c.Sq;
   a.Sk = c.seqlens_k ? c.max_seqlen_k : c.Sk;
   a.H = c.H;
   a.Hkv = c.Hkv;
   a.G = c.H / c.Hkv;
-  a.R = c.Sq * a.G;
+  a.R = a.Sq * a.G;
   a.splits = splits;
   a.chunk = chunk;
   a.causal = c.causal ? 1 : 0;
@@ -558,10 +626,16 @@ int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, 
   a.v_scale = kv.v_scale;
   a.ks_bs = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_bs = kv.vs_os, a.vs_rs = kv.vs_rs;
   a.seqlens_k = c.seqlens_k;
-  a.seqlen_offset = c.seqlens_k ? c.seqlen_offset : 0;
+  a.seqlen_offset = c.seqlens_k && !mixed ? c.seqlen_offset : 0;
   a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+  a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, c.seqlen_offset ? 1 : 0};
+  a.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
+  const PagedSplitArgs& paged = a;
   const SplitArgs& dense = a;
-  if (kv.block_table) launch_for_cache<PagedDevLen, DevLen>(a, c.Dh, c.dtype, st);
+  if (mixed) {
+    if (kv.block_table) launch_for_cache<VarQPagedDevLen, VarQDevLen>(a, c.Dh, c.dtype, st);
+    else launch_for_cache<VarQDevLen, VarQDevLen>(a, c.Dh, c.dtype, st);
+  } else if (kv.block_table) launch_for_cache<PagedDevLen, DevLen>(paged, c.Dh, c.dtype, st);
   else if (c.seqlens_k) launch_for_cache<DevLen, DevLen>(dense, c.Dh, c.dtype, st);
   else launch_for_cache<HostLen, HostLen>(dense, c.Dh, c.dtype, st);
   return 0;

@@ -64,6 +64,9 @@ struct KvAttnCall {
   // seqlen_offset the flag lens_before_step (length of b = seqlens_k[b] + Sq_b when set, seqlens_k[b] when clear).  nullptr: the rectangle
   const int* cu_seqlens_q = nullptr;
   int max_seqlen_q = 0, total_q = 0;
+  // a mixed step (awq_varq.hpp, awq_attn_varq and its siblings): the split pair takes a sequence with Sq_b <= split_seqlen_q and
+  // Sk_b >= split_min_keys, the one-pass kernel leaves it alone.  split_seqlen_q = 0: the plain packed launch
+  int split_seqlen_q = 0, split_min_keys = 0;
 };
 
 // Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to
@@ -71,10 +74,12 @@ struct KvAttnCall {
 // cu_seqlens_q set, the packed-token store (awq_varq.hpp): device positions, dense or paged.
 int launch_kv_store(const KvStoreCall& c, hipStream_t st);
 int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
-// the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size
+// the split launch and its combine (awq_attn_splitkv_cdna4.hip); the caller holds the plan and a workspace of the plan's size.  With
+// cu_seqlens_q set and split_seqlen_q > 0, the packed forms of the pair: only the sequences the rule hands to them are touched, and the
+// workspace has split_seqlen_q rows per (sequence, query head)
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
 // the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace; with
-// cu_seqlens_q set, its packed-query form
+// cu_seqlens_q set, its packed-query form; with split_seqlen_q > 0 the form that leaves the split pair's sequences alone
 int launch_kv_prefill(const KvAttnCall& c, hipStream_t st);
 
 // f(element traits, std::integral_constant<int, DH>) for dtype 0 / 1 (F16 / BF16 of awq_device.hpp) and Dh 128 / 64

@@ -13,6 +13,11 @@
 //
 // The kernels select the form by the element traits -- VarQ<DevLen<F16>>, VarQ<Paged<DevLen<Kv8<BF16>>>>, the same traits under another
 // name, as Paged<DT>, DevLen<DT>, Kv8<DT> and FtCache<DT> are -- so the rectangular kernels keep their names and their code.
+//
+// A MIXED step (awq_attn_varq[_kv8], awq_attn_paged_varq[_kv8]) serves every sequence by exactly one of two kernels: the split-KV pair
+// (VarQ<..> forms of awq_attn_splitkv_cdna4.hip) takes the short sequences over a long history, the one-pass kernel (VarQMix<..> forms of
+// awq_attn_prefill_cdna4.hip) everything else.  Who serves a sequence is varq_split_takes below, evaluated by all three launches on what
+// cu_seqlens_q and the lengths hold: the launch set never depends on the step.
 #pragma once
 #include "awq_paged.hpp"
 
@@ -45,12 +50,59 @@ struct IsKv8<VarQ<DT>> {
   static constexpr bool value = IsKv8<DT>::value;
 };
 
+// the one-pass kernel of a mixed step: VarQ in every respect, and a sequence the split pair takes is left alone
+template <typename DT>
+struct VarQMix : DT {};
+template <typename DT>
+using VarQMixDevLen = VarQMix<DevLen<DT>>;
+template <typename DT>
+using VarQMixPagedDevLen = VarQMix<Paged<DevLen<DT>>>;
+template <typename DT>
+struct IsVarQMix {
+  static constexpr bool value = false;
+};
+template <typename DT>
+struct IsVarQMix<VarQMix<DT>> {
+  static constexpr bool value = true;
+};
+template <typename DT>
+struct IsVarQ<VarQMix<DT>> {
+  static constexpr bool value = true;
+};
+template <typename DT>
+struct IsPaged<VarQMix<DT>> {
+  static constexpr bool value = IsPaged<DT>::value;
+};
+template <typename DT>
+struct IsDevLen<VarQMix<DT>> {
+  static constexpr bool value = IsDevLen<DT>::value;
+};
+template <typename DT>
+struct IsKv8<VarQMix<DT>> {
+  static constexpr bool value = IsKv8<DT>::value;
+};
+
 // the launch arguments of a packed step that every varq kernel takes
 struct VarQArgs {
   const int* cu_seqlens_q;  // device int32 [B + 1]
   int total_q, max_seqlen_q;
   int lens_before_step;  // attention only: Sk_b = seqlens_k[b] + Sq_b (the lengths the store launch took) instead of seqlens_k[b]
 };
+
+// the two host thresholds of a mixed step; a struct of its own behind VarQArgs, so that the argument blocks of the plain varq kernels stay
+// what they were
+struct VarQSplitArgs {
+  int split_seqlen_q;  // the split pair takes at most this many new tokens; split_seqlen_q * (H / Hkv) <= 128
+  int split_min_keys;  // .. over at least this many keys, >= 1
+};
+
+// Who serves sequence b of a mixed step.  sq_b = cu[b + 1] - cu[b] and sk_b = the length as the varq kernels form it (64 bits, with
+// lens_before_step), both block-uniform.  true: the split pair; false: the one-pass kernel, exactly as in a plain varq launch -- inactive
+// sequences (zero rows), Sq_b = 0 and prompt chunks among them.
+__device__ __forceinline__ bool varq_split_takes(long long sq_b, long long sk_b, int max_seqlen_q, int max_seqlen_k, const VarQSplitArgs& sp) {
+  const bool active = sq_b >= 1 && sq_b <= max_seqlen_q && sk_b >= 1 && sk_b <= max_seqlen_k;
+  return active && sq_b <= sp.split_seqlen_q && sk_b >= sp.split_min_keys;
+}
 
 // cu_seqlens_q is read through the constant address space, as the block table is: nothing writes it while a kernel runs, and the loads
 // of a block-uniform index stay scalar loads

@@ -1073,6 +1073,9 @@ struct PackedStep {
   int64_t max_seqlen_q = 0;
   const c10::optional<torch::Tensor>* out = nullptr;
   bool lens_before_step = false;  // attention only
+  // attention only, a mixed step (attn_varq and its siblings): the split pair takes the sequences with at most split_seqlen_q new tokens over
+  // at least split_min_keys keys.  split_seqlen_q < 0: not a mixed call
+  int64_t split_seqlen_q = -1, split_min_keys = 0;
 };
 
 static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
@@ -1242,6 +1245,7 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
                                        int64_t max_seqlen_k, int64_t seqlen_offset, double softmax_scale, bool causal, bool one_pass = false,
                                        const PackedStep& step = {}) {
   const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, packed = step.cu != nullptr;
+  const bool mixed = packed && step.split_seqlen_q >= 0;
   TORCH_CHECK(q.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
   TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
@@ -1269,11 +1273,17 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap,
               paged ? " (pages_per_seq * page_size)" : " (the cache length)");
   TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
+  if (mixed)
+    TORCH_CHECK(step.split_min_keys >= 1 && step.split_seqlen_q * (nheads / nheads_kv) <= 128, who, ": split_min_keys ", step.split_min_keys,
+                " must be at least 1 and split_seqlen_q * (H / Hkv) = ", step.split_seqlen_q * (nheads / nheads_kv), " at most 128");
   check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor out = packed ? packed_out(who, "out", *step.out, q, total, nheads, headdim)
                           : torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
-  const size_t wsb = one_pass ? 0 : awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
+  const size_t wsb = mixed      ? awq_attn_varq_split_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim,
+                                                                      (int)step.split_seqlen_q, (int)max_seqlen_k)
+                     : one_pass ? 0
+                                : awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
   at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
   void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   void *qp = q.data_ptr(), *kp = k.data_ptr(), *vp = v.data_ptr(), *op = out.data_ptr();
@@ -1289,7 +1299,22 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   const int* btp = paged ? kv.block_table->data_ptr<int>() : nullptr;
   const int pages = (int)outer, page = (int)rows, pps = paged ? (int)kv.block_table->size(1) : 0;
   const int64_t btrs = paged ? kv.block_table->stride(0) : 0;
-  if (packed) {
+  if (mixed) {
+    const int ssq = (int)step.split_seqlen_q, smk = (int)std::min<int64_t>(step.split_min_keys, 0x7FFFFFFF);
+    void* wp = wsb ? ws.data_ptr() : nullptr;
+    if (paged && fp8)
+      raise_on(awq_attn_paged_varq_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs,
+                                       vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ssq, smk, wp, wsb, st));
+    else if (paged)
+      raise_on(awq_attn_paged_varq(qp, kp, vp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs,
+                                   scale, cz, dt, ssq, smk, wp, wsb, st));
+    else if (fp8)
+      raise_on(awq_attn_varq_kv8(qp, kp, vp, ksp, vsp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, ksbs, ksrs, vsbs,
+                                 vsrs, scale, cz, dt, ssq, smk, wp, wsb, st));
+    else
+      raise_on(awq_attn_varq(qp, kp, vp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, scale, cz, dt, ssq, smk, wp, wsb,
+                             st));
+  } else if (packed) {
     if (paged && fp8)
       raise_on(awq_attn_prefill_paged_varq_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs,
                                                kbs, krs, vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, st));
@@ -1444,6 +1469,53 @@ torch::Tensor attn_prefill_paged_varq_kv8(const torch::Tensor q, const torch::Te
                                           double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
   return attn_kvcache_impl("attn_prefill_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0,
                            softmax_scale, causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step});
+}
+
+// attn_varq[_kv8] / attn_paged_varq[_kv8]: attn_prefill_varq[_kv8] / attn_prefill_paged_varq[_kv8] with (split_seqlen_q, split_min_keys) behind
+// max_seqlen_k -- a mixed step: the packed split-KV pair serves the sequences with at most split_seqlen_q new tokens over at least
+// split_min_keys keys, the one-pass kernel the others; three launches, the partials in a buffer of the caching allocator.
+torch::Tensor attn_varq(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor cu_seqlens_q,
+                        int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q, int64_t split_min_keys,
+                        bool lens_before_step, double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0, "attn_varq: split_seqlen_q must not be negative");
+  return attn_kvcache_impl("attn_varq", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal, true,
+                           {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys});
+}
+
+torch::Tensor attn_varq_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                            const torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k,
+                            int64_t max_seqlen_k, int64_t split_seqlen_q, int64_t split_min_keys, bool lens_before_step, double softmax_scale,
+                            bool causal, c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0, "attn_varq_kv8: split_seqlen_q must not be negative");
+  return attn_kvcache_impl("attn_varq_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal, true,
+                           {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys});
+}
+
+torch::Tensor attn_paged_varq(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                              const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k,
+                              int64_t split_seqlen_q, int64_t split_min_keys, bool lens_before_step, double softmax_scale, bool causal,
+                              c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0, "attn_paged_varq: split_seqlen_q must not be negative");
+  return attn_kvcache_impl("attn_paged_varq", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal,
+                           true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys});
+}
+
+torch::Tensor attn_paged_varq_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                  const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q,
+                                  int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q,
+                                  int64_t split_min_keys, bool lens_before_step, double softmax_scale, bool causal,
+                                  c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0, "attn_paged_varq_kv8: split_seqlen_q must not be negative");
+  return attn_kvcache_impl("attn_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys});
+}
+
+// (splits, chunk) of awq_attn_varq_split_plan: attn_kvcache_plan's for the same bound.  Host only.
+std::tuple<int64_t, int64_t> attn_varq_split_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t split_seqlen_q,
+                                                  int64_t max_seqlen_k) {
+  int splits = 1, chunk = 0;
+  raise_on(awq_attn_varq_split_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)split_seqlen_q, (int)max_seqlen_k, &splits, &chunk));
+  return {splits, chunk};
 }
 
 // (q_tile_rows, blocks) of awq_attn_varq_plan.  Host only.
@@ -1911,6 +1983,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
         py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"),
         py::arg("out") = py::none());
+  m.def("attn_varq", &attn_varq,
+        "A mixed packed step: attn_prefill_varq with the sequences of at most split_seqlen_q new tokens over at least split_min_keys keys served by the split-KV pair",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_kv8", &attn_varq_kv8, "attn_varq on the FP8 cache", py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"),
+        py::arg("out") = py::none());
+  m.def("attn_paged_varq", &attn_paged_varq, "attn_varq over a paged KV cache", py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"),
+        py::arg("out") = py::none());
+  m.def("attn_paged_varq_kv8", &attn_paged_varq_kv8, "attn_paged_varq on FP8 pools", py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_split_plan", &attn_varq_split_plan, "(splits, chunk) of the split pair of a mixed step: attn_kvcache_plan's for the same bound",
+        py::arg("batch"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("split_seqlen_q"), py::arg("max_seqlen_k"));
   m.def("attn_varq_plan", &attn_varq_plan, "(q_tile_rows, blocks) of a packed-query launch: a provisional host rule", py::arg("batch"),
         py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("max_seqlen_q"));
   m.def("attn_varlen_qkvpacked", &attn_varlen_qkvpacked,

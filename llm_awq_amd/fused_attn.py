@@ -215,7 +215,35 @@ class QuantLlamaAttentionFused(nn.Module):
         rope_kv_store_natural_varq[_fp8] / rope_kv_store_paged_varq[_fp8] followed by attn_prefill_varq[_kv8] / attn_prefill_paged_varq
         [_kv8] with lens_before_step: start_pos is what both launches take, and no length or token count reaches the host.  Returns
         [1, T, hidden].  The rows of the sequences' last tokens (what the LM head needs) are out[:, cu_seqlens_q[1:] - 1], a device gather
-        that a graph captures.  Errors are raised before any work."""
+        that a graph captures.  Errors are raised before any work.
+
+        `forward_packed_split` is the same step with the short sequences over a long history served by the split-KV pair."""
+        return self._forward_packed(x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen, block_table, page_size, None)
+
+    @torch.no_grad()
+    def forward_packed_split(self, x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, split_seqlen_q=1, split_min_keys=None,
+                             decode_max_seqlen=None, block_table=None, page_size=None):
+        """`forward_packed` with the attention of the step routed to attn_varq[_kv8] / attn_paged_varq[_kv8]: a sequence that brings at most
+        `split_seqlen_q` new tokens over at least `split_min_keys` keys (default `ops.ATTN_SPLIT_MIN_KEYS`) is served by the packed split-KV
+        pair, every other sequence by the one-pass kernel as in `forward_packed` -- decided on the device, so one captured graph serves
+        any mix of decodes and prompt chunks.  split_seqlen_q * (H / Hkv) <= 128; split_seqlen_q = 0 is `forward_packed`'s attention.  The
+        store launch, the cache bytes and the rows of the sequences the pair does not take are `forward_packed`'s.  A method of its own:
+        `forward_packed` keeps its parameter list.  Errors are raised before any work."""
+        who = "QuantLlamaAttentionFused"
+        from .ops import ATTN_SPLIT_MIN_KEYS
+
+        split_seqlen_q = int(split_seqlen_q)
+        split_min_keys = ATTN_SPLIT_MIN_KEYS if split_min_keys is None else int(split_min_keys)
+        if split_seqlen_q < 0 or split_seqlen_q * self.num_key_value_groups > 128:
+            raise ValueError(f"{who}: split_seqlen_q {split_seqlen_q} must lie in 0 .. {128 // self.num_key_value_groups} "
+                             "(split_seqlen_q * (H / Hkv) <= 128)")
+        if split_min_keys < 1:
+            raise ValueError(f"{who}: split_min_keys {split_min_keys} must be at least 1")
+        return self._forward_packed(x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen, block_table, page_size,
+                                    (split_seqlen_q, split_min_keys))
+
+    def _forward_packed(self, x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen, block_table, page_size, split):
+        """The packed step; split = (split_seqlen_q, split_min_keys) routes its attention to the mixed entries."""
         self._check_packed(x, start_pos, cu_seqlens_q, max_seqlen_q)
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
@@ -247,7 +275,11 @@ class QuantLlamaAttentionFused(nn.Module):
         store = getattr(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""))
         attn = getattr(eng, "attn_prefill" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
         xq = store(xqkv, freqs, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
-        output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, True, scale, True)
+        if split is not None:
+            attn = getattr(eng, "attn" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
+            output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, split[0], split[1], True, scale, True)
+        else:
+            output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, True, scale, True)
         return self.o_proj(output.view(1, total, -1))
 
     def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None):

@@ -978,11 +978,12 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
     return q_out
 
 
-def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None):
+def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None, split=None):
     """The device-length attention entries of the C ABI over a described cache (q and kv checked by the caller): the four of the split
     pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace).  packed = (cu_seqlens_q, max_seqlen_q, out or
     None), checked by the caller (one_pass only): q is the packed rows [total_q, H, Dh] of a step, the four varq entries serve and
-    seqlen_offset carries the flag lens_before_step."""
+    seqlen_offset carries the flag lens_before_step.  split = (split_seqlen_q, split_min_keys), with packed: a mixed step, the four
+    awq_attn_[paged_]varq entries and the split pair's workspace."""
     if packed:
         cu, Sq, out = packed
         (T, H, Dh), B = q.shape, cu.shape[0] - 1
@@ -998,6 +999,13 @@ def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_sc
     where = (kv.block_table.data_ptr(), *lens, *kv.table()) if kv.paged else (*lens, kv.rows)
     # q's strides: the batch stride (a rectangle's only) and the row stride
     head = (q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, *q.stride()[:-2], *kv.strides(), scale, int(bool(causal)), _dt(q))
+    if split is not None:
+        wsb = L.awq_attn_varq_split_workspace_bytes(B, H, kv.Hkv, Dh, split[0], int(max_seqlen_k))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
+        entry = getattr(L, "awq_attn_" + ("paged_" if kv.paged else "") + "varq" + ("_kv8" if kv.fp8 else ""))
+        with torch.cuda.device(q.device):
+            _capi.check(entry(*head, split[0], split[1], ws.data_ptr(), wsb, _stream(q)))
+        return out
     if one_pass:
         entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_varq" if packed else "") + ("_kv8" if kv.fp8 else ""))
         with torch.cuda.device(q.device):
@@ -1327,6 +1335,55 @@ def attn_prefill_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_s
         raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [.., Hkv, Dh] must share Dh, got {q.shape[2]} and {kv.Dh}")
     return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, bool(lens_before_step), softmax_scale, causal, one_pass=True,
                          packed=(cu_seqlens_q, max_seqlen_q, out))
+
+
+# ---- mixed packed steps: the split-KV pair for the short sequences of a step, the one-pass kernel for the rest ---------------------------
+ATTN_SPLIT_MIN_KEYS = 2048  # the host-length plan's floor (attn_splitkv_plan never splits below it): the default split_min_keys
+
+
+def attn_varq_split_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, split_seqlen_q: int, max_seqlen_k: int):
+    """Host-side awq_attn_varq_split_plan: (splits, chunk) of the split pair inside `attn_varq` (no GPU needed) -- `attn_kvcache_plan`'s for
+    the same bound, the knob attn_splitkv_chunk included.  split_seqlen_q * (H / Hkv) > 128 and head dims other than 64 / 128 are refused."""
+    import ctypes
+
+    s, c = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_varq_split_plan(batch, nheads, nheads_kv, head_dim, split_seqlen_q, max_seqlen_k, ctypes.byref(s),
+                                                     ctypes.byref(c)))
+    return s.value, c.value
+
+
+def attn_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, split_seqlen_q: int = 1, split_min_keys=None,
+              lens_before_step: bool = True, block_table=None, softmax_scale=None, causal: bool = True, k_scale=None, v_scale=None, out=None):
+    """C-ABI awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8]: `attn_prefill_varq`'s arguments and contract for a MIXED packed step.  Three
+    launches in one stream -- the packed one-pass kernel, the packed split-KV kernel and its combine -- and every sequence is served by
+    exactly one of the two kernels, chosen on the device: the split pair takes sequence b iff it is active with 1 <= Sq_b <=
+    split_seqlen_q and Sk_b >= split_min_keys (default 2048, the floor below which `attn_splitkv_plan` never splits); prompt chunks, short
+    histories, Sq_b = 0 and inactive sequences stay with the one-pass kernel exactly as in `attn_prefill_varq`.  A taken sequence's rows
+    are bit-identical to `attn_kvcache` (`attn_kvcache_paged`) on that sequence alone with seqlen_offset = Sq_b under lens_before_step
+    (else 0) and the same max_seqlen_k; every other row to `attn_prefill_varq`.  split_seqlen_q * (H / Hkv) <= 128; split_seqlen_q = 0
+    splits nothing and is `attn_prefill_varq`, one launch.  The launch set depends on host arguments only: one captured graph replays any
+    mix of decodes, short bursts and prompt chunks.  Errors are raised before any work.  Returns out [total_q, H, Dh]."""
+    who = "attn_varq"
+    split_seqlen_q = int(split_seqlen_q)
+    split_min_keys = ATTN_SPLIT_MIN_KEYS if split_min_keys is None else int(split_min_keys)
+    if split_seqlen_q < 0:
+        raise ValueError(f"{who}: split_seqlen_q {split_seqlen_q} must not be negative")
+    if split_min_keys < 1:
+        raise ValueError(f"{who}: split_min_keys {split_min_keys} must be at least 1")
+    _on_gpu(q)
+    if q.dim() != 3 or q.stride(2) != 1 or q.stride(1) != q.shape[2]:
+        raise ValueError(f"{who}: q must be the packed rows [total_q, H, Dh] with contiguous heads")
+    B = _check_packed(who, "q", q, cu_seqlens_q, max_seqlen_q)
+    if block_table is not None:
+        kv = _check_pools(who, q, k, v, block_table, k_scale, v_scale, B)
+    else:
+        kv = _check_caches(who, q, k, v, k_scale, v_scale, packed_batch=B)
+    if kv.Dh != q.shape[2]:
+        raise ValueError(f"{who}: q [total_q, H, Dh] and k / v [.., Hkv, Dh] must share Dh, got {q.shape[2]} and {kv.Dh}")
+    if kv.Hkv >= 1 and q.shape[1] % kv.Hkv == 0 and split_seqlen_q * (q.shape[1] // kv.Hkv) > 128:
+        raise ValueError(f"{who}: split_seqlen_q * (H / Hkv) = {split_seqlen_q * (q.shape[1] // kv.Hkv)} exceeds 128")
+    return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, bool(lens_before_step), softmax_scale, causal, one_pass=True,
+                         packed=(cu_seqlens_q, max_seqlen_q, out), split=(split_seqlen_q, min(split_min_keys, 0x7FFFFFFF)))
 
 
 def _ft_caches(who, ref, k_cache, v_cache):
