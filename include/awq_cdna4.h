@@ -296,6 +296,41 @@ int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab
                       const void* top_p, const void* repetition_penalty, void* history, void* hist_len, int max_history, void* seqlens,
                       const void* stop_ids, int num_stop, void* finished, int max_len, int flags, void* tokens, void* stream);
 
+/* ---- Prompt-lookup speculative decoding on the device: four launches around a packed step of the KV-cache path (cu_seqlens_q, a token budget
+ * total_q, awq_attn_varq*), none of which reads anything on the host.  DESIGN.md "Speculative decoding" states each result by values.  batch = the
+ * slots of the sampler; history int32 [batch, max_history], hist_len / seqlens int32 [batch] are awq_sample_logits' arrays (seqlens[b] < 0 = an
+ * inactive slot); 0 <= kmax <= 15 is the longest draft.  Every array is device memory, 4-byte aligned (AWQ_ERR_ALIGN); required pointers give
+ * AWQ_ERR_NULL, sizes outside the limits AWQ_ERR_SHAPE, all checked before anything is launched.  No workspace, no global atomics; capturable.
+ *
+ * awq_spec_draft_ngram: with L = hist_len[b], draft_len[b] = 0 for an inactive slot, for L > max_history and for L < ngram_min + 1.  Otherwise
+ *   m_i = the length of the longest common suffix of history[.. i] and history[.. L - 1], capped at ngram_max, for the ends 0 <= i <= L - 2; the
+ *   match is the i that maximises (m_i, i) among m_i >= ngram_min (none: draft_len[b] = 0); the draft is history[i + 1 ..] cut to the first of kmax,
+ *   max(0, max_draft[b]) (max_draft int32 [batch] or NULL), L - 1 - i, max_len - seqlens[b] - 1 and the first id outside [0, vocab).  drafts int32
+ *   [batch, kmax] holds it with -1 behind; every element of both outputs is written.  1 <= ngram_min <= ngram_max <= 8, batch, max_history, vocab >= 1.
+ * awq_spec_pack: A = the active slots; the R = total_q - A extra rows go to the drafts in slot order, c_b = clamp(R - sum_{a < b} draft_len[a], 0,
+ *   draft_len[b]) (draft_len clamped into [0, kmax], 0 for inactive slots); draft_len[b] = c_b and drafts[b, c_b:] = -1 are written back; n_b = 1 + c_b
+ *   for an active slot, else 0; cu_seqlens_q int32 [batch + 1] = its exclusive prefix sum; input_ids int32 [total_q]: last_tokens[b], then the
+ *   slot's c_b drafts, at cu[b]; -1 from cu[batch] on.  1 <= batch <= 65535, total_q >= batch.
+ * awq_spec_verify: row_tokens[r] for every row r < total_q of logits [total_q, vocab] (dtype, alignment and vocab limit of awq_sample_logits) = steps
+ *   1 to 8 of the sampling contract with the parameters of the row's owner b (temperature / top_k / top_p / repetition_penalty [batch], each may be
+ *   NULL) and u[r] (fp32 [total_q]); the penalty set is history[b, :min(hist_len[b], max_history)] plus, for the row j = r - cu[b], the inputs
+ *   input_ids[cu[b] + i], 1 <= i <= j, with 0 <= hist_len[b] + i - 1 < max_history.  A row at or behind cu[batch] gets -1.  Nothing else is written.
+ * awq_spec_accept: per slot with n_b = cu[b + 1] - cu[b] >= 1 rows (capped at kmax + 1) and seqlens[b] >= 0: a = the number of leading j in
+ *   [0, n_b - 2] with row_tokens[cu + j] == input_ids[cu + j + 1]; for j = 0 .. a in order the token row_tokens[cu + j] is emitted and taken through
+ *   the append / stop / advance of awq_sample_logits (same flags, same arrays), stopping after the first that sets seqlens[b] = -1.  out_tokens
+ *   int32 [batch, kmax + 1] holds the emitted tokens with -1 behind, num_emitted [batch] their count, last_tokens [batch] the last one (the next
+ *   awq_spec_pack's input).  Any other slot: num_emitted 0, last_tokens -1, out_tokens -1, nothing else touched. ---- */
+int awq_spec_draft_ngram(const void* history, const void* hist_len, const void* seqlens, const void* max_draft, void* drafts, void* draft_len,
+                         int batch, int max_history, int vocab, int kmax, int ngram_min, int ngram_max, int max_len, void* stream);
+int awq_spec_pack(const void* last_tokens, void* drafts, void* draft_len, const void* seqlens, void* cu_seqlens_q, void* input_ids, int batch,
+                  int kmax, int total_q, void* stream);
+int awq_spec_verify(const void* logits, int logits_dtype, int total_q, int vocab, const void* u, const void* cu_seqlens_q, const void* input_ids,
+                    int batch, const void* temperature, const void* top_k, const void* top_p, const void* repetition_penalty, const void* history,
+                    const void* hist_len, int max_history, void* row_tokens, void* stream);
+int awq_spec_accept(const void* row_tokens, const void* input_ids, const void* cu_seqlens_q, int batch, int total_q, int kmax, void* history,
+                    void* hist_len, int max_history, void* seqlens, const void* stop_ids, int num_stop, void* finished, int max_len, int flags,
+                    void* out_tokens, void* num_emitted, void* last_tokens, void* stream);
+
 /* ---- LM head for decode: the reference's `self.norm` + `lm_head` (tinychat/models/llama.py:395,412: an RMSNorm and an unquantised
  * nn.Linear(hidden, vocab)) as ONE launch that reads the weight matrix once whatever m is.  DESIGN.md "LM head" states the result by values:
  *   x       T [m, k], row stride ldx elements (ldx % 8 == 0, ldx >= k): a prompt's last rows are selected by ldx, nothing is copied

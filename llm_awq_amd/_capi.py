@@ -65,7 +65,11 @@ SIGNATURES = {
     "awq_moe_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_moe_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_sample_logits": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "awq_lm_head": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "awq_spec_draft_ngram": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
+    "awq_spec_pack": (_i, [_vp] * 6 + [_i] * 3 + [_vp]),
+    "awq_spec_verify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 6 + [_i, _vp, _vp]),
+    "awq_spec_accept": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "awq_lm_head": (_i,[_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awq_lm_head_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_embed_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_quantize_group": (_i, [_vp, ctypes.c_long] + [_vp] * 7 + [_i] * 6 + [_vp]),

@@ -1377,6 +1377,69 @@ int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab
   return finish_launch();
 }
 
+// ---- prompt-lookup speculative decoding on the device (awq_spec_cdna4.hip) ----
+int awq_spec_draft_ngram(const void* history, const void* hist_len, const void* seqlens, const void* max_draft, void* drafts, void* draft_len,
+                         int batch, int max_history, int vocab, int kmax, int ngram_min, int ngram_max, int max_len, void* stream) {
+  if (!history || !hist_len || !seqlens || !draft_len || (kmax > 0 && !drafts)) return AWQ_ERR_NULL;
+  if (batch < 1 || max_history < 1 || vocab < 1 || kmax < 0 || kmax > 15 || ngram_min < 1 || ngram_min > ngram_max || ngram_max > 8)
+    return AWQ_ERR_SHAPE;
+  const void* words[] = {history, hist_len, seqlens, max_draft, drafts, draft_len};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_spec_draft_ngram(history, hist_len, seqlens, max_draft, drafts, draft_len, batch, max_history, vocab, kmax, ngram_min, ngram_max,
+                                   max_len, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_spec_pack(const void* last_tokens, void* drafts, void* draft_len, const void* seqlens, void* cu_seqlens_q, void* input_ids, int batch,
+                  int kmax, int total_q, void* stream) {
+  if (!last_tokens || !draft_len || !seqlens || !cu_seqlens_q || !input_ids || (kmax > 0 && !drafts)) return AWQ_ERR_NULL;
+  if (batch < 1 || batch > 65535 || kmax < 0 || kmax > 15 || total_q < batch) return AWQ_ERR_SHAPE;
+  const void* words[] = {last_tokens, drafts, draft_len, seqlens, cu_seqlens_q, input_ids};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_spec_pack(last_tokens, drafts, draft_len, seqlens, cu_seqlens_q, input_ids, batch, kmax, total_q, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_spec_verify(const void* logits, int logits_dtype, int total_q, int vocab, const void* u, const void* cu_seqlens_q, const void* input_ids,
+                    int batch, const void* temperature, const void* top_k, const void* top_p, const void* repetition_penalty, const void* history,
+                    const void* hist_len, int max_history, void* row_tokens, void* stream) {
+  if (!logits || !u || !cu_seqlens_q || !input_ids || !row_tokens) return AWQ_ERR_NULL;
+  if ((history != nullptr) != (hist_len != nullptr)) return AWQ_ERR_NULL;  // a history comes with its lengths
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (total_q < 1 || batch < 1 || batch > 65535 || vocab < 1 || vocab > (1 << 20) || (history && max_history < 1)) return AWQ_ERR_SHAPE;
+  if (!aligned_to(logits, logits_dtype == AWQ_F32 ? 4 : 2)) return AWQ_ERR_ALIGN;  // rows are walked from the 16-byte boundary below them
+  const void* words[] = {u, cu_seqlens_q, input_ids, temperature, top_k, top_p, repetition_penalty, history, hist_len, row_tokens};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_spec_verify(logits, logits_dtype, total_q, vocab, u, cu_seqlens_q, input_ids, batch, temperature, top_k, top_p, repetition_penalty,
+                              history, hist_len, max_history, row_tokens, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_spec_accept(const void* row_tokens, const void* input_ids, const void* cu_seqlens_q, int batch, int total_q, int kmax, void* history,
+                    void* hist_len, int max_history, void* seqlens, const void* stop_ids, int num_stop, void* finished, int max_len, int flags,
+                    void* out_tokens, void* num_emitted, void* last_tokens, void* stream) {
+  if (!row_tokens || !input_ids || !cu_seqlens_q || !out_tokens || !num_emitted || !last_tokens) return AWQ_ERR_NULL;
+  if ((history != nullptr) != (hist_len != nullptr)) return AWQ_ERR_NULL;  // a history comes with its lengths
+  if ((flags & AWQ_SAMPLE_APPEND) && !history) return AWQ_ERR_NULL;
+  if ((flags & AWQ_SAMPLE_ADVANCE) && !seqlens) return AWQ_ERR_NULL;
+  if (num_stop > 0 && !stop_ids) return AWQ_ERR_NULL;
+  if (batch < 1 || batch > 65535 || total_q < 1 || kmax < 0 || kmax > 15 || (history && max_history < 1) || num_stop < 0 || (flags & ~3))
+    return AWQ_ERR_SHAPE;
+  const void* words[] = {row_tokens, input_ids, cu_seqlens_q, history, hist_len, seqlens, stop_ids, finished, out_tokens, num_emitted, last_tokens};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_spec_accept(row_tokens, input_ids, cu_seqlens_q, batch, total_q, kmax, history, hist_len, max_history, seqlens, stop_ids, num_stop,
+                              finished, max_len, flags, out_tokens, num_emitted, last_tokens, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- LM head for decode and the token embedding gather (awq_lm_head_cdna4.hip) ----
 int awq_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                 int out_dtype, int m, int v, int k, int dtype, int max_blocks, void* stream) {

@@ -158,6 +158,19 @@ int launch_moe_combine(const void* ys, const void* inv, const void* topk_w, void
 int launch_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
                          const void* top_p, const void* penalty, void* history, void* hist_len, int max_history, void* seqlens, const void* stop_ids,
                          int num_stop, void* finished, int max_len, int flags, void* tokens, hipStream_t st);
+// prompt-lookup speculative decoding on the device (awq_spec_cdna4.hip): the n-gram drafter (one block per slot), the packer of the step's
+// cu_seqlens_q / input ids (one block), the sampler's row routine on every packed row, and the accept chain (step 9 per emitted token); -1 if the
+// sizes are outside the documented limits, pointers validated by the caller
+int launch_spec_draft_ngram(const void* history, const void* hist_len, const void* seqlens, const void* max_draft, void* drafts, void* draft_len,
+                            int batch, int max_history, int vocab, int kmax, int ngram_min, int ngram_max, int max_len, hipStream_t st);
+int launch_spec_pack(const void* last_tokens, void* drafts, void* draft_len, const void* seqlens, void* cu_seqlens_q, void* input_ids, int batch,
+                     int kmax, int total_q, hipStream_t st);
+int launch_spec_verify(const void* logits, int logits_dtype, int total_q, int vocab, const void* u, const void* cu_seqlens_q, const void* input_ids,
+                       int batch, const void* temperature, const void* top_k, const void* top_p, const void* penalty, const void* history,
+                       const void* hist_len, int max_history, void* row_tokens, hipStream_t st);
+int launch_spec_accept(const void* row_tokens, const void* input_ids, const void* cu_seqlens_q, int batch, int total_q, int kmax, void* history,
+                       void* hist_len, int max_history, void* seqlens, const void* stop_ids, int num_stop, void* finished, int max_len, int flags,
+                       void* out_tokens, void* num_emitted, void* last_tokens, hipStream_t st);
 // LM head for decode (awq_lm_head_cdna4.hip): out[m, v] = rmsnorm(x)[m, k] W[v, k]^T (+ bias) in one launch, rows with seqlens[b] < 0 left untouched;
 // the plan is {blocks, vocabulary rows per tile, waves, k split}; -1 if the sizes are outside the documented limits, pointers validated by the caller
 int lm_head_plan(int m, int v, int k, int out[4]);

@@ -602,6 +602,117 @@ torch::Tensor sample_logits(torch::Tensor logits, torch::Tensor u, c10::optional
   return tokens;
 }
 
+// ---- prompt-lookup speculative decoding on the device: drafter, packer, packed verifier and accept chain (awq_spec_*) ----
+namespace {
+// a contiguous int32 GPU tensor of n elements (n < 0: any size) on `dev` -> its pointer; nullptr for an absent optional
+void* spec_i32(const torch::Tensor& t, int64_t n, const at::Device& dev, const char* who, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kInt && t.device() == dev && (n < 0 || t.numel() == n), who, ": ", name,
+              " must be a contiguous int32 GPU tensor of its documented size");
+  return t.data_ptr();
+}
+void* spec_i32(const c10::optional<torch::Tensor>& t, int64_t n, const at::Device& dev, const char* who, const char* name) {
+  return t.has_value() ? spec_i32(*t, n, dev, who, name) : nullptr;
+}
+void* spec_f32(const c10::optional<torch::Tensor>& t, int64_t n, const at::Device& dev, const char* who, const char* name) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->device() == dev && t->numel() == n, who, ": ", name,
+              " must be a contiguous float32 [B] GPU tensor");
+  return t->data_ptr();
+}
+}  // namespace
+
+std::vector<torch::Tensor> spec_draft_ngram(torch::Tensor history, torch::Tensor hist_len, torch::Tensor seqlens, int64_t vocab, int64_t kmax,
+                                            int64_t ngram_min, int64_t ngram_max, int64_t max_len, c10::optional<torch::Tensor> max_draft) {
+  const char* who = "spec_draft_ngram";
+  TORCH_CHECK(history.dim() == 2 && history.size(1) >= 1, who, ": history must be int32 [B, Lh]");
+  const auto dev = history.device();
+  const int64_t b = history.size(0);
+  spec_i32(history, -1, dev, who, "history");
+  TORCH_CHECK(kmax >= 0 && kmax <= 15, who, ": 0 <= kmax <= 15");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+  at::Tensor drafts = torch::empty({b, kmax}, history.options()), draft_len = torch::empty({b}, history.options());
+  raise_on(awq_spec_draft_ngram(history.data_ptr(), spec_i32(hist_len, b, dev, who, "hist_len"), spec_i32(seqlens, b, dev, who, "seqlens"),
+                                spec_i32(max_draft, b, dev, who, "max_draft"), kmax > 0 ? drafts.data_ptr() : nullptr, draft_len.data_ptr(), (int)b,
+                                (int)history.size(1), (int)vocab, (int)kmax, (int)ngram_min, (int)ngram_max, (int)max_len,
+                                (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {drafts, draft_len};
+}
+
+std::vector<torch::Tensor> spec_pack(torch::Tensor last_tokens, torch::Tensor drafts, torch::Tensor draft_len, torch::Tensor seqlens, int64_t total_q) {
+  const char* who = "spec_pack";
+  const auto dev = last_tokens.device();
+  const int64_t b = last_tokens.numel();
+  TORCH_CHECK(drafts.dim() == 2 && drafts.size(0) == b, who, ": drafts must be int32 [B, kmax]");
+  TORCH_CHECK(total_q >= b && b >= 1, who, ": total_q >= B >= 1");
+  const int64_t kmax = drafts.size(1);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+  at::Tensor cu = torch::empty({b + 1}, last_tokens.options()), ids = torch::empty({total_q}, last_tokens.options());
+  raise_on(awq_spec_pack(spec_i32(last_tokens, b, dev, who, "last_tokens"), kmax > 0 ? spec_i32(drafts, -1, dev, who, "drafts") : nullptr,
+                         spec_i32(draft_len, b, dev, who, "draft_len"), spec_i32(seqlens, b, dev, who, "seqlens"), cu.data_ptr(), ids.data_ptr(),
+                         (int)b, (int)kmax, (int)total_q, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {cu, ids};
+}
+
+torch::Tensor spec_verify(torch::Tensor logits, torch::Tensor u, torch::Tensor cu_seqlens_q, torch::Tensor input_ids,
+                          c10::optional<torch::Tensor> temperature, c10::optional<torch::Tensor> top_k, c10::optional<torch::Tensor> top_p,
+                          c10::optional<torch::Tensor> repetition_penalty, c10::optional<torch::Tensor> history, c10::optional<torch::Tensor> hist_len) {
+  const char* who = "spec_verify";
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2, "awq_inference_engine: logits must be a contiguous [total_q, V] GPU tensor");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, who, ": float32 / bfloat16 / float16 logits");
+  const int code = st == at::kFloat ? AWQ_F32 : dtype_code(logits);
+  const auto dev = logits.device();
+  const int64_t tq = logits.size(0), v = logits.size(1), b = cu_seqlens_q.numel() - 1;
+  TORCH_CHECK(b >= 1, who, ": cu_seqlens_q must be int32 [B + 1]");
+  TORCH_CHECK(u.is_cuda() && u.is_contiguous() && u.scalar_type() == at::kFloat && u.numel() == tq, who, ": u must be float32 [total_q] on the GPU");
+  TORCH_CHECK(history.has_value() == hist_len.has_value(), who, ": history and hist_len come together");
+  int64_t lh = 0;
+  if (history.has_value()) {
+    TORCH_CHECK(history->dim() == 2 && history->size(0) == b && history->size(1) >= 1, who, ": history must be int32 [B, Lh]");
+    lh = history->size(1);
+  }
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+  at::Tensor row_tokens = torch::empty({tq}, logits.options().dtype(at::kInt));
+  raise_on(awq_spec_verify(logits.data_ptr(), code, (int)tq, (int)v, u.data_ptr(), spec_i32(cu_seqlens_q, b + 1, dev, who, "cu_seqlens_q"),
+                           spec_i32(input_ids, tq, dev, who, "input_ids"), (int)b, spec_f32(temperature, b, dev, who, "temperature"),
+                           spec_i32(top_k, b, dev, who, "top_k"), spec_f32(top_p, b, dev, who, "top_p"),
+                           spec_f32(repetition_penalty, b, dev, who, "repetition_penalty"), spec_i32(history, -1, dev, who, "history"),
+                           spec_i32(hist_len, b, dev, who, "hist_len"), (int)lh, row_tokens.data_ptr(),
+                           (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return row_tokens;
+}
+
+std::vector<torch::Tensor> spec_accept(torch::Tensor row_tokens, torch::Tensor input_ids, torch::Tensor cu_seqlens_q, int64_t kmax,
+                                       c10::optional<torch::Tensor> history, c10::optional<torch::Tensor> hist_len,
+                                       c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> stop_ids,
+                                       c10::optional<torch::Tensor> finished, int64_t max_len, bool append, bool advance) {
+  const char* who = "spec_accept";
+  const auto dev = row_tokens.device();
+  const int64_t tq = row_tokens.numel(), b = cu_seqlens_q.numel() - 1;
+  TORCH_CHECK(b >= 1 && tq >= 1, who, ": cu_seqlens_q must be int32 [B + 1] and row_tokens [total_q]");
+  TORCH_CHECK(kmax >= 0 && kmax <= 15, who, ": 0 <= kmax <= 15");
+  TORCH_CHECK(history.has_value() == hist_len.has_value(), who, ": history and hist_len come together");
+  int64_t lh = 0;
+  if (history.has_value()) {
+    TORCH_CHECK(history->dim() == 2 && history->size(0) == b && history->size(1) >= 1, who, ": history must be int32 [B, Lh]");
+    lh = history->size(1);
+  }
+  TORCH_CHECK(!append || history.has_value(), who, ": append needs history and hist_len");
+  TORCH_CHECK(!advance || seqlens.has_value(), who, ": advance needs seqlens");
+  TORCH_CHECK(!stop_ids.has_value() || stop_ids->dim() == 1, who, ": stop_ids must be int32 [S]");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+  const auto opt = row_tokens.options();
+  at::Tensor out = torch::empty({b, kmax + 1}, opt), num = torch::empty({b}, opt), last = torch::empty({b}, opt);
+  raise_on(awq_spec_accept(spec_i32(row_tokens, tq, dev, who, "row_tokens"), spec_i32(input_ids, tq, dev, who, "input_ids"),
+                           spec_i32(cu_seqlens_q, b + 1, dev, who, "cu_seqlens_q"), (int)b, (int)tq, (int)kmax,
+                           spec_i32(history, -1, dev, who, "history"), spec_i32(hist_len, b, dev, who, "hist_len"), (int)lh,
+                           spec_i32(seqlens, b, dev, who, "seqlens"), spec_i32(stop_ids, -1, dev, who, "stop_ids"),
+                           stop_ids.has_value() ? (int)stop_ids->numel() : 0, spec_i32(finished, b, dev, who, "finished"), (int)max_len,
+                           (append ? AWQ_SAMPLE_APPEND : 0) | (advance ? AWQ_SAMPLE_ADVANCE : 0), out.data_ptr(), num.data_ptr(), last.data_ptr(),
+                           (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {out, num, last};
+}
+
 // ---- LM head for decode (final RMSNorm + vocabulary GEMV, one launch) and the token embedding gather that takes the sampler's -1 ----
 torch::Tensor lm_head(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
                       c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out, at::ScalarType out_dtype, int64_t max_blocks) {
@@ -2075,6 +2186,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_logits", &sample_logits, "logits [B, V], u [B] -> next tokens int32 [B]: temperature, repetition penalty, top-p, top-k and the draw, one launch",
         py::arg("logits"), py::arg("u"), py::kw_only(), py::arg("temperature") = py::none(), py::arg("top_k") = py::none(),
         py::arg("top_p") = py::none(), py::arg("repetition_penalty") = py::none(), py::arg("history") = py::none(),
+        py::arg("hist_len") = py::none(), py::arg("seqlens") = py::none(), py::arg("stop_ids") = py::none(), py::arg("finished") = py::none(),
+        py::arg("max_len") = 0, py::arg("append") = false, py::arg("advance") = false);
+  m.def("spec_draft_ngram", &spec_draft_ngram, "prompt-lookup drafter over the sampler's history -> (drafts int32 [B, kmax], draft_len int32 [B])",
+        py::arg("history"), py::arg("hist_len"), py::arg("seqlens"), py::kw_only(), py::arg("vocab"), py::arg("kmax"), py::arg("ngram_min") = 1,
+        py::arg("ngram_max") = 3, py::arg("max_len") = 2147483647, py::arg("max_draft") = py::none());
+  m.def("spec_pack", &spec_pack, "the layout of a speculative step -> (cu_seqlens_q int32 [B + 1], input_ids int32 [total_q]); drafts / draft_len are rewritten",
+        py::arg("last_tokens"), py::arg("drafts"), py::arg("draft_len"), py::arg("seqlens"), py::arg("total_q"));
+  m.def("spec_verify", &spec_verify, "sample_logits' row routine on every row of a packed step -> row_tokens int32 [total_q]", py::arg("logits"),
+        py::arg("u"), py::arg("cu_seqlens_q"), py::arg("input_ids"), py::kw_only(), py::arg("temperature") = py::none(),
+        py::arg("top_k") = py::none(), py::arg("top_p") = py::none(), py::arg("repetition_penalty") = py::none(), py::arg("history") = py::none(),
+        py::arg("hist_len") = py::none());
+  m.def("spec_accept", &spec_accept, "the accepted drafts and the token behind them, each through append / stop / advance -> (out_tokens [B, kmax + 1], num_emitted [B], last_tokens [B])",
+        py::arg("row_tokens"), py::arg("input_ids"), py::arg("cu_seqlens_q"), py::arg("kmax"), py::kw_only(), py::arg("history") = py::none(),
         py::arg("hist_len") = py::none(), py::arg("seqlens") = py::none(), py::arg("stop_ids") = py::none(), py::arg("finished") = py::none(),
         py::arg("max_len") = 0, py::arg("append") = false, py::arg("advance") = false);
   m.def("lm_head", &lm_head, "logits [M, V] = rmsnorm(x) @ weight^T (+ bias): final RMSNorm and vocabulary GEMV in one launch, inactive rows (seqlens < 0) untouched",

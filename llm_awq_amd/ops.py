@@ -584,6 +584,156 @@ def sample_logits(logits, u, *, temperature=None, top_k=None, top_p=None, repeti
     return tokens
 
 
+# ---- prompt-lookup speculative decoding on the device (awq_spec_cdna4.hip): four launches, nothing read back to the host ----
+
+def _spec_i32(who, dev, **ts):
+    """every given tensor: int32, contiguous, on the GPU `dev`"""
+    for name, t in ts.items():
+        if t is None:
+            continue
+        _need_gpu(t)
+        if t.dtype != torch.int32 or t.device != dev:
+            raise ValueError(f"{who}: {name} must be an int32 tensor on {dev}")
+
+
+def spec_draft_ngram(history, hist_len, seqlens, *, vocab, kmax, ngram_min=1, ngram_max=3, max_len=2 ** 31 - 1, max_draft=None, drafts=None,
+                     draft_len=None):
+    """C-ABI awq_spec_draft_ngram: the prompt-lookup drafter over the sampler's history int32 [B, Lh] / hist_len [B] / seqlens [B] (-1 = inactive)
+    -> (drafts int32 [B, kmax], -1 behind the draft; draft_len int32 [B]).  The longest earlier occurrence of the history's last n-gram
+    (ngram_min .. ngram_max tokens, the most recent among equals) is continued for at most kmax / max_draft[b] tokens, never past the cache
+    (max_len) and never over an id outside [0, vocab).  drafts / draft_len: persistent outputs to write into (a captured graph's)."""
+    _need_gpu(history)
+    dev = history.device
+    _spec_i32("spec_draft_ngram", dev, history=history, hist_len=hist_len, seqlens=seqlens, max_draft=max_draft, drafts=drafts, draft_len=draft_len)
+    if history.dim() != 2 or history.shape[1] < 1:
+        raise ValueError("spec_draft_ngram: history must be int32 [B, Lh] with Lh >= 1")
+    b, lh = history.shape
+    for name, t in (("hist_len", hist_len), ("seqlens", seqlens), ("max_draft", max_draft), ("draft_len", draft_len)):
+        if t is not None and t.numel() != b:
+            raise ValueError(f"spec_draft_ngram: {name} must hold B values")
+    kmax = int(kmax)
+    if drafts is None:
+        drafts = torch.empty(b, kmax, dtype=torch.int32, device=dev)
+    elif tuple(drafts.shape) != (b, kmax):
+        raise ValueError("spec_draft_ngram: drafts must be [B, kmax]")
+    if draft_len is None:
+        draft_len = torch.empty(b, dtype=torch.int32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().awq_spec_draft_ngram(history.data_ptr(), hist_len.data_ptr(), seqlens.data_ptr(), ptr(max_draft),
+                                                     drafts.data_ptr() if kmax > 0 else None, draft_len.data_ptr(), b, lh, int(vocab), kmax,
+                                                     int(ngram_min), int(ngram_max), int(max_len), _stream(history)))
+    return drafts, draft_len
+
+
+def spec_pack(last_tokens, drafts, draft_len, seqlens, total_q, *, cu_seqlens_q=None, input_ids=None):
+    """C-ABI awq_spec_pack: the layout of a speculative step.  last_tokens int32 [B] (what the previous sample_logits / spec_accept returned),
+    drafts int32 [B, kmax] and draft_len int32 [B] (from any drafter; REWRITTEN to what the budget grants), seqlens int32 [B] -> (cu_seqlens_q int32
+    [B + 1], input_ids int32 [total_q]).  Every active slot gets one row, the other total_q - A rows go to the drafts in slot order; the rows behind
+    cu_seqlens_q[B] hold -1."""
+    _need_gpu(last_tokens)
+    dev = last_tokens.device
+    _spec_i32("spec_pack", dev, last_tokens=last_tokens, drafts=drafts, draft_len=draft_len, seqlens=seqlens, cu_seqlens_q=cu_seqlens_q,
+              input_ids=input_ids)
+    b = last_tokens.numel()
+    if drafts.dim() != 2 or drafts.shape[0] != b or draft_len.numel() != b or seqlens.numel() != b:
+        raise ValueError("spec_pack: drafts must be [B, kmax], draft_len and seqlens [B]")
+    kmax, total_q = drafts.shape[1], int(total_q)
+    if cu_seqlens_q is None:
+        cu_seqlens_q = torch.empty(b + 1, dtype=torch.int32, device=dev)
+    elif cu_seqlens_q.numel() != b + 1:
+        raise ValueError("spec_pack: cu_seqlens_q must be [B + 1]")
+    if input_ids is None:
+        input_ids = torch.empty(max(total_q, 0), dtype=torch.int32, device=dev)
+    elif input_ids.numel() != total_q:
+        raise ValueError("spec_pack: input_ids must be [total_q]")
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().awq_spec_pack(last_tokens.data_ptr(), drafts.data_ptr() if kmax > 0 else None, draft_len.data_ptr(),
+                                              seqlens.data_ptr(), cu_seqlens_q.data_ptr(), input_ids.data_ptr(), b, kmax, total_q,
+                                              _stream(last_tokens)))
+    return cu_seqlens_q, input_ids
+
+
+def spec_verify(logits, u, cu_seqlens_q, input_ids, *, temperature=None, top_k=None, top_p=None, repetition_penalty=None, history=None,
+                hist_len=None, row_tokens=None):
+    """C-ABI awq_spec_verify: sample_logits' row routine on every row of a packed step.  logits [total_q, V] (fp32 / bf16 / fp16), u fp32 [total_q],
+    cu_seqlens_q int32 [B + 1] and input_ids int32 [total_q] (spec_pack's) -> row_tokens int32 [total_q]: the token sample_logits would draw from
+    the row with its owner's parameters ([B] tensors or None) and u[r], the penalty set being the owner's history plus the burst's earlier inputs
+    (those the serial loop would have appended by then).  -1 for the padding rows.  Nothing is appended or advanced."""
+    params = (u, temperature, top_k, top_p, repetition_penalty, history, hist_len, cu_seqlens_q, input_ids, row_tokens)
+    _need_gpu(logits, *params)
+    if logits.dim() != 2:
+        raise ValueError("spec_verify: logits must be [total_q, V]")
+    code = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}.get(logits.dtype)
+    if code is None:
+        raise TypeError(f"spec_verify: expected float32/bfloat16/float16 logits, got {logits.dtype}")
+    tq, v = logits.shape
+    dev = logits.device
+    _spec_i32("spec_verify", dev, cu_seqlens_q=cu_seqlens_q, input_ids=input_ids, top_k=top_k, history=history, hist_len=hist_len,
+              row_tokens=row_tokens)
+    b = cu_seqlens_q.numel() - 1
+    if b < 1 or input_ids.numel() != tq or u is None or u.dtype != torch.float32 or u.numel() != tq or u.device != dev:
+        raise ValueError("spec_verify: cu_seqlens_q must be [B + 1], input_ids int32 [total_q] and u float32 [total_q] on the logits' device")
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_p", top_p, torch.float32),
+                        ("repetition_penalty", repetition_penalty, torch.float32), ("top_k", top_k, torch.int32), ("hist_len", hist_len, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != b or t.device != dev):
+            raise ValueError(f"spec_verify: {name} must be {dt} [B] on the logits' device")
+    if (history is None) != (hist_len is None):
+        raise ValueError("spec_verify: history and hist_len come together")
+    if history is not None and (history.dim() != 2 or history.shape[0] != b or history.shape[1] < 1):
+        raise ValueError("spec_verify: history must be int32 [B, Lh] with Lh >= 1")
+    if row_tokens is None:
+        row_tokens = torch.empty(tq, dtype=torch.int32, device=dev)
+    elif row_tokens.numel() != tq:
+        raise ValueError("spec_verify: row_tokens must be [total_q]")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().awq_spec_verify(logits.data_ptr(), code, tq, v, u.data_ptr(), cu_seqlens_q.data_ptr(), input_ids.data_ptr(), b,
+                                                ptr(temperature), ptr(top_k), ptr(top_p), ptr(repetition_penalty), ptr(history), ptr(hist_len),
+                                                0 if history is None else history.shape[1], row_tokens.data_ptr(), _stream(logits)))
+    return row_tokens
+
+
+def spec_accept(row_tokens, input_ids, cu_seqlens_q, kmax, *, history=None, hist_len=None, seqlens=None, stop_ids=None, finished=None, max_len=0,
+                append=False, advance=False, out_tokens=None, num_emitted=None, last_tokens=None):
+    """C-ABI awq_spec_accept: what a speculative step emits.  Per slot, the drafts (input_ids behind the slot's first row) are accepted while they
+    equal the token sampled from the row before them; the samples up to and including the first mismatch (or the bonus token behind the last
+    draft) are emitted, each through sample_logits' append / stop / advance, ending early once the slot has finished.  -> (out_tokens int32
+    [B, kmax + 1] with -1 behind, num_emitted int32 [B], last_tokens int32 [B])."""
+    _need_gpu(row_tokens)
+    dev = row_tokens.device
+    _spec_i32("spec_accept", dev, row_tokens=row_tokens, input_ids=input_ids, cu_seqlens_q=cu_seqlens_q, history=history, hist_len=hist_len,
+              seqlens=seqlens, stop_ids=stop_ids, finished=finished, out_tokens=out_tokens, num_emitted=num_emitted, last_tokens=last_tokens)
+    tq, b, kmax = row_tokens.numel(), cu_seqlens_q.numel() - 1, int(kmax)
+    if b < 1 or input_ids.numel() != tq:
+        raise ValueError("spec_accept: cu_seqlens_q must be [B + 1] and input_ids [total_q] like row_tokens")
+    for name, t in (("hist_len", hist_len), ("seqlens", seqlens), ("finished", finished), ("num_emitted", num_emitted), ("last_tokens", last_tokens)):
+        if t is not None and t.numel() != b:
+            raise ValueError(f"spec_accept: {name} must hold B values")
+    if (history is None) != (hist_len is None):
+        raise ValueError("spec_accept: history and hist_len come together")
+    if history is not None and (history.dim() != 2 or history.shape[0] != b or history.shape[1] < 1):
+        raise ValueError("spec_accept: history must be int32 [B, Lh] with Lh >= 1")
+    if append and history is None:
+        raise ValueError("spec_accept: append needs history and hist_len")
+    if advance and seqlens is None:
+        raise ValueError("spec_accept: advance needs seqlens")
+    if out_tokens is None:
+        out_tokens = torch.empty(b, kmax + 1, dtype=torch.int32, device=dev)
+    elif tuple(out_tokens.shape) != (b, kmax + 1):
+        raise ValueError("spec_accept: out_tokens must be [B, kmax + 1]")
+    num_emitted = torch.empty(b, dtype=torch.int32, device=dev) if num_emitted is None else num_emitted
+    last_tokens = torch.empty(b, dtype=torch.int32, device=dev) if last_tokens is None else last_tokens
+    ptr = lambda t: None if t is None else t.data_ptr()
+    flags = (_capi.AWQ_SAMPLE_APPEND if append else 0) | (_capi.AWQ_SAMPLE_ADVANCE if advance else 0)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().awq_spec_accept(row_tokens.data_ptr(), input_ids.data_ptr(), cu_seqlens_q.data_ptr(), b, tq, kmax, ptr(history),
+                                                ptr(hist_len), 0 if history is None else history.shape[1], ptr(seqlens), ptr(stop_ids),
+                                                0 if stop_ids is None else stop_ids.numel(), ptr(finished), int(max_len), flags,
+                                                out_tokens.data_ptr(), num_emitted.data_ptr(), last_tokens.data_ptr(), _stream(row_tokens)))
+    return out_tokens, num_emitted, last_tokens
+
+
 # ---- LM head for decode and the token embedding gather (awq_lm_head_cdna4.hip) ----
 
 def lm_head_plan(m: int, v: int, k: int) -> dict:
