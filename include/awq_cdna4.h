@@ -351,6 +351,40 @@ int awq_lm_head_plan(int m, int v, int k, int out[4]);
  * causes a read outside the table.  n >= 1, v >= 1, k >= 8, k % 8 == 0 (AWQ_ERR_SHAPE); table / out 16-byte, tokens 4-byte aligned. */
 int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, int dtype, void* stream);
 
+/* ---- Multi-LoRA on packed steps: y[t, :] += scaling[a] (x[t, :] A_a^T) B_a^T with a = adapter_ids[owner of row t], in TWO launches per adapted
+ * linear whatever the mix of adapters, decodes and prompt chunks (shrink, then expand).  DESIGN.md "Multi-LoRA" states the result by values:
+ *   x             T [total_q, k], row stride ldx elements (ldx % 8 == 0, ldx >= k): the packed rows of the step
+ *   a_pool        T [slots, rs, k] contiguous, rs = n_slices * r: slot a, slice j owns rows j r .. (j + 1) r - 1
+ *   b_pool        T [slots, n, r] contiguous: output column n of slot a is row n
+ *   scaling       fp32 [slots]: alpha / rank of every slot
+ *   adapter_ids   int32 [batch]: the slot of sequence b; any value outside [0, slots) = no adapter (-1 is the canonical value)
+ *   cu_seqlens_q  int32 [batch + 1] or NULL: the packed-step contract of awq_attn_prefill_kvcache_varq (Sq_b = cu[b + 1] - cu[b], 0 is legal,
+ *                 Sq_b > max_seqlen_q is inactive, rows >= cu[batch] are padding).  NULL = rectangular: sequence b owns rows b max_seqlen_q ..
+ *                 (b + 1) max_seqlen_q - 1 and total_q must equal batch * max_seqlen_q (AWQ_ERR_BATCH)
+ *   slice_end     HOST ints [n_slices]: slice j is output columns [slice_end[j - 1], slice_end[j]), multiples of 16, strictly increasing, last == n
+ *   y             T [total_q, n] contiguous, updated in place (the base linear's output)
+ *   workspace     fp32 [KS, total_q, rs], awq_lora_workspace_bytes: the K-split partials carried from shrink to expand
+ * For every row t of an active sequence b with 0 <= a = adapter_ids[b] < slots:
+ *   shrink: workspace[s, t, c] = sum over the k of split s of f32(x[t, k]) f32(A_a[c, k]), fp32, c < rs
+ *   expand: hT[t, c] = T(scaling[a] * (workspace[0, t, c] + workspace[1, t, c] + ... in this order)): one fp32 product, one nearest-even rounding;
+ *           y[t, n] = T(f32(y[t, n]) + sum_{i < r} f32(hT[t, j(n) r + i]) f32(B_a[n, i])): the fp32 delta is NOT rounded before the add
+ * Every other row (padding, no adapter, inactive or empty sequence) keeps every bit of y; its x is not read, its workspace rows are neither written
+ * nor read; pool slots no active sequence names are not read.  KS and the order of every sum depend on (k, rs) alone, so a row's bits do not depend
+ * on the batch it is served in.  No atomics, no host read, bit-stable from run to run; both launches can be captured.  A row index formed from
+ * cu_seqlens_q is clamped into [0, total_q - 1] before it forms an address and every write is guarded.
+ * Limits, checked before anything is launched: r in {16, 32, 64}, n_slices in {1, 2, 3}, k >= 64, k % 64 == 0, n % 16 == 0, ldx and slice_end as
+ * above (AWQ_ERR_SHAPE); 1 <= batch <= 65535, 1 <= max_seqlen_q <= 1048560, total_q >= 1, slots >= 1 (AWQ_ERR_BATCH); workspace_bytes
+ * (AWQ_ERR_WORKSPACE); x / a_pool / b_pool / y / workspace 16-byte, the int32 and fp32 vectors 4-byte aligned (AWQ_ERR_ALIGN).
+ * awq_lora_plan (host only): out[4] = {KS, k per split, output columns per expand block, waves per block}; split s sums k in
+ * [s out[1], min(k, (s + 1) out[1])).  awq_lora_workspace_bytes (host only): 0 for sizes outside the limits. ---- */
+int awq_lora_plan(int k, int r, int n_slices, int out[4]);
+size_t awq_lora_workspace_bytes(int total_q, int k, int r, int n_slices);
+int awq_lora_shrink(const void* x, long ldx, const void* a_pool, const int* adapter_ids, const int* cu_seqlens_q, void* workspace,
+                    size_t workspace_bytes, int batch, int max_seqlen_q, int total_q, int slots, int k, int r, int n_slices, int dtype, void* stream);
+int awq_lora_expand(const void* workspace, size_t workspace_bytes, const void* b_pool, const float* scaling, const int* adapter_ids,
+                    const int* cu_seqlens_q, void* y, int batch, int max_seqlen_q, int total_q, int slots, int n, int k, int r, const int* slice_end,
+                    int n_slices, int dtype, void* stream);
+
 /* ---- AWQ quantisation: the asymmetric per-group grid of the reference's pseudo_quantize_tensor(zero_point=True)
  * (awq/quantize/quantizer.py:61-103) evaluated as torch evaluates it on T tensors -- every operation in fp32 on T values and rounded to T
  * (nearest-even, fp16 subnormals kept) before the next one, IEEE division, no fused multiply-add across two of torch's roundings.  DESIGN.md

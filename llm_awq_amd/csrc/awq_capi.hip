@@ -1470,6 +1470,56 @@ int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int
   return finish_launch();
 }
 
+// ---- Multi-LoRA on packed steps: shrink + expand (awq_lora_cdna4.hip) ----
+static int lora_check_batch(const int* cu_seqlens_q, int batch, int max_seqlen_q, int total_q, int slots) {
+  if (batch < 1 || batch > 65535 || max_seqlen_q < 1 || max_seqlen_q > 1048560 || total_q < 1 || slots < 1) return AWQ_ERR_BATCH;
+  if (!cu_seqlens_q && (long long)batch * max_seqlen_q != (long long)total_q) return AWQ_ERR_BATCH;  // rectangular: every row is owned
+  return AWQ_OK;
+}
+
+int awq_lora_plan(int k, int r, int n_slices, int out[4]) {
+  if (!out) return AWQ_ERR_NULL;
+  return awq::lora_plan(k, r, n_slices, out) != 0 ? AWQ_ERR_SHAPE : AWQ_OK;
+}
+
+size_t awq_lora_workspace_bytes(int total_q, int k, int r, int n_slices) { return awq::lora_workspace_bytes(total_q, k, r, n_slices); }
+
+int awq_lora_shrink(const void* x, long ldx, const void* a_pool, const int* adapter_ids, const int* cu_seqlens_q, void* workspace,
+                    size_t workspace_bytes, int batch, int max_seqlen_q, int total_q, int slots, int k, int r, int n_slices, int dtype, void* stream) {
+  if (!x || !a_pool || !adapter_ids || !workspace) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  int plan[4];
+  if (awq::lora_plan(k, r, n_slices, plan) != 0 || ldx < k || (ldx % 8) != 0) return AWQ_ERR_SHAPE;
+  if (const int st = lora_check_batch(cu_seqlens_q, batch, max_seqlen_q, total_q, slots)) return st;
+  if (workspace_bytes < awq::lora_workspace_bytes(total_q, k, r, n_slices)) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(x) || !aligned16(a_pool) || !aligned16(workspace) || !aligned_to(adapter_ids, 4) || !aligned_to(cu_seqlens_q, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_lora_shrink(x, ldx, a_pool, adapter_ids, cu_seqlens_q, workspace, batch, max_seqlen_q, total_q, slots, k, r, n_slices, dtype,
+                              (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_lora_expand(const void* workspace, size_t workspace_bytes, const void* b_pool, const float* scaling, const int* adapter_ids,
+                    const int* cu_seqlens_q, void* y, int batch, int max_seqlen_q, int total_q, int slots, int n, int k, int r, const int* slice_end,
+                    int n_slices, int dtype, void* stream) {
+  if (!workspace || !b_pool || !scaling || !adapter_ids || !y || !slice_end) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  int plan[4];
+  if (awq::lora_plan(k, r, n_slices, plan) != 0 || n < 16 || (n % 16) != 0) return AWQ_ERR_SHAPE;
+  for (int j = 0, prev = 0; j < n_slices; prev = slice_end[j++])
+    if (slice_end[j] <= prev || (slice_end[j] % 16) != 0 || slice_end[j] > n) return AWQ_ERR_SHAPE;
+  if (slice_end[n_slices - 1] != n) return AWQ_ERR_SHAPE;
+  if (const int st = lora_check_batch(cu_seqlens_q, batch, max_seqlen_q, total_q, slots)) return st;
+  if (workspace_bytes < awq::lora_workspace_bytes(total_q, k, r, n_slices)) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace) || !aligned16(b_pool) || !aligned16(y) || !aligned_to(scaling, 4) || !aligned_to(adapter_ids, 4) ||
+      !aligned_to(cu_seqlens_q, 4))
+    return AWQ_ERR_ALIGN;
+  if (awq::launch_lora_expand(workspace, b_pool, scaling, adapter_ids, cu_seqlens_q, y, batch, max_seqlen_q, total_q, slots, n, k, r, slice_end,
+                              n_slices, dtype, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- AWQ quantisation: group quantiser + packer, clip search (awq_quant_cdna4.hip) ----
 int awq_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
                        void* zeros, void* qweight, int qweight_layout, int n, int k, int group_size, int n_bit, int dtype, void* stream) {

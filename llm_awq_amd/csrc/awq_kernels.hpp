@@ -177,6 +177,15 @@ int lm_head_plan(int m, int v, int k, int out[4]);
 int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                    int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st);
 int launch_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, hipStream_t st);  // zeros for an id outside [0, v)
+// Multi-LoRA on packed steps (awq_lora_cdna4.hip): shrink (x A_a^T into the fp32 K-split workspace) and expand (scale, round, B_a^T, add into y in
+// place), the adapter of a row read on the device; the plan is {KS, k per split, expand column tile, waves}; -1 if the sizes are outside the documented
+// limits, pointers / alignment / workspace size validated by the caller
+int lora_plan(int k, int r, int n_slices, int out[4]);
+size_t lora_workspace_bytes(int total_q, int k, int r, int n_slices);
+int launch_lora_shrink(const void* x, long ldx, const void* a_pool, const int* adapter_ids, const int* cu_seqlens_q, void* ws, int batch,
+                       int max_seqlen_q, int total_q, int slots, int k, int r, int n_slices, int dtype, hipStream_t st);
+int launch_lora_expand(const void* ws, const void* b_pool, const float* scaling, const int* adapter_ids, const int* cu_seqlens_q, void* y, int batch,
+                       int max_seqlen_q, int total_q, int slots, int n, int k, int r, const int* slice_end, int n_slices, int dtype, hipStream_t st);
 // AWQ quantisation (awq_quant_cdna4.hip): the group quantiser + packer (layout 0 = v2, 1 = cdna4; every output optional) and the clip search;
 // -1 if the sizes are outside the documented limits, pointers / alignment validated by the caller
 int launch_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,

@@ -760,6 +760,70 @@ torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
   return out;
 }
 
+// ---- Multi-LoRA on packed steps: shrink (x A_a^T into the fp32 K-split workspace) and expand (scale, round, B_a^T, add into y in place) ----
+struct LoraBatch {
+  const int* ids;
+  const int* cu;
+  int batch, max_seqlen_q, total_q;
+};
+
+LoraBatch lora_batch(const char* who, const torch::Tensor& rows, const torch::Tensor& adapter_ids, const c10::optional<torch::Tensor>& cu_seqlens_q,
+                     int64_t max_seqlen_q) {
+  TORCH_CHECK(adapter_ids.is_cuda() && adapter_ids.is_contiguous() && adapter_ids.scalar_type() == at::kInt && adapter_ids.dim() == 1 &&
+                  adapter_ids.numel() >= 1 && adapter_ids.device() == rows.device(),
+              "awq_inference_engine: ", who, ": adapter_ids must be a contiguous int32 [B] tensor on the rows' GPU");
+  const int64_t b = adapter_ids.numel();
+  if (cu_seqlens_q.has_value())
+    TORCH_CHECK(cu_seqlens_q->is_cuda() && cu_seqlens_q->is_contiguous() && cu_seqlens_q->scalar_type() == at::kInt && cu_seqlens_q->dim() == 1 &&
+                    cu_seqlens_q->numel() == b + 1 && cu_seqlens_q->device() == rows.device(),
+                "awq_inference_engine: ", who, ": cu_seqlens_q must be a contiguous int32 [B + 1] tensor on the rows' GPU");
+  return {(const int*)adapter_ids.data_ptr(), cu_seqlens_q.has_value() ? (const int*)cu_seqlens_q->data_ptr() : nullptr, (int)b, (int)max_seqlen_q,
+          (int)rows.size(0)};
+}
+
+void lora_ws_check(const char* who, const torch::Tensor& ws, const torch::Tensor& rows) {
+  TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() && ws.scalar_type() == at::kFloat && ws.device() == rows.device(), "awq_inference_engine: ", who,
+              ": ws must be a contiguous float32 tensor on the rows' GPU");
+}
+
+torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a_pool, torch::Tensor adapter_ids, torch::Tensor ws, int64_t rank,
+                          c10::optional<torch::Tensor> cu_seqlens_q, int64_t max_seqlen_q) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.size(0) >= 1 && (x.stride(1) == 1 || x.size(1) <= 1),
+              "awq_inference_engine: lora_shrink: x must be a [total_q, K] GPU tensor with a contiguous last dimension");
+  TORCH_CHECK(a_pool.is_cuda() && a_pool.is_contiguous() && a_pool.dim() == 3 && a_pool.size(2) == x.size(1) && a_pool.scalar_type() == x.scalar_type() &&
+                  a_pool.device() == x.device() && rank >= 1 && a_pool.size(1) % rank == 0,
+              "awq_inference_engine: lora_shrink: a_pool must be a contiguous [S, n_slices * R, K] GPU tensor of x's dtype");
+  lora_ws_check("lora_shrink", ws, x);
+  const LoraBatch lb = lora_batch("lora_shrink", x, adapter_ids, cu_seqlens_q, max_seqlen_q);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const int64_t ldx = x.size(0) > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), x.size(1)) / 8 * 8;
+  raise_on(awq_lora_shrink(x.data_ptr(), (long)ldx, a_pool.data_ptr(), lb.ids, lb.cu, ws.data_ptr(), (size_t)ws.numel() * 4, lb.batch, lb.max_seqlen_q,
+                           lb.total_q, (int)a_pool.size(0), (int)x.size(1), (int)rank, (int)(a_pool.size(1) / rank), dtype_code(x),
+                           (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return ws;
+}
+
+torch::Tensor lora_expand(torch::Tensor ws, torch::Tensor b_pool, torch::Tensor scaling, torch::Tensor adapter_ids, torch::Tensor y, int64_t k,
+                          std::vector<int64_t> slice_end, c10::optional<torch::Tensor> cu_seqlens_q, int64_t max_seqlen_q) {
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && y.dim() == 2 && y.size(0) >= 1, "awq_inference_engine: lora_expand: y must be a contiguous [total_q, N] GPU tensor");
+  TORCH_CHECK(b_pool.is_cuda() && b_pool.is_contiguous() && b_pool.dim() == 3 && b_pool.size(1) == y.size(1) && b_pool.scalar_type() == y.scalar_type() &&
+                  b_pool.device() == y.device(),
+              "awq_inference_engine: lora_expand: b_pool must be a contiguous [S, N, R] GPU tensor of y's dtype");
+  TORCH_CHECK(scaling.is_cuda() && scaling.is_contiguous() && scaling.scalar_type() == at::kFloat && scaling.numel() == b_pool.size(0) &&
+                  scaling.device() == y.device(),
+              "awq_inference_engine: lora_expand: scaling must be a contiguous float32 [S] tensor on y's GPU");
+  TORCH_CHECK(slice_end.size() >= 1 && slice_end.size() <= 3, "awq_inference_engine: lora_expand: slice_end must hold 1 .. 3 column ends");
+  lora_ws_check("lora_expand", ws, y);
+  const LoraBatch lb = lora_batch("lora_expand", y, adapter_ids, cu_seqlens_q, max_seqlen_q);
+  int ends[3] = {0, 0, 0};
+  for (size_t j = 0; j < slice_end.size(); ++j) ends[j] = (int)slice_end[j];
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  raise_on(awq_lora_expand(ws.data_ptr(), (size_t)ws.numel() * 4, b_pool.data_ptr(), (const float*)scaling.data_ptr(), lb.ids, lb.cu, y.data_ptr(),
+                           lb.batch, lb.max_seqlen_q, lb.total_q, (int)b_pool.size(0), (int)y.size(1), (int)k, (int)b_pool.size(2), ends,
+                           (int)slice_end.size(), dtype_code(y), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return y;
+}
+
 // ---- AWQ quantisation: group quantiser + packer and clip search, one launch each ----
 std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
            c10::optional<torch::Tensor>>
@@ -2206,6 +2270,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
   m.def("embed_tokens", &embed_tokens, "out[i] = table[tokens[i]], zeros for an id outside the table (-1 = a finished slot)", py::arg("tokens"),
         py::arg("table"));
+  m.def("lora_shrink", &lora_shrink, "multi-LoRA shrink: ws[s, t, :] = x[t, k of split s] @ A_{adapter of t}^T in fp32 (rows without an adapter untouched)",
+        py::arg("x"), py::arg("a_pool"), py::arg("adapter_ids"), py::arg("ws"), py::arg("rank"), py::arg("cu_seqlens_q") = py::none(),
+        py::arg("max_seqlen_q") = 1);
+  m.def("lora_expand", &lora_expand, "multi-LoRA expand: y[t, :] += T(scaling * sum_s ws[s, t, :]) @ B_{adapter of t}^T in place, one rounding",
+        py::arg("ws"), py::arg("b_pool"), py::arg("scaling"), py::arg("adapter_ids"), py::arg("y"), py::arg("k"), py::arg("slice_end"),
+        py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 1);
   m.def("quantize_pack", &quantize_pack,
         "AWQ group quantiser + packer, one launch: (w_fake, scales, scaled_zeros, zeros, qweight), None where not wanted", py::arg("w"),
         py::arg("col_scale") = py::none(), py::arg("clip_max") = py::none(), py::arg("n_bit") = 4, py::arg("layout") = "cdna4",

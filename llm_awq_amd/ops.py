@@ -797,6 +797,148 @@ def embed_tokens(tokens, table):
     return out
 
 
+# ---- multi-LoRA on packed steps: per-sequence adapters, read on the device (awq_lora_cdna4.hip) ----
+
+def lora_plan(k: int, r: int, n_slices: int = 1) -> dict:
+    """C-ABI awq_lora_plan (host only): the K split of the shrink launch and the shape of both launches for in_features k, pool rank r and
+    n_slices output slices.  A function of (k, r * n_slices) alone: split s sums k in [s * k_per_split, min(k, (s + 1) * k_per_split))."""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    _capi.check(_capi.lib().awq_lora_plan(int(k), int(r), int(n_slices), out))
+    return {"k_splits": out[0], "k_per_split": out[1], "col_tile": out[2], "waves": out[3]}
+
+
+def lora_workspace_bytes(total_q: int, k: int, r: int, n_slices: int = 1) -> int:
+    """C-ABI awq_lora_workspace_bytes (host only): bytes of the fp32 [k_splits, total_q, n_slices * r] workspace; 0 for sizes outside the limits."""
+    return int(_capi.lib().awq_lora_workspace_bytes(int(total_q), int(k), int(r), int(n_slices)))
+
+
+def _lora_rows(who, name, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _capi.AwqNativeError(f"{who}: {name} must be a GPU tensor (llm_awq_amd ops run on the GPU only, no CPU fallback)")
+    if t.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{who}: {name} must be float16 or bfloat16, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError(f"{who}: {name} must be a [total_q, features] matrix with at least one row")
+
+
+def _lora_pool(who, name, t, ref, shape):
+    if not t.is_cuda:
+        raise _capi.AwqNativeError(f"{who}: {name} must be a GPU tensor (llm_awq_amd ops run on the GPU only, no CPU fallback)")
+    if t.dtype != ref.dtype or t.device != ref.device:
+        raise TypeError(f"{who}: {name} must have the rows' dtype {ref.dtype} and device, got {t.dtype} on {t.device}")
+    if t.dim() != 3 or not t.is_contiguous() or any(s is not None and t.shape[i] != s for i, s in enumerate(shape)):
+        raise ValueError(f"{who}: {name} must be a contiguous {list(shape)} tensor (None = any), got {list(t.shape)}")
+
+
+def _lora_batch(who, ref, adapter_ids, cu_seqlens_q, max_seqlen_q):
+    """adapter_ids int32 [B] and the optional cu_seqlens_q int32 [B + 1] of a step whose packed rows are `ref`; returns B"""
+    for name, t in (("adapter_ids", adapter_ids), ("cu_seqlens_q", cu_seqlens_q)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise _capi.AwqNativeError(f"{who}: {name} must be a GPU tensor (it is read on the device, never by the host)")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{who}: {name} must be int32, got {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous() or t.device != ref.device:
+            raise ValueError(f"{who}: {name} must be a contiguous 1-D tensor on the rows' GPU")
+    b = adapter_ids.shape[0]
+    if b < 1 or b > 65535:
+        raise ValueError(f"{who}: adapter_ids must hold 1 .. 65535 sequences, got {b}")
+    if int(max_seqlen_q) < 1:
+        raise ValueError(f"{who}: max_seqlen_q >= 1 is expected")
+    if cu_seqlens_q is not None and cu_seqlens_q.shape[0] != b + 1:
+        raise ValueError(f"{who}: cu_seqlens_q must be int32 [B + 1] = [{b + 1}], got {list(cu_seqlens_q.shape)}")
+    if cu_seqlens_q is None and b * int(max_seqlen_q) != ref.shape[0]:
+        raise ValueError(f"{who}: without cu_seqlens_q the rows are rectangular: {ref.shape[0]} rows != B * max_seqlen_q = {b * int(max_seqlen_q)}")
+    return b
+
+
+def _lora_ws(who, ws, ref, need):
+    if ws is None:
+        return torch.empty(need // 4, dtype=torch.float32, device=ref.device)
+    if not ws.is_cuda or ws.device != ref.device or ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise ValueError(f"{who}: ws must be a contiguous float32 tensor on the rows' GPU")
+    if ws.numel() * 4 < need:
+        raise ValueError(f"{who}: ws holds {ws.numel() * 4} bytes, lora_workspace_bytes asks for {need}")
+    return ws
+
+
+def lora_shrink(x, a_pool, adapter_ids, rank: int, cu_seqlens_q=None, max_seqlen_q: int = 1, ws=None):
+    """C-ABI awq_lora_shrink: ws[s, t, :] = sum over the k of split s of x[t, k] * A_a[:, k] in fp32, a = adapter_ids[owner of row t].
+    x [total_q, K] (a row-strided view is passed on, nothing is copied), a_pool [S, n_slices * rank, K].  Rows without an adapter, padding rows and
+    the rows of inactive sequences are neither read nor written.  Returns ws (allocated when None)."""
+    who = "lora_shrink"
+    _lora_rows(who, "x", x)
+    k = x.shape[1]
+    if x.stride(1) != 1 and k > 1:
+        raise ValueError(f"{who}: the last dimension of x must be contiguous")
+    _lora_pool(who, "a_pool", a_pool, x, (None, None, k))
+    rs = a_pool.shape[1]
+    if int(rank) < 1 or rs % int(rank) != 0:
+        raise ValueError(f"{who}: a_pool holds {rs} rows per slot, not a multiple of rank {rank}")
+    b = _lora_batch(who, x, adapter_ids, cu_seqlens_q, max_seqlen_q)
+    total_q, n_slices = x.shape[0], rs // int(rank)
+    lora_plan(k, rank, n_slices)  # refuses the shape before anything is allocated
+    ws = _lora_ws(who, ws, x, lora_workspace_bytes(total_q, k, rank, n_slices))
+    ldx = x.stride(0) if total_q > 1 else max(x.stride(0), k) // 8 * 8
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_lora_shrink(x.data_ptr(), ldx, a_pool.data_ptr(), adapter_ids.data_ptr(),
+                                                None if cu_seqlens_q is None else cu_seqlens_q.data_ptr(), ws.data_ptr(), ws.numel() * 4, b,
+                                                int(max_seqlen_q), total_q, a_pool.shape[0], k, int(rank), n_slices, _dt(x), _stream(x)))
+    return ws
+
+
+def lora_expand(ws, b_pool, scaling, adapter_ids, y, k: int, slice_end=None, cu_seqlens_q=None, max_seqlen_q: int = 1):
+    """C-ABI awq_lora_expand: y[t, n] = T(y[t, n] + sum_r hT[t, j(n) R + r] * B_a[n, r]) in place, hT = T(scaling[a] * sum_s ws[s, t, :]).
+    b_pool [S, N, R], scaling float32 [S], slice_end: the ends of the output slices (default (N,)), k: the in_features the shrink launch summed
+    over (it fixes the number of K splits)."""
+    who = "lora_expand"
+    _lora_rows(who, "y", y)
+    if not y.is_contiguous():
+        raise ValueError(f"{who}: y must be contiguous (it is updated in place)")
+    total_q, n = y.shape
+    _lora_pool(who, "b_pool", b_pool, y, (None, n, None))
+    s, _, r = b_pool.shape
+    if not scaling.is_cuda:
+        raise _capi.AwqNativeError(f"{who}: scaling must be a GPU tensor (llm_awq_amd ops run on the GPU only, no CPU fallback)")
+    if scaling.dtype != torch.float32 or scaling.numel() != s or scaling.device != y.device or not scaling.is_contiguous():
+        raise ValueError(f"{who}: scaling must be a contiguous float32 [S] = [{s}] tensor on y's GPU")
+    ends = [n] if slice_end is None else [int(e) for e in slice_end]
+    if not 1 <= len(ends) <= 3:
+        raise ValueError(f"{who}: slice_end must hold 1 .. 3 column ends, got {len(ends)}")
+    b = _lora_batch(who, y, adapter_ids, cu_seqlens_q, max_seqlen_q)
+    lora_plan(k, r, len(ends))
+    need = lora_workspace_bytes(total_q, k, r, len(ends))
+    if ws is None:
+        raise ValueError(f"{who}: ws (the output of lora_shrink) is required")
+    _lora_ws(who, ws, y, need)
+    import ctypes
+    with torch.cuda.device(y.device):
+        _capi.check(_capi.lib().awq_lora_expand(ws.data_ptr(), ws.numel() * 4, b_pool.data_ptr(), scaling.data_ptr(), adapter_ids.data_ptr(),
+                                                None if cu_seqlens_q is None else cu_seqlens_q.data_ptr(), y.data_ptr(), b, int(max_seqlen_q),
+                                                total_q, s, n, int(k), r, (ctypes.c_int * len(ends))(*ends), len(ends), _dt(y), _stream(y)))
+    return y
+
+
+def lora_apply(x, y, a_pool, b_pool, scaling, adapter_ids, slice_end=None, cu_seqlens_q=None, max_seqlen_q: int = 1, ws=None):
+    """Both launches: y[t, :] += scaling[a] * (x[t, :] @ A_a^T) @ B_a^T in place for a = adapter_ids[owner of row t]; every other row of y keeps its
+    bits.  x [total_q, K], y [total_q, N] (the base linear's output), a_pool [S, n_slices * R, K], b_pool [S, N, R], scaling float32 [S],
+    adapter_ids int32 [B] (outside [0, S): no adapter), slice_end: the ends of the output slices (multiples of 16, last == N; default one slice),
+    cu_seqlens_q int32 [B + 1] (None: B sequences of max_seqlen_q rows each).  Nothing is read by the host: the pair can be captured with a
+    workspace allocated beforehand (`ws`, lora_workspace_bytes).  Returns y."""
+    _lora_rows("lora_apply", "x", x)
+    _lora_rows("lora_apply", "y", y)
+    if x.shape[0] != y.shape[0] or x.dtype != y.dtype or x.device != y.device:
+        raise ValueError("lora_apply: x and y must hold the same rows, dtype and device")
+    _lora_pool("lora_apply", "b_pool", b_pool, y, (None, y.shape[1], None))
+    r = b_pool.shape[2]
+    n_slices = 1 if slice_end is None else len(slice_end)
+    _lora_pool("lora_apply", "a_pool", a_pool, x, (b_pool.shape[0], n_slices * r, x.shape[1]))
+    ws = lora_shrink(x, a_pool, adapter_ids, r, cu_seqlens_q, max_seqlen_q, ws)
+    return lora_expand(ws, b_pool, scaling, adapter_ids, y, x.shape[1], slice_end, cu_seqlens_q, max_seqlen_q)
+
+
 # ---- AWQ quantisation: group quantiser + packer and clip search (awq_quant_cdna4.hip) ----
 
 def _quant_weight(who, w):
