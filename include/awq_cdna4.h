@@ -385,6 +385,25 @@ int awq_lora_expand(const void* workspace, size_t workspace_bytes, const void* b
                     const int* cu_seqlens_q, void* y, int batch, int max_seqlen_q, int total_q, int slots, int n, int k, int r, const int* slice_end,
                     int n_slices, int dtype, void* stream);
 
+/* The expand launch on QuantLlamaMLP's gate / up pair, fused with the SiLU * mul tail (F = n2 / 2, two slices: 0 = gate, 1 = up):
+ *   workspace     the shrink launch's fp32 [KS, total_q, 2 r] with n_slices = 2 (gate's A rows first)
+ *   b_pool        T [slots, n2, r] in natural order: rows 0 .. F - 1 are B_gate, rows F .. 2F - 1 are B_up
+ *   y2            T [total_q, n2] contiguous, READ ONLY: the output of the 8 + 8 interleaved gate / up stream without its epilogue -- columns
+ *                 16 j .. 16 j + 7 are gate rows 8 j .., columns 16 j + 8 .. 16 j + 15 the matching up rows
+ *   h             T [total_q, F] contiguous, written
+ * For every row t of an active sequence b and every f < F, j = f / 8, c = f % 8:
+ *   with 0 <= a = adapter_ids[b] < slots:  g' = T(f32(y2[t, 16 j + c]) + sum_i f32(hT[t, i]) f32(B_a[f, i])),
+ *                                          u' = T(f32(y2[t, 16 j + 8 + c]) + sum_i f32(hT[t, r + i]) f32(B_a[F + f, i]))   (hT as in awq_lora_expand)
+ *   otherwise:                             g' = y2[t, 16 j + c], u' = y2[t, 16 j + 8 + c]; no workspace row, pool slot or scaling entry is read
+ *   h[t, f] = T(T(silu(g')) u'), the library's one SiLU * mul tail.
+ * The bits are those of awq_lora_expand with slice_end = {F, 2F} on the de-interleaved pair followed by awq_silu_mul (F % 16 == 8: with each slice
+ * zero-padded to a multiple of 16 columns, which that call asks of its slice ends).  Rows of inactive or empty
+ * sequences and padding rows: y2 is not read, h is not written.  Grid from host arguments only, no atomics, no host read; can be captured.
+ * Limits and error codes as awq_lora_expand with n = n2 and n_slices = 2 (n2 >= 16, n2 % 16 == 0); y2 / h 16-byte aligned. ---- */
+int awq_lora_expand_gate_up(const void* workspace, size_t workspace_bytes, const void* b_pool, const float* scaling, const int* adapter_ids,
+                            const int* cu_seqlens_q, const void* y2, void* h, int batch, int max_seqlen_q, int total_q, int slots, int n2, int k,
+                            int r, int dtype, void* stream);
+
 /* ---- AWQ quantisation: the asymmetric per-group grid of the reference's pseudo_quantize_tensor(zero_point=True)
  * (awq/quantize/quantizer.py:61-103) evaluated as torch evaluates it on T tensors -- every operation in fp32 on T values and rounded to T
  * (nearest-even, fp16 subnormals kept) before the next one, IEEE division, no fused multiply-add across two of torch's roundings.  DESIGN.md

@@ -76,6 +76,7 @@ SIGNATURES = {
     "awq_lora_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awq_lora_shrink": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _sz] + [_i] * 8 + [_vp]),
     "awq_lora_expand": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp] + [_i] * 7 + [ctypes.POINTER(ctypes.c_int), _i, _i, _vp]),
+    "awq_lora_expand_gate_up": (_i, [_vp, _sz] + [_vp] * 6 + [_i] * 8 + [_vp]),
     "awq_quantize_group": (_i, [_vp, ctypes.c_long] + [_vp] * 7 + [_i] * 6 + [_vp]),
     "awq_quantize_group_host": (_i, [_vp, ctypes.c_long] + [_vp] * 7 + [_i] * 5),
     "awq_clip_search": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp] + [_i] * 8 + [_vp]),

@@ -1520,6 +1520,24 @@ int awq_lora_expand(const void* workspace, size_t workspace_bytes, const void* b
   return finish_launch();
 }
 
+int awq_lora_expand_gate_up(const void* workspace, size_t workspace_bytes, const void* b_pool, const float* scaling, const int* adapter_ids,
+                            const int* cu_seqlens_q, const void* y2, void* h, int batch, int max_seqlen_q, int total_q, int slots, int n2, int k,
+                            int r, int dtype, void* stream) {
+  if (!workspace || !b_pool || !scaling || !adapter_ids || !y2 || !h) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  int plan[4];
+  if (awq::lora_plan(k, r, 2, plan) != 0 || n2 < 16 || (n2 % 16) != 0) return AWQ_ERR_SHAPE;
+  if (const int st = lora_check_batch(cu_seqlens_q, batch, max_seqlen_q, total_q, slots)) return st;
+  if (workspace_bytes < awq::lora_workspace_bytes(total_q, k, r, 2)) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace) || !aligned16(b_pool) || !aligned16(y2) || !aligned16(h) || !aligned_to(scaling, 4) || !aligned_to(adapter_ids, 4) ||
+      !aligned_to(cu_seqlens_q, 4))
+    return AWQ_ERR_ALIGN;
+  if (awq::launch_lora_expand_gate_up(workspace, b_pool, scaling, adapter_ids, cu_seqlens_q, y2, h, batch, max_seqlen_q, total_q, slots, n2, k, r,
+                                      dtype, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- AWQ quantisation: group quantiser + packer, clip search (awq_quant_cdna4.hip) ----
 int awq_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,
                        void* zeros, void* qweight, int qweight_layout, int n, int k, int group_size, int n_bit, int dtype, void* stream) {

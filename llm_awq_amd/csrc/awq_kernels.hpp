@@ -186,6 +186,12 @@ int launch_lora_shrink(const void* x, long ldx, const void* a_pool, const int* a
                        int max_seqlen_q, int total_q, int slots, int k, int r, int n_slices, int dtype, hipStream_t st);
 int launch_lora_expand(const void* ws, const void* b_pool, const float* scaling, const int* adapter_ids, const int* cu_seqlens_q, void* y, int batch,
                        int max_seqlen_q, int total_q, int slots, int n, int k, int r, const int* slice_end, int n_slices, int dtype, hipStream_t st);
+// expand on QuantLlamaMLP's gate / up pair: y2 [total_q, n2] is the unfused output of the 8 + 8 interleaved stream (read only), b_pool [slots, n2, r]
+// holds B_gate rows then B_up rows, h [total_q, n2 / 2] = T(T(silu(gate')) up') with the two deltas added first; rows of an active sequence without
+// an adapter get the plain tail; two slices in the workspace (lora_plan(k, r, 2))
+int launch_lora_expand_gate_up(const void* ws, const void* b_pool, const float* scaling, const int* adapter_ids, const int* cu_seqlens_q,
+                               const void* y2, void* h, int batch, int max_seqlen_q, int total_q, int slots, int n2, int k, int r, int dtype,
+                               hipStream_t st);
 // AWQ quantisation (awq_quant_cdna4.hip): the group quantiser + packer (layout 0 = v2, 1 = cdna4; every output optional) and the clip search;
 // -1 if the sizes are outside the documented limits, pointers / alignment validated by the caller
 int launch_quantize_group(const void* w, long ldw, const void* col_scale, const void* clip_max, void* w_fake, void* scales, void* scaled_zeros,

@@ -17,7 +17,16 @@
 //            16-column groups w, w + 4, ... of the tile: one k-step (R = 16: its upper half zero; R = 32) or two (R = 64) of
 //            v_mfma_f32_16x16x32 against B_a fragments loaded straight to VGPRs, and the fused read-add-round-store of y.  A group never
 //            straddles a slice (slice ends are multiples of 16).
-// Both grids come from host arguments only.  KS and the order of every sum depend on (K, RS) alone: a row's bits do not depend on the batch it
+//   expand on the gate / up pair   h[t, 8 j + c] = T(T(silu(g')) u'),  g' = T(f32(y2[t, 16 j + c]) + d_gate),  u' = T(f32(y2[t, 16 j + 8 + c]) + d_up)
+//                                                                                                  grid (ceil(2F / 256), ceil(max_seqlen_q / 16), B)
+//            y2 [total_q, 2F] is the UNFUSED output of QuantLlamaMLP's 8 + 8 interleaved gate / up stream (read only), h [total_q, F] is written.
+//            A 16-column group of y2 holds 8 gate and 8 up columns: lane c < 8 loads row f of B_gate, lane c >= 8 row F + f of B_up, and the
+//            k-step(s) are issued twice with these B registers, once against the gate half of hT and once against the up half; a lane keeps the
+//            accumulator of its own slice, so every column's MFMA operands are those of lora_expand_kernel and g' / u' are its bits.  The
+//            rounded pair meets in an LDS image of the block's [16][256] tile; after one barrier thread (row, group) reads a gate octet and an
+//            up octet from it, silu_mul_octet, one 16-byte store of h.  A tile of an active sequence WITHOUT an adapter leaves in front of the
+//            first barrier through the same 16-byte tail on y2 itself (no ws row, pool slot or scaling entry is read).
+// All grids come from host arguments only.  KS and the order of every sum depend on (K, RS) alone: a row's bits do not depend on the batch it
 // was served in.  No atomics: the fp32 workspace carries the partials from one launch to the next.
 // Row indices formed from cu_seqlens_q are clamped into [0, total_q - 1] before they form an address and every write is guarded (awq_varq.hpp).
 #include "awq_device.hpp"
@@ -204,6 +213,121 @@ __global__ __launch_bounds__(kLoraThreads) void lora_expand_kernel(const LoraExp
   }
 }
 
+struct LoraGateUpArgs {
+  const float* ws;
+  const uint16_t* b_pool;
+  const float* scaling;
+  const int* ids;
+  const int* cu;
+  const uint16_t* y2;
+  uint16_t* h;
+  int max_sq, total_q, slots, n2, ks;
+};
+
+// lora_tile that also answers "active, but no adapter": false = the tile has no rows (inactive or empty sequence, tile beyond Sq_b);
+// has_adapter says whether slot names one.
+__device__ __forceinline__ bool lora_tile_active(const int* cu_p, const int* ids_p, int b, int rt, int max_sq, int slots, long long& start,
+                                                 long long& sq, int& slot, bool& has_adapter) {
+  if (cu_p) {
+    const const_i32_t cu = as_const_i32(cu_p);
+    const int c0 = cu[b], c1 = cu[b + 1];
+    start = c0;
+    sq = (long long)c1 - c0;
+  } else {
+    start = (long long)b * max_sq;
+    sq = max_sq;
+  }
+  slot = as_const_i32(ids_p)[b];
+  has_adapter = (unsigned)slot < (unsigned)slots;
+  return sq >= 1 && sq <= max_sq && (long long)rt * kLoraRows < sq;
+}
+
+template <typename DT, int R>
+__global__ __launch_bounds__(kLoraThreads) void lora_expand_gate_up_kernel(const LoraGateUpArgs a) {
+  constexpr int RS = 2 * R;
+  constexpr int LDH = RS + 8;            // elements per row of the hT image: 16 bytes of padding
+  constexpr int LDP = kLoraColTile + 8;  // ... and of the g' / u' image
+  constexpr int KSTEPS = R == 64 ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) uint16_t hs[kLoraRows * LDH];
+  __shared__ __attribute__((aligned(16))) uint16_t ps[kLoraRows * LDP];
+  const int ctile = blockIdx.x, rt = blockIdx.y, b = blockIdx.z;
+  long long start, sq;
+  int slot;
+  bool has_adapter;
+  if (!lora_tile_active(a.cu, a.ids, b, rt, a.max_sq, a.slots, start, sq, slot, has_adapter)) return;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+  const int N2 = a.n2, F = N2 >> 1;
+  const int nbeg = ctile * kLoraColTile, nend = nbeg + kLoraColTile < N2 ? nbeg + kLoraColTile : N2;
+  // the tail's share of the tile: thread (row, group) owns the gate octet and the up octet of one 16-column group of one row
+  const int trow = tid >> 4, tn0 = nbeg + 16 * (tid & 15);
+  const bool town = tn0 < nend && lora_row_owned(start, sq, rt, trow, a.total_q);
+  const size_t tt = (size_t)(start + (long long)rt * kLoraRows + trow);  // (formed into an address only where town holds)
+
+  if (!has_adapter) {  // block-uniform, in front of the first barrier: the interleaved tail on y2 itself
+    if (town) {
+      const uint16_t* py = a.y2 + tt * (size_t)N2 + tn0;
+      *reinterpret_cast<u32x4*>(a.h + tt * (size_t)F + (tn0 >> 1)) =
+          silu_mul_octet<DT>(*reinterpret_cast<const u32x4*>(py), *reinterpret_cast<const u32x4*>(py + 8));
+    }
+    return;
+  }
+
+  // hT of the tile's rows, both slices: KS partials in split order, one product, one rounding (lora_expand_kernel's statement)
+  const float scale = a.scaling[slot];
+  constexpr int ncol4 = RS / 4;  // float4 granules per row
+  const size_t split_stride = (size_t)a.total_q * (size_t)RS;
+  for (int idx = tid; idx < kLoraRows * ncol4; idx += kLoraThreads) {
+    const int row = idx / ncol4, col = (idx - row * ncol4) * 4;
+    u32x2 packed = {0u, 0u};
+    if (lora_row_owned(start, sq, rt, row, a.total_q)) {
+      const float* p = a.ws + (size_t)(start + (long long)rt * kLoraRows + row) * (size_t)RS + col;
+      f32x4 sum = *reinterpret_cast<const f32x4*>(p);
+      for (int s = 1; s < a.ks; ++s) sum += *reinterpret_cast<const f32x4*>(p + (size_t)s * split_stride);
+      packed.x = (u32)DT::from_float(scale * sum[0]) | ((u32)DT::from_float(scale * sum[1]) << 16);
+      packed.y = (u32)DT::from_float(scale * sum[2]) | ((u32)DT::from_float(scale * sum[3]) << 16);
+    }
+    *reinterpret_cast<u32x2*>(&hs[row * LDH + col]) = packed;
+  }
+  __syncthreads();
+
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  const bool is_up = c >= 8;
+  for (int n0 = nbeg + wave * 16; n0 < nend; n0 += kLoraWaves * 16) {
+    const int f = (n0 >> 1) + (c & 7);  // y2 column n0 + c is gate row f (c < 8) or up row f (c >= 8): pool row f or F + f
+    const uint16_t* brow = a.b_pool + ((size_t)slot * (size_t)N2 + (is_up ? F + f : f)) * (size_t)R;
+    f32x4 acc_g = {0.f, 0.f, 0.f, 0.f}, acc_u = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < KSTEPS; ++kk) {
+      const int r0 = kk * 32 + 8 * g;  // lane (c, g) holds r = r0 + {0..7} of row c of a half of hT (A operand) and of its row of B_a (B operand)
+      u32x4 hg = zero, hu = zero, bv = zero;
+      if (r0 < R) {
+        bv = *reinterpret_cast<const u32x4*>(brow + r0);
+        hg = *reinterpret_cast<const u32x4*>(&hs[c * LDH + r0]);
+        hu = *reinterpret_cast<const u32x4*>(&hs[c * LDH + R + r0]);
+      }
+      const typename DT::vec8 bf = __builtin_bit_cast(typename DT::vec8, bv);
+      acc_g = DT::mfma(__builtin_bit_cast(typename DT::vec8, hg), bf, acc_g);
+      acc_u = DT::mfma(__builtin_bit_cast(typename DT::vec8, hu), bf, acc_u);
+    }
+    // D: column lane % 16 = y2 column n0 + c, row 4 g + i = row of the tile; the lane keeps the accumulator of its own slice
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * g + i;
+      if (lora_row_owned(start, sq, rt, row, a.total_q)) {
+        const uint16_t yv = a.y2[(size_t)(start + (long long)rt * kLoraRows + row) * (size_t)N2 + n0 + c];
+        ps[row * LDP + (n0 - nbeg) + c] = DT::from_float(DT::to_float(yv) + (is_up ? acc_u[i] : acc_g[i]));
+      }
+    }
+  }
+  __syncthreads();
+  if (town) {
+    const uint16_t* pp = &ps[trow * LDP + (tn0 - nbeg)];
+    *reinterpret_cast<u32x4*>(a.h + tt * (size_t)F + (tn0 >> 1)) =
+        silu_mul_octet<DT>(*reinterpret_cast<const u32x4*>(pp), *reinterpret_cast<const u32x4*>(pp + 8));
+  }
+}
+
 template <typename DT>
 int lora_shrink_dispatch(const LoraShrinkArgs& a, dim3 grid, hipStream_t st) {
   switch (a.rs / 16) {
@@ -225,6 +349,17 @@ int lora_expand_dispatch(const LoraExpandArgs& a, dim3 grid, hipStream_t st) {
     case 16: hipLaunchKernelGGL((lora_expand_kernel<DT, 16>), grid, dim3(kLoraThreads), 0, st, a); break;
     case 32: hipLaunchKernelGGL((lora_expand_kernel<DT, 32>), grid, dim3(kLoraThreads), 0, st, a); break;
     case 64: hipLaunchKernelGGL((lora_expand_kernel<DT, 64>), grid, dim3(kLoraThreads), 0, st, a); break;
+    default: return -1;
+  }
+  return 0;
+}
+
+template <typename DT>
+int lora_gate_up_dispatch(const LoraGateUpArgs& a, int r, dim3 grid, hipStream_t st) {
+  switch (r) {
+    case 16: hipLaunchKernelGGL((lora_expand_gate_up_kernel<DT, 16>), grid, dim3(kLoraThreads), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((lora_expand_gate_up_kernel<DT, 32>), grid, dim3(kLoraThreads), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((lora_expand_gate_up_kernel<DT, 64>), grid, dim3(kLoraThreads), 0, st, a); break;
     default: return -1;
   }
   return 0;
@@ -285,6 +420,17 @@ int launch_lora_expand(const void* ws, const void* b_pool, const float* scaling,
   if (prev != n) return -1;
   const dim3 grid((n + kLoraColTile - 1) / kLoraColTile, (max_seqlen_q + kLoraRows - 1) / kLoraRows, batch);
   return dtype == 0 ? lora_expand_dispatch<F16>(a, grid, st) : lora_expand_dispatch<BF16>(a, grid, st);
+}
+
+int launch_lora_expand_gate_up(const void* ws, const void* b_pool, const float* scaling, const int* adapter_ids, const int* cu_seqlens_q,
+                               const void* y2, void* h, int batch, int max_seqlen_q, int total_q, int slots, int n2, int k, int r, int dtype,
+                               hipStream_t st) {
+  int plan[4];
+  if (lora_plan(k, r, 2, plan) != 0 || !lora_batch_ok(batch, max_seqlen_q, total_q, slots) || n2 < 16 || (n2 % 16) != 0) return -1;
+  const LoraGateUpArgs a = {(const float*)ws, (const uint16_t*)b_pool, scaling, adapter_ids, cu_seqlens_q, (const uint16_t*)y2, (uint16_t*)h,
+                            max_seqlen_q, total_q, slots, n2, plan[0]};
+  const dim3 grid((n2 + kLoraColTile - 1) / kLoraColTile, (max_seqlen_q + kLoraRows - 1) / kLoraRows, batch);
+  return dtype == 0 ? lora_gate_up_dispatch<F16>(a, r, grid, st) : lora_gate_up_dispatch<BF16>(a, r, grid, st);
 }
 
 }  // namespace awq

@@ -824,6 +824,30 @@ torch::Tensor lora_expand(torch::Tensor ws, torch::Tensor b_pool, torch::Tensor 
   return y;
 }
 
+// expand on QuantLlamaMLP's gate / up pair: h [total_q, F] = silu(gate') * up' from the unfused interleaved output y2 [total_q, 2F] (read only)
+torch::Tensor lora_expand_gate_up(torch::Tensor ws, torch::Tensor b_pool, torch::Tensor scaling, torch::Tensor adapter_ids, torch::Tensor y2, int64_t k,
+                                  c10::optional<torch::Tensor> h, c10::optional<torch::Tensor> cu_seqlens_q, int64_t max_seqlen_q) {
+  TORCH_CHECK(y2.is_cuda() && y2.is_contiguous() && y2.dim() == 2 && y2.size(0) >= 1 && y2.size(1) >= 16 && y2.size(1) % 16 == 0,
+              "awq_inference_engine: lora_expand_gate_up: y2 must be a contiguous [total_q, 2F] GPU tensor, 2F a multiple of 16");
+  TORCH_CHECK(b_pool.is_cuda() && b_pool.is_contiguous() && b_pool.dim() == 3 && b_pool.size(1) == y2.size(1) && b_pool.scalar_type() == y2.scalar_type() &&
+                  b_pool.device() == y2.device(),
+              "awq_inference_engine: lora_expand_gate_up: b_pool must be a contiguous [S, 2F, R] GPU tensor of y2's dtype");
+  TORCH_CHECK(scaling.is_cuda() && scaling.is_contiguous() && scaling.scalar_type() == at::kFloat && scaling.numel() == b_pool.size(0) &&
+                  scaling.device() == y2.device(),
+              "awq_inference_engine: lora_expand_gate_up: scaling must be a contiguous float32 [S] tensor on y2's GPU");
+  lora_ws_check("lora_expand_gate_up", ws, y2);
+  const LoraBatch lb = lora_batch("lora_expand_gate_up", y2, adapter_ids, cu_seqlens_q, max_seqlen_q);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y2.device());
+  torch::Tensor out = h.has_value() ? *h : torch::empty({y2.size(0), y2.size(1) / 2}, y2.options());
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 2 && out.size(0) == y2.size(0) && out.size(1) * 2 == y2.size(1) &&
+                  out.scalar_type() == y2.scalar_type() && out.device() == y2.device(),
+              "awq_inference_engine: lora_expand_gate_up: h must be a contiguous [total_q, F] GPU tensor of y2's dtype");
+  raise_on(awq_lora_expand_gate_up(ws.data_ptr(), (size_t)ws.numel() * 4, b_pool.data_ptr(), (const float*)scaling.data_ptr(), lb.ids, lb.cu,
+                                   y2.data_ptr(), out.data_ptr(), lb.batch, lb.max_seqlen_q, lb.total_q, (int)b_pool.size(0), (int)y2.size(1), (int)k,
+                                   (int)b_pool.size(2), dtype_code(y2), (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return out;
+}
+
 // ---- AWQ quantisation: group quantiser + packer and clip search, one launch each ----
 std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
            c10::optional<torch::Tensor>>
@@ -2275,6 +2299,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_seqlen_q") = 1);
   m.def("lora_expand", &lora_expand, "multi-LoRA expand: y[t, :] += T(scaling * sum_s ws[s, t, :]) @ B_{adapter of t}^T in place, one rounding",
         py::arg("ws"), py::arg("b_pool"), py::arg("scaling"), py::arg("adapter_ids"), py::arg("y"), py::arg("k"), py::arg("slice_end"),
+        py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 1);
+  m.def("lora_expand_gate_up", &lora_expand_gate_up,
+        "multi-LoRA expand on the 8 + 8 interleaved gate / up pair fused with the SiLU * mul tail: h = silu(gate + delta) * (up + delta)", py::arg("ws"),
+        py::arg("b_pool"), py::arg("scaling"), py::arg("adapter_ids"), py::arg("y2"), py::arg("k"), py::arg("h") = py::none(),
         py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 1);
   m.def("quantize_pack", &quantize_pack,
         "AWQ group quantiser + packer, one launch: (w_fake, scales, scaled_zeros, zeros, qweight), None where not wanted", py::arg("w"),

@@ -12,8 +12,16 @@ forward keeps its signature: `QuantLlamaAttentionFused.forward_packed[_split]` c
     pool.set_batch(adapter_ids, cu_seqlens_q, max_seqlen_q)   # device tensors, kept by reference: a captured graph sees in-place updates
     out = attn.forward_packed(x, start_pos, freqs, cu_seqlens_q, max_seqlen_q)
 
-Out of scope: the gate / up pair of `QuantLlamaMLP`.  Its fused SiLU * mul epilogue consumes gate and up inside the GEMM launch, before a delta
-could be added; `attach_lora` refuses those names instead of adapting them approximately.
+The gate / up pair of `QuantLlamaMLP` is adapted by `LoRAGateUp` (`attach_lora_mlp`).  The fused SiLU * mul epilogue of the base launch consumes
+gate and up before a delta could be added, so a step with a batch set runs the interleaved gate / up stream WITHOUT its epilogue (`forward_cdna4`
+on the same weight), the shrink launch with two slices (x is read once for gate's and up's A) and `ops.lora_expand_gate_up`, which adds the two
+deltas and applies the SiLU * mul tail in the same pass: three launches, no adapted [T, 2F] intermediate.  A sequence without an adapter inside such
+a step goes through the unfused base launch too; with no batch set the fused launch runs untouched.
+
+    done = attach_lora_mlp(block, pool)                       # {"mlp": LoRAGateUp, "mlp.down_proj": LoRALinear}
+    block.mlp.load_adapter(3, {"gate_proj": (A_g, B_g), "up_proj": (A_u, B_u)}, alpha=32, rank=16)
+
+`attach_lora` itself keeps refusing the names gate_proj / up_proj: they are no WQLinear children of the fused module.  3-bit MLPs are out of scope.
 """
 from __future__ import annotations
 
@@ -201,6 +209,106 @@ class LoRALinear(nn.Module):
         return f"slots={self.pool.num_slots}, rank={self.pool.rank}, slice_end={self.slice_end}"
 
 
+class LoRAGateUp(nn.Module):
+    """A `QuantLlamaMLP` (w_bit = 4) plus the adapter pool of its gate / up pair: `a_pool` [S, 2R, K] (gate's rows first, then up's), `b_pool`
+    [S, 2F, R] in natural order (B_gate rows, then B_up rows), `scaling` [S].  forward(x) with no batch set on the pool is `mlp(x)`, the fused
+    launch untouched; with a batch it is the unfused interleaved stream, `ops.lora_apply_gate_up` and `mlp.down_proj` (which may itself be a
+    LoRALinear)."""
+
+    def __init__(self, mlp, pool: LoRAPool, name=None):
+        super().__init__()
+        from .fused_mlp import QuantLlamaMLP
+        if not isinstance(mlp, QuantLlamaMLP):
+            raise TypeError(f"LoRAGateUp: a QuantLlamaMLP is expected, got {type(mlp).__name__}")
+        if mlp.w_bit != 4:
+            raise ValueError(f"LoRAGateUp: w_bit = {mlp.w_bit} is not supported: only the 4-bit gate / up stream has an unfused base launch (W3 is out of scope)")
+        k, f = int(mlp.in_features), int(mlp.intermediate_size)
+        if k < 64 or k % 64 or f < 8 or f % 8:
+            raise ValueError(f"LoRAGateUp: in_features {k} must be a multiple of 64 and the intermediate size {f} a multiple of 8")
+        self.mlp, self.pool, self.in_features, self.intermediate_size = mlp, pool, k, f
+        self.lora_name = name
+        s, r = pool.num_slots, pool.rank
+        self.register_buffer("a_pool", torch.zeros(s, 2 * r, k, dtype=pool.dtype, device=pool.device))
+        self.register_buffer("b_pool", torch.zeros(s, 2 * f, r, dtype=pool.dtype, device=pool.device))
+        self.register_buffer("scaling", torch.zeros(s, dtype=torch.float32, device=pool.device))
+        pool.layers.append(self)
+
+    # what the users of a QuantLlamaMLP read of it
+    @property
+    def down_proj(self):
+        return self.mlp.down_proj
+
+    @property
+    def out_features(self):
+        return self.mlp.out_features
+
+    @property
+    def w_bit(self):
+        return self.mlp.w_bit
+
+    def load_adapter(self, slot: int, tensors: dict, alpha: float, rank: int):
+        """{"gate_proj": pair, "up_proj": pair} into slot `slot`, IN PLACE; a pair is (lora_A.weight [r, K], lora_B.weight [F, r]) or a dict holding
+        those two PEFT keys.  Either key may be missing (an adapter that targets one of the two): that half is zeros.  r <= the pool's rank, the rest
+        is zero-padded, scaling[slot] = alpha / r.  A refused load writes nothing."""
+        who = "LoRAGateUp.load_adapter"
+        R, r, K, F = self.pool.rank, int(rank), self.in_features, self.intermediate_size
+        if not 0 <= int(slot) < self.pool.num_slots:
+            raise IndexError(f"{who}: slot {slot} outside [0, {self.pool.num_slots})")
+        if r < 1 or r > R:
+            raise ValueError(f"{who}: rank {r} outside [1, {R}] (the pool's rank; build the pool with a larger one)")
+        if not isinstance(tensors, dict) or not tensors or any(k not in ("gate_proj", "up_proj") for k in tensors):
+            raise ValueError(f"{who}: expected a dict with the keys gate_proj and / or up_proj, got {sorted(tensors) if isinstance(tensors, dict) else type(tensors).__name__}")
+        pairs = {}
+        for key, t in tensors.items():
+            a, b = _pair(t, who)
+            if tuple(a.shape) != (r, K) or tuple(b.shape) != (F, r):
+                raise ValueError(f"{who}: {key} expects lora_A.weight [{r}, {K}] and lora_B.weight [{F}, {r}], got {list(a.shape)} and {list(b.shape)}")
+            pairs[key] = (a, b)
+        with torch.no_grad():
+            for j, key in enumerate(("gate_proj", "up_proj")):
+                rows, cols = self.a_pool[slot, j * R:(j + 1) * R], self.b_pool[slot, j * F:(j + 1) * F]
+                if key in pairs:
+                    rows[:r].copy_(pairs[key][0])
+                    rows[r:].zero_()
+                    cols[:, :r].copy_(pairs[key][1])
+                    cols[:, r:].zero_()
+                else:
+                    rows.zero_()
+                    cols.zero_()
+            self.scaling[slot] = float(alpha) / r
+
+    def unload(self, slot: int):
+        with torch.no_grad():
+            self.a_pool[slot].zero_()
+            self.b_pool[slot].zero_()
+            self.scaling[slot] = 0.0
+
+    @torch.no_grad()
+    def gate_up(self, x):
+        """h [.., F] of a step with a batch set: the unfused interleaved stream, shrink, the fused expand"""
+        from . import load_engine
+        m, p = self.mlp, self.pool
+        if m._fused is None or m._fused[0].device != x.device:
+            m._build(x.device)
+        c4, s, z, szp, szh = m._fused
+        x2 = x.reshape(-1, self.in_features)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        y2 = load_engine().forward_cdna4(x2, c4, s, z, szp, None, szh)  # [T, 2F], columns interleaved 8 + 8, no epilogue
+        ws = p.reserve(ops.lora_workspace_bytes(x2.shape[0], self.in_features, p.rank, 2))
+        h = ops.lora_apply_gate_up(x2, y2, self.a_pool, self.b_pool, self.scaling, p.adapter_ids, p.cu_seqlens_q, p.max_seqlen_q, ws)
+        return h.view(*x.shape[:-1], self.intermediate_size)
+
+    @torch.no_grad()
+    def forward(self, x):
+        if not self.pool.has_batch:
+            return self.mlp(x)
+        return self.mlp.down_proj(self.gate_up(x))
+
+    def extra_repr(self) -> str:
+        return f"slots={self.pool.num_slots}, rank={self.pool.rank}"
+
+
 DEFAULT_TARGETS = ("qkv_proj", "o_proj", "down_proj")
 _REFUSED = ("gate_proj", "up_proj", "gate_up_proj")
 
@@ -209,13 +317,14 @@ def attach_lora(module: nn.Module, pool: LoRAPool, targets=DEFAULT_TARGETS):
     """Replace the children of `module` (searched recursively) whose attribute name is in `targets` and that are WQLinear modules with LoRALinear
     wrappers on `pool`.  The fused qkv layer of a QuantLlamaAttentionFused gets its three slices from the module's head counts (q: num_heads *
     head_dim columns, k and v: num_key_value_heads * head_dim each); every other target is one slice.  The gate / up pair of QuantLlamaMLP is
-    out of scope (its fused SiLU * mul epilogue consumes gate and up before a delta could be added) and naming it raises.  Returns the
-    {qualified name: LoRALinear} that were attached; those names are what LoRAPool.load_adapter takes."""
+    no WQLinear child (one fused stream): naming it raises, attach_lora_mlp adapts it.  Returns the {qualified name: LoRALinear} that were
+    attached; those names are what LoRAPool.load_adapter takes."""
     from .qmodule import WQLinear
 
     bad = [t for t in targets if t in _REFUSED]
     if bad:
-        raise ValueError(f"attach_lora: {bad} cannot be adapted: the fused gate/up launch applies SiLU * mul before a delta could be added")
+        raise ValueError(f"attach_lora: {bad} cannot be adapted here: the gate / up pair of QuantLlamaMLP is one fused stream, not a WQLinear child; "
+                         "use attach_lora_mlp")
     done = {}
     for prefix, parent in list(module.named_modules()):
         for name in targets:
@@ -233,4 +342,30 @@ def attach_lora(module: nn.Module, pool: LoRAPool, targets=DEFAULT_TARGETS):
             done[qual] = wrapped
     if not done:
         raise ValueError(f"attach_lora: no WQLinear child named one of {tuple(targets)} was found")
+    return done
+
+
+def attach_lora_mlp(module: nn.Module, pool: LoRAPool, down_proj: bool = True):
+    """Replace every QuantLlamaMLP child of `module` (searched recursively) with a LoRAGateUp on `pool`, and wrap the MLP's down_proj in a LoRALinear
+    unless it is wrapped already or down_proj=False.  Returns the {qualified name: module} that were attached: the MLP's own name for the
+    LoRAGateUp, "<that name>.down_proj" for the LoRALinear; those names are what LoRAPool.load_adapter takes.  W3 MLPs are refused by name."""
+    from .fused_mlp import QuantLlamaMLP
+    from .qmodule import WQLinear
+
+    found = [(prefix, parent, name, child) for prefix, parent in list(module.named_modules()) if not isinstance(parent, LoRAGateUp)
+             for name, child in list(parent.named_children()) if isinstance(child, QuantLlamaMLP)]
+    if not found:
+        raise ValueError("attach_lora_mlp: no QuantLlamaMLP child was found")
+    bad = [f"{prefix}.{name}" if prefix else name for prefix, _, name, child in found if child.w_bit != 4]
+    if bad:
+        raise ValueError(f"attach_lora_mlp: {bad} are w_bit = 3 MLPs (W3): their gate / up pair cannot be adapted, only the 4-bit stream has an unfused base launch")
+    done = {}
+    for prefix, parent, name, child in found:
+        qual = f"{prefix}.{name}" if prefix else name
+        wrapped = LoRAGateUp(child, pool, name=qual)
+        setattr(parent, name, wrapped)
+        done[qual] = wrapped
+        if down_proj and isinstance(child.down_proj, WQLinear):
+            child.down_proj = LoRALinear(child.down_proj, pool, name=f"{qual}.down_proj")
+            done[f"{qual}.down_proj"] = child.down_proj
     return done

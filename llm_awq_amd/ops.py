@@ -939,6 +939,60 @@ def lora_apply(x, y, a_pool, b_pool, scaling, adapter_ids, slice_end=None, cu_se
     return lora_expand(ws, b_pool, scaling, adapter_ids, y, x.shape[1], slice_end, cu_seqlens_q, max_seqlen_q)
 
 
+def lora_expand_gate_up(ws, b_pool, scaling, adapter_ids, y2, k: int, h=None, cu_seqlens_q=None, max_seqlen_q: int = 1):
+    """C-ABI awq_lora_expand_gate_up: the expand launch on QuantLlamaMLP's gate / up pair, fused with the SiLU * mul tail.  y2 [total_q, 2F] is the
+    output of the 8 + 8 interleaved gate / up stream WITHOUT its epilogue (columns 16 j .. 16 j + 7 gate rows 8 j .., 16 j + 8 .. 16 j + 15 the
+    matching up rows; read only), ws the shrink launch's workspace with n_slices = 2 (gate's A first), b_pool [S, 2F, R] in natural order (B_gate
+    rows, then B_up rows).  h[t, f] = T(T(silu(g')) * u') with g' / u' the pair plus its deltas, one rounding each; rows of an active sequence
+    without an adapter get the plain tail, every other row of h is not written.  Returns h [total_q, F] (allocated when None)."""
+    who = "lora_expand_gate_up"
+    _lora_rows(who, "y2", y2)
+    if not y2.is_contiguous():
+        raise ValueError(f"{who}: y2 must be contiguous")
+    total_q, n2 = y2.shape
+    if n2 < 16 or n2 % 16:
+        raise ValueError(f"{who}: y2 must hold 2F columns, a multiple of 16 (the 8 + 8 interleaved pair), got {n2}")
+    _lora_pool(who, "b_pool", b_pool, y2, (None, n2, None))
+    s, _, r = b_pool.shape
+    if not scaling.is_cuda:
+        raise _capi.AwqNativeError(f"{who}: scaling must be a GPU tensor (llm_awq_amd ops run on the GPU only, no CPU fallback)")
+    if scaling.dtype != torch.float32 or scaling.numel() != s or scaling.device != y2.device or not scaling.is_contiguous():
+        raise ValueError(f"{who}: scaling must be a contiguous float32 [S] = [{s}] tensor on y2's GPU")
+    b = _lora_batch(who, y2, adapter_ids, cu_seqlens_q, max_seqlen_q)
+    lora_plan(k, r, 2)
+    if ws is None:
+        raise ValueError(f"{who}: ws (the output of lora_shrink with two slices) is required")
+    _lora_ws(who, ws, y2, lora_workspace_bytes(total_q, k, r, 2))
+    if h is None:
+        h = torch.empty(total_q, n2 // 2, dtype=y2.dtype, device=y2.device)
+    elif (not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != y2.dtype or h.device != y2.device or tuple(h.shape) != (total_q, n2 // 2)
+          or not h.is_contiguous()):
+        raise ValueError(f"{who}: h must be a contiguous [{total_q}, {n2 // 2}] tensor of y2's dtype on y2's GPU")
+    with torch.cuda.device(y2.device):
+        _capi.check(_capi.lib().awq_lora_expand_gate_up(ws.data_ptr(), ws.numel() * 4, b_pool.data_ptr(), scaling.data_ptr(), adapter_ids.data_ptr(),
+                                                        None if cu_seqlens_q is None else cu_seqlens_q.data_ptr(), y2.data_ptr(), h.data_ptr(), b,
+                                                        int(max_seqlen_q), total_q, s, n2, int(k), r, _dt(y2), _stream(y2)))
+    return h
+
+
+def lora_apply_gate_up(x, y2, a_pool, b_pool, scaling, adapter_ids, cu_seqlens_q=None, max_seqlen_q: int = 1, ws=None, h=None):
+    """Shrink with two slices plus lora_expand_gate_up: h = silu(gate + delta_gate) * (up + delta_up) for QuantLlamaMLP's pair.  x [total_q, K],
+    y2 [total_q, 2F] (the interleaved stream's unfused output, read only), a_pool [S, 2R, K] (gate's A rows first), b_pool [S, 2F, R] (B_gate rows,
+    then B_up rows), scaling float32 [S], adapter_ids int32 [B], cu_seqlens_q int32 [B + 1] or None.  x is read once for both projections; no
+    [total_q, 2F] adapted intermediate is written.  The bits are those of lora_apply with slice_end = (F, 2F) on the de-interleaved pair followed
+    by silu_mul (F % 16 == 8: with each slice zero-padded to whole 16-column groups, which lora_expand asks of its slice ends).  Returns h [total_q, F]."""
+    who = "lora_apply_gate_up"
+    _lora_rows(who, "x", x)
+    _lora_rows(who, "y2", y2)
+    if x.shape[0] != y2.shape[0] or x.dtype != y2.dtype or x.device != y2.device:
+        raise ValueError(f"{who}: x and y2 must hold the same rows, dtype and device")
+    _lora_pool(who, "b_pool", b_pool, y2, (None, y2.shape[1], None))
+    r = b_pool.shape[2]
+    _lora_pool(who, "a_pool", a_pool, x, (b_pool.shape[0], 2 * r, x.shape[1]))
+    ws = lora_shrink(x, a_pool, adapter_ids, r, cu_seqlens_q, max_seqlen_q, ws)
+    return lora_expand_gate_up(ws, b_pool, scaling, adapter_ids, y2, x.shape[1], h, cu_seqlens_q, max_seqlen_q)
+
+
 # ---- AWQ quantisation: group quantiser + packer and clip search (awq_quant_cdna4.hip) ----
 
 def _quant_weight(who, w):
