@@ -199,10 +199,22 @@ int awq_w4a16_gemm_cdna4_narrow_kernel(int m, int n_cols, int k, int bits, int h
 /* host-side query: how awq_w4a16_decode_cdna4 / awq_w4a16_mlp_gate_up_forward_cdna4 serve m <= 8 rows of an [n, k] matrix.  *kernel: 0 =
  * the LDS-DMA streaming kernel (awq_gemv_dma.hip; x staged per slab), 1 = the skinny kernel (awq_skinny_cdna4.hip; x through registers,
  * one weight pass -- where the streaming kernel's staging of m x k x 2 bytes per slab would crowd its ring out of LDS, and, since round 6, from two rows on
- * every launch that is not a wide fused pair or between one and 1.5 slabs per CU: csrc/awq_gemv_dma.hip skinny_takes).  Returns the number
- * of weight passes (1; more when the streaming kernel serves the rows in chunks), 0 if the shape is not served.  The reference's GEMV
- * handles its batch inside one pass, gemv_cuda.cu:187-208, 291-329. */
+ * every launch that is not a wide fused pair or between one and 1.5 slabs per CU).  Returns the number of weight passes (1; more when
+ * the streaming kernel serves the rows in chunks), 0 if the shape is not served.  The reference's GEMV handles its batch inside one pass,
+ * gemv_cuda.cu:187-208, 291-329.
+ * Both queries read the plan the launcher walks: decode_plan in csrc/awq_decode_plan.hpp, one pure function of (m, n, k, epilogue, CU
+ * count, knobs) whose rules are one commented row each.  The knobs awq_tune_set can force on it: decode_skinny_from, gemvd_waves, gemvd_d,
+ * gemvd_want, gemvd_il (and gemvd_probe, which no rule reads).  *kernel names ONE kernel for the call -- 1 when a single skinny launch serves
+ * all rows, else 0 -- while a call served in row chunks asks the rule per chunk; the rule is monotonic in the row count, and no chunk of any
+ * shape with epilogue 0 - 2, 1 - 8 rows, n / 16 in 1 - 4200, k / 128 in 1 - 129, 224, 448 runs the skinny kernel under an answer of 0 (default
+ * knobs, decode_skinny_from 1 and 9). */
 int awq_w4a16_decode_cdna4_plan(int m, int n, int k, int epilogue, int* kernel);
+/* the same plan chunk by chunk.  Returns the number of chunks (= launches = weight passes), 0 if the shape is not served; for
+ * 0 <= chunk < that number, out = { rows, kernel (0 streaming, 1 skinny), then for a streaming chunk: waves per block, k-steps per wave,
+ * ring depth, dynamic LDS bytes, flags (bit 0: K split interleaved over the waves, bit 1: the straight-line one-row kernel), 0; for a skinny
+ * chunk: 0, 0, 0, 0, 0, block shape x 8 + x pieces staged per step (shape 0 = 8 waves x 1 slab, 1 = 16 x 1, 2 = 8 x 2, 3 = 8 x 7; pieces 1 - 4) }.
+ * out may be NULL. */
+int awq_w4a16_decode_cdna4_plan_detail(int m, int n, int k, int epilogue, int chunk, int out[8]);
 int awq_w4a16_gemm_cdna4(const void* x, const void* qweight_cdna4, const void* scales, const void* scaled_zeros,
                          const void* sz_packed, void* out, int m, int n, int k, int group_size, int dtype,
                          void* workspace, size_t workspace_bytes, void* stream);

@@ -1115,6 +1115,7 @@ int awq_w4a16_gemm_cdna4_narrow_kernel(int m, int n_cols, int k, int bits, int h
   return awq::gemm_cdna4_v3_narrow_kernel(m, n_cols, k, bits, has_workspace, epilogue);
 }
 int awq_w4a16_decode_cdna4_plan(int m, int n, int k, int epilogue, int* kernel) { return awq::gemv_dma_plan(m, n, k, epilogue, kernel); }
+int awq_w4a16_decode_cdna4_plan_detail(int m, int n, int k, int epilogue, int chunk, int out[8]) { return awq::gemv_dma_plan_detail(m, n, k, epilogue, chunk, out); }
 
 int awq_w4a16_gemm_cdna4(const void* x, const void* qweight, const void* scales, const void* scaled_zeros,
                          const void* sz_packed, void* out, int m, int n, int k, int group_size, int dtype, void* workspace,

@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "../../include/awq_cdna4.h"
+#include "awq_decode_plan.hpp"
 #include "awq_device.hpp"
 #include "awq_dma.hpp"
 #include "awq_kernels.hpp"
@@ -406,130 +407,49 @@ __global__ __launch_bounds__(64 * WAVES) void gemv_dma_kernel_m1(const uint16_t*
 }
 
 namespace {
-struct DmaCfg {
-  int waves, tx, d;
-  size_t smem;
-};
-int g_dma_skinny_from = 0;  // knob decode_skinny_from: 0 = by shape (skinny_takes below), 1..8 = from that row count, 9 = never
-int g_dma_waves = 0, g_dma_d = 0, g_dma_probe = 0, g_dma_four = 1, g_dma_want = 0, g_dma_wide8 = 2, g_dma_skinny_small = 1, g_dma_skinny_m1 = 1, g_dma_il = 2;  // decode_skinny_m1 (one row): bit 0 = launches with >= 1.5 slabs per CU (qkv: -4 % per launch, 0 ... -1.2 % per token over three boxes), bit 1 = the long-K 16-wave launches (down_proj: neutral, off)  // gemvd_il: 0 = contiguous K ranges per wave everywhere, 1 = interleaved everywhere, 2 (default) = interleaved for eight-wave blocks whose ring is shallower than a wave's K range (qkv -1.2 %, o_proj -3.2 % at one row; 16-wave down_proj no different: profiles/r06_decode_cfg.txt (7))  // gemvd_four: four ring-7 blocks per CU where there are > 3 slabs per CU (rounds 4 + 3 instead of 3 + 3 + 1: +0.6 % decode tok/s, profiles/r03_gemvps.txt)
-
-size_t dma_smem(int waves, int d, int ns, int tx, int m) {
-  const int txp = (tx + 3) & ~3;
-  return (size_t)waves * ((size_t)d * ns * 1024 + (size_t)ns * txp * 64 + (size_t)m * (txp * 256 + 16));
-}
-
-// Batched decode: this kernel stages m x K x 2 bytes of x per SLAB by LDS-DMA -- at m = 4 as many bytes as the slab's weights -- and the
-// staging region crowds the ring out of LDS (gate/up at m = 5: ring depth 1) or forces row chunks that re-stream the weights (K = 14336 at
-// m >= 6).  The skinny kernel (awq_skinny_cdna4.hip: x through registers, shared by a block's slabs, one weight pass for up to 16 rows)
-// costs the same for every m <= 8 and takes over where that staging exceeds ~128 KiB per CU (profiles/r03_decode_m_sweep.txt: gate/up
-// and down_proj from 5 rows, qkv at 8, o_proj never; a Llama-3-8B layer at m = 7: 56.0 -> 38.6 us).
-bool skinny_takes(int m, int n_rows, int k, int epi) {
-  if (epi == 1) return false;  // (the stacked [gate; up] form has no skinny epilogue)
-  if (g_dma_skinny_from) return m >= g_dma_skinny_from;
-  const double blocks_per_cu = (double)(n_rows / 16) / 256.0;
-  // more than three slabs per CU (the fused gate/up pair; eight-wave blocks from two rows, pick_dma): three co-resident blocks stage 3 m K 2 bytes --
-  // K = 4096: the skinny kernel from five rows (15.97 vs 16.99 us), K = 8192 (70B): from three (47.5 vs 51.0 us; at two rows 46.4 vs 47.1 the other way)
-  if (blocks_per_cu > 3.0 && k >= 32 * 128 && k < 96 * 128 && g_dma_wide8 != 0) return (size_t)m * (size_t)k * 2 * 3 >= (size_t)(k >= 64 * 128 ? 96 : 112) * 1024;
-  // Since the skinny kernel stages only the x pieces that hold rows (round 6, third session: one 4-row piece per k-step up to four rows instead of four) it is AHEAD of this
-  // kernel from ONE row wherever a CU holds at least 1.5 slabs or the K loop is long enough for its 16-wave shape -- qkv 5.0 vs 5.35 us, down_proj 8.2 vs 8.7 at one row, 7.85 vs
-  // 9.2 at four; Llama-3-70B qkv / o / down -8 ... -9 % at one row -- while ONE slab per CU against a short K keeps this kernel's deeper ring (o_proj 4.2 vs 4.5, Llama-2-7B
-  // down_proj 7.8 vs 9.1): profiles/r06_decode_cfg.txt (9).  Knob decode_skinny_small: 0 = the rule of the first two sessions below, 1 (default) = from two rows, 2 = from one row.
-  // (ONE row stays here: in the token's chain of dependent launches the skinny kernel's isolated -6 % does not show -- bench.py A/B: 0.9766-0.9801 vs 0.9704-0.9772 ms per step,
-  // drop-in leg -2 % -- while four rows gain 5 %: 1.012-1.019 vs 1.066-1.070 ms)
-  // ... except where a CU holds two or more slabs (Llama-3-70B qkv / o / down: its four-launch decode layer 93.9 -> 91.2-92.7 us at one row)
-  if (g_dma_skinny_small && (m >= 2 || g_dma_skinny_small == 2 || blocks_per_cu >= 2.0 || ((g_dma_skinny_m1 & 1) && blocks_per_cu >= 1.5) || ((g_dma_skinny_m1 & 2) && k >= 96 * 128)) && n_rows / 16 < 1024 &&
-      (blocks_per_cu >= 1.5 || k >= 96 * 128 || (blocks_per_cu <= 1.0 && k >= 32 * 128)))  // (one slab per CU: the skinny kernel's 16-wave shape, o_proj 4.15-4.44 vs 4.26-4.6 us at 2 .. 7 rows)
-    return true;
-  const int want = blocks_per_cu <= 1.0 ? 1 : (blocks_per_cu <= 2.0 ? 2 : (blocks_per_cu <= 3.0 ? 3 : 4));
-  // (from five rows -- or from the row count at which ONE block's staging reaches 100 KiB: Llama-3-70B's down_proj, K = 28672, two slabs per CU, 56 KiB of x per
-  // row: 39 / 64 / 75 us on the streaming kernel at 2 / 3 / 4 rows (one eight-wave block per CU, then row chunks that re-stream the weights) against 31.5 - 35 on
-  // the skinny kernel; Llama-3-8B's down_proj at four rows -- 112 KiB, ONE slab per CU -- stays: 9.4 vs 9.9 us.  profiles/r06_decode_cfg.txt (6))
-  return (m >= 5 || (size_t)m * (size_t)k * 2 >= 100 * 1024) && (size_t)m * (size_t)k * 2 * want >= 128 * 1024;
-}
-
-// K split and ring depth: as many tiles in flight per CU as LDS allows (<= ~150 KiB per CU over the blocks that share it),
-// every wave at least 2 steps
-bool pick_dma(int m, int n_rows, int k, int ns, DmaCfg& c) {
-  // measured on MI355X (tools/gemvd_sweep.py, tools/gemvd_probe.py; profiles/r02_gemvd_*): few waves with a deep ring when many
-  // slabs share a CU (gate/up: 4 waves x 8 tiles), 8 waves x 2..4 tiles for 1..2 slabs per CU, 16 waves x 1..2 for a long K
-  const int nit = k / kGroup, slabs = n_rows / 16 / ns;
-  const double blocks_per_cu = (double)slabs / 256.0;
-  // > 3 slabs per CU (the fused gate/up pair): eight-wave blocks whose ring holds a wave's whole K range (K = 4096: four tiles, nothing re-issued inside the
-  // loop), three co-resident per CU.  The x staging is m x K x 2 bytes per BLOCK, so half as many blocks stage half as much and leave the ring its depth:
-  // gate/up -7 ... -13 % at 2 .. 4 rows, -2.5 % at one row against rounds 2 - 5's four-wave blocks with a ring of seven (profiles/r06_decode_cfg.txt;
-  // knob gemvd_wide8: 0 = the four-wave blocks at every m, 1 = eight waves from two rows only, 2 (default) = at every m)
-  bool wide8 = blocks_per_cu > 3.0 && nit >= 32 && nit < 96 && m >= (g_dma_wide8 == 2 ? 1 : 2) && g_dma_wide8 != 0;  // (measured at K = 4096 and 8192; the short K ranges of tensor-parallel shards keep the four-wave blocks)
-  int waves = nit >= 96 ? 16 : (blocks_per_cu > 3.0 && !wide8 ? 4 : 8);
-  if (g_dma_waves) waves = g_dma_waves;
-  while (waves > 4 && waves > nit) waves >>= 1;  // (waves beyond the step count idle: their steps are clamped and skipped)
-  int want = blocks_per_cu <= 1.0 ? 1 : (blocks_per_cu <= 2.0 ? 2 : (blocks_per_cu <= 3.0 ? 3 : 4));
-  if (g_dma_want) want = g_dma_want;  // knob gemvd_want (experiments): blocks per CU the LDS budget is sized for
-  if (waves == 4 && want > 3 && !g_dma_four) want = 3;  // (three ring-8 blocks beat four ring-4 ones: 14.8 vs 15.1 us; four ring-7 blocks beat both)
-  // x staging is m * k * 2 bytes per block whatever the wave count: when it crowds out the ring, fewer, longer waves
-  while (waves > 4 && dma_smem(waves, 1, ns, (nit + waves - 1) / waves, m) > 150 * 1024) waves >>= 1;
-  if (waves != 8) wide8 = false;
-  const int tx = (nit + waves - 1) / waves;
-  int d = tx < 8 ? tx : 8;
-  if (waves == 16 && !g_dma_d) d = 1;            // 16 waves per block already keep 16+ KiB per CU in flight (8.2 vs 8.7 us at d = 2)
-  if (waves == 8 && !g_dma_d && d > 2 && !wide8 && (m < 3 || blocks_per_cu <= 1.0)) d = 2;  // (two blocks per CU from three rows: a ring of four, qkv -2 %; o_proj keeps two)
-  if (wide8 && !g_dma_want) want = tx > 4 ? 2 : 3;  // three eight-wave blocks per CU (two when a wave's K range is eight tiles: K = 8192); the LDS budget below picks the depth (4 / 4 / 2 / 2 at 1 .. 4 rows against K = 4096)
-  if (g_dma_d) d = g_dma_d < tx ? g_dma_d : tx;
-  // LDS: blocks that want to be co-resident on a CU must fit in 160 KiB
-  while (d > 1 && dma_smem(waves, d, ns, tx, m) * want > 156 * 1024) --d;
-  // compiled ring depths: 1, 2, 4, 8 (7 with 16 waves: K = 14336)
-  if (d == 3) d = 2;
-  if (d == 5 || d == 6 || (d == 7 && waves == 8)) d = 4;
-  if (d == 8 && waves == 16) d = 7;
-  c = {waves, tx, d, dma_smem(waves, d, ns, tx, m)};
-  return c.smem <= 160 * 1024 && tx >= d;
-}
+DecodeKnobs g_knobs;  // awq_tune_set (tests, tools); the rules that read them: awq_decode_plan.hpp
 }  // namespace
 
 int gemv_dma_tune_set(const char* key, int value) {
-  if (!strcmp(key, "gemvd_waves")) g_dma_waves = value;
-  else if (!strcmp(key, "gemvd_d")) g_dma_d = value;
-  else if (!strcmp(key, "gemvd_probe")) g_dma_probe = value;
-  else if (!strcmp(key, "gemvd_four")) g_dma_four = value;
-  else if (!strcmp(key, "gemvd_want")) g_dma_want = value;
-  else if (!strcmp(key, "gemvd_wide8")) g_dma_wide8 = value;
-  else if (!strcmp(key, "gemvd_il")) g_dma_il = value;
-  else if (!strcmp(key, "decode_skinny_small")) g_dma_skinny_small = value;
-  else if (!strcmp(key, "decode_skinny_m1")) g_dma_skinny_m1 = value;
-  else if (!strcmp(key, "decode_skinny_from")) g_dma_skinny_from = value;
+  if (!strcmp(key, "gemvd_waves")) g_knobs.waves = value;
+  else if (!strcmp(key, "gemvd_d")) g_knobs.d = value;
+  else if (!strcmp(key, "gemvd_probe")) g_knobs.probe = value;
+  else if (!strcmp(key, "gemvd_want")) g_knobs.want = value;
+  else if (!strcmp(key, "gemvd_il")) g_knobs.il = value;
+  else if (!strcmp(key, "decode_skinny_from")) g_knobs.skinny_from = value;
   else return -1;
   return 0;
 }
 
 template <typename DT, int WAVES, int D, int DQ, int EPI>
 static void launch_dma_cfg(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
-                           const DmaCfg& c, hipStream_t st, int f32out) {
+                           const DecodeChunk& c, hipStream_t st, int f32out) {
   constexpr int NS = EPI == 1 ? 2 : 1;
-  const int flags = (g_dma_probe & 0xFF) | (f32out ? kDmaF32Out : 0) | ((g_dma_il == 1 || (g_dma_il == 2 && c.d < c.tx && c.waves == 8)) ? kDmaInterleave : 0);
+  const int flags = (g_knobs.probe & 0xFF) | (f32out ? kDmaF32Out : 0) | (c.interleaved ? kDmaInterleave : 0);
   // one row against the K ranges of the decoded token (Llama-3-8B: K = 4096 over eight waves -- gate/up, o, qkv; K = 14336 over sixteen -- down_proj):
   // the straight-line, pipelined form.  Everything else -- more rows, other step counts, a ragged K split -- runs the general body.
   constexpr int TXC = EPI == 1 ? 0 : ((WAVES == 8 && (D == 2 || D == 4)) ? 4 : ((WAVES == 16 && D == 1) ? 7 : 0));  // (EPI 1's two slabs per step would not fit 80 VGPRs: general body)
+  static_assert(TXC == one_row_tx(EPI, WAVES, D), "the plan's one_row_form speaks of this mapping");
   if constexpr (TXC != 0) {
-    if (m == 1 && c.tx == TXC && k == WAVES * TXC * kGroup) {
+    if (c.one_row_form) {
       auto kern1 = gemv_dma_kernel_m1<DT, WAVES, D, DQ, EPI, TXC>;
       static LdsOptIn optin1;
-      if (c.smem > 64 * 1024) optin1.ensure(reinterpret_cast<const void*>(kern1));
-      hipLaunchKernelGGL(kern1, dim3(n / 16 / NS), dim3(64 * WAVES), c.smem, st, (const uint16_t*)x, (const u32*)qw, (const u32*)szp,
+      if (c.smem_bytes > 64 * 1024) optin1.ensure(reinterpret_cast<const void*>(kern1));
+      hipLaunchKernelGGL(kern1, dim3(n / 16 / NS), dim3(64 * WAVES), c.smem_bytes, st, (const uint16_t*)x, (const u32*)qw, (const u32*)szp,
                          (const uint16_t*)bias, (uint16_t*)out, m, n, k, c.tx, flags);
       return;
     }
   }
   auto kern = gemv_dma_kernel<DT, WAVES, D, DQ, EPI>;
   static LdsOptIn optin;
-  if (c.smem > 64 * 1024) optin.ensure(reinterpret_cast<const void*>(kern));
-  hipLaunchKernelGGL(kern, dim3(n / 16 / NS), dim3(64 * WAVES), c.smem, st, (const uint16_t*)x, (const u32*)qw, (const u32*)szp,
+  if (c.smem_bytes > 64 * 1024) optin.ensure(reinterpret_cast<const void*>(kern));
+  hipLaunchKernelGGL(kern, dim3(n / 16 / NS), dim3(64 * WAVES), c.smem_bytes, st, (const uint16_t*)x, (const u32*)qw, (const u32*)szp,
                      (const uint16_t*)bias, (uint16_t*)out, m, n, k, c.tx, flags);
 }
 
 template <typename DT, int EPI, int DQ>
 static int launch_dma_dt(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
-                         hipStream_t st, int f32out) {
-  DmaCfg c;
-  if (!pick_dma(m, n, k, EPI == 1 ? 2 : 1, c)) return -1;
+                         const DecodeChunk& c, hipStream_t st, int f32out) {
 #define AWQ_DCASE(W_, D_)                                                           \
   if (c.waves == W_ && c.d == D_) {                                                 \
     launch_dma_cfg<DT, W_, D_, DQ, EPI>(x, qw, szp, bias, out, m, n, k, c, st, f32out); \
@@ -539,50 +459,15 @@ static int launch_dma_dt(const void* x, const void* qw, const void* szp, const v
   AWQ_DCASE(16, 1) AWQ_DCASE(16, 2) AWQ_DCASE(16, 4) AWQ_DCASE(16, 7)
   AWQ_DCASE(4, 1) AWQ_DCASE(4, 2) AWQ_DCASE(4, 4) AWQ_DCASE(4, 7) AWQ_DCASE(4, 8)
 #undef AWQ_DCASE
-  return -1;
+  return -1;  // (a forced gemvd_waves / gemvd_d pair that is not compiled)
 }
 
-// host-side: how launch_gemv_dma serves the call (awq_w4a16_decode_cdna4_plan): weight passes, *kernel 0 streaming / 1 skinny
-int gemv_dma_plan(int m, int n, int k, int epi, int* kernel) {
-  if (m < 1 || m > 8 || k < 128 || (k % 128) != 0 || epi < 0 || epi > 2 || n < (epi == 1 ? 32 : 16) || (n % (epi == 1 ? 32 : 16)) != 0) return 0;
-  if (skinny_takes(m, n, k, epi)) {
-    if (kernel) *kernel = 1;
-    return 1;
-  }
-  if (kernel) *kernel = 0;
-  DmaCfg c;
-  int mc = m;
-  while (mc > 1 && !pick_dma(mc, n, k, epi == 1 ? 2 : 1, c)) --mc;
-  if (!pick_dma(mc, n, k, epi == 1 ? 2 : 1, c)) return 0;
-  return (m + mc - 1) / mc;
-}
-
-// epi as in the kernel header; returns -1 if the shape is not served.  The kernel stages every row's x slice in LDS up front
-// (m * k * 2 bytes per block): when m rows do not fit (m * k > ~50 k elements: batched decode against K >= 8 k) the rows are
-// served in chunks of as many rows as do fit, each chunk re-streaming the weights -- as the reference's GEMV does per row
-// (gemv_cuda.cu:187-208 loops over the batch inside one weight pass; here the LDS budget decides).
-int launch_gemv_dma(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi,
-                    int dtype, int szfmt, hipStream_t st, int f32out) {
-  if (m < 1 || m > 8 || (k % 128) != 0 || (n % (epi == 1 ? 32 : 16)) != 0 || (f32out && (epi != 0 || bias != nullptr))) return -1;
-  if (skinny_takes(m, n, k, epi) && launch_skinny_decode(x, qw, szp, bias, out, m, n, k, epi, dtype, szfmt, st, f32out) == 0) return 0;
-  DmaCfg probe_cfg;
-  int mc = m;
-  while (mc > 1 && !pick_dma(mc, n, k, epi == 1 ? 2 : 1, probe_cfg)) --mc;
-  if (mc < m) {
-    if (!pick_dma(mc, n, k, epi == 1 ? 2 : 1, probe_cfg)) return -1;
-    const size_t ncols = epi ? (size_t)n / 2 : (size_t)n;
-    for (int r = 0; r < m; r += mc) {
-      const int rows = m - r < mc ? m - r : mc;
-      const int rc = launch_gemv_dma((const char*)x + (size_t)r * k * 2, qw, szp, bias, (char*)out + (size_t)r * ncols * (f32out ? 4 : 2), rows, n, k,
-                                     epi, dtype, szfmt, st, f32out);
-      if (rc != 0) return rc;
-    }
-    return 0;
-  }
-#define AWQ_DDT(DT_, DQ_)                                                                   \
-  if (epi == 0) return launch_dma_dt<DT_, 0, DQ_>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-  if (epi == 1) return launch_dma_dt<DT_, 1, DQ_>(x, qw, szp, bias, out, m, n, k, st, 0);      \
-  return launch_dma_dt<DT_, 2, DQ_>(x, qw, szp, bias, out, m, n, k, st, 0);
+static int launch_dma_chunk(const void* x, const void* qw, const void* szp, const void* bias, void* out, int n, int k, int epi, int dtype,
+                            int szfmt, const DecodeChunk& c, hipStream_t st, int f32out) {
+#define AWQ_DDT(DT_, DQ_)                                                                           \
+  if (epi == 0) return launch_dma_dt<DT_, 0, DQ_>(x, qw, szp, bias, out, c.rows, n, k, c, st, f32out); \
+  if (epi == 1) return launch_dma_dt<DT_, 1, DQ_>(x, qw, szp, bias, out, c.rows, n, k, c, st, 0);      \
+  return launch_dma_dt<DT_, 2, DQ_>(x, qw, szp, bias, out, c.rows, n, k, c, st, 0);
   if (szfmt == 1) {
     if (dtype == 0) {
       AWQ_DDT(F16, 1)
@@ -594,6 +479,49 @@ int launch_gemv_dma(const void* x, const void* qw, const void* szp, const void* 
   }
   AWQ_DDT(BF16, 0)
 #undef AWQ_DDT
+}
+
+// host-side readers of the plan launch_gemv_dma walks (awq_w4a16_decode_cdna4_plan, awq_w4a16_decode_cdna4_plan_detail).
+// gemv_dma_plan: weight passes (0 = not served), *kernel 0 streaming / 1 skinny.  It names ONE kernel for the call: 1 when a single skinny
+// launch serves all rows, else 0.  A call served in row chunks asks skinny_takes per chunk, so a chunk could in principle run the skinny
+// kernel under an answer of 0; skinny_takes is monotonic in the row count, and over the grid epilogue 0 - 2 x 1 - 8 rows x 1 - 4200 slabs x
+// k / 128 in 1 - 129, 224, 448 no chunk does, at the default knobs or with decode_skinny_from forced to 1 or 9.
+int gemv_dma_plan(int m, int n, int k, int epi, int* kernel) {
+  const DecodePlan p = decode_plan(m, n, k, epi, device_cu_count(), g_knobs);
+  if (kernel && p.in_range) *kernel = p.served && p.nchunks == 1 && p.chunk[0].kernel == kDecodeSkinny ? 1 : 0;
+  return p.served ? p.nchunks : 0;
+}
+// out: rows, kernel, waves, tx, d, smem bytes, flags (bit 0 interleaved, bit 1 one-row form), skinny shape x 8 + x_pieces; returns the chunk count
+int gemv_dma_plan_detail(int m, int n, int k, int epi, int chunk, int out[8]) {
+  const DecodePlan p = decode_plan(m, n, k, epi, device_cu_count(), g_knobs);
+  if (!p.served) return 0;
+  if (out != nullptr && chunk >= 0 && chunk < p.nchunks) {
+    const DecodeChunk& c = p.chunk[chunk];
+    const int w[8] = {c.rows, c.kernel, c.waves, c.tx, c.d, c.smem_bytes, (c.interleaved ? 1 : 0) | (c.one_row_form ? 2 : 0),
+                      c.kernel == kDecodeSkinny ? c.shape * 8 + c.x_pieces : 0};
+    for (int i = 0; i < 8; ++i) out[i] = w[i];
+  }
+  return p.nchunks;
+}
+
+// epi as in the kernel header; returns -1 if the shape is not served.  One launch per chunk of the plan, each a pass over the weights.
+int launch_gemv_dma(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi,
+                    int dtype, int szfmt, hipStream_t st, int f32out) {
+  if (f32out && (epi != 0 || bias != nullptr)) return -1;
+  DecodeKnobs knobs = g_knobs;
+  if (!szp || (epi == 2 && bias)) knobs.skinny_from = 9;  // (what launch_skinny_decode does not serve stays on the streaming kernel)
+  const DecodePlan p = decode_plan(m, n, k, epi, device_cu_count(), knobs);
+  if (!p.served) return -1;
+  const size_t ncols = epi ? (size_t)n / 2 : (size_t)n;
+  for (int i = 0, r = 0; i < p.nchunks; r += p.chunk[i].rows, ++i) {  // r: the chunk's first row
+    const DecodeChunk& c = p.chunk[i];
+    const void* xr = (const char*)x + (size_t)r * k * 2;
+    void* outr = (char*)out + (size_t)r * ncols * (f32out ? 4 : 2);
+    const int rc = c.kernel == kDecodeSkinny ? launch_skinny_decode(xr, qw, szp, bias, outr, c.rows, n, k, epi, dtype, szfmt, st, f32out)
+                                             : launch_dma_chunk(xr, qw, szp, bias, outr, n, k, epi, dtype, szfmt, c, st, f32out);
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 }  // namespace awq

@@ -136,6 +136,7 @@ size_t gemm_cdna4_v3_workspace_bytes(int m, int n, int k);
 int gemm_cdna4_v3_plan(int m, int n, int bits, int* mode, int* cols_main);
 int gemm_cdna4_v3_narrow_kernel(int m, int n_cols, int k, int bits, int has_workspace, int epi);  // 1 v6 (NS = 2), 0 v4n unsplit, >= 2 v4n split-K ranges
 int gemv_dma_plan(int m, int n, int k, int epi, int* kernel);  // weight passes of the decode entry (0: not served); *kernel 0 streaming, 1 skinny
+int gemv_dma_plan_detail(int m, int n, int k, int epi, int chunk, int out[8]);  // chunk count; out = the words of chunk `chunk` (awq_decode_plan.hpp)
 size_t gemm_cdna4_v3_workspace_bytes_w3(int m, int n, int k);  // same rule for w3c tiles (every m > 8 takes the tile kernels)
 bool moe_v4_enabled();  // knob moe_v4 (default on): the grouped skinny / tile kernels; 0 = the 128 x 128 grouped kernel for every batch above 8 rows
 // the same grouped GEMM on the v6 tile (awq_gemm_v6.hip: one pipelined wave per SIMD, weights in registers); total >= 256

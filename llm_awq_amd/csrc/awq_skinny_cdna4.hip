@@ -13,6 +13,7 @@
 
 #include <atomic>
 
+#include "awq_decode_plan.hpp"
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
 
@@ -311,21 +312,11 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_splitk_kernel(const uint16_
 
 namespace {
 constexpr int kTicketGroups = 512;  // slab groups of a split launch (its ticket words: splitk_ticket_words, awq_midm_cdna4.hip -- private to the launch)
-int g_skinny_ks = -1;
-int g_skinny_deep64 = 32;  // knob skinny_deep64: the k-step count from which a launch of at most ONE slab per CU takes the 16-wave shape (0 = only from 96 steps, as rounds 3 - 5) for batched decode (<= 8 rows; at 12 / 16 rows it measured 0.6-0.9 % slower): o_proj -2 ... -3.5 %, Llama-2-7B down_proj (86 steps) 8.5 -> 6.6 us
-int g_skinny_xu = 1;  // knob skinny_xu: 0 = batched decode stages all sixteen x rows per step as rounds 3 - 5 did
-// seven slabs per block make ONE round of one block per CU (Llama-3-8B gate/up: 1792 slabs -> 256 blocks)?  Then the x slices are read by that many blocks
-// instead of 1.75 - 3.5 times as many (profiles/r05_skinny_splitk.txt)
-bool seven_slab_round(int nslab) {
-  const int groups = (nslab + 6) / 7, cus = device_cu_count();
-  return groups <= cus + 16 && groups >= cus * 9 / 10;
-}  // knob skinny_splitk: -1 = by shape, 0 = off, 2 / 4 = force that many K parts where the shape allows it
+int g_skinny_ks = -1;  // knob skinny_splitk: -1 = by shape, 0 = off, 2 / 4 = force that many K parts where the shape allows it
 }  // namespace
 
 int skinny_tune_set(const char* key, int value) {
   if (!strcmp(key, "skinny_splitk")) g_skinny_ks = value;
-  else if (!strcmp(key, "skinny_xu")) g_skinny_xu = value;
-  else if (!strcmp(key, "skinny_deep64")) g_skinny_deep64 = value;
   else return -1;
   return 0;
 }
@@ -408,14 +399,14 @@ static int launch_skinny_64(const void* x, const void* qw, const void* szp, cons
     }
   }
   if (m <= 16) {
-    if (nslab >= 1024 && seven_slab_round(nslab)) launch_skinny<DT, 8, 7, 1, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);  // (-2 % on the 7-row decode leg, -4 % at 16 rows)
+    if (nslab >= 1024 && seven_slab_round(nslab, device_cu_count())) launch_skinny<DT, 8, 7, 1, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);  // (-2 % on the 7-row decode leg, -4 % at 16 rows)
     else if (nslab >= 1024) launch_skinny<DT, 8, 2, 1, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);
     else if (k / 128 >= 96) launch_skinny<DT, 16, 1, 1, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);
     else launch_skinny<DT, 8, 1, 1, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);
   } else if (m <= 32) {
     if (nslab >= 512) launch_skinny<DT, 8, 2, 2, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);
     else launch_skinny<DT, 8, 1, 2, 0, EPI>(x, qw, szp, bias, out, m, n, k, st, f32out);
-  } else if (nslab >= 512 && seven_slab_round(nslab)) {
+  } else if (nslab >= 512 && seven_slab_round(nslab, device_cu_count())) {
     // seven slabs per block where that is ONE round of one block per CU (Llama-3-8B gate/up: 1792 slabs -> 256 blocks): the x slices are read by
     // 256 blocks instead of 448 -- -7 % at 40 / 48 rows, -13 % at 64 and 128 (profiles/r05_skinny_splitk.txt); a two-deep prefetch of the packed words
     // for its single wave per SIMD measured 3 % slower again
@@ -473,54 +464,44 @@ int launch_skinny_w3(const void* x, const void* qw, const void* szp, const void*
   return 0;
 }
 
+template <typename DT, int DQ, int EPI, int XU>
+static void launch_skinny_shape(int shape, const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, hipStream_t st,
+                                int f32out) {
+  if (shape == kSkinnyWide8x7) launch_skinny<DT, 8, 7, 1, DQ, EPI, 4, XU>(x, qw, szp, bias, out, m, n, k, st, f32out);
+  else if (shape == kSkinnyWide8x2) launch_skinny<DT, 8, 2, 1, DQ, EPI, 4, XU>(x, qw, szp, bias, out, m, n, k, st, f32out);
+  else if (shape == kSkinnyDeep16x1) launch_skinny<DT, 16, 1, 1, DQ, EPI, 4, XU>(x, qw, szp, bias, out, m, n, k, st, f32out);
+  else launch_skinny<DT, 8, 1, 1, DQ, EPI, 4, XU>(x, qw, szp, bias, out, m, n, k, st, f32out);
+}
+template <typename DT, int DQ, int EPI>
+static void launch_skinny_pieces(const DecodeChunk& c, const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
+                                 hipStream_t st, int f32out) {
+  // the x pieces staged per step are a template parameter (a run-time bound around the same loads measured 2-3 % slower)
+  if (c.x_pieces == 1) launch_skinny_shape<DT, DQ, EPI, 1>(c.shape, x, qw, szp, bias, out, m, n, k, st, f32out);
+  else if (c.x_pieces == 2) launch_skinny_shape<DT, DQ, EPI, 2>(c.shape, x, qw, szp, bias, out, m, n, k, st, f32out);
+  else if (c.x_pieces == 3) launch_skinny_shape<DT, DQ, EPI, 3>(c.shape, x, qw, szp, bias, out, m, n, k, st, f32out);
+  else launch_skinny_shape<DT, DQ, EPI, 4>(c.shape, x, qw, szp, bias, out, m, n, k, st, f32out);
+}
 // Batched decode (launch_gemv_dma hands over the row counts where one weight pass with x in registers beats its LDS-DMA staging of
 // m x K x 2 bytes per slab, profiles/r03_decode_m_sweep.txt): m <= 16 rows, one 16-row x block; szfmt 1 = szp is "sz_half";
 // epi 0 (bias fused) or 2 (8 + 8 interleaved gate / up pair -> silu(gate) * up, out [m, n / 2]).  Returns -1 if unsupported.
 int launch_skinny_decode(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi,
                          int dtype, int szfmt, hipStream_t st, int f32out) {
   if (!szp || m < 1 || m > 16 || (n % 16) != 0 || (k % 128) != 0 || (epi != 0 && epi != 2) || (epi == 2 && bias) || (f32out && (epi || bias))) return -1;
-  const bool wide = n / 16 >= 1024, deep = !wide && (k / 128 >= 96 || (g_skinny_deep64 && m <= 8 && k / 128 >= g_skinny_deep64 && n / 16 <= device_cu_count()));  // deep: 16 waves split a long K (down_proj: 112 steps; knob skinny_deep64 = the step count from which that also holds where a CU holds one slab)
-#define AWQ_SD(DT_, DQ_, EPI_)                                                                    \
-  {                                                                                               \
-    if (m <= 4 && g_skinny_xu) {  /* (Llama-3-70B's long-K launches hand over from two / three rows: one piece per step) */ \
-      if (wide && seven_slab_round(n / 16)) launch_skinny<DT_, 8, 7, 1, DQ_, EPI_, 4, 1>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else if (wide) launch_skinny<DT_, 8, 2, 1, DQ_, EPI_, 4, 1>(x, qw, szp, bias, out, m, n, k, st, f32out);       \
-      else if (deep) launch_skinny<DT_, 16, 1, 1, DQ_, EPI_, 4, 1>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else launch_skinny<DT_, 8, 1, 1, DQ_, EPI_, 4, 1>(x, qw, szp, bias, out, m, n, k, st, f32out);            \
-      return 0;                                                                                   \
-    }                                                                                             \
-    if (m <= 8 && g_skinny_xu) {  /* batched decode: rows 8 .. 15 of the x block are never staged (two of the four pieces per step) */ \
-      if (wide && seven_slab_round(n / 16)) launch_skinny<DT_, 8, 7, 1, DQ_, EPI_, 4, 2>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else if (wide) launch_skinny<DT_, 8, 2, 1, DQ_, EPI_, 4, 2>(x, qw, szp, bias, out, m, n, k, st, f32out);       \
-      else if (deep) launch_skinny<DT_, 16, 1, 1, DQ_, EPI_, 4, 2>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else launch_skinny<DT_, 8, 1, 1, DQ_, EPI_, 4, 2>(x, qw, szp, bias, out, m, n, k, st, f32out);            \
-      return 0;                                                                                   \
-    }                                                                                             \
-    if (m <= 12 && g_skinny_xu) {  /* 9 .. 12 rows: three of the four pieces */ \
-      if (wide && seven_slab_round(n / 16)) launch_skinny<DT_, 8, 7, 1, DQ_, EPI_, 4, 3>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else if (wide) launch_skinny<DT_, 8, 2, 1, DQ_, EPI_, 4, 3>(x, qw, szp, bias, out, m, n, k, st, f32out);       \
-      else if (deep) launch_skinny<DT_, 16, 1, 1, DQ_, EPI_, 4, 3>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-      else launch_skinny<DT_, 8, 1, 1, DQ_, EPI_, 4, 3>(x, qw, szp, bias, out, m, n, k, st, f32out);            \
-      return 0;                                                                                   \
-    }                                                                                             \
-    if (wide && seven_slab_round(n / 16)) launch_skinny<DT_, 8, 7, 1, DQ_, EPI_>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-    else if (wide) launch_skinny<DT_, 8, 2, 1, DQ_, EPI_>(x, qw, szp, bias, out, m, n, k, st, f32out);       \
-    else if (deep) launch_skinny<DT_, 16, 1, 1, DQ_, EPI_>(x, qw, szp, bias, out, m, n, k, st, f32out); \
-    else launch_skinny<DT_, 8, 1, 1, DQ_, EPI_>(x, qw, szp, bias, out, m, n, k, st, f32out);            \
-    return 0;                                                                                     \
-  }
-#define AWQ_SD_DT(DT_)                          \
-  if (szfmt == 1) {                             \
-    if (epi == 2) AWQ_SD(DT_, 1, 2)             \
-    AWQ_SD(DT_, 1, 0)                           \
-  }                                             \
-  if (epi == 2) AWQ_SD(DT_, 0, 2)               \
-  AWQ_SD(DT_, 0, 0)
+  const DecodeChunk c = skinny_decode_chunk(m, n / 16, k / 128, device_cu_count());  // block shape and x pieces: awq_decode_plan.hpp
+#define AWQ_SD(DT_, DQ_)                                                                             \
+  if (epi == 2) launch_skinny_pieces<DT_, DQ_, 2>(c, x, qw, szp, bias, out, m, n, k, st, f32out);    \
+  else launch_skinny_pieces<DT_, DQ_, 0>(c, x, qw, szp, bias, out, m, n, k, st, f32out);             \
+  return 0;
   if (dtype == 0) {
-    AWQ_SD_DT(F16)
+    if (szfmt == 1) {
+      AWQ_SD(F16, 1)
+    }
+    AWQ_SD(F16, 0)
   }
-  AWQ_SD_DT(BF16)
-#undef AWQ_SD_DT
+  if (szfmt == 1) {
+    AWQ_SD(BF16, 1)
+  }
+  AWQ_SD(BF16, 0)
 #undef AWQ_SD
 }
 

@@ -1,5 +1,5 @@
 """GPU experiment: batched decode (M = 2..4) on the streaming kernel -- ring depth / wave count forced through the knobs gemvd_d / gemvd_waves
-against pick_dma's choice (which sizes the ring so that the SAME number of blocks stays co-resident as at M = 1, i.e. shrinks it to depth 1
+against the plan's choice (streaming_chunk, csrc/awq_decode_plan.hpp) (which sizes the ring so that the SAME number of blocks stays co-resident as at M = 1, i.e. shrinks it to depth 1
 once the staged x takes the LDS).  Needs AWQ_TUNING=1.  usage: python tools/decode_m_ring_sweep.py"""
 import os
 import sys

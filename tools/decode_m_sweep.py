@@ -48,7 +48,7 @@ def main():
                                                      128, 1, epi, st))
 
             res, outs = {}, {}
-            for v, frm in (("dma", 9), ("skinny", 1), ("auto", 0)):  # auto = the product routing (skinny_takes, awq_gemv_dma.hip)
+            for v, frm in (("dma", 9), ("skinny", 1), ("auto", 0)):  # auto = the product routing (skinny_takes, csrc/awq_decode_plan.hpp)
                 _capi.tune(decode_skinny_from=frm)
                 out.zero_()
                 fn(copies[0])

@@ -38,19 +38,19 @@ def main():
                                                           None, out.data_ptr(), M, N, K, 128, 1, None, 0, st))
             if fmt == "szp" and epi == 2:
                 continue
-            for cfg in ((0, 0, 0), (8, 4, 1), (8, 2, 1), (16, 4, 1), (16, 2, 1), (8, 4, 2), (16, 2, 2), (4, 8, 1), (4, 8, 2), (4, 4, 4)):
-                if fmt == "szp" and cfg != (0, 0, 0):
+            for cfg in ((0, 0), (8, 4), (8, 2), (16, 4), (16, 2), (4, 8), (4, 4)):   # (gemvd_waves, gemvd_d); 0 = the plan's own (csrc/awq_decode_plan.hpp)
+                if fmt == "szp" and cfg != (0, 0):
                     continue
                 row = []
                 for probe in (0, 1, 2, 3):
-                    _capi.tune(gemvd_waves=cfg[0], gemvd_d=cfg[1], gemvd_bpc=cfg[2], gemvd_probe=probe)
+                    _capi.tune(gemvd_waves=cfg[0], gemvd_d=cfg[1], gemvd_probe=probe)
                     try:
                         row.append(time_graph(fn, copies))
                     except Exception as e:  # noqa
                         row.append(float("nan"))
-                print(f"K={K:6d} N={N:6d} epi={epi} {fmt} waves={cfg[0]:2d} d={cfg[1]} bpc={cfg[2]}  full {row[0]:6.2f}  stream-only {row[1]:6.2f}  math-only {row[2]:6.2f}  "
+                print(f"K={K:6d} N={N:6d} epi={epi} {fmt} waves={cfg[0]:2d} d={cfg[1]}  full {row[0]:6.2f}  stream-only {row[1]:6.2f}  math-only {row[2]:6.2f}  "
                       f"neither {row[3]:6.2f} us   ({ab / row[0] / 1e3:6.0f} GB/s full, {ab / row[1] / 1e3:6.0f} stream-only)", flush=True)
-        _capi.tune(gemvd_waves=0, gemvd_d=0, gemvd_probe=0, gemvd_bpc=0)
+        _capi.tune(gemvd_waves=0, gemvd_d=0, gemvd_probe=0)
         del copies
         torch.cuda.empty_cache()
 
