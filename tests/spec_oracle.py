@@ -10,7 +10,10 @@ tokens, history, hist_len, seqlens and finished exactly -- both are float64 comp
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
+import torch
 
 from tests import sample_oracle as SO
 
@@ -86,8 +89,8 @@ def penalty_set(history_row, hist_len_b, ids, cu_b, j):
     return out
 
 
-def verify(logits_f32, u, cu, ids, B, t, k, p, r, history=None, hist_len=None):
-    """-> (row_tokens int32 [total_q], margins [total_q]); t / k / p / r are per-slot arrays"""
+def verify(logits_f32, u, cu, ids, B, t, k, p, r, history=None, hist_len=None, mutant=None):
+    """-> (row_tokens int32 [total_q], margins [total_q]); t / k / p / r are per-slot arrays; mutant: a fault of sample_oracle.MUTANTS"""
     T = logits_f32.shape[0]
     toks, margins = np.full(T, -1, np.int32), np.full(T, np.inf)
     for row in range(T):
@@ -96,7 +99,7 @@ def verify(logits_f32, u, cu, ids, B, t, k, p, r, history=None, hist_len=None):
             continue
         j = row - int(cu[b])
         hist = penalty_set(history[b], hist_len[b], ids, int(cu[b]), j) if history is not None else ()
-        toks[row], margins[row], _ = SO.sample_row(logits_f32[row], u[row], t[b], p[b], int(k[b]), r[b], hist)
+        toks[row], margins[row], _ = SO.sample_row(logits_f32[row], u[row], t[b], p[b], int(k[b]), r[b], hist, mutant=mutant)
     return toks, margins
 
 
@@ -291,3 +294,67 @@ def stream(tokens_per_step):
     a = np.asarray(tokens_per_step)
     a = a[:, :, None] if a.ndim == 2 else a
     return [[int(x) for x in a[:, b].ravel() if x >= 0] for b in range(a.shape[1])]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the verifier on sample_oracle's edge rows
+# ------------------------------------------------------------------------------------------------------------------------
+# the grid rows a configuration's three slots bring: u = 0 alone; u = 1 - 2^-24 and one more; five inside
+EDGE_BURSTS = ((SO.U_GRID,), (SO.U_GRID + 1, 3), (17, 30, 41, 52, 60))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_verify_case(V, dtype_name):
+    """Every configuration of sample_oracle.build_edge_case as three slots (bursts of 1, 2 and 5 rows) with the configuration's parameters and
+    history; every row is the configuration's logits row under one of its grid uniforms.  The inputs behind a slot's first row are an id its
+    history holds already (penalty slots) or any id, so the penalty set is the configuration's and the oracle's tokens are the grid's.  Three
+    padding rows (NaN) behind.  -> arrays, `grid`: the grid's tokens per row, `want` / `margin`: verify's own.  Shared, never written."""
+    cfgs = SO.build_edge_case(V, dtype_name)
+    slots = [(ci, picks) for ci in range(len(cfgs)) for picks in EDGE_BURSTS]
+    B = len(slots)
+    cu = np.zeros(B + 1, np.int32)
+    cu[1:] = np.cumsum([len(picks) for _, picks in slots])
+    T = int(cu[-1]) + 3
+    ids, u, src, grid = np.full(T, -1, np.int32), np.zeros(T, np.float32), np.zeros(T, np.int64), np.full(T, -1, np.int64)
+    par = dict(t=np.ones(B, np.float32), k=np.zeros(B, np.int32), p=np.ones(B, np.float32), r=np.ones(B, np.float32),
+               history=np.zeros((B, SO.HIST_LEN), np.int32), hist_len=np.zeros(B, np.int32))
+    for b, (ci, picks) in enumerate(slots):
+        c = cfgs[ci]
+        for name in ("t", "k", "p", "r", "history", "hist_len"):
+            par[name][b] = c[name]
+        for j, i in enumerate(picks):
+            row = cu[b] + j
+            u[row], src[row], grid[row] = c["u"][i], ci, c["token"][i]
+            ids[row] = (3 * b + 1) % V if j == 0 else SO.head_ids(V)[0] if c["r"] > 1 else (7 * j + b) % V
+    logits = torch.stack([c["logits"] for c in cfgs])[torch.from_numpy(src)].contiguous()
+    logits[cu[-1]:] = float("nan")        # padding rows are not read
+    want, margin = verify(logits.float().numpy(), u, cu, ids, B, par["t"], par["k"], par["p"], par["r"], par["history"], par["hist_len"])
+    return dict(case=par, cu=cu, ids=ids, u=u, logits=logits, want=want, margin=margin, grid=grid, T=T, M=B)
+
+
+PEN_BURST = 5   # rows per slot of penalty_burst_case
+
+
+@functools.lru_cache(maxsize=None)
+def penalty_burst_case(V, dtype_name):
+    """32 slots (16 on the ladder from 2.0, 16 on the one from -1.0), penalty 1.5, an EMPTY history: the penalty set of a row is the burst's
+    earlier inputs alone -- nothing, then the top head id, then V + (the rank-2 head id), which the contract ignores, then the top id again, then
+    the rank-1 id.  Slot s draws every row near u = (s % 16 + 0.5) / 16.  -> as edge_verify_case"""
+    B = 32
+    h = SO.head_ids(V)
+    cu = (np.arange(B + 1) * PEN_BURST).astype(np.int32)
+    T = int(cu[-1])
+    ids = np.tile(np.array([(V // 2) | 1, h[0], V + h[2], h[0], h[1]], np.int32), B)
+    par = dict(t=np.ones(B, np.float32), k=np.zeros(B, np.int32), p=np.ones(B, np.float32), r=np.full(B, 1.5, np.float32),
+               history=np.zeros((B, SO.HIST_LEN), np.int32), hist_len=np.zeros(B, np.int32))
+    xs = [SO.ladder_logits(V, 2.0), SO.ladder_logits(V, -1.0)]
+    u, src = np.zeros(T, np.float32), np.repeat(np.arange(B) // 16, PEN_BURST)
+    for sign in range(2):
+        for j in range(PEN_BURST):
+            row = SO.Row(SO.process(xs[sign], 1.0, 1.5, penalty_set(par["history"][0], 0, ids, 0, j)))
+            mask = row.kept()[0]
+            for s in range(16):
+                u[(16 * sign + s) * PEN_BURST + j] = SO.robust_u(row, mask, np.float32((s + 0.5) / 16))
+    logits = torch.from_numpy(np.stack(xs)).to(SO.TORCH_DTYPES[dtype_name])[torch.from_numpy(src)].contiguous()
+    want, margin = verify(logits.float().numpy(), u, cu, ids, B, par["t"], par["k"], par["p"], par["r"], par["history"], par["hist_len"])
+    return dict(case=par, cu=cu, ids=ids, u=u, logits=logits, want=want, margin=margin, T=T, M=B)

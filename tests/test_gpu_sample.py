@@ -89,6 +89,48 @@ def test_u_grid_follows_the_distribution():
         assert got[i] in order[max(j - 1, 0):j + 2], i
 
 
+def _launch_edge(picks, u=None):
+    """one launch over the given grid rows of the given edge configurations, every parameter its own tensor; each row is its own copy of the
+    configuration's logits, so for an odd V the rows behind the first start off a 16-byte boundary -> (tokens, the oracle's)"""
+    rep = lambda name, dt: np.concatenate([np.repeat(np.asarray(c[name], dtype=dt)[None], len(i), 0) for c, i in picks])
+    logits = torch.cat([c["logits"].expand(len(i), -1) for c, i in picks])
+    got = ops.sample_logits(_dev(logits), _dev(np.concatenate([c["u"][i] for c, i in picks]) if u is None else u), temperature=_dev(rep("t", np.float32)),
+                            top_k=_dev(rep("k", np.int32)), top_p=_dev(rep("p", np.float32)), repetition_penalty=_dev(rep("r", np.float32)),
+                            history=_dev(rep("history", np.int32)), hist_len=_dev(rep("hist_len", np.int32))).cpu().numpy()
+    return got, np.concatenate([c["token"][i] for c, i in picks])
+
+
+def _mixed(cfgs):
+    return [(c, (7 * ci + 11 * np.arange(5)) % (O.U_GRID + 2)) for ci, c in enumerate(cfgs)]
+
+
+@pytest.mark.parametrize("V,dtype_name", O.EDGE_SHAPES)
+def test_edge_rows_equal_the_oracle(V, dtype_name):
+    """The rows whose kept set decides the token (sample_oracle.build_edge_case): ladders of twelve near-equal head tokens at the row's structural
+    places, from 2.0 and from -1.0, under top-k 8 over a tie group / top-k 5 / top-p / penalty over a history with repeats, wrapping and stale
+    ids / all of them / greedy; dense runs of consecutive values around 1, -1 and +-0 under a top-k whose tau the last select pass decides; a
+    +-0 top group.  Each configuration is one launch of its 64-point u grid and u = 0, u = 1 - 2^-24; then five rows of every configuration in
+    one mixed launch.  Token equality, no exclusions; tests/test_sample_host.py proves that each fault of MUTANTS changes some of these tokens."""
+    cfgs = O.build_edge_case(V, dtype_name)
+    every = np.arange(O.U_GRID + 2)
+    for c in cfgs:
+        assert c["margin"].min() >= O.MARGIN
+        got, want = _launch_edge([(c, every)])
+        assert np.array_equal(got, want), (c["name"], np.flatnonzero(got != want), got, want)
+    got, want = _launch_edge(_mixed(cfgs))
+    assert np.array_equal(got, want), (np.flatnonzero(got != want), got, want)
+
+
+def test_the_edge_rows_of_the_two_iteration_shape_three_times():
+    cfgs = O.build_edge_case(40965, "fp32")
+    picks = _mixed(cfgs)
+    u = torch.rand(5 * len(cfgs), generator=torch.Generator().manual_seed(5)).numpy()   # arbitrary u (no margin asked)
+    (a, _), (b, _), (c, _) = (_launch_edge(picks, u=u) for _ in range(3))
+    assert np.array_equal(a, b) and np.array_equal(a, c) and ((a >= 0) & (a < 40965)).all()
+    (a, want), (b, _), (c, _) = (_launch_edge(picks) for _ in range(3))                   # and on the grid: the oracle's, three times
+    assert np.array_equal(a, want) and np.array_equal(b, want) and np.array_equal(c, want)
+
+
 def test_inactive_rows_are_skipped_and_untouched():
     case = O.build_case(1023, "bf16")
     rows = np.arange(8)

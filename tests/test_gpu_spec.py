@@ -199,14 +199,12 @@ def test_verify_equals_the_oracle_on_every_mode_and_burst(V, dtype_name):
     assert (got[~live] == -1).all() and ((got[live] >= 0) & (got[live] < V)).all()
 
 
-@pytest.mark.parametrize("V,dtype_name", VERIFY_SHAPES)
-def test_verify_equals_sample_logits_with_no_margin(V, dtype_name):
+def _verify_against_sample_logits(c, seed):
     """the same rows through ops.sample_logits, the owner's parameters replicated per row and the penalty set written out as the row's history:
     the same routine on the same bits, so ARBITRARY uniforms must give equal tokens"""
-    c = _verify_case(V, dtype_name)
     case, cu, ids, T, M = c["case"], c["cu"], c["ids"], c["T"], c["M"]
     live = int(cu[-1])
-    u = np.random.default_rng(V).random(T).astype(np.float32)
+    u = np.random.default_rng(seed).random(T).astype(np.float32)
     own = np.array([S.owner(cu, M, r) for r in range(live)])
     Lh = case["history"].shape[1]
     hist, hl = np.zeros((live, Lh + 8), np.int32), np.zeros(live, np.int32)
@@ -222,6 +220,37 @@ def test_verify_equals_sample_logits_with_no_margin(V, dtype_name):
     # and without a history or any parameter at all: t = 1, no filter, no penalty
     plain = _np(ops.spec_verify(_dev(c["logits"]), _dev(u), _dev(cu), _dev(ids)))
     assert np.array_equal(plain[:live], _np(ops.sample_logits(_dev(c["logits"][:live]), _dev(u[:live])))) and (plain[live:] == -1).all()
+
+
+@pytest.mark.parametrize("V,dtype_name", VERIFY_SHAPES)
+def test_verify_equals_sample_logits_with_no_margin(V, dtype_name):
+    _verify_against_sample_logits(_verify_case(V, dtype_name), V)
+
+
+@pytest.mark.parametrize("V,dtype_name", SO.EDGE_SHAPES)
+def test_verify_equals_the_oracle_on_the_edge_rows(V, dtype_name):
+    """sample_oracle's edge rows (flat heads, dense runs, the +-0 group: the rows that tests/test_sample_host.py proves sensitive to every fault
+    of MUTANTS) as bursts of 1, 2 and 5 rows per slot under the slot's parameters and history: the oracle's tokens, which are the sampler's"""
+    c = S.edge_verify_case(V, dtype_name)
+    live = np.arange(c["T"]) < c["cu"][-1]
+    assert (c["margin"][live] >= SO.MARGIN).all() and np.array_equal(c["want"][live], c["grid"][live])
+    got = _run_verify(c)
+    assert np.array_equal(got, c["want"]), (np.flatnonzero(got != c["want"]), got, c["want"])
+
+
+@pytest.mark.parametrize("V,dtype_name", SO.EDGE_SHAPES)
+def test_verify_equals_sample_logits_on_the_edge_rows(V, dtype_name):
+    _verify_against_sample_logits(S.edge_verify_case(V, dtype_name), V)
+
+
+@pytest.mark.parametrize("V,dtype_name", [(1025, "fp32"), (1025, "bf16")])
+def test_a_burst_whose_earlier_inputs_are_the_whole_penalty_set(V, dtype_name):
+    """32 slots of five rows on the two ladders, penalty 1.5, empty histories: the top head id, V + (a head id), the top id again and another head id
+    enter the penalty set row by row.  tests/test_spec_host.py proves that a wrapped id and a penalty per occurrence change these tokens."""
+    c = S.penalty_burst_case(V, dtype_name)
+    assert (c["margin"] >= SO.MARGIN).all()
+    got = _run_verify(c)
+    assert np.array_equal(got, c["want"]), (np.flatnonzero(got != c["want"]), got, c["want"])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

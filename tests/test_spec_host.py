@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from llm_awq_amd import _capi
+from tests import sample_oracle as SO
 from tests import spec_oracle as S
 
 
@@ -72,6 +73,38 @@ def test_oracle_verify_and_accept_on_hand_worked_bursts():
     out, num, last = S.accept(np.array([1, 2, 6, 3, -1, -1], np.int32), ids, cu, 2, state["history"], state["hist_len"], state["seqlens"], [2],
                               state["finished"], 100)
     assert out[0].tolist() == [1, 2, -1] and num[0] == 2 and state["seqlens"][0] == -1 and state["finished"].tolist() == [1, 0, 0]
+
+
+@pytest.mark.parametrize("V,dtype_name", SO.EDGE_SHAPES)
+def test_the_verifier_case_on_the_edge_rows_keeps_the_grid_tokens(V, dtype_name):
+    """three slots per edge configuration (1, 2 and 5 rows): the burst's inputs add nothing to a penalty set, so `verify` gives the tokens the
+    sampler's grid gives, every row with the margin"""
+    c = S.edge_verify_case(V, dtype_name)
+    live = np.arange(c["T"]) < c["cu"][-1]
+    assert sorted(set(np.diff(c["cu"]).tolist())) == [1, 2, 5] and c["M"] == 3 * len(SO.build_edge_case(V, dtype_name))
+    assert (c["margin"][live] >= SO.MARGIN).all() and np.array_equal(c["want"][live], c["grid"][live]) and (c["want"][~live] == -1).all()
+
+
+@pytest.mark.parametrize("V,dtype_name", [(1025, "fp32"), (1025, "bf16")])
+def test_the_penalty_burst_sees_wrapped_and_repeated_inputs(V, dtype_name):
+    """the burst whose earlier inputs ARE the penalty set (the history is empty): V + (a head id) entering at row 2 changes tokens under pen_wrap,
+    the top id entering a second time at row 3 changes tokens under pen_per_occurrence -- with the margin on both sides"""
+    c = S.penalty_burst_case(V, dtype_name)
+    par = c["case"]
+    h = SO.head_ids(V)
+    assert S.penalty_set(par["history"][0], 0, c["ids"], 0, 1) == [h[0]] and S.penalty_set(par["history"][0], 0, c["ids"], 0, 3) == [h[0], V + h[2], h[0]]
+    assert (c["margin"] >= SO.MARGIN).all()
+
+    def kills(mutant):
+        tok, margin = S.verify(c["logits"].float().numpy(), c["u"], c["cu"], c["ids"], c["M"], par["t"], par["k"], par["p"], par["r"], par["history"],
+                               par["hist_len"], mutant=mutant)
+        k = (tok != c["want"]) & (margin >= SO.MARGIN)
+        return [int(k[j::S.PEN_BURST].sum()) for j in range(S.PEN_BURST)]
+
+    wrap, rep = kills("pen_wrap"), kills("pen_per_occurrence")
+    assert wrap[:2] == [0, 0] and wrap[2] >= 3, wrap
+    assert rep[:3] == [0, 0, 0] and rep[3] >= 3, rep
+    assert kills("pen_always_div")[1] >= 3           # (the ladder from -1.0: its head is negative)
 
 
 @pytest.mark.parametrize("seed", range(20))
