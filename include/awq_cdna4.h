@@ -952,6 +952,57 @@ int awq_attn_paged_varq_kv8(const void* q, const void* k_pool, const void* v_poo
                             long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                             int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- A SLIDING WINDOW on a mixed packed step: awq_attn_varq_window[_kv8] / awq_attn_paged_varq_window[_kv8] take the arguments of
+ *      awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8] with window_left behind split_min_keys (flash-attn's window_size = (window_left, 0)):
+ *          row s of sequence b stands at position p = s + Sk_b - Sq_b and attends keys j with max(0, p - window_left) <= j <= p;
+ *          Sk_b as above (64 bits, with lens_before_step).  p < 0: zeros, as without a window; every other row attends at least its own
+ *          key.  Activity, padding rows, the cu_seqlens_q clamps and Sq_b = 0 are awq_attn_prefill_*_varq's.
+ *      window_left >= max_seqlen_k - 1 hides no key: the rows then carry the bits of awq_attn_varq* on the same step.
+ *      Rule: the split pair takes sequence b  iff  b is active with 1 <= Sq_b <= split_seqlen_q and keys_b >= split_min_keys, where
+ *          keys_b = min(Sk_b, window_left + Sq_b) is the number of keys the sequence attends at all -- a decode over a long history with a
+ *          short window is not "long".  split_seqlen_q = 0: the one-pass launch alone, workspace unused.
+ *      Reads: the one-pass kernel walks 64-key tiles from the tile of max(0, q0 + Sk_b - Sq_b - window_left) (q0 = first row of the q tile);
+ *          the split pair anchors its splits at anchor_b = max(0, Sk_b - Sq_b - window_left) & ~63: split s owns keys
+ *          [anchor_b + s * chunk, min(Sk_b, .. + chunk)).  No key, no scale and no block-table entry below max(0, Sk_b - Sq_b -
+ *          window_left) & ~63 is read: pages wholly below it may be freed or reused.
+ * Plan: awq_attn_varq_window_plan returns awq_attn_kvcache_plan's (splits, chunk) for the bound min(max_seqlen_k, window_left +
+ *     split_seqlen_q + 63), the most keys an anchored walk covers (the knob "attn_splitkv_chunk" applies).  Host arguments only.
+ * Workspace: awq_attn_varq_window_workspace_bytes = batch * nheads * split_seqlen_q * splits * (head_dim + 2) * 4 bytes for that plan.
+ * No atomics, no host read: bit-deterministic and capturable; the launch set depends on host arguments only.
+ * Returns the codes of awq_attn_varq*, and: window_left < 0 AWQ_ERR_SHAPE, causal == 0 AWQ_ERR_SHAPE.  Every check precedes the first
+ *     launch.  The plan refuses what awq_attn_varq_split_plan refuses and window_left < 0 with AWQ_ERR_SHAPE; the byte count is then 0. */
+int awq_attn_varq_window_plan(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int window_left,
+                              int* splits, int* chunk);
+size_t awq_attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k,
+                                            int window_left);
+int awq_attn_varq_window(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q,
+                         int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                         long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                         int window_left, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_varq_window_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                             int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                             int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_row_stride,
+                             long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                             long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                             long long v_scale_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                             int window_left, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq_window(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                               const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                               int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                               int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q,
+                               int split_min_keys, int window_left, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq_window_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                   const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                   const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                   int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                   long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                   long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                   long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                   int split_seqlen_q, int split_min_keys, int window_left, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).
  *     q / k / v [total_rows, H, Dh] with row strides of their own (elements; heads contiguous), out [total_rows, H, Dh] contiguous; a
  *     packed qkv [total_rows, 3, H, Dh] is three pointers into one buffer with row stride 3 H Dh.

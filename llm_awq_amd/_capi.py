@@ -166,6 +166,17 @@ SIGNATURES = {
                             [ctypes.c_float, _i, _i] + [_i, _i, _vp, _sz, _vp]),
     "awq_attn_paged_varq_kv8": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 9 +
                                 [ctypes.c_float, _i, _i] + [_i, _i, _vp, _sz, _vp]),
+    # a sliding window on a mixed step: awq_attn_varq*'s arguments with window_left behind split_min_keys
+    "awq_attn_varq_window_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "awq_attn_varq_window_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "awq_attn_varq_window": (_i, [_vp] * 4 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i] +
+                             [_i, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_varq_window_kv8": (_i, [_vp] * 6 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i] +
+                                 [_i, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_paged_varq_window": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                   [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i] + [_i, _i, _i, _vp, _sz, _vp]),
+    "awq_attn_paged_varq_window_kv8": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                       [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i] + [_i, _i, _i, _vp, _sz, _vp]),
     "awq_rope_kv_store_natural_varq": (_i, [_vp] * 6 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
     "awq_rope_kv_store_natural_varq_fp8": (_i, [_vp] * 8 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
     "awq_rope_kv_store_paged_varq": (_i, [_vp] * 7 + [_i, _vp] + [_i] * 10 + [ctypes.c_longlong] * 6 + [_i, _vp]),

@@ -31,6 +31,7 @@
 #include "awq_paged.hpp"
 #include "awq_rope.hpp"
 #include "awq_varq.hpp"
+#include "awq_window.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -80,15 +81,26 @@ struct PrefillMixArgs : PrefillLenArgs {
   VarQSplitArgs sp;
 };
 
+// Window<VarQMix<..>> only (awq_window.hpp): the window behind the thresholds.  A struct of its own once more: the VarQMix kernels keep their
+// PrefillMixArgs block
+struct PrefillWinArgs : PrefillMixArgs {
+  WindowArgs w;
+};
+
 struct NoLenArgs {};
 template <typename DT>
-using LenArgsOf = typename std::conditional<IsVarQMix<DT>::value, PrefillMixArgs,
-                                            typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type>::type;
+using LenArgsOf = typename std::conditional<
+    IsWindow<DT>::value, PrefillWinArgs,
+    typename std::conditional<IsVarQMix<DT>::value, PrefillMixArgs,
+                              typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type>::type>::type;
 __device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}, VarQArgs{nullptr, 0, 0, 0}}; }
 __device__ __forceinline__ PrefillLenArgs len_args(const PrefillLenArgs& x) { return x; }
 __device__ __forceinline__ VarQSplitArgs split_args(const NoLenArgs&) { return VarQSplitArgs{0, 0}; }
 __device__ __forceinline__ VarQSplitArgs split_args(const PrefillLenArgs&) { return VarQSplitArgs{0, 0}; }
 __device__ __forceinline__ VarQSplitArgs split_args(const PrefillMixArgs& x) { return x.sp; }
+__device__ __forceinline__ WindowArgs window_args(const NoLenArgs&) { return WindowArgs{0}; }
+__device__ __forceinline__ WindowArgs window_args(const PrefillLenArgs&) { return WindowArgs{0}; }
+__device__ __forceinline__ WindowArgs window_args(const PrefillWinArgs& x) { return x.w; }
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
 //   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
@@ -156,6 +168,15 @@ struct IsFtCache<FtCache<DT>> {
 // varq_split_takes (awq_varq.hpp) on its sequence; a sequence the split pair takes is not this kernel's: the block returns before any
 // vector load and writes nothing.  The test is uniform over the block and no barrier precedes it.  Every other sequence runs the VarQ code.
 //
+// Window<VarQMix<..>> (awq_window.hpp, awq_attn_varq_window[_kv8], awq_attn_paged_varq_window[_kv8]): row s attends keys
+// max(0, lim - left) .. lim, lim = s + shift.  The rule is varq_window_split_takes.  The block's first key is a_blk = max(0, q0 + shift - left)
+// and its walk begins at tile t_lo = a_blk / 64 in the place of tile 0: staging, the page walk (one division at the head of the block, ids
+// still requested a tile ahead) and the loop all start there, so no key and no table entry below t_lo * 64 is read.  t_lo < nt in every
+// live block: a_blk <= q0 + shift < kv_end.  A tile wholly below the wave's first window start max(0, wq0 + shift - left) is skipped by a
+// wave-uniform test, as a tile above the diagonal is; the low mask key >= max(0, lim - left) runs only in tiles below the wave's LAST window
+// start.  A row may meet its first attended key tiles after its wave's first one: the running max is still -inf then, the DevLen guards'
+// case.  With left >= Sk_b - 1 every one of these is the VarQMix expression: t_lo = 0, no tile skipped, no key masked -- same bits.
+//
 // The device-length forms take their PrefillLenArgs as a SECOND kernel argument.  For the host-length forms that argument is the empty
 // NoLenArgs -- one padded byte behind PrefillArgs that no instruction reads: their PrefillArgs, their registers and their instruction
 // stream are those of the one-argument kernel.
@@ -167,9 +188,11 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
+  constexpr bool WINDOW = IsWindow<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!FT || !DEVLEN, "the FT caches take a host length");
   static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
+  static_assert(!WINDOW || IsVarQMix<DT>::value, "a window exists on the mixed packed form only");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = NW * 64;
@@ -211,7 +234,11 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
     // 64 bits: no entry can wrap into an active length
     const long long len = (long long)x.seqlens_k[b] + (VARQ ? (x.vq.lens_before_step ? sq_b : 0ll) : (long long)x.seqlen_offset);
     if constexpr (IsVarQMix<DT>::value) {  // the split pair's sequence: nothing of it is read or written here
-      if (varq_split_takes(sq_b, len, x.vq.max_seqlen_q, x.max_seqlen_k, split_args(xs))) return;
+      if constexpr (WINDOW) {
+        if (varq_window_split_takes(sq_b, len, x.vq.max_seqlen_q, x.max_seqlen_k, split_args(xs), window_args(xs))) return;
+      } else {
+        if (varq_split_takes(sq_b, len, x.vq.max_seqlen_q, x.max_seqlen_k, split_args(xs))) return;
+      }
     }
     Sk = (int)len;
     live = len >= 1 && len <= x.max_seqlen_k;
@@ -231,6 +258,19 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   const int lim = a.causal ? qi + shift : Sk - 1;                                 // last key this lane's row attends
   const int wave_max = a.causal ? min(wq0 + kMfmaRows - 1, Sq - 1) + shift : Sk - 1;  // .. any row of the wave
   const int wave_min = a.causal ? wq0 + shift : Sk - 1;                           // every row of the wave attends keys <= this
+  // Window (causal only): the block's first tile, this lane's first key, and the first / last window start of the wave's rows
+  int t_lo = 0, lo = 0, wave_lo = 0, wave_lo_max = 0;
+  unsigned span = 0;  // lim - lo, the width of this lane's window
+  (void)lo, (void)span, (void)wave_lo, (void)wave_lo_max;
+  if constexpr (WINDOW) {
+    const long long left = window_args(xs).left;
+    t_lo = (int)(max(0ll, (long long)q0 + shift - left) / kKV);
+    // a row that attends nothing (lim < 0) gets a start no key reaches and an empty span
+    lo = lim < 0 ? 0x40000000 : (int)max(0ll, (long long)lim - left);
+    span = lim < 0 ? 0u : (unsigned)(lim - lo);
+    wave_lo = (int)max(0ll, (long long)wave_min - left);
+    wave_lo_max = (int)max(0ll, (long long)wave_max - left);
+  }
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   // VarQ: the packed row of (b, qi), clamped into the tensors before it forms an address; a store is guarded by row < min(cu[b + 1], total_q)
@@ -337,7 +377,7 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   // wait the barrier needs anyway has covered it.
   typedef const int __attribute__((address_space(4))) * const_table_t;
   const const_table_t table = PAGED ? reinterpret_cast<const_table_t>(reinterpret_cast<uintptr_t>(x.pg.block_table + (long long)b * x.pg.bt_rs)) : nullptr;
-  int pg_i = 0, pg_ro = 0, pg_cur = 0, pg_nxt = 0, ro_nxt = 0;
+  int pg_i = 0, pg_ro = 0, pg_cur = 0, ro_cur = 0, pg_nxt = 0, ro_nxt = 0;
   auto next_entry = [&]() {  // (pg_i, pg_ro) -> the tile 64 keys on; returns its table entry, not yet clamped
     pg_ro += kKV;
     if (pg_ro == x.pg.page_size) {
@@ -347,22 +387,27 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
     return table[pg_i];
   };
   if constexpr (PAGED) {
-    pg_cur = page_id(table[0], x.pg.num_pages);
-    if (nt > 1) {
+    if constexpr (WINDOW) {  // the walk starts at tile t_lo: the block's one division
+      pg_i = t_lo * kKV / x.pg.page_size;
+      pg_ro = t_lo * kKV - pg_i * x.pg.page_size;
+      ro_cur = pg_ro;
+    }
+    pg_cur = page_id(table[pg_i], x.pg.num_pages);
+    if (t_lo + 1 < nt) {
       pg_nxt = page_id(next_entry(), x.pg.num_pages);
       ro_nxt = pg_ro;
     }
   }
 
-  stage_load(0, pg_cur, 0);
-  stage_write(0);
+  stage_load(t_lo * kKV, pg_cur, ro_cur);
+  stage_write(t_lo & 1);
   // Q has arrived before the loop starts: a wait for it inside the loop would be a vmcnt(0) behind the loads the loop has just
   // issued (the counter retires in order), which is exactly the overlap the staging exists for
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
   __syncthreads();
 
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_lo; t < nt; ++t) {
     const int buf = t & 1, t0 = t * kKV;
     const bool more = t + 1 < nt;
     int pg_n2 = pg_nxt, ro_n2 = ro_nxt;
@@ -374,7 +419,9 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
     }
     if (more) stage_load(t0 + kKV, pg_nxt, ro_nxt);
 
-    if (wave_on && t0 <= wave_max) {
+    bool below = false;  // Window: the tile lies wholly below every window start of the wave
+    if constexpr (WINDOW) below = t0 + kKV <= wave_lo;
+    if (wave_on && t0 <= wave_max && !below) {
       // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, query row r ----
       f32x16 s[2];
 #pragma unroll
@@ -389,13 +436,19 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
       }
       // ---- online softmax (base 2: the logits are scaled by scale * log2 e) ----
       const bool need_mask = t0 + kKV - 1 > wave_min;
+      const bool need_lo = WINDOW && t0 < wave_lo_max;  // some row of the wave starts inside or behind this tile
       float mx = -INFINITY;
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           float x = s[kb2][e] * a.scale_log2e;
-          if (need_mask) {
+          if constexpr (WINDOW) {
+            if (need_mask || need_lo) {  // both ends in one unsigned compare: lo <= key <= lim  <=>  key - lo <= lim - lo
+              const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+              x = (unsigned)(key - lo) <= span ? x : -INFINITY;
+            }
+          } else if (need_mask) {
             const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
             x = key <= lim ? x : -INFINITY;
           }
@@ -769,6 +822,20 @@ int launch_kv_prefill(const KvAttnCall& c, hipStream_t st) {
     attn_varq_plan(c.B, c.H, c.Hkv, c.Dh, c.Sq, &rows, &blocks);
     a.ntiles = (c.Sq + rows - 1) / rows;
     const int nw = rows / kMfmaRows;
+    if (c.window_left >= 0) {  // a windowed step (awq_window.hpp): the mixed form for every split_seqlen_q, 0 hands nothing to the split pair
+      PrefillWinArgs m;
+      static_cast<PrefillLenArgs&>(m) = x;
+      m.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
+      m.w = WindowArgs{c.window_left};
+      if (kv.block_table) {
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, WindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+      } else {
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, WindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+      }
+      return 0;
+    }
     if (c.split_seqlen_q > 0) {  // a mixed step: the same launch, with the sequences of the split pair left alone
       PrefillMixArgs m;
       static_cast<PrefillLenArgs&>(m) = x;

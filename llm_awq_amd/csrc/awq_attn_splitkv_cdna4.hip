@@ -49,6 +49,7 @@
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
 #include "awq_varq.hpp"
+#include "awq_window.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -103,15 +104,24 @@ struct VarQSplitKArgs : PagedSplitArgs {
   VarQArgs vq;
   VarQSplitArgs sp;
 };
+// Window<VarQ<..>> only (awq_window.hpp): the window behind everything above, for both kernels of the pair
+struct WindowSplitKArgs : VarQSplitKArgs {
+  WindowArgs w;
+};
 template <typename DT>
-using SplitArgsOf = typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
-                                              typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type;
+using SplitArgsOf = typename std::conditional<
+    IsWindow<DT>::value, WindowSplitKArgs,
+    typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
+                              typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type>::type;
 template <typename DT>
-using CombineArgsOf = typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs, SplitArgs>::type;
+using CombineArgsOf = typename std::conditional<IsWindow<DT>::value, WindowSplitKArgs,
+                                                typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs, SplitArgs>::type>::type;
 __device__ __forceinline__ VarQArgs varq_args(const SplitArgs&) { return VarQArgs{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ VarQArgs varq_args(const VarQSplitKArgs& a) { return a.vq; }
 __device__ __forceinline__ VarQSplitArgs split_args(const SplitArgs&) { return VarQSplitArgs{0, 0}; }
 __device__ __forceinline__ VarQSplitArgs split_args(const VarQSplitKArgs& a) { return a.sp; }
+__device__ __forceinline__ WindowArgs window_args(const SplitArgs&) { return WindowArgs{0}; }
+__device__ __forceinline__ WindowArgs window_args(const WindowSplitKArgs& a) { return a.w; }
 __device__ __forceinline__ PageArgs page_args(const SplitArgs&) { return PageArgs{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ PageArgs page_args(const PagedSplitArgs& a) { return a.pg; }
 
@@ -150,14 +160,23 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // DevLen / Paged kernel with Sq = Sq_b and R = R_b = Sq_b * G (block-uniform) and the q row cu[b] + qi, clamped into [0, total_q - 1].
 // Every early exit is uniform over the block and stands in front of the first barrier.  The workspace keeps a.R = split_seqlen_q * G rows
 // per (sequence, KV head); rows >= R_b are neither written nor read.
+//
+// Window<VarQ<..>> (awq_window.hpp, a windowed mixed step): the rule is varq_window_split_takes, and the splits are anchored at the window and
+// not at key 0 -- k_begin = anchor_b + split * chunk with anchor_b = max(0, Sk_b - Sq_b - left) & ~63, block-uniform, one scalar expression
+// behind the length load.  A split with k_begin >= Sk_b is empty, as above; no key and no table entry below anchor_b is read (the page walk
+// begins at k_begin already).  Row i attends keys max(0, lim - left) .. lim: a tile wholly below the wave's first window start is skipped by
+// a wave-uniform test, the low mask runs only in tiles below the wave's last window start, and a row whose window starts behind the
+// split's last key leaves m = -inf, l = 0 for that split, which the combine skips.  Every row attends its own key, so some split's m is finite.
 template <typename DT, int DH>
 __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> a) {
   constexpr bool KV8 = IsKv8<DT>::value;
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
+  constexpr bool WINDOW = IsWindow<DT>::value;
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
+  static_assert(!WINDOW || VARQ, "a window exists on the packed form only");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -176,7 +195,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   bi /= a.splits;
   const int kvh = bi % a.Hkv;
   const int b = bi / a.Hkv;
-  const int k_begin = split * a.chunk;                  // < Sk: (splits - 1) * chunk < Sk (DevLen: or the block is empty)
+  int k_begin = split * a.chunk;                        // < Sk: (splits - 1) * chunk < Sk (DevLen: or the block is empty)
   int Sk = a.Sk;
   int Sq = a.Sq, R = a.R;  // VarQ: Sq_b and R_b = Sq_b * G, block-uniform; a.R stays the workspace's row count
   long long row0 = 0;      // VarQ: the sequence's first packed row
@@ -187,11 +206,19 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
     const int c0 = cu[b], c1 = cu[b + 1];
     const long long sq_b = (long long)c1 - c0;
     const long long len = (long long)a.seqlens_k[b] + (vq.lens_before_step ? sq_b : 0ll);  // 64 bits, as the one-pass kernel forms it
-    if (!varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a))) return;  // the one-pass kernel's sequence
+    if constexpr (WINDOW) {
+      if (!varq_window_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a), window_args(a))) return;
+    } else {
+      if (!varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a))) return;  // the one-pass kernel's sequence
+    }
     Sq = (int)sq_b;  // 1 .. split_seqlen_q
     R = Sq * a.G;    // <= a.R <= 128
     row0 = c0;
     Sk = (int)len;   // 1 .. a.Sk
+    if constexpr (WINDOW) {  // the splits start at the window: a k_begin at or beyond Sk (or beyond int) is clamped to Sk, an empty split
+      const long long kb = (long long)window_anchor(Sq, Sk, window_args(a).left) + k_begin;
+      k_begin = (int)min(kb, (long long)Sk);
+    }
     if (k_begin >= Sk) {  // empty
       if (tid < R) {
         const long long e = (((long long)b * a.Hkv + kvh) * a.R + tid) * a.splits + split;
@@ -223,6 +250,18 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   const int lim = a.causal ? qi + shift : Sk - 1;                                     // last key this lane's row attends
   const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
   const int wave_min = a.causal ? wr0 / a.G + shift : Sk - 1;                         // every row of the wave attends keys <= this
+  // Window (causal only): this lane's first key, and the first / last window start of the wave's rows
+  int lo = 0, wave_lo = 0, wave_lo_max = 0;
+  unsigned span = 0;  // lim - lo, the width of this lane's window
+  (void)lo, (void)span, (void)wave_lo, (void)wave_lo_max;
+  if constexpr (WINDOW) {
+    const long long left = window_args(a).left;
+    // a row that attends nothing (lim < 0) gets a start no key reaches and an empty span
+    lo = lim < 0 ? 0x40000000 : (int)max(0ll, (long long)lim - left);
+    span = lim < 0 ? 0u : (unsigned)(lim - lo);
+    wave_lo = (int)max(0ll, (long long)wave_min - left);
+    wave_lo_max = (int)max(0ll, (long long)wave_max - left);
+  }
 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   vec8 qf[KS];
@@ -337,7 +376,9 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
     }
     if (more) stage_load(t0 + kKV, pg_nxt, ro_nxt);
 
-    if (wave_on && t0 <= wave_max) {  // wave-uniform: every lane of the wave takes part in the transposed reads
+    bool below = false;  // Window: the tile lies wholly below every window start of the wave
+    if constexpr (WINDOW) below = t0 + kKV <= wave_lo;
+    if (wave_on && t0 <= wave_max && !below) {  // wave-uniform: every lane of the wave takes part in the transposed reads
       // ---- S^T = K Q^T: s[kb2][e] = key t0 + 32 kb2 + (e & 3) + 8 (e >> 2) + 4 hh, packed row r ----
       f32x16 s[2];
 #pragma unroll
@@ -352,13 +393,19 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
       }
       // ---- online softmax (base 2: the logits are scaled by scale * log2 e) ----
       const bool need_mask = t0 + kKV - 1 > wave_min;  // (wave_min <= Sk - 1: the end of K is covered too)
+      const bool need_lo = WINDOW && t0 < wave_lo_max;  // some row of the wave starts inside or behind this tile
       float mx = -INFINITY;
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           float x = s[kb2][e] * a.scale_log2e;
-          if (need_mask) {
+          if constexpr (WINDOW) {
+            if (need_mask || need_lo) {  // both ends in one unsigned compare: lo <= key <= lim  <=>  key - lo <= lim - lo
+              const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+              x = (unsigned)(key - lo) <= span ? x : -INFINITY;
+            }
+          } else if (need_mask) {
             const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
             x = key <= lim ? x : -INFINITY;
           }
@@ -431,7 +478,8 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 //
 // VarQ<DevLen<..>> (a mixed step): one thread = 8 columns of one (b, kvh, row < a.R = split_seqlen_q * G).  It evaluates varq_split_takes
 // on its sequence and leaves if the split kernel did not take it or row >= R_b: such a workspace row was never written.  The result goes
-// to packed row cu[b] + row / G, guarded by row < min(cu[b + 1], total_q).
+// to packed row cu[b] + row / G, guarded by row < min(cu[b + 1], total_q).  Window<VarQ<DevLen<..>>>: the same under the windowed rule; the
+// partials do not know where their split began.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(CombineArgsOf<DT> a) {
   constexpr int CPR = DH / 8;
@@ -451,7 +499,10 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(CombineArgsOf
     const int c0 = cu[b], c1 = cu[b + 1];
     const long long sq_b = (long long)c1 - c0;
     const long long len = (long long)a.seqlens_k[b] + (vq.lens_before_step ? sq_b : 0ll);
-    if (!varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a)) || pr >= sq_b * a.G) return;
+    bool takes;
+    if constexpr (IsWindow<DT>::value) takes = varq_window_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a), window_args(a));
+    else takes = varq_split_takes(sq_b, len, vq.max_seqlen_q, a.Sk, split_args(a));
+    if (!takes || pr >= sq_b * a.G) return;
     out_row = (long long)c0 + pr / a.G;
     if (out_row < 0 || out_row >= min((long long)c1, (long long)vq.total_q)) return;  // (a corrupt array: no address outside the tensor)
   }
@@ -564,6 +615,16 @@ size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int he
   return (size_t)batch * nheads * seqlen_q * splits * (head_dim + 2) * sizeof(float);
 }
 
+// Host plan of a windowed mixed step (awq_window.hpp): attn_kvcache_plan for the most keys an anchored walk can cover,
+// min(max_seqlen_k, left + split_seqlen_q + 63) -- Sk_b - anchor_b never exceeds it.  The knob attn_splitkv_chunk applies.  Host arguments only.
+int attn_varq_window_plan(int batch, int nheads_kv, int split_seqlen_q, int max_seqlen_k, int window_left, int* splits, int* chunk) {
+  return attn_kvcache_plan(batch, nheads_kv, window_plan_bound(split_seqlen_q, max_seqlen_k, window_left), splits, chunk);
+}
+
+size_t attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int window_left) {
+  return attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, split_seqlen_q, window_plan_bound(split_seqlen_q, max_seqlen_k, window_left));
+}
+
 namespace {
 
 // Both launches of one call.  K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
@@ -600,7 +661,7 @@ void launch_for_cache(const A& a, int Dh, int dtype, hipStream_t st) {
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st) {
   const KvView& kv = c.kv;
   const bool mixed = c.cu_seqlens_q && c.split_seqlen_q > 0;  // the packed pair: c.Sq is max_seqlen_q, c.seqlen_offset the flag
-  VarQSplitKArgs a;
+  WindowSplitKArgs a;
   a.q = (const uint16_t*)c.q;
   a.k = (const uint16_t*)kv.k;
   a.v = (const uint16_t*)kv.v;
@@ -630,11 +691,16 @@ int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, 
   a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
   a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, c.seqlen_offset ? 1 : 0};
   a.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
+  a.w = WindowArgs{c.window_left >= 0 ? c.window_left : 0};
+  const VarQSplitKArgs& varq = a;
   const PagedSplitArgs& paged = a;
   const SplitArgs& dense = a;
-  if (mixed) {
-    if (kv.block_table) launch_for_cache<VarQPagedDevLen, VarQDevLen>(a, c.Dh, c.dtype, st);
-    else launch_for_cache<VarQDevLen, VarQDevLen>(a, c.Dh, c.dtype, st);
+  if (mixed && c.window_left >= 0) {  // a windowed step (awq_window.hpp): the caller's plan is awq_attn_varq_window_plan's
+    if (kv.block_table) launch_for_cache<WindowVarQPagedDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
+    else launch_for_cache<WindowVarQDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
+  } else if (mixed) {
+    if (kv.block_table) launch_for_cache<VarQPagedDevLen, VarQDevLen>(varq, c.Dh, c.dtype, st);
+    else launch_for_cache<VarQDevLen, VarQDevLen>(varq, c.Dh, c.dtype, st);
   } else if (kv.block_table) launch_for_cache<PagedDevLen, DevLen>(paged, c.Dh, c.dtype, st);
   else if (c.seqlens_k) launch_for_cache<DevLen, DevLen>(dense, c.Dh, c.dtype, st);
   else launch_for_cache<HostLen, HostLen>(dense, c.Dh, c.dtype, st);

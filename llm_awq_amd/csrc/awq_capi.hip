@@ -433,7 +433,8 @@ using awq::KvView;
 // what an entry requires of its descriptor; KV_ONEPASS: the one-pass prefill kernel serves, any seqlen_q (no seqlen_q * G <= 128 term)
 // KV_VARQ: packed tokens / queries (awq_varq.hpp) -- cu_seqlens_q, max_seqlen_q and total_q in the place of one seqlen for the batch
 // KV_MIX: a mixed step (awq_attn_varq and its siblings) -- split_seqlen_q and split_min_keys join the shape phase
-enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8, KV_VARQ = 16, KV_MIX = 32 };
+// KV_WINDOW: a sliding window on a mixed step (awq_window.hpp) -- window_left >= 0 and causal join the shape phase
+enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8, KV_VARQ = 16, KV_MIX = 32, KV_WINDOW = 64 };
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
@@ -538,6 +539,7 @@ static int kv_attn_check(const KvAttnCall& c, int fmt) {
   if ((fmt & KV_MIX) && (c.split_seqlen_q < 0 || c.split_min_keys < 1 ||
                          (c.H >= 1 && c.Hkv >= 1 && (c.H % c.Hkv) == 0 && (long long)c.split_seqlen_q * (c.H / c.Hkv) > 128)))
     return AWQ_ERR_SHAPE;
+  if ((fmt & KV_WINDOW) && (c.window_left < 0 || !c.causal)) return AWQ_ERR_SHAPE;
   // (host lengths: the T entry keeps the one-pass kernel's head dim 72 for the calls the plan hands to it; the FP8 kernels have 64 / 128)
   if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, fmt & KV_ONEPASS)
                : ((!(fmt & KV_FP8) || c.Dh == 64 || c.Dh == 128) && prefill_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal))) ||
@@ -890,16 +892,25 @@ size_t awq_attn_varq_split_workspace_bytes(int batch, int nheads, int nheads_kv,
 
 // check, workspace, then the one-pass launch, the split launch and the combine in one stream.  Every check stands in front of the first
 // launch.  split_seqlen_q = 0: awq_attn_prefill_*_varq, that launch alone and no workspace.
-static int kv_varq_attn(KvAttnCall c, int fmt, int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream) {
+static int window_clamped(int window_left, int max_seqlen_k) { return window_left < max_seqlen_k - 1 ? window_left : max_seqlen_k - 1; }
+
+// windowed (awq_window.hpp, the *_window entries): window_left >= 0 and causal join the shape phase, the window is clamped to
+// max_seqlen_k - 1 (beyond that it hides no key), and the plan and the workspace are the window's.
+static int kv_varq_attn(KvAttnCall c, int fmt, int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream,
+                        bool windowed = false, int window_left = 0) {
   c.split_seqlen_q = split_seqlen_q, c.split_min_keys = split_min_keys;
-  const int rc = kv_attn_check(c, fmt | KV_ONEPASS | KV_MIX);
+  if (windowed) c.window_left = window_left;
+  const int rc = kv_attn_check(c, fmt | KV_ONEPASS | KV_MIX | (windowed ? KV_WINDOW : 0));
   if (rc != AWQ_OK) return rc;
   if (c.max_seqlen_k > c.kv.capacity() || c.seqlen_offset < 0) return AWQ_ERR_SHAPE;
   if (!aligned4(c.seqlens_k)) return AWQ_ERR_ALIGN;
+  if (windowed) c.window_left = window_clamped(window_left, c.max_seqlen_k);
   int splits = 1, chunk = 0;
   if (split_seqlen_q > 0) {
-    awq::attn_kvcache_plan(c.B, c.Hkv, c.max_seqlen_k, &splits, &chunk);
-    const size_t need = awq::attn_kvcache_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, split_seqlen_q, c.max_seqlen_k);
+    if (windowed) awq::attn_varq_window_plan(c.B, c.Hkv, split_seqlen_q, c.max_seqlen_k, c.window_left, &splits, &chunk);
+    else awq::attn_kvcache_plan(c.B, c.Hkv, c.max_seqlen_k, &splits, &chunk);
+    const size_t need = windowed ? awq::attn_varq_window_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, split_seqlen_q, c.max_seqlen_k, c.window_left)
+                                 : awq::attn_kvcache_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, split_seqlen_q, c.max_seqlen_k);
     if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
     if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
     if ((long long)c.B * c.Hkv * splits > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
@@ -959,6 +970,77 @@ int awq_attn_paged_varq_kv8(const void* q, const void* k_pool, const void* v_poo
   return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
                                      nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
                       KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream);
+}
+
+// ---- a sliding window on a mixed step (awq_window.hpp): the four entries above with window_left behind split_min_keys
+
+int awq_attn_varq_window_plan(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int window_left,
+                              int* splits, int* chunk) {
+  if (!splits || !chunk) return AWQ_ERR_NULL;
+  if (!varq_split_shape_ok(batch, nheads, nheads_kv, head_dim, split_seqlen_q, max_seqlen_k) || window_left < 0) return AWQ_ERR_SHAPE;
+  return awq::attn_varq_window_plan(batch, nheads_kv, split_seqlen_q, max_seqlen_k, window_clamped(window_left, max_seqlen_k), splits, chunk);
+}
+
+size_t awq_attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k,
+                                            int window_left) {
+  if (!varq_split_shape_ok(batch, nheads, nheads_kv, head_dim, split_seqlen_q, max_seqlen_k) || window_left < 0) return 0;
+  return awq::attn_varq_window_workspace_bytes(batch, nheads, nheads_kv, head_dim, split_seqlen_q, max_seqlen_k,
+                                               window_clamped(window_left, max_seqlen_k));
+}
+
+int awq_attn_varq_window(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q,
+                         int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                         long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                         int window_left, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left);
+}
+
+int awq_attn_varq_window_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                             int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                             int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_row_stride,
+                             long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                             long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                             long long v_scale_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                             int window_left, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_scales(kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale,
+                                v_scale, k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_FP8 | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left);
+}
+
+int awq_attn_paged_varq_window(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                               const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                               int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                               int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q,
+                               int split_min_keys, int window_left, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left);
+}
+
+int awq_attn_paged_varq_window_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                   const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                   const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                   int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                   long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                   long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                   long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                   int split_seqlen_q, int split_min_keys, int window_left, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left);
 }
 
 int awq_rope_kv_store_natural_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,

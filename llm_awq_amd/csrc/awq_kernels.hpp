@@ -256,6 +256,9 @@ int launch_attn_prefill_kv8(const void* q, const void* k, const void* v, const f
 // the plan of the device-length form (awq_devlen.hpp): made from the host bound max_seqlen_k alone
 int attn_kvcache_plan(int batch, int nheads_kv, int max_seqlen_k, int* splits, int* chunk);
 size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_seqlen_k);
+// the plan of a windowed mixed step (awq_window.hpp): attn_kvcache_plan for the bound min(max_seqlen_k, window_left + split_seqlen_q + 63)
+int attn_varq_window_plan(int batch, int nheads_kv, int split_seqlen_q, int max_seqlen_k, int window_left, int* splits, int* chunk);
+size_t attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int window_left);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

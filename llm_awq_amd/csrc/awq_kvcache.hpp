@@ -67,6 +67,9 @@ struct KvAttnCall {
   // a mixed step (awq_varq.hpp, awq_attn_varq and its siblings): the split pair takes a sequence with Sq_b <= split_seqlen_q and
   // Sk_b >= split_min_keys, the one-pass kernel leaves it alone.  split_seqlen_q = 0: the plain packed launch
   int split_seqlen_q = 0, split_min_keys = 0;
+  // a sliding window on a packed step (awq_window.hpp, awq_attn_varq_window and its siblings): a row attends its own key and the
+  // window_left keys before it, clamped by the entry to max_seqlen_k - 1.  -1: no window, the kernels above
+  int window_left = -1;
 };
 
 // Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to

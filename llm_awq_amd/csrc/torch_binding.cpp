@@ -1275,6 +1275,9 @@ struct PackedStep {
   // attention only, a mixed step (attn_varq and its siblings): the split pair takes the sequences with at most split_seqlen_q new tokens over
   // at least split_min_keys keys.  split_seqlen_q < 0: not a mixed call
   int64_t split_seqlen_q = -1, split_min_keys = 0;
+  // a mixed step with a sliding window (attn_varq_window and its siblings): a row attends its own key and the window_left keys before it.
+  // window_left < 0: no window
+  int64_t window_left = -1;
 };
 
 static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
@@ -1475,11 +1478,16 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   if (mixed)
     TORCH_CHECK(step.split_min_keys >= 1 && step.split_seqlen_q * (nheads / nheads_kv) <= 128, who, ": split_min_keys ", step.split_min_keys,
                 " must be at least 1 and split_seqlen_q * (H / Hkv) = ", step.split_seqlen_q * (nheads / nheads_kv), " at most 128");
+  const bool windowed = mixed && step.window_left >= 0;
+  const int wl = (int)std::min<int64_t>(step.window_left, 0x7FFFFFFF);
+  if (windowed) TORCH_CHECK(causal, who, ": a sliding window needs causal = true");
   check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor out = packed ? packed_out(who, "out", *step.out, q, total, nheads, headdim)
                           : torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
-  const size_t wsb = mixed      ? awq_attn_varq_split_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim,
+  const size_t wsb = windowed   ? awq_attn_varq_window_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim,
+                                                                       (int)step.split_seqlen_q, (int)max_seqlen_k, wl)
+                     : mixed    ? awq_attn_varq_split_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim,
                                                                       (int)step.split_seqlen_q, (int)max_seqlen_k)
                      : one_pass ? 0
                                 : awq_attn_kvcache_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_seqlen_k);
@@ -1501,7 +1509,19 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   if (mixed) {
     const int ssq = (int)step.split_seqlen_q, smk = (int)std::min<int64_t>(step.split_min_keys, 0x7FFFFFFF);
     void* wp = wsb ? ws.data_ptr() : nullptr;
-    if (paged && fp8)
+    if (windowed && paged && fp8)
+      raise_on(awq_attn_paged_varq_window_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs,
+                                              kbs, krs, vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ssq, smk, wl, wp, wsb, st));
+    else if (windowed && paged)
+      raise_on(awq_attn_paged_varq_window(qp, kp, vp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs, vbs,
+                                          vrs, scale, cz, dt, ssq, smk, wl, wp, wsb, st));
+    else if (windowed && fp8)
+      raise_on(awq_attn_varq_window_kv8(qp, kp, vp, ksp, vsp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, ksbs, ksrs,
+                                        vsbs, vsrs, scale, cz, dt, ssq, smk, wl, wp, wsb, st));
+    else if (windowed)
+      raise_on(awq_attn_varq_window(qp, kp, vp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, scale, cz, dt, ssq, smk,
+                                    wl, wp, wsb, st));
+    else if (paged && fp8)
       raise_on(awq_attn_paged_varq_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs,
                                        vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ssq, smk, wp, wsb, st));
     else if (paged)
@@ -1707,6 +1727,56 @@ torch::Tensor attn_paged_varq_kv8(const torch::Tensor q, const torch::Tensor k_p
   TORCH_CHECK(split_seqlen_q >= 0, "attn_paged_varq_kv8: split_seqlen_q must not be negative");
   return attn_kvcache_impl("attn_paged_varq_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale,
                            causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys});
+}
+
+// attn_varq_window[_kv8] / attn_paged_varq_window[_kv8]: attn_varq[_kv8] / attn_paged_varq[_kv8] with window_left behind split_min_keys -- row
+// s of sequence b attends its own key and the window_left keys before it (flash-attn's window_size = (window_left, 0)); causal only.
+torch::Tensor attn_varq_window(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor cu_seqlens_q,
+                               int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q,
+                               int64_t split_min_keys, int64_t window_left, bool lens_before_step, double softmax_scale, bool causal,
+                               c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_varq_window: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_varq_window", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal,
+                           true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left});
+}
+
+torch::Tensor attn_varq_window_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                                   const torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
+                                   const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q, int64_t split_min_keys,
+                                   int64_t window_left, bool lens_before_step, double softmax_scale, bool causal,
+                                   c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_varq_window_kv8: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_varq_window_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left});
+}
+
+torch::Tensor attn_paged_varq_window(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                     const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k,
+                                     int64_t split_seqlen_q, int64_t split_min_keys, int64_t window_left, bool lens_before_step,
+                                     double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_paged_varq_window: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_paged_varq_window", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left});
+}
+
+torch::Tensor attn_paged_varq_window_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                         const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q,
+                                         int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q,
+                                         int64_t split_min_keys, int64_t window_left, bool lens_before_step, double softmax_scale, bool causal,
+                                         c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_paged_varq_window_kv8: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_paged_varq_window_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0,
+                           softmax_scale, causal, true,
+                           {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left});
+}
+
+// (splits, chunk) of awq_attn_varq_window_plan: attn_kvcache_plan's for min(max_seqlen_k, window_left + split_seqlen_q + 63).  Host only.
+std::tuple<int64_t, int64_t> attn_varq_window_plan(int64_t batch, int64_t nheads, int64_t nheads_kv, int64_t head_dim, int64_t split_seqlen_q,
+                                                   int64_t max_seqlen_k, int64_t window_left) {
+  int splits = 1, chunk = 0;
+  raise_on(awq_attn_varq_window_plan((int)batch, (int)nheads, (int)nheads_kv, (int)head_dim, (int)split_seqlen_q, (int)max_seqlen_k,
+                                     (int)std::min<int64_t>(window_left, 0x7FFFFFFF), &splits, &chunk));
+  return {splits, chunk};
 }
 
 // (splits, chunk) of awq_attn_varq_split_plan: attn_kvcache_plan's for the same bound.  Host only.
@@ -2199,6 +2269,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
         py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("lens_before_step"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_window", &attn_varq_window, "attn_varq with a sliding window: a row attends its own key and the window_left keys before it",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("lens_before_step"),
+        py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_window_kv8", &attn_varq_window_kv8, "attn_varq_window on the FP8 cache", py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_paged_varq_window", &attn_paged_varq_window, "attn_varq_window over a paged KV cache", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_paged_varq_window_kv8", &attn_paged_varq_window_kv8, "attn_paged_varq_window on FP8 pools", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
+        py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"),
+        py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_window_plan", &attn_varq_window_plan,
+        "(splits, chunk) of the split pair of a windowed mixed step: attn_kvcache_plan's for min(max_seqlen_k, window_left + split_seqlen_q + 63)",
+        py::arg("batch"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("split_seqlen_q"), py::arg("max_seqlen_k"),
+        py::arg("window_left"));
   m.def("attn_varq_split_plan", &attn_varq_split_plan, "(splits, chunk) of the split pair of a mixed step: attn_kvcache_plan's for the same bound",
         py::arg("batch"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("split_seqlen_q"), py::arg("max_seqlen_k"));
   m.def("attn_varq_plan", &attn_varq_plan, "(q_tile_rows, blocks) of a packed-query launch: a provisional host rule", py::arg("batch"),

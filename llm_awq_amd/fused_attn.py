@@ -45,6 +45,11 @@ with one `forward` per chunk; a chunked prefill is one captured graph, replayed 
 sequences in one run of rows with per-sequence counts read on the device (`rope_kv_store_{natural,paged}_varq[_fp8]`,
 `attn_prefill[_paged]_varq[_kv8]`, csrc/awq_varq.hpp) -- decodes, prompt chunks and idle slots in one store launch and one attention
 launch, and one captured graph for every step of a fixed token budget.
+
+`sliding_window=W` (Mistral-7B-v0.1, Gemma-2/3 local layers, Qwen2 with `use_sliding_window`; `make_quant_attn_window`) makes every row attend W keys, itself included
+-- the HF eager mask -- on the packed routes: `forward_packed`, `forward_packed_split` and `forward` under a tensor `start_pos` call
+`attn_varq_window[_kv8]` / `attn_paged_varq_window[_kv8]` with window_left = W - 1 (csrc/awq_window.hpp).  A decode step then reads W keys
+however long the history is, and `PageTable.release_before` returns the pages the window has left behind.
 """
 from __future__ import annotations
 
@@ -61,10 +66,17 @@ class QuantLlamaAttentionFused(nn.Module):
     reference's long-context mode (QuantLlamaAttentionFusedFlash with kv_max_seq_len > 8192): both caches are
     [max_batch_size, kv_max_seq_len, Hkv, Dh] and forward is long_forward's data flow for every seqlen.  `kv_dtype="fp8"` (with
     `kv_layout="natural"`) makes them float8_e4m3fn and adds `cache_k_scale` / `cache_v_scale` [max_batch_size, kv_max_seq_len, Hkv]
-    float32; `kv_dtype=None` is the cache of the activations' dtype."""
+    float32; `kv_dtype=None` is the cache of the activations' dtype.  `sliding_window=W` (an int >= 1; None: full attention, nothing
+    changes): each row attends W keys, itself included; the config is never read for it.  It is served on the packed routes of the
+    natural layout only: an int `start_pos`, `kv_layout="ft"` and `chunk_prefilling` on the FT path raise NotImplementedError."""
 
-    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft", kv_dtype=None):
+    def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft", kv_dtype=None,
+                 sliding_window=None):
         super().__init__()
+        if sliding_window is not None and (isinstance(sliding_window, bool) or int(sliding_window) != sliding_window or int(sliding_window) < 1):
+            raise ValueError(f"QuantLlamaAttentionFused: sliding_window {sliding_window!r} must be None or an int >= 1 (the keys a row attends, "
+                             "itself included)")
+        self.sliding_window = None if sliding_window is None else int(sliding_window)
         if kv_layout not in ("ft", "natural"):
             raise ValueError(f"QuantLlamaAttentionFused: kv_layout {kv_layout!r} is not supported (supported: 'ft', 'natural')")
         if kv_dtype not in (None, "fp8"):
@@ -125,11 +137,25 @@ class QuantLlamaAttentionFused(nn.Module):
         p of sequence b lives in row p % page_size of page block_table[b, p // page_size].  `decode_max_seqlen` defaults to
         pages_per_seq * page_size.
 
-        A PACKED step of continuous batching (per-sequence numbers of new tokens) is `forward_packed`."""
+        A PACKED step of continuous batching (per-sequence numbers of new tokens) is `forward_packed`.
+
+        With `sliding_window` the call needs a tensor `start_pos`: it builds the uniform cu_seqlens_q = [0, seqlen, 2 seqlen, ..] on the
+        device and is `forward_packed_split` on the batch as one packed step (split_seqlen_q = seqlen while seqlen * (H / Hkv) <= 128,
+        else 0)."""
+        if self.sliding_window is not None:
+            self._check_window(start_pos, chunk_prefilling)
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
         eng = load_engine()
         bsz, seqlen, _ = x.shape
+        if self.sliding_window is not None:
+            from .ops import ATTN_SPLIT_MIN_KEYS
+
+            cu = torch.arange(0, (bsz + 1) * seqlen, seqlen, dtype=torch.int32, device=x.device)
+            ssq = seqlen if seqlen * self.num_key_value_groups <= 128 else 0
+            out = self._forward_packed(x.reshape(1, bsz * seqlen, -1), start_pos, freqs, cu, seqlen, decode_max_seqlen, block_table, page_size,
+                                       (ssq, ATTN_SPLIT_MIN_KEYS))
+            return out.view(bsz, seqlen, -1)
         if isinstance(start_pos, torch.Tensor):
             return self._forward_device_pos(eng, x, start_pos, freqs, decode_max_seqlen, block_table, page_size)
         xqkv = self.qkv_proj(x)
@@ -170,6 +196,18 @@ class QuantLlamaAttentionFused(nn.Module):
                                                 self.rope_scaling, True)
             output = output.reshape(bsz, 1, -1)
         return self.o_proj(output)
+
+    def _check_window(self, start_pos, chunk_prefilling=False):
+        """What `sliding_window` is not built for, refused before any work."""
+        who = "QuantLlamaAttentionFused"
+        if self.kv_layout != "natural":
+            if chunk_prefilling:
+                raise NotImplementedError(f"{who}: sliding_window is not implemented for chunk_prefilling on the FT cache (kv_layout 'ft'); "
+                                          "use kv_layout 'natural' with start_pos as a tensor")
+            raise NotImplementedError(f"{who}: sliding_window is not implemented on the FT cache (kv_layout 'ft'); use kv_layout 'natural'")
+        if not isinstance(start_pos, torch.Tensor):
+            raise NotImplementedError(f"{who}: sliding_window is not implemented for an int start_pos (the host-length path); pass start_pos "
+                                      "as an int32 tensor [bsz] on the GPU")
 
     def _check_paged(self, start_pos, block_table, page_size):
         """The paged call's conditions, before any work."""
@@ -243,7 +281,10 @@ class QuantLlamaAttentionFused(nn.Module):
                                     (split_seqlen_q, split_min_keys))
 
     def _forward_packed(self, x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen, block_table, page_size, split):
-        """The packed step; split = (split_seqlen_q, split_min_keys) routes its attention to the mixed entries."""
+        """The packed step; split = (split_seqlen_q, split_min_keys) routes its attention to the mixed entries.  With `sliding_window` the
+        windowed mixed entries serve every call; no split is then split_seqlen_q = 0."""
+        if self.sliding_window is not None:
+            self._check_window(start_pos)
         self._check_packed(x, start_pos, cu_seqlens_q, max_seqlen_q)
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
@@ -275,7 +316,13 @@ class QuantLlamaAttentionFused(nn.Module):
         store = getattr(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""))
         attn = getattr(eng, "attn_prefill" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
         xq = store(xqkv, freqs, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
-        if split is not None:
+        if self.sliding_window is not None:
+            from .ops import ATTN_SPLIT_MIN_KEYS
+
+            ssq, smk = split if split is not None else (0, ATTN_SPLIT_MIN_KEYS)
+            attn = getattr(eng, "attn" + where[1] + "_varq_window" + ("_kv8" if fp8 else ""))
+            output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, ssq, smk, self.sliding_window - 1, True, scale, True)
+        elif split is not None:
             attn = getattr(eng, "attn" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
             output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, split[0], split[1], True, scale, True)
         else:
@@ -365,14 +412,29 @@ def fuse_qkv(q_proj, k_proj, v_proj):
 def make_quant_attn(model, dev, max_batch_size=1, kv_layout="ft", kv_dtype=None):
     """tinychat/modules/fused_attn.py:549-634: replace every module that carries q_proj, k_proj, v_proj, o_proj, `args` and
     `kv_max_seq_len` (the reference's LlamaAttentionFused / Qwen2AttentionFused) by a QuantLlamaAttentionFused over one fused
-    qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode, `kv_dtype="fp8"` its FP8 cache."""
+    qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode, `kv_dtype="fp8"` its FP8 cache.
+    `make_quant_attn_window` is the same with a sliding window."""
+    return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, None)
+
+
+def make_quant_attn_window(model, dev, sliding_window, max_batch_size=1, kv_layout="natural", kv_dtype=None):
+    """`make_quant_attn` for a model with a sliding window (Mistral-7B-v0.1, Gemma-2/3 local layers, Qwen2 with `use_sliding_window`): every
+    module is built with `sliding_window=W`, a window of W keys per row, the row's own included.  W is passed through; the model's config is
+    not read for it.  A function of its own: `make_quant_attn` keeps its parameter list."""
+    if sliding_window is None:
+        raise ValueError("make_quant_attn_window: sliding_window must be an int >= 1 (`make_quant_attn` builds the modules without a window)")
+    return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window)
+
+
+def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window):
     want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
     for name, m in list(model.named_modules()):
         if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
             continue
         qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
         attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
-                                        max_batch_size=max_batch_size, kv_layout=kv_layout, kv_dtype=kv_dtype)
+                                        max_batch_size=max_batch_size, kv_layout=kv_layout, kv_dtype=kv_dtype,
+                                        sliding_window=sliding_window)
         if "." in name:
             parent_name, child_name = name.rsplit(".", 1)
             parent = model.get_submodule(parent_name)

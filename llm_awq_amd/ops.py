@@ -1324,12 +1324,13 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
     return q_out
 
 
-def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None, split=None):
+def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None, split=None,
+                  window=None):
     """The device-length attention entries of the C ABI over a described cache (q and kv checked by the caller): the four of the split
     pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace).  packed = (cu_seqlens_q, max_seqlen_q, out or
     None), checked by the caller (one_pass only): q is the packed rows [total_q, H, Dh] of a step, the four varq entries serve and
     seqlen_offset carries the flag lens_before_step.  split = (split_seqlen_q, split_min_keys), with packed: a mixed step, the four
-    awq_attn_[paged_]varq entries and the split pair's workspace."""
+    awq_attn_[paged_]varq entries and the split pair's workspace.  window = window_left, with split: the four *_window entries and their plan."""
     if packed:
         cu, Sq, out = packed
         (T, H, Dh), B = q.shape, cu.shape[0] - 1
@@ -1346,11 +1347,14 @@ def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_sc
     # q's strides: the batch stride (a rectangle's only) and the row stride
     head = (q.data_ptr(), *kv.ptrs(), out.data_ptr(), *where, H, kv.Hkv, Dh, *q.stride()[:-2], *kv.strides(), scale, int(bool(causal)), _dt(q))
     if split is not None:
-        wsb = L.awq_attn_varq_split_workspace_bytes(B, H, kv.Hkv, Dh, split[0], int(max_seqlen_k))
+        if window is None:
+            wsb = L.awq_attn_varq_split_workspace_bytes(B, H, kv.Hkv, Dh, split[0], int(max_seqlen_k))
+        else:
+            wsb = L.awq_attn_varq_window_workspace_bytes(B, H, kv.Hkv, Dh, split[0], int(max_seqlen_k), window)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
-        entry = getattr(L, "awq_attn_" + ("paged_" if kv.paged else "") + "varq" + ("_kv8" if kv.fp8 else ""))
+        entry = getattr(L, "awq_attn_" + ("paged_" if kv.paged else "") + "varq" + ("" if window is None else "_window") + ("_kv8" if kv.fp8 else ""))
         with torch.cuda.device(q.device):
-            _capi.check(entry(*head, split[0], split[1], ws.data_ptr(), wsb, _stream(q)))
+            _capi.check(entry(*head, split[0], split[1], *(() if window is None else (window,)), ws.data_ptr(), wsb, _stream(q)))
         return out
     if one_pass:
         entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_varq" if packed else "") + ("_kv8" if kv.fp8 else ""))
@@ -1698,6 +1702,18 @@ def attn_varq_split_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int,
     return s.value, c.value
 
 
+def attn_varq_window_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, split_seqlen_q: int, max_seqlen_k: int, window_left: int):
+    """Host-side awq_attn_varq_window_plan: (splits, chunk) of the split pair inside `attn_varq_window` (no GPU needed) --
+    `attn_kvcache_plan`'s for the bound min(max_seqlen_k, window_left + split_seqlen_q + 63), the most keys a walk anchored at the window
+    covers; the knob attn_splitkv_chunk included.  A negative window_left is refused, and whatever `attn_varq_split_plan` refuses."""
+    import ctypes
+
+    s, c = ctypes.c_int(0), ctypes.c_int(0)
+    _capi.check(_capi.lib().awq_attn_varq_window_plan(batch, nheads, nheads_kv, head_dim, split_seqlen_q, max_seqlen_k,
+                                                      min(int(window_left), 0x7FFFFFFF), ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
 def attn_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, split_seqlen_q: int = 1, split_min_keys=None,
               lens_before_step: bool = True, block_table=None, softmax_scale=None, causal: bool = True, k_scale=None, v_scale=None, out=None):
     """C-ABI awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8]: `attn_prefill_varq`'s arguments and contract for a MIXED packed step.  Three
@@ -1708,8 +1724,39 @@ def attn_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k:
     are bit-identical to `attn_kvcache` (`attn_kvcache_paged`) on that sequence alone with seqlen_offset = Sq_b under lens_before_step
     (else 0) and the same max_seqlen_k; every other row to `attn_prefill_varq`.  split_seqlen_q * (H / Hkv) <= 128; split_seqlen_q = 0
     splits nothing and is `attn_prefill_varq`, one launch.  The launch set depends on host arguments only: one captured graph replays any
-    mix of decodes, short bursts and prompt chunks.  Errors are raised before any work.  Returns out [total_q, H, Dh]."""
-    who = "attn_varq"
+    mix of decodes, short bursts and prompt chunks.  Errors are raised before any work.  Returns out [total_q, H, Dh].
+
+    `attn_varq_window` is the same step under a sliding window."""
+    return _attn_varq("attn_varq", q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k, split_seqlen_q, split_min_keys, lens_before_step,
+                      block_table, softmax_scale, causal, k_scale, v_scale, out, None)
+
+
+def attn_varq_window(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, window_left: int, split_seqlen_q: int = 1,
+                     split_min_keys=None, lens_before_step: bool = True, block_table=None, softmax_scale=None, causal: bool = True,
+                     k_scale=None, v_scale=None, out=None):
+    """C-ABI awq_attn_varq_window[_kv8] / awq_attn_paged_varq_window[_kv8]: `attn_varq`'s arguments and contract under a sliding window,
+    flash-attn's window_size = (L, 0) with L = window_left (an int >= 0): row s of sequence b stands at position p = s + Sk_b - Sq_b and
+    attends keys max(0, p - L) .. p.  A row with p < 0 is zeros as before; every other row attends at least its own key.  The split pair
+    takes a sequence iff keys_b = min(Sk_b, L + Sq_b) >= split_min_keys -- the keys it attends at all -- and anchors its splits at
+    max(0, Sk_b - Sq_b - L) & ~63 (`attn_varq_window_plan`); no key, scale or table entry below that is read
+    (`PageTable.release_before`).  L >= max_seqlen_k - 1 hides nothing and returns the bits of `attn_varq`.  causal = False and a negative
+    L are refused before any work.  A function of its own: `attn_varq` keeps its parameter list."""
+    if window_left is None:
+        raise ValueError("attn_varq_window: window_left must be an int >= 0 (`attn_varq` is the call without a window)")
+    return _attn_varq("attn_varq_window", q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k, split_seqlen_q, split_min_keys,
+                      lens_before_step, block_table, softmax_scale, causal, k_scale, v_scale, out, window_left)
+
+
+def _attn_varq(who, q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k, split_seqlen_q, split_min_keys, lens_before_step, block_table,
+               softmax_scale, causal, k_scale, v_scale, out, window_left):
+    """The body of `attn_varq` (window_left None) and `attn_varq_window`."""
+    if window_left is not None:
+        window_left = int(window_left)
+        if window_left < 0:
+            raise ValueError(f"{who}: window_left {window_left} must not be negative")
+        if not causal:
+            raise ValueError(f"{who}: a sliding window (window_left) needs causal = True")
+        window_left = min(window_left, 0x7FFFFFFF)
     split_seqlen_q = int(split_seqlen_q)
     split_min_keys = ATTN_SPLIT_MIN_KEYS if split_min_keys is None else int(split_min_keys)
     if split_seqlen_q < 0:
@@ -1729,7 +1776,7 @@ def attn_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k:
     if kv.Hkv >= 1 and q.shape[1] % kv.Hkv == 0 and split_seqlen_q * (q.shape[1] // kv.Hkv) > 128:
         raise ValueError(f"{who}: split_seqlen_q * (H / Hkv) = {split_seqlen_q * (q.shape[1] // kv.Hkv)} exceeds 128")
     return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, bool(lens_before_step), softmax_scale, causal, one_pass=True,
-                         packed=(cu_seqlens_q, max_seqlen_q, out), split=(split_seqlen_q, min(split_min_keys, 0x7FFFFFFF)))
+                         packed=(cu_seqlens_q, max_seqlen_q, out), split=(split_seqlen_q, min(split_min_keys, 0x7FFFFFFF)), window=window_left)
 
 
 def _ft_caches(who, ref, k_cache, v_cache):
