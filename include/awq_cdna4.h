@@ -764,6 +764,74 @@ int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_
                                long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Shared-prefix decode on the paged cache: the sequences of a GROUP hold the same keys below a common prefix (one system prompt, the n
+ *      samples of a request, beams) and the prefix is fetched ONCE for the group, with the query rows of all members in one MFMA tile.
+ * awq_attn_kvcache_paged_shared[_kv8]: the arguments of awq_attn_kvcache_paged[_kv8], and
+ *     group_members  device int32 [num_groups, group_cap], row stride members_row_stride >= group_cap (entries), -1 padding
+ *     group_prefix   device int32 [num_groups]: the tokens group g shares
+ *     seq_prefix     device int32 [batch]: the tokens sequence b shares with its group; below 64: ungrouped
+ *     num_groups >= 1, group_cap >= 1 with group_cap * seqlen_q * (nheads / nheads_kv) <= 128; max_prefix % 64 == 0 and
+ *     64 <= max_prefix <= max_seqlen_k, the host bound of every effective prefix.
+ *   Sk_b = seqlens_k[b] + seqlen_offset, b ACTIVE iff 1 <= Sk_b <= max_seqlen_k.  The effective prefix of P tokens for a sequence of Sk keys
+ *     is pfx(P, Sk) = min(P, max_prefix, max(0, Sk - seqlen_q)) & ~63, and 0 for P < 64.
+ *   Suffix: P_b = pfx(seq_prefix[b], Sk_b).  Suffix split s owns keys [P_b + s * chunk_s, min(Sk_b, P_b + (s + 1) * chunk_s)), read through
+ *     b's own table row with the masks, clamps, empty-block rule and rounding points of awq_attn_kvcache_paged.  No key, scale or table
+ *     entry of b below P_b is read.
+ *   Prefix: the LEAD of group g is its first member in list order that is a slot index in [0, batch) and active; P_g =
+ *     pfx(group_prefix[g], Sk_lead).  Without a lead, or with P_g = 0, the group's blocks write nothing.  Prefix split s owns keys
+ *     [s * chunk_p, min(P_g, (s + 1) * chunk_p)), read through the lead's table row ONLY; every row attends every key of it (the prefix
+ *     lies below every causal limit; P_g % 64 == 0 leaves nothing to clamp).  MFMA row (j * seqlen_q + i) * G + gh is query position i,
+ *     head gh of the KV head's group, of member j; it is stored, into the workspace rows of that member's slot, only when the member is a
+ *     valid, active slot.
+ *   Combine: awq_attn_kvcache's rule (partials with m = -inf skipped, ascending order, one division, zeros when nothing was attended) over
+ *     the first ceil(P_b / chunk_p) prefix splits, then all suffix splits.
+ *   Defined results.  Required of every active b with seq_prefix[b] >= 64: b is listed in exactly one group; that group's group_prefix
+ *     equals seq_prefix[b] and is <= Sk_m - seqlen_q for every active member m; the members' keys below the prefix hold the same values
+ *     (normally the same page ids).  Then out[b] is the function awq_attn_kvcache_paged computes for b.  A row's partial depends only on
+ *     its q row, its keys and the split boundaries -- not on the other rows of its tile nor on whose table named the pages -- so with
+ *     chunk_p == chunk_s == c and P_b % c == 0 out[b] is BIT-IDENTICAL to awq_attn_kvcache_paged[_kv8] under chunk c.  An ungrouped
+ *     sequence gets awq_attn_kvcache_paged's bits under chunk_s.  A violated requirement gives unspecified values for the sequences
+ *     involved and never an address outside a tensor: every index taken from a device array is clamped or guarded before it forms one.
+ *   Plan: awq_attn_kvcache_shared_plan gives (splits_p, chunk_p) = awq_attn_kvcache_plan's rule for the bound max_prefix and (splits_s,
+ *     chunk_s) = the rule for max_seqlen_k; the knob attn_splitkv_chunk forces both chunks.  Workspace: batch * nheads * seqlen_q *
+ *     (splits_p + splits_s) * (head_dim + 2) * 4 bytes (awq_attn_kvcache_shared_workspace_bytes), 16-byte aligned.
+ *   Three launches, their set and grids from host arguments only: num_groups * Hkv * splits_p prefix blocks, batch * Hkv * splits_s suffix
+ *     blocks, the combine.  No atomics, no host read; capturable, a replay follows in-place changes of lengths, tables and group arrays.
+ *   Returns the codes of awq_attn_kvcache_paged[_kv8], and AWQ_ERR_NULL for a null group array, AWQ_ERR_ALIGN for one that is not 4-byte
+ *     aligned, AWQ_ERR_SHAPE for num_groups < 1, group_cap < 1, members_row_stride < group_cap, group_cap * seqlen_q * G > 128 or a
+ *     max_prefix that is not a multiple of 64 in [64, max_seqlen_k]; all of them before any launch.
+ * awq_kv_page_copy[_fp8]: ONE launch copies the K and V rows (and, _fp8, the K and V scale rows) of n pages inside the pools: page
+ *     dst_pages[i] := page src_pages[i], both device int32 [n], 4-byte aligned.  A pair with an id outside [0, num_pages) or with equal
+ *     ids is skipped.  K / V moves are 16 bytes wide; page and row strides are honoured and no other byte is written.  A page that is both
+ *     a source and a destination of one call gives unspecified contents.  Capturable.  This is the copy-on-write of the partly filled tail
+ *     page of a fork.  AWQ_ERR_NULL / AWQ_ERR_SHAPE (n < 1, the pool terms above, head_dim not 64 / 128) / AWQ_ERR_ALIGN as above. */
+int awq_attn_kvcache_shared_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix, int max_seqlen_k,
+                                 int* splits_p, int* chunk_p, int* splits_s, int* chunk_s);
+size_t awq_attn_kvcache_shared_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix,
+                                               int max_seqlen_k);
+int awq_attn_kvcache_paged_shared(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                                  int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size,
+                                  int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                  long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                                  long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype,
+                                  const int* group_members, const int* group_prefix, const int* seq_prefix, int num_groups, int group_cap,
+                                  long long members_row_stride, int max_prefix, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_kvcache_paged_shared_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                      const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                                      int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                                      int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride,
+                                      long long k_row_stride, long long v_page_stride, long long v_row_stride, long long k_scale_page_stride,
+                                      long long k_scale_row_stride, long long v_scale_page_stride, long long v_scale_row_stride,
+                                      float softmax_scale, int causal, int dtype, const int* group_members, const int* group_prefix,
+                                      const int* seq_prefix, int num_groups, int group_cap, long long members_row_stride, int max_prefix,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int awq_kv_page_copy(void* k_pool, void* v_pool, const int* src_pages, const int* dst_pages, int n, int num_pages, int page_size, int nheads_kv,
+                     int head_dim, long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, void* stream);
+int awq_kv_page_copy_fp8(void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* src_pages, const int* dst_pages, int n,
+                         int num_pages, int page_size, int nheads_kv, int head_dim, long long k_page_stride, long long k_row_stride,
+                         long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                         long long v_scale_page_stride, long long v_scale_row_stride, void* stream);
+
 /* ---- Prompt chunks of any length on the device-length and paged caches: the ONE-PASS prefill kernel of awq_attn_prefill[_kv8] with every
  *      sequence's length read on the device, K / V from the dense caches or fetched from the pool through the table.  The arguments are
  *      those of awq_attn_kvcache[_kv8] / awq_attn_kvcache_paged[_kv8] without the workspace; seqlen_q >= 1 of ANY size (the split pair above

@@ -139,6 +139,15 @@ SIGNATURES = {
                                [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
     "awq_attn_kvcache_paged_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
                                    [ctypes.c_float, _i, _i, _vp, _sz, _vp]),
+    # shared-prefix decode on the paged cache: the paged entries' arguments, then the group arrays and their four host ints
+    "awq_attn_kvcache_shared_plan": (_i, [_i] * 7 + [ctypes.POINTER(_i)] * 4),
+    "awq_attn_kvcache_shared_workspace_bytes": (_sz, [_i] * 7),
+    "awq_attn_kvcache_paged_shared": (_i, [_vp] * 5 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 6 +
+                                      [ctypes.c_float, _i, _i] + [_vp] * 3 + [_i, _i, ctypes.c_longlong, _i] + [_vp, _sz, _vp]),
+    "awq_attn_kvcache_paged_shared_kv8": (_i, [_vp] * 7 + [_i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_longlong] * 10 +
+                                          [ctypes.c_float, _i, _i] + [_vp] * 3 + [_i, _i, ctypes.c_longlong, _i] + [_vp, _sz, _vp]),
+    "awq_kv_page_copy": (_i, [_vp] * 4 + [_i] * 5 + [ctypes.c_longlong] * 4 + [_vp]),
+    "awq_kv_page_copy_fp8": (_i, [_vp] * 6 + [_i] * 5 + [ctypes.c_longlong] * 8 + [_vp]),
     "awq_attn_prefill_kvcache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 6 + [ctypes.c_float, _i, _i, _vp]),
     "awq_attn_prefill_kvcache_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [ctypes.c_longlong] * 10 +
                                      [ctypes.c_float, _i, _i, _vp]),

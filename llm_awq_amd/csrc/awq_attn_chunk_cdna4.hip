@@ -233,4 +233,51 @@ int launch_kv_store(const KvStoreCall& c, hipStream_t st) {
   return 0;
 }
 
+// ---- awq_kv_page_copy[_fp8]: the copy-on-write of a fork's partly filled tail page (PageTable.fork, awq_shared.hpp) ------------------
+// One thread = one 16-byte chunk of one row of one (src, dst) pair, in K and in V; under FP8 the threads of chunks 0 .. Hkv - 1 move the
+// row's K and V scales as well (a row of codes has Hkv * Dh / 16 >= Hkv chunks).  A pair whose ids are equal or not both inside the pool
+// is skipped; rows and pages are addressed by their strides, so no byte between rows or pages is touched.
+namespace {
+
+struct PageCopyArgs {
+  uint8_t* k;
+  uint8_t* v;
+  float* ks;
+  float* vs;
+  long long k_os, k_rs, v_os, v_rs;      // bytes
+  long long ks_os, ks_rs, vs_os, vs_rs;  // floats
+  const int* src;
+  const int* dst;
+  int n, page_size, num_pages, cpr, Hkv;  // cpr: 16-byte chunks per row
+};
+
+__global__ __launch_bounds__(256) void kv_page_copy_kernel(PageCopyArgs a) {
+  const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (long long)a.n * a.page_size * a.cpr) return;
+  const int ch = (int)(id % a.cpr);
+  const long long pr = id / a.cpr;
+  const int row = (int)(pr % a.page_size);
+  const long long pair = pr / a.page_size;
+  const int s = as_const_i32(a.src)[pair], d = as_const_i32(a.dst)[pair];
+  if (s < 0 || s >= a.num_pages || d < 0 || d >= a.num_pages || s == d) return;
+  *reinterpret_cast<u32x4*>(a.k + d * a.k_os + row * a.k_rs + ch * 16) = *reinterpret_cast<const u32x4*>(a.k + s * a.k_os + row * a.k_rs + ch * 16);
+  *reinterpret_cast<u32x4*>(a.v + d * a.v_os + row * a.v_rs + ch * 16) = *reinterpret_cast<const u32x4*>(a.v + s * a.v_os + row * a.v_rs + ch * 16);
+  if (a.ks && ch < a.Hkv) {
+    a.ks[d * a.ks_os + row * a.ks_rs + ch] = a.ks[s * a.ks_os + row * a.ks_rs + ch];
+    a.vs[d * a.vs_os + row * a.vs_rs + ch] = a.vs[s * a.vs_os + row * a.vs_rs + ch];
+  }
+}
+
+}  // namespace
+
+int launch_kv_page_copy(const KvPageCopyCall& c, hipStream_t st) {
+  const KvView& kv = c.kv;
+  const int eb = kv.k_scale ? 1 : 2;  // bytes per element: codes or T
+  PageCopyArgs a{(uint8_t*)kv.k, (uint8_t*)kv.v, (float*)kv.k_scale, (float*)kv.v_scale, kv.k_os * eb, kv.k_rs * eb, kv.v_os * eb, kv.v_rs * eb,
+                 kv.ks_os, kv.ks_rs, kv.vs_os, kv.vs_rs, c.src_pages, c.dst_pages, c.n, kv.rows, kv.outer, c.Hkv * c.Dh * eb / 16, c.Hkv};
+  const long long threads = (long long)c.n * kv.rows * a.cpr;
+  hipLaunchKernelGGL(kv_page_copy_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, a);
+  return 0;
+}
+
 }  // namespace awq

@@ -42,12 +42,17 @@
 // awq_attn_varq[_kv8] / awq_attn_paged_varq[_kv8] run the pair inside a PACKED step (VarQ<..> instantiations of both kernels, awq_varq.hpp):
 // q / out are packed rows, sequence b brings Sq_b = cu[b + 1] - cu[b] of them, and the pair serves only the sequences varq_split_takes
 // hands to it -- few new tokens over a long history.  Every other sequence belongs to the one-pass launch of the same call.
+//
+// awq_attn_kvcache_paged_shared[_kv8] is the paged pair for sequences that share a prefix (Shared..<..> instantiations, awq_shared.hpp):
+// a prefix launch of the split kernel with the query rows of a whole GROUP in its tile, a suffix launch anchored behind each
+// sequence's prefix, and the combine over both sets of partials.
 #include "awq_device.hpp"
 #include "awq_devlen.hpp"
 #include "awq_kernels.hpp"
 #include "awq_kv8.hpp"
 #include "awq_kvcache.hpp"
 #include "awq_paged.hpp"
+#include "awq_shared.hpp"
 #include "awq_varq.hpp"
 #include "awq_window.hpp"
 
@@ -108,14 +113,24 @@ struct VarQSplitKArgs : PagedSplitArgs {
 struct WindowSplitKArgs : VarQSplitKArgs {
   WindowArgs w;
 };
+// Shared<..> only (awq_shared.hpp): the group arrays behind the paged arguments, for all three launches of the call
+struct SharedSplitArgs : PagedSplitArgs {
+  SharedArgs sh;
+};
 template <typename DT>
 using SplitArgsOf = typename std::conditional<
-    IsWindow<DT>::value, WindowSplitKArgs,
-    typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
-                              typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type>::type;
+    IsShared<DT>::value, SharedSplitArgs,
+    typename std::conditional<
+        IsWindow<DT>::value, WindowSplitKArgs,
+        typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
+                                  typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type>::type>::type;
 template <typename DT>
-using CombineArgsOf = typename std::conditional<IsWindow<DT>::value, WindowSplitKArgs,
-                                                typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs, SplitArgs>::type>::type;
+using CombineArgsOf = typename std::conditional<
+    IsShared<DT>::value, SharedSplitArgs,
+    typename std::conditional<IsWindow<DT>::value, WindowSplitKArgs,
+                              typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs, SplitArgs>::type>::type>::type;
+__device__ __forceinline__ SharedArgs shared_args(const SplitArgs&) { return SharedArgs{nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0}; }
+__device__ __forceinline__ SharedArgs shared_args(const SharedSplitArgs& a) { return a.sh; }
 __device__ __forceinline__ VarQArgs varq_args(const SplitArgs&) { return VarQArgs{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ VarQArgs varq_args(const VarQSplitKArgs& a) { return a.vq; }
 __device__ __forceinline__ VarQSplitArgs split_args(const SplitArgs&) { return VarQSplitArgs{0, 0}; }
@@ -167,6 +182,17 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // begins at k_begin already).  Row i attends keys max(0, lim - left) .. lim: a tile wholly below the wave's first window start is skipped by
 // a wave-uniform test, the low mask runs only in tiles below the wave's last window start, and a row whose window starts behind the
 // split's last key leaves m = -inf, l = 0 for that split, which the combine skips.  Every row attends its own key, so some split's m is finite.
+//
+// SharedSuffix<Paged<DevLen<..>>> (awq_shared.hpp, awq_attn_kvcache_paged_shared): the Paged block with k_begin = P_b + split * chunk,
+// P_b = pfx(seq_prefix[b], Sk_b) one scalar expression behind the length load, and its partial in entry ws_first + split of the
+// workspace's ws_splits entries per row.  No key, scale or table entry below P_b is read (the page walk begins at k_begin).
+// SharedPrefix<Paged<DevLen<..>>>: the block is (group, KV head, prefix split).  Its head loads group_prefix[g] (below 64: the block
+// leaves), then the member list through the constant address space, lane j of EVERY wave member j (j + 64 in a second round): the first
+// set bit of one ballot of "valid slot and active" names the lead, the same in every wave, and its slot and length are read from that
+// lane.  No lead, or k_begin >= P_g = pfx(group_prefix[g], Sk_lead): the block leaves, writing nothing.  Otherwise the Paged block with
+// Sk = P_g (a multiple of 64: the clamp and the mask are idle), no causal mask, the lead's table row, and R = group_cap * Sq * G rows:
+// packed row (j * Sq + i) * G + gh reads q of member j's slot, clamped into [0, B - 1], and is stored -- into THAT slot's workspace rows
+// -- only when member j is a valid, active slot.  Every exit is block-uniform and stands in front of the first barrier.
 template <typename DT, int DH>
 __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> a) {
   constexpr bool KV8 = IsKv8<DT>::value;
@@ -177,6 +203,8 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
   static_assert(!WINDOW || VARQ, "a window exists on the packed form only");
+  constexpr bool SH_PFX = IsSharedPrefix<DT>::value, SH_SFX = IsSharedSuffix<DT>::value;
+  static_assert(!(SH_PFX || SH_SFX) || (PAGED && !VARQ), "a shared prefix exists on the rectangular paged form only");
   using vec8 = typename DT::vec8;
   using elem = typename DT::elem;
   constexpr int NT = kNW * 64;
@@ -194,13 +222,43 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   const int split = bi % a.splits;
   bi /= a.splits;
   const int kvh = bi % a.Hkv;
-  const int b = bi / a.Hkv;
+  const int b = bi / a.Hkv;                             // SharedPrefix: the group
+  // Shared: the workspace holds ws_splits entries per row, this launch's from ws_first on.  (A macro, and the constexpr selects below:
+  // every unshared form keeps the very expressions it had, and with them its instruction stream.)
+#define WS_ENTRY(row) ((row) * ((SH_PFX || SH_SFX) ? shared_args(a).ws_splits : a.splits) + ((SH_PFX || SH_SFX) ? shared_args(a).ws_first + split : split))
   int k_begin = split * a.chunk;                        // < Sk: (splits - 1) * chunk < Sk (DevLen: or the block is empty)
   int Sk = a.Sk;
   int Sq = a.Sq, R = a.R;  // VarQ: Sq_b and R_b = Sq_b * G, block-uniform; a.R stays the workspace's row count
   long long row0 = 0;      // VarQ: the sequence's first packed row
   (void)row0;
-  if constexpr (VARQ) {
+  int tb = b;              // the sequence whose table row the block walks (SharedPrefix: the lead)
+  const_i32_t members = nullptr;  // SharedPrefix: the group's member list
+  (void)members;
+  if constexpr (SH_PFX) {
+    const SharedArgs sh = shared_args(a);
+    const int gp = as_const_i32(sh.group_prefix)[b];
+    if (gp < kKV) return;  // nothing shared
+    members = as_const_i32(sh.group_members) + (long long)b * sh.gm_rs;
+    int lead = -1, sk_lead = 0;
+    for (int j0 = 0; j0 < sh.group_cap && lead < 0; j0 += 64) {  // group_cap <= 128: two rounds at most, uniform
+      const int j = j0 + lane;
+      const int m = j < sh.group_cap ? members[j] : -1;
+      long long len = 0;
+      if (m >= 0 && m < a.B) len = (long long)a.seqlens_k[m] + a.seqlen_offset;
+      const bool ok = len >= 1 && len <= a.Sk;  // a valid slot, and active
+      const unsigned long long live = __ballot(ok);
+      if (live) {
+        const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(live));
+        lead = __builtin_amdgcn_readlane(m, src);
+        sk_lead = __builtin_amdgcn_readlane((int)len, src);
+      }
+    }
+    if (lead < 0) return;
+    Sk = shared_pfx(gp, sh.max_prefix, sk_lead, a.Sq);  // P_g: a multiple of 64, <= Sk_lead - Sq
+    if (k_begin >= Sk) return;                          // (P_g = 0 included) nothing is written: the combine does not read this entry
+    tb = lead;
+    R = sh.group_cap * a.R;                             // <= 128 (checked by the entry)
+  } else if constexpr (VARQ) {
     const VarQArgs vq = varq_args(a);
     const const_i32_t cu = as_const_i32(vq.cu_seqlens_q);
     const int c0 = cu[b], c1 = cu[b + 1];
@@ -230,9 +288,16 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   } else if constexpr (DEVLEN) {
     const long long len = (long long)a.seqlens_k[b] + a.seqlen_offset;  // 64 bits: no entry can wrap into an active length
     Sk = (int)len;
+    if constexpr (SH_SFX) {  // the splits start behind the prefix; a k_begin at or beyond Sk (or beyond int) is clamped to Sk, an empty split
+      if (len >= 1 && len <= a.Sk) {
+        const SharedArgs sh = shared_args(a);
+        const long long kb = (long long)shared_pfx(as_const_i32(sh.seq_prefix)[b], sh.max_prefix, Sk, a.Sq) + k_begin;
+        k_begin = (int)min(kb, (long long)Sk);
+      }
+    }
     if (len < 1 || len > a.Sk || k_begin >= Sk) {  // empty
       if (tid < a.R) {
-        const long long e = (((long long)b * a.Hkv + kvh) * a.R + tid) * a.splits + split;
+        const long long e = WS_ENTRY(((long long)b * a.Hkv + kvh) * a.R + tid);
         a.ws_m[e] = -INFINITY;
         a.ws_l[e] = 0.f;
       }
@@ -243,13 +308,25 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   const int k_end = min(Sk, k_begin + a.chunk);         // keys [k_begin, k_end) are this block's
   const int nt = (k_end - k_begin + kKV - 1) / kKV;
 
+#define CAUSAL (SH_PFX ? 0 : a.causal)  // SharedPrefix: the prefix lies below every row's causal limit
   const int wr0 = wave * kMfmaRows;                     // first packed row of the wave
   const bool wave_on = wr0 < R;                         // (a wave without rows still stages K / V and meets the barriers)
   const int pr = min(wr0 + r, R - 1);                   // rows >= R compute row R - 1 again and are not stored
-  const int qi = pr / a.G, h = kvh * a.G + pr % a.G;    // packed row = i * G + g
-  const int lim = a.causal ? qi + shift : Sk - 1;                                     // last key this lane's row attends
-  const int wave_max = a.causal ? min(wr0 + kMfmaRows - 1, R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
-  const int wave_min = a.causal ? wr0 / a.G + shift : Sk - 1;                         // every row of the wave attends keys <= this
+  const int sr = SH_PFX ? pr % a.R : pr;                // SharedPrefix: packed row = (j * Sq + i) * G + g, sr = the member's own row
+  const int qi = (SH_PFX ? sr : pr) / a.G, h = kvh * a.G + (SH_PFX ? sr : pr) % a.G;    // packed row = i * G + g
+  const int lim = CAUSAL ? qi + shift : Sk - 1;                                       // last key this lane's row attends
+  const int wave_max = CAUSAL ? min(wr0 + kMfmaRows - 1, R - 1) / a.G + shift : Sk - 1;    // .. any row of the wave
+  const int wave_min = CAUSAL ? wr0 / a.G + shift : Sk - 1;                         // every row of the wave attends keys <= this
+#undef CAUSAL
+  long long qb = b;      // the sequence of this lane's row
+  bool row_live = true;  // SharedPrefix: the row's member is a valid, active slot
+  if constexpr (SH_PFX) {
+    const int m = members[pr / a.R];  // pr / a.R < group_cap
+    long long len = 0;
+    if (m >= 0 && m < a.B) len = (long long)a.seqlens_k[m] + a.seqlen_offset;
+    row_live = len >= 1 && len <= a.Sk;
+    qb = min(max(m, 0), a.B - 1);  // clamped before it forms an address; a dead row is computed and not stored
+  }
   // Window (causal only): this lane's first key, and the first / last window start of the wave's rows
   int lo = 0, wave_lo = 0, wave_lo_max = 0;
   unsigned span = 0;  // lim - lo, the width of this lane's window
@@ -266,7 +343,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   // Q: the B operand of S^T = K Q^T, lane (r, hh) holds Q[row r][16 ks + 8 hh + 0..7]
   vec8 qf[KS];
   {
-    const uint16_t* qp = a.q + (long long)b * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
+    const uint16_t* qp = a.q + (SH_PFX ? qb : (long long)b) * a.q_bs + (long long)qi * a.q_rs + (long long)h * DH + 8 * hh;
     if constexpr (VARQ)  // the packed row of (b, qi), clamped into the tensor before it forms an address
       qp = a.q + min(max(row0 + qi, 0ll), (long long)varq_args(a).total_q - 1) * a.q_rs + (long long)h * DH + 8 * hh;
 #pragma unroll
@@ -337,7 +414,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 
   // Paged: the ids of tiles 0 and 1, both in flight before the first K / V load is issued
   const PageArgs pg = page_args(a);
-  const int* table = PAGED ? pg.block_table + (long long)b * pg.bt_rs : nullptr;
+  const int* table = PAGED ? pg.block_table + (long long)(SH_PFX ? tb : b) * pg.bt_rs : nullptr;
   int pg_i = 0, pg_ro = 0, pg_cur = 0, ro_cur = 0, pg_nxt = 0, ro_nxt = 0;
   auto next_page = [&]() {  // (pg_i, pg_ro) -> the tile 64 keys on; returns its page id
     pg_ro += kKV;
@@ -458,8 +535,9 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 
   // ---- the unnormalised partial; lane (r, hh) holds O[row r][32 db + 8 g4 + 4 hh + 0..3] in o[db][4 g4 + 0..3] ----
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  if (wr0 + r < R) {
-    const long long e = (((long long)b * a.Hkv + kvh) * a.R + pr) * a.splits + split;
+  if (wr0 + r < R && (!SH_PFX || row_live)) {
+    const long long e = WS_ENTRY(((SH_PFX ? qb : (long long)b) * a.Hkv + kvh) * a.R + (SH_PFX ? sr : pr));
+#undef WS_ENTRY
     float* op = a.ws_o + e * DH + 4 * hh;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
@@ -480,10 +558,15 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 // on its sequence and leaves if the split kernel did not take it or row >= R_b: such a workspace row was never written.  The result goes
 // to packed row cu[b] + row / G, guarded by row < min(cu[b + 1], total_q).  Window<VarQ<DevLen<..>>>: the same under the windowed rule; the
 // partials do not know where their split began.
+//
+// SharedCombine<DevLen<..>> (awq_shared.hpp): a.splits = splits_p + splits_s entries per row.  The thread forms P_b as the suffix block
+// did and runs the rule over entries 0 .. ceil(P_b / chunk_p) - 1 and splits_p .. a.splits - 1, ascending; the prefix entries between
+// belong to no key of this sequence, were never written for it, and are not read.
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(CombineArgsOf<DT> a) {
   constexpr int CPR = DH / 8;
   constexpr bool VARQ = IsVarQ<DT>::value;
+  constexpr bool SHARED = IsSharedCombine<DT>::value;
   const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long long)a.B * a.Hkv * a.R * CPR) return;
   const int ch = (int)(id % CPR);
@@ -506,14 +589,28 @@ __global__ __launch_bounds__(256) void attn_splitkv_combine_kernel(CombineArgsOf
     out_row = (long long)c0 + pr / a.G;
     if (out_row < 0 || out_row >= min((long long)c1, (long long)vq.total_q)) return;  // (a corrupt array: no address outside the tensor)
   }
+  // SharedCombine: entries [own_p, skip_to) are prefix splits behind this sequence's prefix -- never written for it, never read.  The
+  // loops below count the entries that ARE read, t -> s = t below own_p, t - own_p + skip_to behind it: no branch inside them, so the
+  // loads of the first loop pipeline as the dense form's do
+  int own_p = 0, skip_to = 0;
+  (void)own_p, (void)skip_to;
+  if constexpr (SHARED) {
+    const SharedArgs sh = shared_args(a);
+    const long long len = (long long)a.seqlens_k[b] + a.seqlen_offset;
+    const int p = len >= 1 && len <= a.Sk ? shared_pfx(as_const_i32(sh.seq_prefix)[b], sh.max_prefix, (int)len, a.Sq) : 0;
+    own_p = (p + sh.chunk_p - 1) / sh.chunk_p;  // <= splits_p: p <= max_prefix <= splits_p * chunk_p
+    skip_to = sh.splits_p;
+  }
   const float* pm = a.ws_m + row * a.splits;
   const float* pl = a.ws_l + row * a.splits;
   const float* po = a.ws_o + row * a.splits * DH + ch * 8;
+  const int n_read = SHARED ? own_p + a.splits - skip_to : a.splits;
   float M = -INFINITY;
-  for (int s = 0; s < a.splits; ++s) M = fmaxf(M, pm[s]);
+  for (int t = 0; t < n_read; ++t) M = fmaxf(M, pm[SHARED ? (t < own_p ? t : t - own_p + skip_to) : t]);
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float L = 0.f;
-  for (int s = 0; s < a.splits; ++s) {
+  for (int t = 0; t < n_read; ++t) {
+    const int s = SHARED ? (t < own_p ? t : t - own_p + skip_to) : t;
     const float m = pm[s];
     if (m == -INFINITY) continue;  // nothing attended in this split: contributes exactly nothing
     const float w = __builtin_amdgcn_exp2f(m - M);
@@ -625,9 +722,23 @@ size_t attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, in
   return attn_kvcache_workspace_bytes(batch, nheads, nheads_kv, head_dim, split_seqlen_q, window_plan_bound(split_seqlen_q, max_seqlen_k, window_left));
 }
 
+// Host plan of a shared-prefix decode (awq_shared.hpp): attn_kvcache_plan's rule twice, for the bound max_prefix of the prefix walk and
+// for max_seqlen_k of the suffix walk (a suffix is as long as max_seqlen_k when a sequence shares nothing).  The knob forces both chunks.
+// Nothing here is tuned to a measurement of the shared call.  Host arguments only.
+int attn_kvcache_shared_plan(int batch, int nheads_kv, int max_prefix, int max_seqlen_k, int* splits_p, int* chunk_p, int* splits_s, int* chunk_s) {
+  attn_kvcache_plan(batch, nheads_kv, max_prefix, splits_p, chunk_p);
+  return attn_kvcache_plan(batch, nheads_kv, max_seqlen_k, splits_s, chunk_s);
+}
+
+size_t attn_kvcache_shared_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix, int max_seqlen_k) {
+  int sp = 1, cp = 0, ss = 1, cs = 0;
+  attn_kvcache_shared_plan(batch, nheads_kv, max_prefix, max_seqlen_k, &sp, &cp, &ss, &cs);
+  return (size_t)batch * nheads * seqlen_q * ((size_t)sp + ss) * (head_dim + 2) * sizeof(float);
+}
+
 namespace {
 
-// Both launches of one call.  K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
+// Both launches of one call. K is the traits of the split kernel (DT, or Kv8<DT> for the FP8 cache); the combine launch reads fp32
 // partials only, so it is the T cache's in either case.
 // L is the identity for host lengths, DevLen for lengths on the device and PagedDevLen for those over a pool of pages; C is what L is to
 // the combine launch (the paged form combines with the dense DevLen kernel: the partials do not know where K / V came from).
@@ -704,6 +815,70 @@ int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, 
   } else if (kv.block_table) launch_for_cache<PagedDevLen, DevLen>(paged, c.Dh, c.dtype, st);
   else if (c.seqlens_k) launch_for_cache<DevLen, DevLen>(dense, c.Dh, c.dtype, st);
   else launch_for_cache<HostLen, HostLen>(dense, c.Dh, c.dtype, st);
+  return 0;
+}
+
+namespace {
+
+template <template <typename> class K>
+void launch_shared(const SharedSplitArgs& a, int splits_s, int chunk_s, int Dh, int dtype, hipStream_t st) {
+  const SharedArgs& sh = a.sh;
+  SharedSplitArgs pfx = a, sfx = a, cmb = a;
+  pfx.splits = sh.splits_p, pfx.chunk = sh.chunk_p, pfx.sh.ws_first = 0;
+  sfx.splits = splits_s, sfx.chunk = chunk_s, sfx.sh.ws_first = sh.splits_p;
+  cmb.splits = sh.ws_splits;
+  const dim3 pgrid((unsigned)((long long)sh.num_groups * a.Hkv * sh.splits_p));
+  const dim3 sgrid((unsigned)((long long)a.B * a.Hkv * splits_s));
+  const dim3 cgrid((unsigned)(((long long)a.B * a.Hkv * a.R * (Dh / 8) + 255) / 256));
+  for_dtype_dh<F16, BF16>(dtype, Dh, [&](auto dt, auto dh) {
+    using DT = decltype(dt);
+    constexpr int DH = decltype(dh)::value;
+    hipLaunchKernelGGL((attn_splitkv_kernel<SharedPrefixPagedDevLen<K<DT>>, DH>), pgrid, dim3(kNW * 64), 0, st, pfx);
+    hipLaunchKernelGGL((attn_splitkv_kernel<SharedSuffixPagedDevLen<K<DT>>, DH>), sgrid, dim3(kNW * 64), 0, st, sfx);
+    hipLaunchKernelGGL((attn_splitkv_combine_kernel<SharedCombineDevLen<DT>, DH>), cgrid, dim3(256), 0, st, cmb);
+  });
+}
+
+}  // namespace
+
+// The three launches of awq_attn_kvcache_paged_shared[_kv8] (awq_shared.hpp).  The set of launches and their grids come from host
+// arguments only; which blocks do work is decided on the device, so a captured call follows the lengths, tables and group arrays in place.
+int launch_kv_attn_shared(const KvAttnCall& c, const KvSharedCall& s, void* workspace, hipStream_t st) {
+  const KvView& kv = c.kv;
+  int splits_p = 1, chunk_p = 0, splits_s = 1, chunk_s = 0;
+  attn_kvcache_shared_plan(c.B, c.Hkv, s.max_prefix, c.max_seqlen_k, &splits_p, &chunk_p, &splits_s, &chunk_s);
+  SharedSplitArgs a;
+  a.q = (const uint16_t*)c.q;
+  a.k = (const uint16_t*)kv.k;
+  a.v = (const uint16_t*)kv.v;
+  a.out = (uint16_t*)c.out;
+  a.q_bs = c.q_bs, a.q_rs = c.q_rs;
+  a.k_bs = kv.k_os, a.k_rs = kv.k_rs, a.v_bs = kv.v_os, a.v_rs = kv.v_rs;
+  a.B = c.B;
+  a.Sq = c.Sq;
+  a.Sk = c.max_seqlen_k;
+  a.H = c.H;
+  a.Hkv = c.Hkv;
+  a.G = c.H / c.Hkv;
+  a.R = a.Sq * a.G;
+  a.splits = splits_p + splits_s;
+  a.chunk = chunk_s;
+  a.causal = c.causal ? 1 : 0;
+  a.scale_log2e = c.scale * 1.4426950408889634f;
+  const long long n = (long long)c.B * c.Hkv * a.R * a.splits;
+  a.ws_o = (float*)workspace;
+  a.ws_m = a.ws_o + n * c.Dh;
+  a.ws_l = a.ws_m + n;
+  a.k_scale = kv.k_scale;
+  a.v_scale = kv.v_scale;
+  a.ks_bs = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_bs = kv.vs_os, a.vs_rs = kv.vs_rs;
+  a.seqlens_k = c.seqlens_k;
+  a.seqlen_offset = c.seqlen_offset;
+  a.pg = PageArgs{kv.block_table, kv.bt_rs, kv.rows, kv.outer};
+  a.sh = SharedArgs{s.group_members, s.members_row_stride, s.group_prefix, s.seq_prefix, s.num_groups, s.group_cap, s.max_prefix,
+                    splits_p, chunk_p, splits_p + splits_s, 0};
+  if (kv.k_scale) launch_shared<Kv8>(a, splits_s, chunk_s, c.Dh, c.dtype, st);
+  else launch_shared<TCache>(a, splits_s, chunk_s, c.Dh, c.dtype, st);
   return 0;
 }
 

@@ -751,6 +751,111 @@ int awq_attn_kvcache_paged_kv8(const void* q, const void* k_pool, const void* v_
                  KV_FP8 | KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
 }
 
+// ---- shared-prefix decode on the paged cache (awq_shared.hpp): attn_kvcache_paged's phases with the group arrays' terms in each ----
+using awq::KvSharedCall;
+
+static bool shared_shape_ok(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix, int max_seqlen_k) {
+  return kvcache_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_seqlen_k) && max_prefix >= 64 && (max_prefix % 64) == 0 &&
+         max_prefix <= max_seqlen_k;
+}
+
+int awq_attn_kvcache_shared_plan(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix, int max_seqlen_k,
+                                 int* splits_p, int* chunk_p, int* splits_s, int* chunk_s) {
+  if (!splits_p || !chunk_p || !splits_s || !chunk_s) return AWQ_ERR_NULL;
+  if (!shared_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_prefix, max_seqlen_k)) return AWQ_ERR_SHAPE;
+  return awq::attn_kvcache_shared_plan(batch, nheads_kv, max_prefix, max_seqlen_k, splits_p, chunk_p, splits_s, chunk_s);
+}
+
+size_t awq_attn_kvcache_shared_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix,
+                                               int max_seqlen_k) {
+  if (!shared_shape_ok(batch, nheads, nheads_kv, head_dim, seqlen_q, max_prefix, max_seqlen_k)) return 0;
+  return awq::attn_kvcache_shared_workspace_bytes(batch, nheads, nheads_kv, head_dim, seqlen_q, max_prefix, max_seqlen_k);
+}
+
+static int kv_attn_shared(const KvAttnCall& c, const KvSharedCall& s, int fmt, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView& kv = c.kv;
+  if (!s.group_members || !s.group_prefix || !s.seq_prefix) return AWQ_ERR_NULL;
+  const int rc = kv_attn_check(c, fmt);
+  if (rc != AWQ_OK) return rc;
+  // (every row of a group shares one MFMA tile: group_cap * Sq * G <= 128; kv_attn_check has made H / Hkv safe)
+  if (s.num_groups < 1 || s.group_cap < 1 || s.members_row_stride < s.group_cap || (long long)s.group_cap * c.Sq * (c.H / c.Hkv) > 128 ||
+      s.max_prefix < 64 || (s.max_prefix % 64) != 0 || s.max_prefix > c.max_seqlen_k || c.max_seqlen_k > kv.capacity() || c.seqlen_offset < 0)
+    return AWQ_ERR_SHAPE;
+  if (!aligned4(c.seqlens_k) || !aligned4(s.group_members) || !aligned4(s.group_prefix) || !aligned4(s.seq_prefix)) return AWQ_ERR_ALIGN;
+  int splits_p = 1, chunk_p = 0, splits_s = 1, chunk_s = 0;
+  awq::attn_kvcache_shared_plan(c.B, c.Hkv, s.max_prefix, c.max_seqlen_k, &splits_p, &chunk_p, &splits_s, &chunk_s);
+  const size_t need = awq::attn_kvcache_shared_workspace_bytes(c.B, c.H, c.Hkv, c.Dh, c.Sq, s.max_prefix, c.max_seqlen_k);
+  if (!workspace || workspace_bytes < need) return AWQ_ERR_WORKSPACE;
+  if (!aligned16(workspace)) return AWQ_ERR_ALIGN;
+  if ((long long)c.B * c.Hkv * splits_s > 0x7FFFFFFFll || (long long)s.num_groups * c.Hkv * splits_p > 0x7FFFFFFFll) return AWQ_ERR_SHAPE;
+  awq::launch_kv_attn_shared(c, s, workspace, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_attn_kvcache_paged_shared(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                                  int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k, int num_pages, int page_size,
+                                  int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                  long long q_batch_stride, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                                  long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype,
+                                  const int* group_members, const int* group_prefix, const int* seq_prefix, int num_groups, int group_cap,
+                                  long long members_row_stride, int max_prefix, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  KvSharedCall s;
+  s.group_members = group_members, s.group_prefix = group_prefix, s.seq_prefix = seq_prefix, s.members_row_stride = members_row_stride;
+  s.num_groups = num_groups, s.group_cap = group_cap, s.max_prefix = max_prefix;
+  return kv_attn_shared({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                         q_row_stride, softmax_scale, causal, dtype},
+                        s, KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
+}
+
+int awq_attn_kvcache_paged_shared_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                      const int* block_table, int batch, int seqlen_q, const int* seqlens_k, int seqlen_offset, int max_seqlen_k,
+                                      int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv,
+                                      int head_dim, long long q_batch_stride, long long q_row_stride, long long k_page_stride,
+                                      long long k_row_stride, long long v_page_stride, long long v_row_stride, long long k_scale_page_stride,
+                                      long long k_scale_row_stride, long long v_scale_page_stride, long long v_scale_row_stride,
+                                      float softmax_scale, int causal, int dtype, const int* group_members, const int* group_prefix,
+                                      const int* seq_prefix, int num_groups, int group_cap, long long members_row_stride, int max_prefix,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  KvSharedCall s;
+  s.group_members = group_members, s.group_prefix = group_prefix, s.seq_prefix = seq_prefix, s.members_row_stride = members_row_stride;
+  s.num_groups = num_groups, s.group_cap = group_cap, s.max_prefix = max_prefix;
+  return kv_attn_shared({q, out, kv, 0, seqlens_k, seqlen_offset, max_seqlen_k, batch, seqlen_q, nheads, nheads_kv, head_dim, q_batch_stride,
+                         q_row_stride, softmax_scale, causal, dtype},
+                        s, KV_FP8 | KV_PAGED | KV_DEVLEN, workspace, workspace_bytes, stream);
+}
+
+// the copy-on-write of a fork's tail page: n (src, dst) pairs of pages of the pools, K and V rows (and the scales of FP8 pools)
+static int kv_page_copy(const KvView& kv, int fmt, const int* src_pages, const int* dst_pages, int n, int nheads_kv, int head_dim, void* stream) {
+  if (!kv.k || !kv.v || ((fmt & KV_FP8) && (!kv.k_scale || !kv.v_scale)) || !src_pages || !dst_pages) return AWQ_ERR_NULL;
+  if (n < 1 || nheads_kv < 1 || (head_dim != 64 && head_dim != 128) || kv.outer < 1 || kv.rows < 64 || (kv.rows % 64) != 0 ||
+      !kv_shape_ok(kv, fmt & KV_FP8, true, nheads_kv, head_dim) ||
+      ((long long)n * kv.rows * (nheads_kv * head_dim / 8) + 255) / 256 > 0x7FFFFFFFll)
+    return AWQ_ERR_SHAPE;
+  if (!kv_aligned(kv, fmt & KV_FP8, true) || !aligned4(src_pages) || !aligned4(dst_pages)) return AWQ_ERR_ALIGN;
+  awq::launch_kv_page_copy({kv, src_pages, dst_pages, n, nheads_kv, head_dim}, (hipStream_t)stream);
+  return finish_launch();
+}
+
+int awq_kv_page_copy(void* k_pool, void* v_pool, const int* src_pages, const int* dst_pages, int n, int num_pages, int page_size, int nheads_kv,
+                     int head_dim, long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride, void* stream) {
+  return kv_page_copy(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride), 0, src_pages,
+                      dst_pages, n, nheads_kv, head_dim, stream);
+}
+
+int awq_kv_page_copy_fp8(void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* src_pages, const int* dst_pages, int n,
+                         int num_pages, int page_size, int nheads_kv, int head_dim, long long k_page_stride, long long k_row_stride,
+                         long long v_page_stride, long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                         long long v_scale_page_stride, long long v_scale_row_stride, void* stream) {
+  return kv_page_copy(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride), k_scale,
+                                  v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                      KV_FP8, src_pages, dst_pages, n, nheads_kv, head_dim, stream);
+}
+
 int awq_attn_prefill_kvcache(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, int seqlen_q, const int* seqlens_k,
                              int seqlen_offset, int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_batch_stride,
                              long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,

@@ -259,6 +259,9 @@ size_t attn_kvcache_workspace_bytes(int batch, int nheads, int nheads_kv, int he
 // the plan of a windowed mixed step (awq_window.hpp): attn_kvcache_plan for the bound min(max_seqlen_k, window_left + split_seqlen_q + 63)
 int attn_varq_window_plan(int batch, int nheads_kv, int split_seqlen_q, int max_seqlen_k, int window_left, int* splits, int* chunk);
 size_t attn_varq_window_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int split_seqlen_q, int max_seqlen_k, int window_left);
+// the plan of a shared-prefix decode (awq_shared.hpp): attn_kvcache_plan for the bound max_prefix, and again for max_seqlen_k
+int attn_kvcache_shared_plan(int batch, int nheads_kv, int max_prefix, int max_seqlen_k, int* splits_p, int* chunk_p, int* splits_s, int* chunk_s);
+size_t attn_kvcache_shared_workspace_bytes(int batch, int nheads, int nheads_kv, int head_dim, int seqlen_q, int max_prefix, int max_seqlen_k);
 int launch_rope_with_pos(const void* in, const float* freqs, void* out, int n0, int n1, int h, int d, int d2, long long s0, long long s1,
                          long long sh, long long o0, long long o1, long long oh, int dtype, hipStream_t st);
 int launch_rope_neox(const long long* positions, void* query, void* key, const void* cache, int tokens, int heads, int head_size, int rot_dim,

@@ -72,6 +72,23 @@ struct KvAttnCall {
   int window_left = -1;
 };
 
+// what awq_attn_kvcache_paged_shared[_kv8] takes beside attn_kvcache_paged's KvAttnCall (awq_shared.hpp)
+struct KvSharedCall {
+  const int* group_members = nullptr;  // device int32 [num_groups, group_cap], -1 padding
+  const int* group_prefix = nullptr;   // device int32 [num_groups]
+  const int* seq_prefix = nullptr;     // device int32 [B]
+  long long members_row_stride = 0;
+  int num_groups = 0, group_cap = 0, max_prefix = 0;
+};
+
+// awq_kv_page_copy[_fp8]: n (src, dst) page pairs of the pools in v (awq_paged.hpp), rows of Hkv * Dh elements or codes
+struct KvPageCopyCall {
+  KvView kv;  // the pools; k / v are written
+  const int* src_pages;
+  const int* dst_pages;
+  int n, Hkv, Dh;
+};
+
 // Arguments validated by the caller.  awq_attn_chunk_cdna4.hip serves the T cache and hands a view with scales to
 // awq_attn_kv8_cdna4.hip: each file keeps its own kernel and argument struct; the form and the grid come from awq_kvstore.hpp.  With
 // cu_seqlens_q set, the packed-token store (awq_varq.hpp): device positions, dense or paged.
@@ -81,6 +98,11 @@ int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st);
 // cu_seqlens_q set and split_seqlen_q > 0, the packed forms of the pair: only the sequences the rule hands to them are touched, and the
 // workspace has split_seqlen_q rows per (sequence, query head)
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st);
+// the three launches of a shared-prefix decode (awq_shared.hpp): prefix blocks, suffix blocks, combine; the plan is
+// attn_kvcache_shared_plan's and the workspace has its size
+int launch_kv_attn_shared(const KvAttnCall& c, const KvSharedCall& s, void* workspace, hipStream_t st);
+// one launch: the K and V rows (and the scales of an FP8 pool) of n pages, 16 bytes per move
+int launch_kv_page_copy(const KvPageCopyCall& c, hipStream_t st);
 // the one-pass prefill kernel under device lengths, dense or paged (awq_attn_prefill_cdna4.hip): any seqlen_q, no workspace; with
 // cu_seqlens_q set, its packed-query form; with split_seqlen_q > 0 the form that leaves the split pair's sequences alone
 int launch_kv_prefill(const KvAttnCall& c, hipStream_t st);

@@ -1598,6 +1598,124 @@ torch::Tensor attn_kvcache_paged_kv8(const torch::Tensor q, const torch::Tensor 
                            softmax_scale, causal);
 }
 
+// attn_kvcache_paged_shared[_kv8](q, pools .., block_table, seqlens_k, max_seqlen_k, group_members, group_prefix, seq_prefix, max_prefix,
+// seqlen_offset, softmax_scale, causal) -> out: attn_kvcache_paged for a batch whose groups read their common prefix once (csrc/awq_shared.hpp).
+static torch::Tensor attn_shared_impl(const char* who, const torch::Tensor& q, const KvTensors& kv, const torch::Tensor& seqlens_k,
+                                      int64_t max_seqlen_k, const torch::Tensor& group_members, const torch::Tensor& group_prefix,
+                                      const torch::Tensor& seq_prefix, int64_t max_prefix, int64_t seqlen_offset, double softmax_scale, bool causal) {
+  const bool fp8 = kv.k_scale != nullptr;
+  TORCH_CHECK(q.is_cuda(), who, ": q must live on the GPU");
+  TORCH_CHECK(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, who, ": float16 / bfloat16 only, got ", q.scalar_type());
+  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3), who, ": q [B, Sq, H, Dh] with contiguous heads is expected");
+  const int64_t batch = q.size(0), sq = q.size(1), nheads = q.size(2), headdim = q.size(3);
+  TORCH_CHECK(headdim == 64 || headdim == 128, who, ": head dim ", headdim, " is not supported (supported head dims: 64, 128)");
+  check_kv(who, kv, q, "q", batch, /*contiguous=*/false);
+  const torch::Tensor &k = kv.k, &v = kv.v, &bt = *kv.block_table;
+  const int64_t pages = k.size(0), page = k.size(1), nheads_kv = k.size(2), cap = bt.size(1) * page;
+  TORCH_CHECK(k.size(3) == headdim, who, ": k_pool / v_pool must be [num_pages, page_size, Hkv, ", headdim, "]");
+  TORCH_CHECK(batch >= 1 && sq >= 1 && nheads_kv >= 1 && nheads % nheads_kv == 0, who,
+              ": empty tensors are not supported and H must be a multiple of Hkv");
+  TORCH_CHECK(max_seqlen_k >= 1 && max_seqlen_k <= cap, who, ": max_seqlen_k ", max_seqlen_k, " must lie in 1 .. ", cap, " (pages_per_seq * page_size)");
+  TORCH_CHECK(seqlen_offset >= 0, who, ": seqlen_offset must not be negative");
+  check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
+  check_seqlens(who, "seq_prefix", seq_prefix, q, batch);
+  TORCH_CHECK(group_members.is_cuda() && group_members.device() == q.device() && group_members.scalar_type() == at::kInt && group_members.dim() == 2 &&
+                  group_members.size(0) >= 1 && group_members.size(1) >= 1 && group_members.stride(1) == 1 &&
+                  group_members.stride(0) >= group_members.size(1),
+              who, ": group_members must be an int32 [num_groups, group_cap] tensor with a unit last stride on the GPU of q");
+  const int64_t groups = group_members.size(0), gcap = group_members.size(1);
+  TORCH_CHECK(group_prefix.is_cuda() && group_prefix.device() == q.device() && group_prefix.scalar_type() == at::kInt && group_prefix.dim() == 1 &&
+                  group_prefix.size(0) == groups && group_prefix.is_contiguous(),
+              who, ": group_prefix must be a contiguous int32 [num_groups] tensor on the GPU of q");
+  TORCH_CHECK(gcap * sq * (nheads / nheads_kv) <= 128, who, ": group_cap * seqlen_q * (H / Hkv) = ", gcap * sq * (nheads / nheads_kv),
+              " exceeds 128 (the rows of a group share one MFMA tile; list a wider group as several groups of the same prefix)");
+  TORCH_CHECK(max_prefix >= 64 && max_prefix % 64 == 0 && max_prefix <= max_seqlen_k, who, ": max_prefix ", max_prefix,
+              " must be a multiple of 64 in 64 .. max_seqlen_k = ", max_seqlen_k);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  at::Tensor out = torch::empty({batch, sq, nheads, headdim}, q.options().memory_format(at::MemoryFormat::Contiguous));
+  const size_t wsb = awq_attn_kvcache_shared_workspace_bytes((int)batch, (int)nheads, (int)nheads_kv, (int)headdim, (int)sq, (int)max_prefix,
+                                                             (int)max_seqlen_k);
+  at::Tensor ws = torch::empty({(int64_t)wsb}, q.options().dtype(at::kByte));  // caching allocator: capturable
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int B = (int)batch, Sq = (int)sq, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim;
+  if (fp8)
+    raise_on(awq_attn_kvcache_paged_shared_kv8(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), kv.k_scale->data_ptr<float>(), kv.v_scale->data_ptr<float>(), out.data_ptr(), bt.data_ptr<int>(), B,
+        Sq, seqlens_k.data_ptr<int>(), (int)seqlen_offset, (int)max_seqlen_k, (int)pages, (int)page, (int)bt.size(1), bt.stride(0), H, Hkv, Dh,
+        q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), kv.k_scale->stride(0), kv.k_scale->stride(1),
+        kv.v_scale->stride(0), kv.v_scale->stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q), group_members.data_ptr<int>(),
+        group_prefix.data_ptr<int>(), seq_prefix.data_ptr<int>(), (int)groups, (int)gcap, group_members.stride(0), (int)max_prefix, ws.data_ptr(),
+        wsb, st));
+  else
+    raise_on(awq_attn_kvcache_paged_shared(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), bt.data_ptr<int>(), B, Sq, seqlens_k.data_ptr<int>(), (int)seqlen_offset,
+        (int)max_seqlen_k, (int)pages, (int)page, (int)bt.size(1), bt.stride(0), H, Hkv, Dh, q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+        v.stride(0), v.stride(1), (float)softmax_scale, causal ? 1 : 0, dtype_code(q), group_members.data_ptr<int>(), group_prefix.data_ptr<int>(),
+        seq_prefix.data_ptr<int>(), (int)groups, (int)gcap, group_members.stride(0), (int)max_prefix, ws.data_ptr(), wsb, st));
+  return out;
+}
+
+torch::Tensor attn_kvcache_paged_shared(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                        const torch::Tensor seqlens_k, int64_t max_seqlen_k, const torch::Tensor group_members,
+                                        const torch::Tensor group_prefix, const torch::Tensor seq_prefix, int64_t max_prefix, int64_t seqlen_offset,
+                                        double softmax_scale, bool causal) {
+  return attn_shared_impl("attn_kvcache_paged_shared", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, group_members,
+                          group_prefix, seq_prefix, max_prefix, seqlen_offset, softmax_scale, causal);
+}
+
+torch::Tensor attn_kvcache_paged_shared_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                            const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor seqlens_k,
+                                            int64_t max_seqlen_k, const torch::Tensor group_members, const torch::Tensor group_prefix,
+                                            const torch::Tensor seq_prefix, int64_t max_prefix, int64_t seqlen_offset, double softmax_scale,
+                                            bool causal) {
+  return attn_shared_impl("attn_kvcache_paged_shared_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k,
+                          group_members, group_prefix, seq_prefix, max_prefix, seqlen_offset, softmax_scale, causal);
+}
+
+// kv_page_copy[_fp8](pools .., src_pages, dst_pages): page dst_pages[i] := page src_pages[i], one launch (the tail page of PageTable.fork)
+static void kv_page_copy_impl(const char* who, torch::Tensor& k_pool, torch::Tensor& v_pool, torch::Tensor* k_scale, torch::Tensor* v_scale,
+                              const torch::Tensor& src_pages, const torch::Tensor& dst_pages) {
+  const bool fp8 = k_scale != nullptr;
+  TORCH_CHECK(k_pool.is_cuda() && v_pool.is_cuda() && v_pool.device() == k_pool.device(), who, ": the pools must live on one GPU");
+  TORCH_CHECK(k_pool.scalar_type() == v_pool.scalar_type() && k_pool.sizes() == v_pool.sizes() && k_pool.dim() == 4, who,
+              ": k_pool and v_pool must have one shape [num_pages, page_size, Hkv, Dh] and one dtype");
+  TORCH_CHECK(fp8 ? k_pool.element_size() == 1 : (k_pool.scalar_type() == at::kHalf || k_pool.scalar_type() == at::kBFloat16), who,
+              ": float16 / bfloat16 pools, or one-byte FP8 codes with their scales, are expected");
+  for (const torch::Tensor* t : {&k_pool, &v_pool})
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(2) == t->size(3), who, ": the pools must have contiguous heads");
+  const int64_t pages = k_pool.size(0), page = k_pool.size(1), nheads_kv = k_pool.size(2), headdim = k_pool.size(3);
+  TORCH_CHECK((headdim == 64 || headdim == 128) && page >= 64 && page % 64 == 0, who, ": head dim 64 / 128 and a page_size that is a multiple of 64");
+  if (fp8)
+    for (const torch::Tensor* t : {k_scale, v_scale})
+      TORCH_CHECK(t->is_cuda() && t->device() == k_pool.device() && t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == pages &&
+                      t->size(1) == page && t->size(2) == nheads_kv && t->stride(2) == 1,
+                  who, ": the scale pools must be float32 [num_pages, page_size, Hkv] with a unit last stride on the GPU of the pools");
+  for (const torch::Tensor* t : {&src_pages, &dst_pages})
+    TORCH_CHECK(t->is_cuda() && t->device() == k_pool.device() && t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == src_pages.size(0) &&
+                    t->size(0) >= 1 && t->is_contiguous(),
+                who, ": src_pages and dst_pages must be contiguous int32 [n >= 1] tensors on the GPU of the pools");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k_pool.device());
+  void* st = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int n = (int)src_pages.size(0);
+  if (fp8)
+    raise_on(awq_kv_page_copy_fp8(k_pool.data_ptr(), v_pool.data_ptr(), k_scale->data_ptr<float>(), v_scale->data_ptr<float>(),
+                                  src_pages.data_ptr<int>(), dst_pages.data_ptr<int>(), n, (int)pages, (int)page, (int)nheads_kv, (int)headdim,
+                                  k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1), k_scale->stride(0), k_scale->stride(1),
+                                  v_scale->stride(0), v_scale->stride(1), st));
+  else
+    raise_on(awq_kv_page_copy(k_pool.data_ptr(), v_pool.data_ptr(), src_pages.data_ptr<int>(), dst_pages.data_ptr<int>(), n, (int)pages, (int)page,
+                              (int)nheads_kv, (int)headdim, k_pool.stride(0), k_pool.stride(1), v_pool.stride(0), v_pool.stride(1), st));
+}
+
+void kv_page_copy(torch::Tensor k_pool, torch::Tensor v_pool, const torch::Tensor src_pages, const torch::Tensor dst_pages) {
+  kv_page_copy_impl("kv_page_copy", k_pool, v_pool, nullptr, nullptr, src_pages, dst_pages);
+}
+
+void kv_page_copy_fp8(torch::Tensor k_pool, torch::Tensor v_pool, torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor src_pages,
+                      const torch::Tensor dst_pages) {
+  kv_page_copy_impl("kv_page_copy_fp8", k_pool, v_pool, &k_scale, &v_scale, src_pages, dst_pages);
+}
+
 // attn_prefill_kvcache[_kv8] / attn_prefill_paged[_kv8]: the arguments of their attn_kvcache* neighbours, served by the one-pass prefill
 // kernel (csrc/awq_attn_prefill_cdna4.hip) for a prompt chunk of any length.
 torch::Tensor attn_prefill_kvcache(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor seqlens_k,
@@ -2210,6 +2328,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_kvcache_paged_kv8", &attn_kvcache_paged_kv8, "attn_kvcache_paged on FP8 pools with per-(key, KV head) fp32 scale pools",
         py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
         py::arg("max_seqlen_k"), py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_kvcache_paged_shared", &attn_kvcache_paged_shared,
+        "attn_kvcache_paged for groups of sequences that share a prefix: the prefix keys are fetched once per group",
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("group_members"), py::arg("group_prefix"), py::arg("seq_prefix"), py::arg("max_prefix"), py::arg("seqlen_offset"),
+        py::arg("softmax_scale"), py::arg("causal"));
+  m.def("attn_kvcache_paged_shared_kv8", &attn_kvcache_paged_shared_kv8, "attn_kvcache_paged_shared on FP8 pools with fp32 scale pools",
+        py::arg("q"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("group_members"), py::arg("group_prefix"), py::arg("seq_prefix"), py::arg("max_prefix"),
+        py::arg("seqlen_offset"), py::arg("softmax_scale"), py::arg("causal"));
+  m.def("kv_page_copy", &kv_page_copy, "Copy pages of a paged KV cache inside the pools: page dst_pages[i] := page src_pages[i]", py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("src_pages"), py::arg("dst_pages"));
+  m.def("kv_page_copy_fp8", &kv_page_copy_fp8, "kv_page_copy on FP8 pools and their scale pools", py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("src_pages"), py::arg("dst_pages"));
   m.def("attn_prefill_kvcache", &attn_prefill_kvcache,
         "The one-pass prefill kernel over natural-layout caches with per-sequence lengths read on the device: a prompt chunk of any length",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("seqlen_offset"),

@@ -35,6 +35,9 @@ With `block_table=` and `page_size=` (and a tensor `start_pos`) the module's cac
 max_batch_size * kv_max_seq_len / page_size pages -- a view, nothing is copied or allocated -- through the per-sequence block table
 (`rope_kv_store_paged_pos[_fp8]`, `attn_kvcache_paged[_kv8]`; `llm_awq_amd.paged_kv.PageTable` hands the pages out): a sequence holds the
 pages its tokens need, not kv_max_seq_len rows, and one sequence may grow past kv_max_seq_len while others are short.
+`forward_shared(x, start_pos, freqs, block_table, page_size, prefix_groups)` is that call for sequences that share a prompt
+(`PageTable.fork`, `llm_awq_amd.paged_kv.PrefixGroups`): the decode attention is `attn_kvcache_paged_shared[_kv8]` (csrc/awq_shared.hpp),
+which fetches the pages below a group's prefix once for the group.
 
 Under a tensor `start_pos` a chunk of ANY length is served, with and without pages, T and FP8: up to seqlen * (H / Hkv) = 128 query rows per
 KV head the attention is the split-KV pair above; a longer chunk -- a prompt -- goes to the one-pass prefill kernel under the same device
@@ -329,7 +332,21 @@ class QuantLlamaAttentionFused(nn.Module):
             output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, True, scale, True)
         return self.o_proj(output.view(1, total, -1))
 
-    def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None):
+    @torch.no_grad()
+    def forward_shared(self, x, start_pos, freqs, block_table, page_size, prefix_groups, decode_max_seqlen=None):
+        """The paged `forward` (tensor `start_pos`, `block_table`, `page_size`) for a batch whose sequences share prefixes:
+        `prefix_groups` is a `llm_awq_amd.paged_kv.PrefixGroups` over the slots of `start_pos`.  The store is `forward`'s -- new tokens land
+        at positions >= the prefix, in a member's own pages -- and, while seqlen * (H / Hkv) * group_cap <= 128, the attention is
+        attn_kvcache_paged_shared[_kv8] (csrc/awq_shared.hpp): the pages below a group's prefix are fetched once for the group.  A longer
+        chunk, or `prefix_groups=None`, is `forward` itself, bit for bit.  (A method of its own: `forward` keeps its signature.)"""
+        self._check_paged(start_pos, block_table, page_size)
+        if self.sliding_window is not None:
+            raise NotImplementedError("QuantLlamaAttentionFused: forward_shared is not implemented with sliding_window")
+        if prefix_groups is not None and prefix_groups.seq_prefix.shape[0] < x.shape[0]:
+            raise ValueError(f"QuantLlamaAttentionFused: prefix_groups covers {prefix_groups.seq_prefix.shape[0]} slots, the batch has {x.shape[0]}")
+        return self._forward_device_pos(load_engine(), x, start_pos, freqs, decode_max_seqlen, block_table, page_size, prefix_groups)
+
+    def _forward_device_pos(self, eng, x, start_pos, freqs, decode_max_seqlen, block_table=None, page_size=None, prefix_groups=None):
         """rope_kv_store_natural_pos[_fp8] followed by attn_kvcache[_kv8] with seqlen_offset = seqlen: no length reaches the host.  With a
         block table: rope_kv_store_paged_pos[_fp8] followed by attn_kvcache_paged[_kv8] on the caches viewed as pages.  A chunk with
         seqlen * num_key_value_groups > 128 is beyond the split pair: attn_prefill_kvcache[_kv8] / attn_prefill_paged[_kv8] take its place
@@ -354,16 +371,20 @@ class QuantLlamaAttentionFused(nn.Module):
             pool = (-1, ps, self.num_key_value_heads, self.head_dim)
             if decode_max_seqlen is None:
                 bound = block_table.shape[1] * ps
+            shared = ()  # the group arrays and their bound, when the shared-prefix call serves
+            if prefix_groups is not None and seqlen * self.num_key_value_groups * prefix_groups.group_cap <= 128:
+                g = prefix_groups
+                shared = (g.group_members, g.group_prefix, g.seq_prefix[:bsz], min(g.max_prefix, bound // 64 * 64))
             if self.kv_dtype == "fp8":
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool), self.cache_k_scale.view(pool[:3]), self.cache_v_scale.view(pool[:3]))
                 xq = eng.rope_kv_store_paged_pos_fp8(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
-                attn = eng.attn_prefill_paged_kv8 if prompt else eng.attn_kvcache_paged_kv8
-                output = attn(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+                attn = eng.attn_prefill_paged_kv8 if prompt else eng.attn_kvcache_paged_shared_kv8 if shared else eng.attn_kvcache_paged_kv8
+                output = attn(xq, *pools, block_table, start_pos, bound, *shared, seqlen, scale, True)
             else:
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool))
                 xq = eng.rope_kv_store_paged_pos(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
-                attn = eng.attn_prefill_paged if prompt else eng.attn_kvcache_paged
-                output = attn(xq, *pools, block_table, start_pos, bound, seqlen, scale, True)
+                attn = eng.attn_prefill_paged if prompt else eng.attn_kvcache_paged_shared if shared else eng.attn_kvcache_paged
+                output = attn(xq, *pools, block_table, start_pos, bound, *shared, seqlen, scale, True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if self.kv_dtype == "fp8":
             xq = eng.rope_kv_store_natural_pos_fp8(xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos,

@@ -1578,6 +1578,99 @@ def _attn_paged(who, one_pass, q, k_pool, v_pool, block_table, seqlens_k, max_se
     return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass)
 
 
+# ---- shared-prefix decode: the sequences of a group read their common prefix once (csrc/awq_shared.hpp) -------------------------------
+def attn_kvcache_shared_plan(batch: int, nheads: int, nheads_kv: int, head_dim: int, seqlen_q: int, max_prefix: int, max_seqlen_k: int):
+    """Host-side awq_attn_kvcache_shared_plan: (splits_p, chunk_p, splits_s, chunk_s) of attn_kvcache_paged_shared (no GPU needed) --
+    `attn_kvcache_plan`'s rule for the bound max_prefix of the prefix walk and again for max_seqlen_k of the suffix walk.  The knob
+    attn_splitkv_chunk forces both chunks."""
+    import ctypes
+
+    v = [ctypes.c_int(0) for _ in range(4)]
+    _capi.check(_capi.lib().awq_attn_kvcache_shared_plan(batch, nheads, nheads_kv, head_dim, seqlen_q, max_prefix, max_seqlen_k,
+                                                         *(ctypes.byref(x) for x in v)))
+    return tuple(x.value for x in v)
+
+
+def _check_groups(who, ref, batch, group_members, group_prefix, seq_prefix):
+    for t in (group_members, group_prefix, seq_prefix):
+        _on_gpu(t)
+        if t.device != ref.device or t.dtype != torch.int32:
+            raise ValueError(f"{who}: the group arrays must be int32 tensors on the GPU of the input")
+    if group_members.dim() != 2 or group_members.shape[0] < 1 or group_members.shape[1] < 1 or group_members.stride(1) != 1 or \
+            group_members.stride(0) < group_members.shape[1]:
+        raise ValueError(f"{who}: group_members must be [num_groups, group_cap] with a unit last stride")
+    if group_prefix.dim() != 1 or group_prefix.shape[0] != group_members.shape[0] or not group_prefix.is_contiguous():
+        raise ValueError(f"{who}: group_prefix must be a contiguous [num_groups] tensor")
+    if seq_prefix.dim() != 1 or seq_prefix.shape[0] != batch or not seq_prefix.is_contiguous():
+        raise ValueError(f"{who}: seq_prefix must be a contiguous [B] tensor")
+
+
+def attn_kvcache_paged_shared(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: int, group_members, group_prefix, seq_prefix,
+                              max_prefix: int, seqlen_offset: int = 0, softmax_scale=None, causal: bool = True, k_scale=None, v_scale=None):
+    """C-ABI awq_attn_kvcache_paged_shared[_kv8]: `attn_kvcache_paged` for a batch whose sequences share prefixes.  group_members int32
+    [num_groups, group_cap] (-1 padding) lists the slots of each group, group_prefix int32 [num_groups] the tokens a group shares,
+    seq_prefix int32 [B] the tokens each sequence shares with its group (below 64: ungrouped); `llm_awq_amd.paged_kv.PrefixGroups` keeps
+    the three consistent.  max_prefix is the host bound of every prefix, a multiple of 64 in [64, max_seqlen_k];
+    group_cap * Sq * (H / Hkv) <= 128.  The keys below a group's prefix are fetched once per (group, KV head, split) through the table row
+    of the group's first active member, each member's own keys as in `attn_kvcache_paged`, anchored behind the prefix.  For every active
+    sequence of a consistent grouping the result is `attn_kvcache_paged`'s function, and its bits when both chunks of
+    `attn_kvcache_shared_plan` are one c with the prefix a multiple of c.  Capturable: a replay follows the lengths, tables and group
+    arrays the tensors hold then."""
+    who = "attn_kvcache_paged_shared"
+    _on_gpu(q)
+    if q.dim() != 4 or q.stride(3) != 1 or q.stride(2) != q.shape[3]:
+        raise ValueError(f"{who}: q must be [B, Sq, H, Dh] with contiguous heads")
+    kv = _check_pools(who, q, k_pool, v_pool, block_table, k_scale, v_scale, q.shape[0])
+    if kv.Dh != q.shape[3]:
+        raise ValueError(f"{who}: q [B, Sq, H, Dh] and k_pool / v_pool [num_pages, page_size, Hkv, Dh] must share Dh, got {q.shape[3]} and {kv.Dh}")
+    B, Sq, H, Dh = q.shape
+    _check_seqlens(who, "seqlens_k", seqlens_k, q, B)
+    _check_groups(who, q, B, group_members, group_prefix, seq_prefix)
+    scale = float(Dh) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    L = _capi.lib()
+    out = torch.empty(B, Sq, H, Dh, dtype=q.dtype, device=q.device)
+    wsb = L.awq_attn_kvcache_shared_workspace_bytes(B, H, kv.Hkv, Dh, Sq, int(max_prefix), int(max_seqlen_k))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
+    entry = getattr(L, "awq_attn_kvcache_paged_shared" + ("_kv8" if kv.fp8 else ""))
+    with torch.cuda.device(q.device):
+        _capi.check(entry(q.data_ptr(), *kv.ptrs(), out.data_ptr(), kv.block_table.data_ptr(), B, Sq, seqlens_k.data_ptr(), int(seqlen_offset),
+                          int(max_seqlen_k), *kv.table(), H, kv.Hkv, Dh, *q.stride()[:-2], *kv.strides(), scale, int(bool(causal)), _dt(q),
+                          group_members.data_ptr(), group_prefix.data_ptr(), seq_prefix.data_ptr(), group_members.shape[0],
+                          group_members.shape[1], group_members.stride(0), int(max_prefix), ws.data_ptr(), wsb, _stream(q)))
+    return out
+
+
+def kv_page_copy(k_pool, v_pool, src_pages, dst_pages, k_scale=None, v_scale=None):
+    """C-ABI awq_kv_page_copy[_fp8]: page dst_pages[i] of the pools := page src_pages[i] (K and V rows, and the scale rows of FP8 pools),
+    one launch for the n pairs.  src_pages / dst_pages int32 [n] on the GPU; a pair with an id outside the pool or with equal ids is
+    skipped.  No other byte of the pools is written.  The copy-on-write of the partly filled tail page `PageTable.fork` returns."""
+    who = "kv_page_copy"
+    fp8 = _fp8_pair(who, k_scale, v_scale)
+    _on_gpu(k_pool, v_pool, src_pages, dst_pages, *((k_scale, v_scale) if fp8 else ()))
+    for name, t in (("k_pool", k_pool), ("v_pool", v_pool)):
+        if fp8:
+            _kv8_codes(who, name, t)
+        elif t.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"{who}: the pools must be float16 / bfloat16, or FP8 codes with their scales")
+        if t.device != k_pool.device or t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+            raise ValueError(f"{who}: {name} must be a [num_pages, page_size, Hkv, Dh] tensor with contiguous heads")
+    if k_pool.shape != v_pool.shape or k_pool.dtype != v_pool.dtype:
+        raise ValueError(f"{who}: k_pool and v_pool must have one shape and dtype")
+    num_pages, page_size, Hkv, Dh = v_pool.shape
+    if fp8:
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.device != k_pool.device or t.dtype != torch.float32 or tuple(t.shape) != (num_pages, page_size, Hkv) or t.stride(2) != 1:
+                raise ValueError(f"{who}: {name} must be a float32 [num_pages, page_size, Hkv] tensor with a unit last stride")
+    for name, t in (("src_pages", src_pages), ("dst_pages", dst_pages)):
+        if t.device != k_pool.device or t.dtype != torch.int32 or t.dim() != 1 or t.shape != src_pages.shape or not t.is_contiguous():
+            raise ValueError(f"{who}: src_pages and dst_pages must be contiguous int32 [n] tensors on the GPU of the pools")
+    kv = _Kv(k_pool, v_pool, k_scale, v_scale)
+    with torch.cuda.device(k_pool.device):
+        _capi.check(getattr(_capi.lib(), "awq_kv_page_copy" + ("_fp8" if fp8 else ""))(
+            *kv.ptrs(), src_pages.data_ptr(), dst_pages.data_ptr(), src_pages.shape[0], num_pages, page_size, Hkv, Dh, *kv.strides(),
+            _stream(k_pool)))
+
+
 def attn_prefill_paged(q, k_pool, v_pool, block_table, seqlens_k, max_seqlen_k: int, seqlen_offset: int = 0, softmax_scale=None,
                        causal: bool = True, k_scale=None, v_scale=None):
     """C-ABI awq_attn_prefill_paged[_kv8]: `attn_prefill_kvcache` over a paged KV cache (`attn_kvcache_paged`'s pools, table and bound): a
