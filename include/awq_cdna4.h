@@ -363,6 +363,34 @@ int awq_lm_head_plan(int m, int v, int k, int out[4]);
  * causes a read outside the table.  n >= 1, v >= 1, k >= 8, k % 8 == 0 (AWQ_ERR_SHAPE); table / out 16-byte, tokens 4-byte aligned. */
 int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, int dtype, void* stream);
 
+/* ---- Token log-probabilities: the LM head fused with log-sum-exp, for scoring text (perplexity, `logprobs`, lm-eval's loglikelihood).  No logit is
+ * ever written to memory.  DESIGN.md "Token log-probabilities" states the result by values; per row i of x (T = dtype):
+ *   xn          as awq_lm_head: with gamma, awq_rmsnorm's arithmetic bit for bit (that launch runs first, into the head of the workspace; ldx must
+ *               then equal k); gamma NULL: xn = x, row stride ldx elements (ldx % 8 == 0, ldx >= k)
+ *   z[i, j]     = sum_k f32(xn[i, k]) f32(weight[j, k]) in fp32, + f32(bias[j]) in fp32 when bias is given; with round_logits != 0 every z is then
+ *               rounded once to T, nearest-even, as an nn.Linear would store it
+ *   lse[i]      = log sum_j exp(z[i, j]);  argmax[i] = the LOWEST j among the maxima of z[i, :] (awq_sample_logits' tie rule)
+ *   target_logit[i] = z[i, targets[i]];  logprob[i] = target_logit[i] - lse[i], one fp32 subtraction
+ *   targets     int32 [t] or NULL.  A row whose target lies outside [0, v) (-1: the sampler's finished slot, -100: torch's ignore_index) is IGNORED:
+ *               its four outputs keep what they held and whatever its x holds, NaN included, changes no other row; a launch whose rows are all
+ *               ignored reads no weight.  With targets NULL every row is active and logprob / target_logit must be NULL (AWQ_ERR_NULL).
+ *   outputs     fp32 [t] (argmax int32 [t]); each may be NULL
+ * Two launches (tiles, combine), no atomics, no host read, capturable.  The vocabulary tile and every sum order depend on (v, k) alone -- not on t, the
+ * row's index, the other rows or max_blocks -- so a row's outputs are the same bits wherever it is served.
+ * Limits: t >= 1, 1 <= v <= 2^30 (both entries), k >= 8, k % 8 == 0, ldx as above, max_blocks >= 0 (0 = the plan's grid, otherwise a cap on it) (AWQ_ERR_SHAPE); dtype
+ * AWQ_F16 / AWQ_BF16 (AWQ_ERR_DTYPE); x / weight / gamma / bias / workspace 16-byte, targets and the outputs 4-byte aligned (AWQ_ERR_ALIGN);
+ * workspace NULL or below awq_lm_head_logprobs_workspace_bytes(t, v, k, gamma != NULL) (AWQ_ERR_WORKSPACE); all checked before anything is launched.
+ * awq_lm_head_logprobs_plan (host only): out[4] = {rows of x per tile, vocabulary rows per tile, blocks, k per step}.
+ * awq_token_logprobs: the same lse / argmax / logprob for logits that already exist -- logits [b, v] of logits_dtype (AWQ_F32 / AWQ_F16 / AWQ_BF16),
+ * row stride ld elements (ld >= v), element-size aligned; one block per row, no workspace; ignored rows and NULL rules as above. ---- */
+int awq_lm_head_logprobs(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                         float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                         void* workspace, size_t workspace_bytes, int max_blocks, void* stream);
+size_t awq_lm_head_logprobs_workspace_bytes(int t, int v, int k, int with_gamma);
+int awq_lm_head_logprobs_plan(int t, int v, int k, int out[4]);
+int awq_token_logprobs(const void* logits, int logits_dtype, long ld, const int* targets, float* logprob, float* lse, int* argmax, int b, int v,
+                       void* stream);
+
 /* ---- Multi-LoRA on packed steps: y[t, :] += scaling[a] (x[t, :] A_a^T) B_a^T with a = adapter_ids[owner of row t], in TWO launches per adapted
  * linear whatever the mix of adapters, decodes and prompt chunks (shrink, then expand).  DESIGN.md "Multi-LoRA" states the result by values:
  *   x             T [total_q, k], row stride ldx elements (ldx % 8 == 0, ldx >= k): the packed rows of the step

@@ -73,6 +73,10 @@ SIGNATURES = {
     "awq_lm_head": (_i,[_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awq_lm_head_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_embed_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "awq_lm_head_logprobs": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float] + [_vp] * 7 + [_i] * 5 + [_vp, _sz, _i, _vp]),
+    "awq_lm_head_logprobs_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "awq_lm_head_logprobs_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
+    "awq_token_logprobs": (_i, [_vp, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "awq_lora_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_lora_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awq_lora_shrink": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _sz] + [_i] * 8 + [_vp]),

@@ -1658,6 +1658,47 @@ int awq_embed_tokens(const int* tokens, const void* table, void* out, int n, int
   return finish_launch();
 }
 
+// ---- Token log-probabilities: LM head fused with log-sum-exp, and the companion for existing logits (awq_lm_logprobs_cdna4.hip) ----
+int awq_lm_head_logprobs_plan(int t, int v, int k, int out[4]) {
+  if (!out) return AWQ_ERR_NULL;
+  return awq::lm_logprobs_plan(t, v, k, out) != 0 ? AWQ_ERR_SHAPE : AWQ_OK;
+}
+
+size_t awq_lm_head_logprobs_workspace_bytes(int t, int v, int k, int with_gamma) { return awq::lm_logprobs_workspace_bytes(t, v, k, with_gamma); }
+
+int awq_lm_head_logprobs(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                         float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                         void* workspace, size_t workspace_bytes, int max_blocks, void* stream) {
+  if (!x || !weight) return AWQ_ERR_NULL;
+  if (!targets && (logprob || target_logit)) return AWQ_ERR_NULL;  // without targets there is no target logit to report
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  int plan[4];
+  if (awq::lm_logprobs_plan(t, v, k, plan) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0 || (gamma && ldx != k)) return AWQ_ERR_SHAPE;
+  if (!aligned16(x) || !aligned16(weight) || !aligned16(gamma) || !aligned16(bias) || !aligned16(workspace)) return AWQ_ERR_ALIGN;
+  const void* words[] = {targets, logprob, lse, target_logit, argmax};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (!workspace || workspace_bytes < awq::lm_logprobs_workspace_bytes(t, v, k, gamma != nullptr)) return AWQ_ERR_WORKSPACE;
+  if (awq::launch_lm_logprobs(x, ldx, gamma, eps, weight, bias, targets, logprob, lse, target_logit, argmax, t, v, k, dtype, round_logits, workspace,
+                              max_blocks, (hipStream_t)stream) != 0)
+    return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+int awq_token_logprobs(const void* logits, int logits_dtype, long ld, const int* targets, float* logprob, float* lse, int* argmax, int b, int v,
+                       void* stream) {
+  if (!logits) return AWQ_ERR_NULL;
+  if (!targets && logprob) return AWQ_ERR_NULL;
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (b < 1 || b > 65535 * 1024 || v < 1 || v > (1 << 30) || ld < v) return AWQ_ERR_SHAPE;
+  if (!aligned_to(logits, logits_dtype == AWQ_F32 ? 4 : 2)) return AWQ_ERR_ALIGN;
+  const void* words[] = {targets, logprob, lse, argmax};
+  for (const void* w : words)
+    if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
+  if (awq::launch_token_logprobs(logits, logits_dtype, ld, targets, logprob, lse, argmax, b, v, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- Multi-LoRA on packed steps: shrink + expand (awq_lora_cdna4.hip) ----
 static int lora_check_batch(const int* cu_seqlens_q, int batch, int max_seqlen_q, int total_q, int slots) {
   if (batch < 1 || batch > 65535 || max_seqlen_q < 1 || max_seqlen_q > 1048560 || total_q < 1 || slots < 1) return AWQ_ERR_BATCH;

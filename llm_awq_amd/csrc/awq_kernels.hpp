@@ -178,6 +178,16 @@ int lm_head_plan(int m, int v, int k, int out[4]);
 int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                    int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st);
 int launch_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, hipStream_t st);  // zeros for an id outside [0, v)
+// Token log-probabilities (awq_lm_logprobs_cdna4.hip): the LM head fused with log-sum-exp (tile launch + combine launch; with gamma the rmsnorm launch
+// runs first into the head of the workspace), and the companion for logits that already exist.  The plan is {row tile, vocabulary tile, blocks, k step};
+// -1 if the sizes are outside the documented limits, pointers / alignment / workspace size validated by the caller
+int lm_logprobs_plan(int t, int v, int k, int out[4]);
+size_t lm_logprobs_workspace_bytes(int t, int v, int k, int with_gamma);
+int launch_lm_logprobs(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets, float* logprob,
+                       float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits, void* workspace, int max_blocks,
+                       hipStream_t st);
+int launch_token_logprobs(const void* logits, int logits_dtype, long ld, const int* targets, float* logprob, float* lse, int* argmax, int b, int v,
+                          hipStream_t st);
 // Multi-LoRA on packed steps (awq_lora_cdna4.hip): shrink (x A_a^T into the fp32 K-split workspace) and expand (scale, round, B_a^T, add into y in
 // place), the adapter of a row read on the device; the plan is {KS, k per split, expand column tile, waves}; -1 if the sizes are outside the documented
 // limits, pointers / alignment / workspace size validated by the caller

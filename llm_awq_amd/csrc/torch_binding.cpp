@@ -760,6 +760,61 @@ torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
   return out;
 }
 
+// ---- Token log-probabilities: LM head fused with log-sum-exp; returns (logprob, lse, target_logit, argmax), zero-filled where a row is ignored (and
+//      logprob / target_logit all zeros without targets) ----
+std::vector<torch::Tensor> lm_head_logprobs(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> targets,
+                                            c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias, bool round_logits,
+                                            int64_t max_blocks) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && (x.stride(1) == 1 || x.size(1) <= 1),
+              "awq_inference_engine: lm_head_logprobs: x must be a [T, K] GPU tensor with a contiguous last dimension");
+  TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() && weight.dim() == 2 && weight.size(1) == x.size(1) && weight.scalar_type() == x.scalar_type(),
+              "lm_head_logprobs: weight must be a contiguous [V, K] GPU tensor of x's dtype");
+  if (gamma.has_value()) x = x.contiguous();
+  const int code = dtype_code(x);
+  const int64_t t = x.size(0), k = x.size(1), v = weight.size(0);
+  auto vec = [&](const c10::optional<torch::Tensor>& a, at::ScalarType want, int64_t n, const char* name) -> void* {
+    if (!a.has_value()) return nullptr;
+    TORCH_CHECK(a->is_cuda() && a->is_contiguous() && a->scalar_type() == want && a->numel() == n && a->device() == x.device(), "lm_head_logprobs: ",
+                name, " must be a contiguous GPU tensor of its size and dtype");
+    return a->data_ptr();
+  };
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const auto f32 = x.options().dtype(at::kFloat);
+  at::Tensor logprob = torch::zeros({t}, f32), lse = torch::zeros({t}, f32), tl = torch::zeros({t}, f32),
+             argmax = torch::zeros({t}, x.options().dtype(at::kInt));
+  const size_t bytes = awq_lm_head_logprobs_workspace_bytes((int)t, (int)v, (int)k, gamma.has_value() ? 1 : 0);
+  at::Tensor ws = torch::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
+  const int64_t ldx = gamma.has_value() ? k : (t > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), k) / 8 * 8);
+  const bool tg = targets.has_value();
+  raise_on(awq_lm_head_logprobs(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
+                                vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(targets, at::kInt, t, "targets"),
+                                tg ? (float*)logprob.data_ptr() : nullptr, (float*)lse.data_ptr(), tg ? (float*)tl.data_ptr() : nullptr,
+                                (int*)argmax.data_ptr(), (int)t, (int)v, (int)k, code, round_logits ? 1 : 0, ws.data_ptr(), bytes, (int)max_blocks,
+                                (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {logprob, lse, tl, argmax};
+}
+
+// (logprob, lse, argmax) of logits [B, V] that already exist
+std::vector<torch::Tensor> token_logprobs(torch::Tensor logits, c10::optional<torch::Tensor> targets) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && (logits.stride(1) == 1 || logits.size(1) <= 1),
+              "awq_inference_engine: token_logprobs: logits must be a [B, V] GPU tensor with a contiguous last dimension");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, "token_logprobs: logits must be float32, bfloat16 or float16");
+  const int64_t b = logits.size(0), v = logits.size(1);
+  TORCH_CHECK(!targets.has_value() || (targets->is_cuda() && targets->is_contiguous() && targets->scalar_type() == at::kInt && targets->numel() == b &&
+                                       targets->device() == logits.device()),
+              "token_logprobs: targets must be a contiguous int32 [B] tensor on the logits' device");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  const auto f32 = logits.options().dtype(at::kFloat);
+  at::Tensor logprob = torch::zeros({b}, f32), lse = torch::zeros({b}, f32), argmax = torch::zeros({b}, logits.options().dtype(at::kInt));
+  const int64_t ld = b > 1 ? logits.stride(0) : std::max<int64_t>(logits.stride(0), v);
+  raise_on(awq_token_logprobs(logits.data_ptr(), st == at::kFloat ? AWQ_F32 : (st == at::kHalf ? AWQ_F16 : AWQ_BF16), (long)ld,
+                              targets.has_value() ? (const int*)targets->data_ptr() : nullptr,
+                              targets.has_value() ? (float*)logprob.data_ptr() : nullptr, (float*)lse.data_ptr(), (int*)argmax.data_ptr(), (int)b,
+                              (int)v, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {logprob, lse, argmax};
+}
+
 // ---- Multi-LoRA on packed steps: shrink (x A_a^T into the fp32 K-split workspace) and expand (scale, round, B_a^T, add into y in place) ----
 struct LoraBatch {
   const int* ids;
@@ -2515,6 +2570,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
   m.def("embed_tokens", &embed_tokens, "out[i] = table[tokens[i]], zeros for an id outside the table (-1 = a finished slot)", py::arg("tokens"),
         py::arg("table"));
+  m.def("lm_head_logprobs", &lm_head_logprobs,
+        "(logprob, lse, target_logit, argmax) per row of x against weight [V, K]: the LM head fused with log-sum-exp, no logits written; rows whose target "
+        "is outside [0, V) are ignored",
+        py::arg("x"), py::arg("weight"), py::arg("targets") = py::none(), py::arg("gamma") = py::none(), py::arg("eps") = 0.0,
+        py::arg("bias") = py::none(), py::arg("round_logits") = false, py::arg("max_blocks") = 0);
+  m.def("token_logprobs", &token_logprobs, "(logprob, lse, argmax) per row of existing logits [B, V] (fp32 / bf16 / fp16)", py::arg("logits"),
+        py::arg("targets") = py::none());
   m.def("lora_shrink", &lora_shrink, "multi-LoRA shrink: ws[s, t, :] = x[t, k of split s] @ A_{adapter of t}^T in fp32 (rows without an adapter untouched)",
         py::arg("x"), py::arg("a_pool"), py::arg("adapter_ids"), py::arg("ws"), py::arg("rank"), py::arg("cu_seqlens_q") = py::none(),
         py::arg("max_seqlen_q") = 1);

@@ -35,6 +35,13 @@ class LMHead(nn.Module):
             h = h[:, -1, :]
         return ops.lm_head(h, self.weight, self.norm_weight, self.eps, self.bias, seqlens, out, self.out_dtype)
 
+    def logprobs(self, h, targets, round_logits=False, want=("logprob", "lse"), ws=None, out=None):
+        """h [T, K] or [B, S, K] -- EVERY position is used, not forward's last token -- and targets int32 of T (B * S) values -> a dict of fp32 [T]
+        tensors (argmax int32), see ops.lm_head_logprobs.  No logit is written to memory.  A position whose target is outside [0, V) is ignored."""
+        h2 = h.reshape(-1, h.shape[-1])
+        tg = None if targets is None else targets.reshape(-1)
+        return ops.lm_head_logprobs(h2, self.weight, tg, self.norm_weight, self.eps, self.bias, round_logits, ws, want, out)
+
 
 class TokenEmbedding(nn.Module):
     """`nn.Embedding.forward` for int32 ids on the device, with zeros for -1 (a finished slot) and every other id outside the table."""

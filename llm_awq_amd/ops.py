@@ -797,6 +797,114 @@ def embed_tokens(tokens, table):
     return out
 
 
+# ---- token log-probabilities: the LM head fused with log-sum-exp (awq_lm_logprobs_cdna4.hip) ----
+
+_LOGPROB_OUTPUTS = ("logprob", "lse", "target_logit", "argmax")
+
+
+def lm_head_logprobs_plan(t: int, v: int, k: int) -> dict:
+    """C-ABI awq_lm_head_logprobs_plan (host only): the tiles awq_lm_head_logprobs cuts [t, k] x [v, k] into."""
+    import ctypes
+    out = (ctypes.c_int * 4)()
+    _capi.check(_capi.lib().awq_lm_head_logprobs_plan(int(t), int(v), int(k), out))
+    return {"row_tile": out[0], "vocab_tile": out[1], "blocks": out[2], "k_step": out[3]}
+
+
+def lm_head_logprobs_workspace_bytes(t: int, v: int, k: int, with_gamma: bool = False) -> int:
+    """C-ABI awq_lm_head_logprobs_workspace_bytes (host only)."""
+    return int(_capi.lib().awq_lm_head_logprobs_workspace_bytes(int(t), int(v), int(k), int(bool(with_gamma))))
+
+
+def _logprob_outputs(who, n, device, targets, want, out):
+    want = tuple(want)
+    for name in want:
+        if name not in _LOGPROB_OUTPUTS:
+            raise ValueError(f"{who}: unknown output {name!r} (one of {_LOGPROB_OUTPUTS})")
+        if targets is None and name in ("logprob", "target_logit"):
+            raise ValueError(f"{who}: {name} needs targets")
+    res = {}
+    for name in want:
+        dt = torch.int32 if name == "argmax" else torch.float32
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.zeros(n, dtype=dt, device=device)
+        elif t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{who}: out[{name!r}] must be a contiguous {dt} tensor of {n} values on the inputs' device")
+        res[name] = t
+    return res
+
+
+def lm_head_logprobs(x, weight, targets=None, gamma=None, eps=0.0, bias=None, round_logits=False, ws=None, want=("logprob", "lse"), out=None,
+                     max_blocks=0):
+    """C-ABI awq_lm_head_logprobs: per row of x [T, K], against weight [V, K] (nn.Linear.weight as loaded): lse = log sum_v exp(z), target_logit =
+    z[targets], logprob = target_logit - lse and argmax (lowest index among the maxima) of z = rmsnorm(x) @ weight^T (+ bias), without the logits ever
+    being written to memory.  round_logits: every z is rounded once to x's dtype first, as an nn.Linear would store it.  targets int32 [T]: a row
+    whose target is outside [0, V) (-1, -100) is ignored -- its outputs keep what they held (zeros in fresh ones).  x may be a strided view with a
+    contiguous last dimension when gamma is None.  ws: a uint8 workspace of at least lm_head_logprobs_workspace_bytes (allocated when None; pass
+    one, and `out`, to capture the call).  Returns a dict with the outputs named in `want`: fp32 [T], argmax int32 [T]."""
+    if x.dim() != 2 or weight.dim() != 2:
+        raise ValueError("lm_head_logprobs: x must be [T, K] and weight [V, K]")
+    for t in (x, weight, gamma, bias, targets, ws):
+        if t is not None and not t.is_cuda:
+            raise _capi.AwqNativeError("llm_awq_amd ops run on the GPU only (no CPU fallback)")
+    n, k = x.shape
+    v = weight.shape[0]
+    if weight.shape[1] != k or weight.dtype != x.dtype or not weight.is_contiguous():
+        raise ValueError("lm_head_logprobs: weight must be a contiguous [V, K] tensor of x's dtype")
+    if gamma is not None:
+        x = x.contiguous()
+    elif x.stride(1) != 1 and k > 1:
+        raise ValueError("lm_head_logprobs: the last dimension of x must be contiguous")
+    for name, t, cnt in (("gamma", gamma, k), ("bias", bias, v)):
+        if t is not None and (t.dtype != x.dtype or t.numel() != cnt or t.device != x.device or not t.is_contiguous()):
+            raise ValueError(f"lm_head_logprobs: {name} must hold {cnt} contiguous values of x's dtype on x's device")
+    if targets is not None and (targets.dtype != torch.int32 or targets.numel() != n or targets.device != x.device or not targets.is_contiguous()):
+        raise ValueError("lm_head_logprobs: targets must be contiguous int32 [T] on x's device")
+    res = _logprob_outputs("lm_head_logprobs", n, x.device, targets, want, out)
+    need = lm_head_logprobs_workspace_bytes(n, v, k, gamma is not None)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or ws.device != x.device or not ws.is_contiguous():
+        raise ValueError(f"lm_head_logprobs: ws must be a contiguous uint8 tensor of at least {need} bytes on x's device")
+    ldx = x.stride(0) if n > 1 else max(x.stride(0), k) // 8 * 8  # (a single row's stride is never used)
+    if gamma is not None:
+        ldx = k
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.lib().awq_lm_head_logprobs(x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(targets),
+                                                     ptr(res.get("logprob")), ptr(res.get("lse")), ptr(res.get("target_logit")),
+                                                     ptr(res.get("argmax")), n, v, k, _dt(x), int(bool(round_logits)), ws.data_ptr(), ws.numel(),
+                                                     int(max_blocks), _stream(x)))
+    return res
+
+
+def token_logprobs(logits, targets=None, want=None, out=None):
+    """C-ABI awq_token_logprobs: lse, argmax and (with targets) logprob = logits[b, targets[b]] - lse[b] for logits [B, V] that already exist (fp32 /
+    bf16 / fp16, any row stride, contiguous last dimension) -- what ops.lm_head hands to the sampler.  Same contract as lm_head_logprobs: rows whose
+    target is outside [0, V) are ignored.  Returns a dict (default: lse, argmax, and logprob when targets is given)."""
+    if logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("token_logprobs: logits must be a [B, V] GPU tensor")
+    codes = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}
+    if logits.dtype not in codes:
+        raise TypeError(f"token_logprobs: logits must be float32, bfloat16 or float16, got {logits.dtype}")
+    b, v = logits.shape
+    if logits.stride(1) != 1 and v > 1:
+        raise ValueError("token_logprobs: the last dimension of logits must be contiguous")
+    if targets is not None and (targets.dtype != torch.int32 or targets.numel() != b or targets.device != logits.device or not targets.is_contiguous()):
+        raise ValueError("token_logprobs: targets must be contiguous int32 [B] on the logits' device")
+    if want is None:
+        want = ("lse", "argmax") + (("logprob",) if targets is not None else ())
+    if "target_logit" in want:
+        raise ValueError("token_logprobs: the target logit is logits[b, targets[b]] itself; it is not an output")
+    res = _logprob_outputs("token_logprobs", b, logits.device, targets, want, out)
+    ld = logits.stride(0) if b > 1 else max(logits.stride(0), v)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(logits.device):
+        _capi.check(_capi.lib().awq_token_logprobs(logits.data_ptr(), codes[logits.dtype], ld, ptr(targets), ptr(res.get("logprob")),
+                                                   ptr(res.get("lse")), ptr(res.get("argmax")), b, v, _stream(logits)))
+    return res
+
+
 # ---- multi-LoRA on packed steps: per-sequence adapters, read on the device (awq_lora_cdna4.hip) ----
 
 def lora_plan(k: int, r: int, n_slices: int = 1) -> dict:
