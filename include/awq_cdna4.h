@@ -1173,6 +1173,73 @@ int awq_gelu_quant_per_token(const void* x, void* out_i8, void* scale, void* tmp
 int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, float eps, void* out_i8, void* scale, int m, int k, int per_token,
                         int dtype, void* stream);
 
+/* ---- Per-head q/k RMSNorm in front of the rotation (Qwen3, Gemma-3): the ten natural-layout stores, each with a _qknorm sibling that takes
+ *      its argument list and, directly after the angles, q_gamma, k_gamma (device fp32 [head_dim], 16-byte aligned) and norm_eps.  Every q head
+ *      and every k head of a token is normalised over its head_dim columns BEFORE the rotation; v is untouched.  One launch, the sibling's
+ *      grid; no workspace, no atomics: bit-deterministic and capturable.
+ * Arithmetic, per (token, head), x the head's head_dim values: ss = the fp32 sum of x[c]^2 (8 consecutive columns folded in ascending order
+ *     with fmaf from 0, the head_dim / 8 partial sums combined pairwise at distances 1, 2, .., head_dim / 16); rstd = rsqrtf(ss / head_dim +
+ *     norm_eps); y[c] = T((x[c] * rstd) * gamma[c]), ONE rounding -- awq_rmsnorm's arithmetic on the head as a row of k = head_dim.  The
+ *     rotation, the FP8 quantiser and the stores then act on y exactly as the sibling's act on x.
+ * Bits: with gammas that T holds, q_out, the caches or pools and the scales are those the sibling leaves on a copy of qkv whose q and k heads
+ *     were replaced by awq_rmsnorm(head rows, gamma in T, norm_eps).  The gammas are fp32 because Gemma-3's 1 + w is formed in fp32 and no
+ *     T holds it.  An inactive sequence gets zero q_out rows and nothing else; padding rows of a packed step are not touched.
+ * Returns the sibling's codes, and: q_gamma or k_gamma NULL AWQ_ERR_NULL; one of them not 16-byte aligned AWQ_ERR_ALIGN; norm_eps negative,
+ *     infinite or NaN AWQ_ERR_SHAPE.  Every check precedes the launch. */
+int awq_rope_kv_store_natural_qknorm(const void* qkv, const float* freqs, const float* q_gamma, const float* k_gamma, float norm_eps, void* q_out,
+                                     void* k_cache, void* v_cache, int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim,
+                                     int rot_dim, int lmax, int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype,
+                                     void* stream);
+int awq_rope_kv_store_natural_fp8_qknorm(const void* qkv, const float* freqs, const float* q_gamma, const float* k_gamma, float norm_eps, void* q_out,
+                                         void* k_cache, void* v_cache, float* k_scale, float* v_scale, int batch, int cache_batch, int seqlen,
+                                         int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
+                                         long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_natural_pos_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                         void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens, int batch, int cache_batch, int seqlen,
+                                         int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
+                                         long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_natural_pos_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                             void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale, const int* cache_seqlens,
+                                             int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                             int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_paged_pos_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                       void* q_out, void* k_pool, void* v_pool, const int* block_table, const int* cache_seqlens, int batch,
+                                       int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size,
+                                       int pages_per_seq, long long table_row_stride, long long k_page_stride, long long k_row_stride,
+                                       long long v_page_stride, long long v_row_stride, long long qkv_batch_stride, long long qkv_row_stride,
+                                       int dtype, void* stream);
+int awq_rope_kv_store_paged_pos_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                           void* q_out, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* block_table,
+                                           const int* cache_seqlens, int batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                           int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                           long long k_scale_page_stride, long long k_scale_row_stride, long long v_scale_page_stride,
+                                           long long v_scale_row_stride, long long qkv_batch_stride, long long qkv_row_stride, int dtype,
+                                           void* stream);
+int awq_rope_kv_store_natural_varq_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                          void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens, int batch, int cache_batch,
+                                          const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim,
+                                          int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_natural_varq_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                              void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale, const int* cache_seqlens,
+                                              int batch, int cache_batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                              int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype,
+                                              void* stream);
+int awq_rope_kv_store_paged_varq_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                        void* q_out, void* k_pool, void* v_pool, const int* block_table, const int* cache_seqlens, int batch,
+                                        const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                        int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                        long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                        long long qkv_row_stride, int dtype, void* stream);
+int awq_rope_kv_store_paged_varq_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                            void* q_out, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* block_table,
+                                            const int* cache_seqlens, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                            int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                            long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                            long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                            long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_row_stride, int dtype,
+                                            void* stream);
+
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
  * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "attn_splitkv_chunk", "tower_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every

@@ -207,6 +207,11 @@ SIGNATURES = {
     "awq_layernorm_quant": (_i, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_tune_set": (_i, [ctypes.c_char_p, _i]),
 }
+# the _qknorm sibling of every natural-layout store: its arguments with q_gamma, k_gamma and norm_eps directly after the angles
+for _n in ("natural", "natural_pos", "paged_pos", "natural_varq", "paged_varq"):
+    for _f in ("", "_fp8"):
+        _args = SIGNATURES["awq_rope_kv_store_" + _n + _f][1]
+        SIGNATURES["awq_rope_kv_store_" + _n + _f + "_qknorm"] = (_i, _args[:2] + [_vp, _vp, ctypes.c_float] + _args[2:])
 
 
 class AwqNativeError(RuntimeError):

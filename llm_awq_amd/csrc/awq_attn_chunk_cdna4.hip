@@ -42,6 +42,11 @@ struct RopeStoreArgs {
   long long k_ps, k_rs, v_ps, v_rs;
   VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
+// what a NORM instantiation of rope_kv_store_natural_kernel takes: the same arguments and the per-head q/k RMSNorm behind them, so the
+// plain instantiations keep their argument block
+struct RopeStoreNormArgs : RopeStoreArgs {
+  QkNormArgs nm;
+};
 
 template <typename DT, int DH>
 __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
@@ -120,8 +125,14 @@ __global__ __launch_bounds__(256) void rope_kv_store_kernel(RopeStoreArgs a) {
 // of one PACKED token t < total_q.  Its sequence b is looked up in cu_seqlens_q (varq_owner), s = t - cu[b], and from there on the thread
 // is the rectangular form's thread (b, s) of a chunk of Sq_b tokens: same position, same angles, same bits.  A sequence with
 // Sq_b > max_seqlen_q is inactive as well.  Rows >= cu[B] leave before they read anything.
-template <typename DT, int DH>
-__global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArgs a) {
+//
+// NORM (the *_qknorm entries; awq_rope.hpp): every q and k head is RMS-normalised over its Dh columns before the rotation.  The Dh / 8
+// lanes of a token own each head row together and meet in a butterfly per head, so the kernel takes the FP8 kernel's shape there: compute,
+// then meet -- the lanes of a head may lie on either side of c0 < rot, and the butterfly runs before they part.  The lanes of a token
+// share every early exit above it (the grid guard, a padding row, an inactive sequence: all are tests of the token or of its sequence), so
+// they leave or stay together and the butterfly never meets a lane that has left.  NORM = false is the kernel without any of this.
+template <typename DT, int DH, bool NORM = false>
+__global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(std::conditional_t<NORM, RopeStoreNormArgs, RopeStoreArgs> a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
@@ -168,7 +179,27 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_kernel(RopeStoreArg
   uint16_t* kd = a.k_cache + crow;
   uint16_t* vd = a.v_cache + vrow;
 
-  if (c0 >= a.rot) {
+  if constexpr (NORM) {
+    const bool rot_lane = c0 < a.rot;
+    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sn[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int pc = c0;
+    float sign = 1.f;
+    if (rot_lane) {
+      const float* fr = a.freqs + (DEVLEN ? (long long)start + s : (long long)s * a.B + b) * a.rot + c0;
+      const f32x4 f0 = *reinterpret_cast<const f32x4*>(fr), f1 = *reinterpret_cast<const f32x4*>(fr + 4);
+      const float ang[8] = {f0[0], f0[1], f0[2], f0[3], f1[0], f1[1], f1[2], f1[3]};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sincosf(ang[e], &sn[e], &cs[e]);
+      const bool first = c0 + half < a.rot;
+      pc = first ? c0 + half : c0 - half;
+      sign = first ? -1.f : 1.f;
+    }
+    const QkNormLane gq(a.nm.q_gamma, c0, pc), gk(a.nm.k_gamma, c0, pc);
+    qk_norm_rotate_heads<DT, DH>(row, a.H, c0, pc, rot_lane, cs, sn, sign, gq, a.nm.eps,
+                                 [&](int hd, const u32x4& w) { *reinterpret_cast<u32x4*>(qd + hd * DH) = w; });
+    qk_norm_rotate_heads<DT, DH>(ks, a.Hkv, c0, pc, rot_lane, cs, sn, sign, gk, a.nm.eps,
+                                 [&](int hd, const u32x4& w) { *reinterpret_cast<u32x4*>(kd + hd * DH) = w; });
+  } else if (c0 >= a.rot) {
     for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = *reinterpret_cast<const u32x4*>(row + hd * DH + c0);
     for (int hd = 0; hd < a.Hkv; ++hd) *reinterpret_cast<u32x4*>(kd + hd * DH) = *reinterpret_cast<const u32x4*>(ks + hd * DH + c0);
   } else {
@@ -224,6 +255,18 @@ int launch_kv_store(const KvStoreCall& c, hipStream_t st) {
     a.k_ps = kv.k_os, a.k_rs = kv.k_rs, a.v_ps = kv.v_os, a.v_rs = kv.v_rs;
   }
   if (c.cu_seqlens_q) a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  if (c.q_gamma) {  // the *_qknorm entries: the NORM instantiation of the same form
+    RopeStoreNormArgs an;
+    static_cast<RopeStoreArgs&>(an) = a;
+    an.nm = QkNormArgs{c.q_gamma, c.k_gamma, c.norm_eps};
+    for_kv_store_form(c, [&](auto form) {
+      for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
+        using DT = typename decltype(form)::template of<decltype(dt)>;
+        hipLaunchKernelGGL((rope_kv_store_natural_kernel<DT, decltype(dh)::value, true>), dim3((unsigned)a.qv_blocks), dim3(256), 0, st, an);
+      });
+    });
+    return 0;
+  }
   for_kv_store_form(c, [&](auto form) {
     for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
       using DT = typename decltype(form)::template of<decltype(dt)>;

@@ -47,6 +47,10 @@ struct RopeStoreFp8Args {
   long long k_ps, k_rs, v_ps, v_rs, ks_ps, ks_rs, vs_ps, vs_rs;
   VarQArgs vq;  // VarQ only (awq_varq.hpp): qkv / q_out are packed rows, S the host's bound max_seqlen_q, bs unused
 };
+// what a NORM instantiation takes: the same arguments and the per-head q/k RMSNorm behind them (rope_kv_store_natural_kernel's)
+struct RopeStoreFp8NormArgs : RopeStoreFp8Args {
+  QkNormArgs nm;
+};
 
 // DevLen<..> (awq_devlen.hpp, awq_rope_kv_store_natural_pos_fp8): rope_kv_store_natural_kernel's device positions.  a.freqs is the whole
 // angle table [a.start rows, rot], pos_b = a.seqlens[b]; an inactive sequence (pos_b < 0 or pos_b + S > min(lmax, table rows)) gets a zero
@@ -59,8 +63,13 @@ struct RopeStoreFp8Args {
 // VarQ<..> over the two device forms (awq_varq.hpp, awq_rope_kv_store_natural_varq_fp8 / awq_rope_kv_store_paged_varq_fp8):
 // rope_kv_store_natural_kernel's packed tokens -- the owner of packed row t is looked up in cu_seqlens_q, and the thread goes on as thread
 // (b, t - cu[b]) of the rectangular form.  The CPR lanes of a token share t, so the lookup keeps them together.
-template <typename DT, int DH>
-__global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStoreFp8Args a) {
+//
+// NORM (the *_fp8_qknorm entries; awq_rope.hpp): rope_kv_store_natural_kernel's per-head RMSNorm of q and k before the rotation.  The sum
+// of squares of a head row travels over the CPR lanes of its token as max |x| does below, for the q heads as well as the k heads; the lanes
+// of a token leave or stay together at every exit above, so that butterfly too never meets a lane that has left.  The quantiser then sees
+// the normalised, rotated k row; V is untouched.  NORM = false is the kernel without any of this.
+template <typename DT, int DH, bool NORM = false>
+__global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(std::conditional_t<NORM, RopeStoreFp8NormArgs, RopeStoreFp8Args> a) {
   constexpr bool DEVLEN = IsDevLen<DT>::value;
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
@@ -152,8 +161,17 @@ __global__ __launch_bounds__(256) void rope_kv_store_natural_fp8_kernel(RopeStor
     return pack8<DT>(res);
   };
 
-  for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = rotated(row + hd * DH);
-  for (int hd = 0; hd < a.Hkv; ++hd) quant_store(rotated(ks + hd * DH), kc, ksc, hd);
+  if constexpr (NORM) {
+    const QkNormLane gq(a.nm.q_gamma, c0, pc), gk(a.nm.k_gamma, c0, pc);
+    qk_norm_rotate_heads<DT, DH>(row, a.H, c0, pc, rot_lane, cs, sn, sign, gq, a.nm.eps,
+                                 [&](int hd, const u32x4& w) { *reinterpret_cast<u32x4*>(qd + hd * DH) = w; });
+    // (n = a.Hkv is the call's: every lane of the wave stores the same heads, so quant_store's butterfly meets all lanes of its token)
+    qk_norm_rotate_heads<DT, DH>(ks, a.Hkv, c0, pc, rot_lane, cs, sn, sign, gk, a.nm.eps,
+                                 [&](int hd, const u32x4& w) { quant_store(w, kc, ksc, hd); });
+  } else {
+    for (int hd = 0; hd < a.H; ++hd) *reinterpret_cast<u32x4*>(qd + hd * DH) = rotated(row + hd * DH);
+    for (int hd = 0; hd < a.Hkv; ++hd) quant_store(rotated(ks + hd * DH), kc, ksc, hd);
+  }
   for (int hd = 0; hd < a.Hkv; ++hd) quant_store(*reinterpret_cast<const u32x4*>(vs + hd * DH + c0), vc, vsc, hd);
 }
 
@@ -171,6 +189,18 @@ int launch_kv_store_fp8(const KvStoreCall& c, hipStream_t st) {
     a.ks_ps = kv.ks_os, a.ks_rs = kv.ks_rs, a.vs_ps = kv.vs_os, a.vs_rs = kv.vs_rs;
   }
   if (c.cu_seqlens_q) a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, 0};
+  if (c.q_gamma) {  // the *_fp8_qknorm entries: the NORM instantiation of the same form
+    RopeStoreFp8NormArgs an;
+    static_cast<RopeStoreFp8Args&>(an) = a;
+    an.nm = QkNormArgs{c.q_gamma, c.k_gamma, c.norm_eps};
+    for_kv_store_form(c, [&](auto form) {
+      for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
+        using DT = typename decltype(form)::template of<decltype(dt)>;
+        hipLaunchKernelGGL((rope_kv_store_natural_fp8_kernel<DT, decltype(dh)::value, true>), dim3(kv_store_blocks(c)), dim3(256), 0, st, an);
+      });
+    });
+    return 0;
+  }
   for_kv_store_form(c, [&](auto form) {
     for_dtype_dh<F16, BF16>(c.dtype, c.Dh, [&](auto dt, auto dh) {
       using DT = typename decltype(form)::template of<decltype(dt)>;

@@ -434,7 +434,9 @@ using awq::KvView;
 // KV_VARQ: packed tokens / queries (awq_varq.hpp) -- cu_seqlens_q, max_seqlen_q and total_q in the place of one seqlen for the batch
 // KV_MIX: a mixed step (awq_attn_varq and its siblings) -- split_seqlen_q and split_min_keys join the shape phase
 // KV_WINDOW: a sliding window on a mixed step (awq_window.hpp) -- window_left >= 0 and causal join the shape phase
-enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8, KV_VARQ = 16, KV_MIX = 32, KV_WINDOW = 64 };
+// KV_QKNORM: a store with the per-head q/k RMSNorm (the *_qknorm entries) -- q_gamma, k_gamma and norm_eps join the null, shape and
+// alignment phases
+enum { KV_FP8 = 1, KV_PAGED = 2, KV_DEVLEN = 4, KV_ONEPASS = 8, KV_VARQ = 16, KV_MIX = 32, KV_WINDOW = 64, KV_QKNORM = 128 };
 
 static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
@@ -481,18 +483,21 @@ static bool varq_shape_ok(int batch, int max_seqlen_q, int total_q) { return bat
 
 static int kv_store(const KvStoreCall& c, int fmt, void* stream) {
   const KvView& kv = c.kv;
-  const bool paged = fmt & KV_PAGED, devlen = fmt & KV_DEVLEN, varq = fmt & KV_VARQ;
-  if (!c.qkv || !c.freqs || !c.q_out || kv_has_null(kv, fmt) || (devlen && !c.cache_seqlens) || (varq && !c.cu_seqlens_q)) return AWQ_ERR_NULL;
+  const bool paged = fmt & KV_PAGED, devlen = fmt & KV_DEVLEN, varq = fmt & KV_VARQ, norm = fmt & KV_QKNORM;
+  if (!c.qkv || !c.freqs || !c.q_out || kv_has_null(kv, fmt) || (devlen && !c.cache_seqlens) || (varq && !c.cu_seqlens_q) ||
+      (norm && (!c.q_gamma || !c.k_gamma)))
+    return AWQ_ERR_NULL;
   if (c.dtype != AWQ_F16 && c.dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
   // tokens of the call: the rectangle, or the packed rows (c.S is then max_seqlen_q)
   const long long tokens = varq ? (long long)c.total_q : (long long)c.B * c.S;
   if (c.B < 1 || c.S < 1 || c.H < 1 || c.Hkv < 1 || (c.Dh != 64 && c.Dh != 128) || c.rot < 16 || (c.rot % 16) != 0 || c.rot > c.Dh || c.bs < 0 ||
       c.rs < ((long long)c.H + 2ll * c.Hkv) * c.Dh || (varq && !varq_shape_ok(c.B, c.max_seqlen_q, c.total_q)) ||
       tokens * (c.Dh / 8) > 0x3FFFFFFFll * 256 || (!paged && (kv.outer < c.B || kv.rows < 1)) || !kv_shape_ok(kv, fmt, paged, c.Hkv, c.Dh) ||
-      (devlen ? c.table_rows < 1 : (c.start_pos < 0 || (long long)c.start_pos + c.S > kv.rows)))
+      (devlen ? c.table_rows < 1 : (c.start_pos < 0 || (long long)c.start_pos + c.S > kv.rows)) ||
+      (norm && !(c.norm_eps >= 0.f && c.norm_eps <= 3.402823466e38f)))  // negative, infinite or NaN
     return AWQ_ERR_SHAPE;
   if (!aligned16(c.qkv) || !aligned16(c.freqs) || !aligned16(c.q_out) || !kv_aligned(kv, fmt, paged) || (devlen && !aligned4(c.cache_seqlens)) ||
-      (varq && !aligned4(c.cu_seqlens_q)) || (c.bs % 8) != 0 || (c.rs % 8) != 0)
+      (varq && !aligned4(c.cu_seqlens_q)) || (c.bs % 8) != 0 || (c.rs % 8) != 0 || (norm && (!aligned16(c.q_gamma) || !aligned16(c.k_gamma))))
     return AWQ_ERR_ALIGN;
   awq::launch_kv_store(c, (hipStream_t)stream);
   return finish_launch();
@@ -505,6 +510,12 @@ static KvStoreCall varq_store_call(const void* qkv, const float* freqs_table, vo
   KvStoreCall c{qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, max_seqlen_q, nheads, nheads_kv, head_dim, rot_dim, 0,
                 qkv_row_stride, dtype};
   c.cu_seqlens_q = cu_seqlens_q, c.max_seqlen_q = max_seqlen_q, c.total_q = total_q;
+  return c;
+}
+
+// a *_qknorm entry's descriptor: its sibling's with the norm's three fields
+static KvStoreCall with_qk_norm(KvStoreCall c, const float* q_gamma, const float* k_gamma, float norm_eps) {
+  c.q_gamma = q_gamma, c.k_gamma = k_gamma, c.norm_eps = norm_eps;
   return c;
 }
 
@@ -649,6 +660,70 @@ int awq_rope_kv_store_paged_pos_fp8(const void* qkv, const float* freqs_table, v
   return kv_store({qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim,
                    qkv_batch_stride, qkv_row_stride, dtype},
                   KV_FP8 | KV_PAGED | KV_DEVLEN, stream);
+}
+
+// The six rectangle stores with the per-head q/k RMSNorm in front of the rotation (awq_rope.hpp): each is its sibling's descriptor with
+// q_gamma, k_gamma (fp32 [head_dim]) and norm_eps set; the NORM instantiation of the same kernel serves.
+int awq_rope_kv_store_natural_qknorm(const void* qkv, const float* freqs, const float* q_gamma, const float* k_gamma, float norm_eps, void* q_out,
+                                     void* k_cache, void* v_cache, int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim,
+                                     int rot_dim, int lmax, int start_pos, long long qkv_batch_stride, long long qkv_row_stride, int dtype,
+                                     void* stream) {
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), start_pos, nullptr, 0, batch, seqlen,
+      nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma, norm_eps), KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_natural_fp8_qknorm(const void* qkv, const float* freqs, const float* q_gamma, const float* k_gamma, float norm_eps, void* q_out,
+                                         void* k_cache, void* v_cache, float* k_scale, float* v_scale, int batch, int cache_batch, int seqlen,
+                                         int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int start_pos, long long qkv_batch_stride,
+                                         long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale), start_pos,
+      nullptr, 0, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma, norm_eps),
+      KV_FP8 | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_natural_pos_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                         void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens, int batch, int cache_batch, int seqlen,
+                                         int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_batch_stride,
+                                         long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs_table, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), 0, cache_seqlens, table_rows, batch,
+      seqlen, nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma, norm_eps), KV_DEVLEN | KV_QKNORM,
+      stream);
+}
+
+int awq_rope_kv_store_natural_pos_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                             void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale, const int* cache_seqlens,
+                                             int batch, int cache_batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int lmax,
+                                             int table_rows, long long qkv_batch_stride, long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs_table, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale), 0,
+      cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim, rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma,
+      norm_eps), KV_FP8 | KV_DEVLEN | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_paged_pos_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                       void* q_out, void* k_pool, void* v_pool, const int* block_table, const int* cache_seqlens, int batch,
+                                       int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size,
+                                       int pages_per_seq, long long table_row_stride, long long k_page_stride, long long k_row_stride,
+                                       long long v_page_stride, long long v_row_stride, long long qkv_batch_stride, long long qkv_row_stride,
+                                       int dtype, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride), block_table,
+      table_row_stride, pages_per_seq);
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim,
+      rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma, norm_eps), KV_PAGED | KV_DEVLEN | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_paged_pos_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                           void* q_out, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* block_table,
+                                           const int* cache_seqlens, int batch, int seqlen, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                           int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                           long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                           long long k_scale_page_stride, long long k_scale_row_stride, long long v_scale_page_stride,
+                                           long long v_scale_row_stride, long long qkv_batch_stride, long long qkv_row_stride, int dtype,
+                                           void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+      k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride), block_table, table_row_stride,
+      pages_per_seq);
+  return kv_store(with_qk_norm(KvStoreCall{qkv, freqs_table, q_out, kv, 0, cache_seqlens, table_rows, batch, seqlen, nheads, nheads_kv, head_dim,
+      rot_dim, qkv_batch_stride, qkv_row_stride, dtype}, q_gamma, k_gamma, norm_eps), KV_FP8 | KV_PAGED | KV_DEVLEN | KV_QKNORM, stream);
 }
 
 int awq_attn_splitkv(const void* q, const void* k, const void* v, void* out, int batch, int seqlen_q, int seqlen_k, int nheads, int nheads_kv,
@@ -1192,6 +1267,54 @@ int awq_rope_kv_store_paged_varq_fp8(const void* qkv, const float* freqs_table, 
   return kv_store(varq_store_call(qkv, freqs_table, q_out, kv, cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q, nheads,
                                   nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype),
                   KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, stream);
+}
+
+// the four packed stores with the per-head q/k RMSNorm
+int awq_rope_kv_store_natural_varq_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                          void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens, int batch, int cache_batch,
+                                          const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim,
+                                          int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype, void* stream) {
+  return kv_store(with_qk_norm(varq_store_call(qkv, freqs_table, q_out, kv_view(k_cache, v_cache, cache_batch, lmax), cache_seqlens, table_rows,
+      batch, cu_seqlens_q, max_seqlen_q, total_q, nheads, nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype), q_gamma, k_gamma, norm_eps),
+      KV_DEVLEN | KV_VARQ | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_natural_varq_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                              void* q_out, void* k_cache, void* v_cache, float* k_scale, float* v_scale, const int* cache_seqlens,
+                                              int batch, int cache_batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                              int nheads_kv, int head_dim, int rot_dim, int lmax, int table_rows, long long qkv_row_stride, int dtype,
+                                              void* stream) {
+  return kv_store(with_qk_norm(varq_store_call(qkv, freqs_table, q_out, with_scales(kv_view(k_cache, v_cache, cache_batch, lmax), k_scale, v_scale),
+      cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q, nheads, nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype), q_gamma,
+      k_gamma, norm_eps), KV_FP8 | KV_DEVLEN | KV_VARQ | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_paged_varq_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                        void* q_out, void* k_pool, void* v_pool, const int* block_table, const int* cache_seqlens, int batch,
+                                        const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads, int nheads_kv, int head_dim, int rot_dim,
+                                        int table_rows, int num_pages, int page_size, int pages_per_seq, long long table_row_stride,
+                                        long long k_page_stride, long long k_row_stride, long long v_page_stride, long long v_row_stride,
+                                        long long qkv_row_stride, int dtype, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride), block_table,
+      table_row_stride, pages_per_seq);
+  return kv_store(with_qk_norm(varq_store_call(qkv, freqs_table, q_out, kv, cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q,
+      nheads, nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype), q_gamma, k_gamma, norm_eps), KV_PAGED | KV_DEVLEN | KV_VARQ | KV_QKNORM, stream);
+}
+
+int awq_rope_kv_store_paged_varq_fp8_qknorm(const void* qkv, const float* freqs_table, const float* q_gamma, const float* k_gamma, float norm_eps,
+                                            void* q_out, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const int* block_table,
+                                            const int* cache_seqlens, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, int nheads,
+                                            int nheads_kv, int head_dim, int rot_dim, int table_rows, int num_pages, int page_size, int pages_per_seq,
+                                            long long table_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                            long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                            long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_row_stride, int dtype,
+                                            void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+      k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride), block_table, table_row_stride,
+      pages_per_seq);
+  return kv_store(with_qk_norm(varq_store_call(qkv, freqs_table, q_out, kv, cache_seqlens, table_rows, batch, cu_seqlens_q, max_seqlen_q, total_q,
+      nheads, nheads_kv, head_dim, rot_dim, qkv_row_stride, dtype), q_gamma, k_gamma, norm_eps), KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ | KV_QKNORM,
+      stream);
 }
 
 static bool varlen_shape_ok(int nseq, int nheads, int head_dim, int max_seqlen) {

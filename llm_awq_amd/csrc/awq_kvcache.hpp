@@ -47,6 +47,11 @@ struct KvStoreCall {
   // S is then the host's bound max_seqlen_q and bs unused.  nullptr: the rectangle [B, S]
   const int* cu_seqlens_q = nullptr;
   int max_seqlen_q = 0, total_q = 0;
+  // per-head RMSNorm of q and k over Dh before the rotation (awq_rope.hpp, the *_qknorm entries): gammas fp32 [Dh], both or neither.
+  // nullptr: no norm, the kernels above
+  const float* q_gamma = nullptr;
+  const float* k_gamma = nullptr;
+  float norm_eps = 0;
 };
 
 struct KvAttnCall {

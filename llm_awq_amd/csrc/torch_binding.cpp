@@ -1357,9 +1357,17 @@ static at::Tensor packed_out(const char* who, const char* name, const c10::optio
 // misaligned).  Otherwise each sequence's position is read on the device and freqs is the model's whole table [P, rot_dim] (not copied:
 // a misaligned one is refused).  step: qkv is the packed tokens [total_q, ..] (device positions only).  One launch
 // (csrc/awq_attn_chunk_cdna4.hip, csrc/awq_attn_kv8_cdna4.hip).
+// the per-head q/k RMSNorm of the *_qknorm bindings: gammas float32 [Dh] on the GPU of qkv (Gemma-3's 1 + w is formed in fp32)
+struct QkNorm {
+  const torch::Tensor* q_gamma;
+  const torch::Tensor* k_gamma;
+  double eps;
+};
+
+// norm: the entry's _qknorm sibling serves -- q and k heads are RMS-normalised over Dh before the rotation, in the same launch.
 static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, const torch::Tensor& freqs, const KvTensors& kv,
                                      const torch::Tensor* cache_seqlens, int64_t start_pos, int64_t nheads, int64_t nheads_kv,
-                                     const PackedStep& step = {}) {
+                                     const PackedStep& step = {}, const QkNorm* norm = nullptr) {
   const bool fp8 = kv.k_scale != nullptr, paged = kv.block_table != nullptr, devlen = cache_seqlens != nullptr, packed = step.cu != nullptr;
   TORCH_CHECK(qkv.scalar_type() != at::kFloat, who, ": float32 is not supported by the MI355X build (use float16 or bfloat16)");
   TORCH_CHECK(qkv.is_cuda() && freqs.is_cuda() && freqs.device() == qkv.device(), who, ": tensors must live on the same GPU");
@@ -1401,6 +1409,13 @@ static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, 
     TORCH_CHECK(rot >= 16 && rot % 16 == 0 && rot <= headdim && freqs.numel() >= batch * seqlen * rot, who,
                 ": freqs must hold B * S * rot_dim angles with rot_dim % 16 == 0 and rot_dim <= head dim");
   }
+  if (norm) {
+    for (const torch::Tensor* g : {norm->q_gamma, norm->k_gamma})
+      TORCH_CHECK(g->is_cuda() && g->device() == qkv.device() && g->scalar_type() == at::kFloat && g->dim() == 1 && g->size(0) == headdim &&
+                      g->is_contiguous() && (reinterpret_cast<uintptr_t>(g->data_ptr()) & 15) == 0,
+                  who, ": q_gamma and k_gamma must be contiguous, 16-byte aligned float32 [Dh] tensors on the GPU of qkv");
+    TORCH_CHECK(norm->eps >= 0 && std::isfinite(norm->eps), who, ": norm_eps must be finite and >= 0");
+  }
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(qkv.device());
   at::Tensor x = qkv;  // rows of a unit stride, every other stride a multiple of 16 bytes
   if (x.stride(-1) != 1 || x.stride(0) % 8 || x.stride(-2) % 8 || (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15)) x = qkv.contiguous();
@@ -1417,35 +1432,40 @@ static torch::Tensor rope_store_impl(const char* who, const torch::Tensor& qkv, 
   const int B = (int)batch, S = (int)seqlen, T = (int)total, H = (int)nheads, Hkv = (int)nheads_kv, Dh = (int)headdim, R = (int)rot,
             P = devlen ? (int)freqs.size(0) : 0, dt = dtype_code(x);
   const int64_t bs = x.stride(0), rs = x.stride(-2);
+  const float *qg = norm ? norm->q_gamma->data_ptr<float>() : nullptr, *kg = norm ? norm->k_gamma->data_ptr<float>() : nullptr;
+  const float eps = norm ? (float)norm->eps : 0.f;
+// the entry, or with norm its _qknorm sibling: the same arguments with the gammas and eps directly after the angles
+#define AWQ_STORE(entry, ...) raise_on(norm ? entry##_qknorm(xp, fp, qg, kg, eps, __VA_ARGS__) : entry(xp, fp, __VA_ARGS__))
   if (paged) {
     const torch::Tensor& bt = *kv.block_table;
     const int pages = (int)outer, page = (int)rows, pps = (int)bt.size(1);
     const int64_t kps = k.stride(0), krs = k.stride(1), vps = v.stride(0), vrs = v.stride(1);
     if (packed && fp8)
-      raise_on(awq_rope_kv_store_paged_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page,
+      AWQ_STORE(awq_rope_kv_store_paged_varq_fp8, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page,
                                                 pps, bt.stride(0), kps, krs, vps, vrs, kv.k_scale->stride(0), kv.k_scale->stride(1),
-                                                kv.v_scale->stride(0), kv.v_scale->stride(1), rs, dt, st));
+                                                kv.v_scale->stride(0), kv.v_scale->stride(1), rs, dt, st);
     else if (packed)
-      raise_on(awq_rope_kv_store_paged_varq(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page, pps,
-                                            bt.stride(0), kps, krs, vps, vrs, rs, dt, st));
+      AWQ_STORE(awq_rope_kv_store_paged_varq, qp, kp, vp, bt.data_ptr<int>(), pos, B, cup, S, T, H, Hkv, Dh, R, P, pages, page, pps,
+                                            bt.stride(0), kps, krs, vps, vrs, rs, dt, st);
     else if (fp8)
-      raise_on(awq_rope_kv_store_paged_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps,
+      AWQ_STORE(awq_rope_kv_store_paged_pos_fp8, qp, kp, vp, ksp, vsp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps,
                                                bt.stride(0), kps, krs, vps, vrs, kv.k_scale->stride(0), kv.k_scale->stride(1),
-                                               kv.v_scale->stride(0), kv.v_scale->stride(1), bs, rs, dt, st));
+                                               kv.v_scale->stride(0), kv.v_scale->stride(1), bs, rs, dt, st);
     else
-      raise_on(awq_rope_kv_store_paged_pos(xp, fp, qp, kp, vp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps, bt.stride(0),
-                                           kps, krs, vps, vrs, bs, rs, dt, st));
+      AWQ_STORE(awq_rope_kv_store_paged_pos, qp, kp, vp, bt.data_ptr<int>(), pos, B, S, H, Hkv, Dh, R, P, pages, page, pps, bt.stride(0),
+                                           kps, krs, vps, vrs, bs, rs, dt, st);
   } else if (packed) {
-    if (fp8) raise_on(awq_rope_kv_store_natural_varq_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
-    else raise_on(awq_rope_kv_store_natural_varq(xp, fp, qp, kp, vp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st));
+    if (fp8) AWQ_STORE(awq_rope_kv_store_natural_varq_fp8, qp, kp, vp, ksp, vsp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st);
+    else AWQ_STORE(awq_rope_kv_store_natural_varq, qp, kp, vp, pos, B, (int)outer, cup, S, T, H, Hkv, Dh, R, (int)rows, P, rs, dt, st);
   } else if (devlen) {
-    if (fp8) raise_on(awq_rope_kv_store_natural_pos_fp8(xp, fp, qp, kp, vp, ksp, vsp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
-    else raise_on(awq_rope_kv_store_natural_pos(xp, fp, qp, kp, vp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st));
+    if (fp8) AWQ_STORE(awq_rope_kv_store_natural_pos_fp8, qp, kp, vp, ksp, vsp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st);
+    else AWQ_STORE(awq_rope_kv_store_natural_pos, qp, kp, vp, pos, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, P, bs, rs, dt, st);
   } else {
     if (fp8)
-      raise_on(awq_rope_kv_store_natural_fp8(xp, fp, qp, kp, vp, ksp, vsp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st));
-    else raise_on(awq_rope_kv_store_natural(xp, fp, qp, kp, vp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st));
+      AWQ_STORE(awq_rope_kv_store_natural_fp8, qp, kp, vp, ksp, vsp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st);
+    else AWQ_STORE(awq_rope_kv_store_natural, qp, kp, vp, B, (int)outer, S, H, Hkv, Dh, R, (int)rows, (int)start_pos, bs, rs, dt, st);
   }
+#undef AWQ_STORE
   return q_out;
 }
 
@@ -1829,6 +1849,68 @@ torch::Tensor rope_kv_store_paged_varq_fp8(const torch::Tensor qkv, const torch:
                                            int64_t nheads, int64_t nheads_kv, c10::optional<torch::Tensor> q_out) {
   return rope_store_impl("rope_kv_store_paged_varq_fp8", qkv, freqs_table, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, &cache_seqlens, 0,
                          nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out});
+}
+
+// rope_kv_store_*_qknorm: each store binding with q_gamma, k_gamma (float32 [Dh]) and norm_eps behind its own arguments -- the per-head q/k
+// RMSNorm of Qwen3 / Gemma-3 in front of the rotation, in the store launch (the C ABI's _qknorm siblings)
+torch::Tensor rope_kv_store_natural_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, int64_t start_pos,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_qknorm", qkv, freqs, {k_cache, v_cache, nullptr, nullptr, nullptr}, nullptr, start_pos, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_natural_fp8_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor k_scale, torch::Tensor v_scale, int64_t start_pos,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_fp8_qknorm", qkv, freqs, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, nullptr, start_pos, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_natural_pos_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_pos_qknorm", qkv, freqs, {k_cache, v_cache, nullptr, nullptr, nullptr}, &cache_seqlens, 0, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_natural_pos_fp8_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_pos_fp8_qknorm", qkv, freqs, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, &cache_seqlens, 0, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_paged_pos_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_pool, torch::Tensor v_pool, const torch::Tensor block_table, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_paged_pos_qknorm", qkv, freqs, {k_pool, v_pool, nullptr, nullptr, &block_table}, &cache_seqlens, 0, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_paged_pos_fp8_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_pool, torch::Tensor v_pool, torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_paged_pos_fp8_qknorm", qkv, freqs, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, &cache_seqlens, 0, nheads, nheads_kv, {}, &norm);
+}
+
+torch::Tensor rope_kv_store_natural_varq_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps, c10::optional<torch::Tensor> q_out) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_varq_qknorm", qkv, freqs, {k_cache, v_cache, nullptr, nullptr, nullptr}, &cache_seqlens, 0, nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out}, &norm);
+}
+
+torch::Tensor rope_kv_store_natural_varq_fp8_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps, c10::optional<torch::Tensor> q_out) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_natural_varq_fp8_qknorm", qkv, freqs, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, &cache_seqlens, 0, nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out}, &norm);
+}
+
+torch::Tensor rope_kv_store_paged_varq_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_pool, torch::Tensor v_pool, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps, c10::optional<torch::Tensor> q_out) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_paged_varq_qknorm", qkv, freqs, {k_pool, v_pool, nullptr, nullptr, &block_table}, &cache_seqlens, 0, nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out}, &norm);
+}
+
+torch::Tensor rope_kv_store_paged_varq_fp8_qknorm(const torch::Tensor qkv, const torch::Tensor freqs, torch::Tensor k_pool, torch::Tensor v_pool, torch::Tensor k_scale, torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor cache_seqlens,
+    int64_t nheads, int64_t nheads_kv, const torch::Tensor q_gamma, const torch::Tensor k_gamma, double norm_eps, c10::optional<torch::Tensor> q_out) {
+  const QkNorm norm{&q_gamma, &k_gamma, norm_eps};
+  return rope_store_impl("rope_kv_store_paged_varq_fp8_qknorm", qkv, freqs, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, &cache_seqlens, 0, nheads, nheads_kv, {&cu_seqlens_q, max_seqlen_q, &q_out}, &norm);
 }
 
 // attn_prefill_varq[_kv8] / attn_prefill_paged_varq[_kv8](q [total_q, H, Dh], caches or pools .., cu_seqlens_q, max_seqlen_q, seqlens_k,
@@ -2424,6 +2506,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"),
         py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"),
         py::arg("q_out") = py::none());
+  m.def("rope_kv_store_natural_qknorm", &rope_kv_store_natural_qknorm, "rope_kv_store_natural with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_natural_fp8_qknorm", &rope_kv_store_natural_fp8_qknorm, "rope_kv_store_natural_fp8 with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("start_pos"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_natural_pos_qknorm", &rope_kv_store_natural_pos_qknorm, "rope_kv_store_natural_pos with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_natural_pos_fp8_qknorm", &rope_kv_store_natural_pos_fp8_qknorm, "rope_kv_store_natural_pos_fp8 with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_paged_pos_qknorm", &rope_kv_store_paged_pos_qknorm, "rope_kv_store_paged_pos with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_paged_pos_fp8_qknorm", &rope_kv_store_paged_pos_fp8_qknorm, "rope_kv_store_paged_pos_fp8 with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"));
+  m.def("rope_kv_store_natural_varq_qknorm", &rope_kv_store_natural_varq_qknorm, "rope_kv_store_natural_varq with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_natural_varq_fp8_qknorm", &rope_kv_store_natural_varq_fp8_qknorm, "rope_kv_store_natural_varq_fp8 with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_paged_varq_qknorm", &rope_kv_store_paged_varq_qknorm, "rope_kv_store_paged_varq with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"), py::arg("q_out") = py::none());
+  m.def("rope_kv_store_paged_varq_fp8_qknorm", &rope_kv_store_paged_varq_fp8_qknorm, "rope_kv_store_paged_varq_fp8 with the per-head q/k RMSNorm (gammas float32 [Dh]) in front of the rotation",
+        py::arg("qkv"), py::arg("freqs_table"), py::arg("k_pool"), py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("cache_seqlens"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("q_gamma"), py::arg("k_gamma"), py::arg("norm_eps"), py::arg("q_out") = py::none());
   m.def("attn_prefill_varq", &attn_prefill_varq,
         "The one-pass prefill kernel over PACKED queries q [total_q, H, Dh] with per-sequence query lengths (cu_seqlens_q) and key lengths on the device",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),

@@ -71,10 +71,15 @@ class QuantLlamaAttentionFused(nn.Module):
     `kv_layout="natural"`) makes them float8_e4m3fn and adds `cache_k_scale` / `cache_v_scale` [max_batch_size, kv_max_seq_len, Hkv]
     float32; `kv_dtype=None` is the cache of the activations' dtype.  `sliding_window=W` (an int >= 1; None: full attention, nothing
     changes): each row attends W keys, itself included; the config is never read for it.  It is served on the packed routes of the
-    natural layout only: an int `start_pos`, `kv_layout="ft"` and `chunk_prefilling` on the FT path raise NotImplementedError."""
+    natural layout only: an int `start_pos`, `kv_layout="ft"` and `chunk_prefilling` on the FT path raise NotImplementedError.
+    `qk_norm=(q_weight, k_weight, eps)` (None: no norm, nothing changes) is the per-head RMSNorm of Qwen3 / Gemma-3: every q head and every k
+    head is normalised over head_dim between the qkv projection and the rotation, inside the store launch of every natural-layout route
+    (the `rope_kv_store_*_qknorm` entries).  The weights [head_dim] are held as the float32 buffers `q_norm_weight` / `k_norm_weight`
+    (Gemma-3 hands in 1 + w, formed in float32); `kv_layout="ft"` with `qk_norm` raises NotImplementedError.  `head_dim` is
+    `args.head_dim` where the config declares one (Qwen3: hidden 1024, 16 heads, head_dim 128), else hidden_size // num_heads."""
 
     def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft", kv_dtype=None,
-                 sliding_window=None):
+                 sliding_window=None, qk_norm=None):
         super().__init__()
         if sliding_window is not None and (isinstance(sliding_window, bool) or int(sliding_window) != sliding_window or int(sliding_window) < 1):
             raise ValueError(f"QuantLlamaAttentionFused: sliding_window {sliding_window!r} must be None or an int >= 1 (the keys a row attends, "
@@ -87,6 +92,9 @@ class QuantLlamaAttentionFused(nn.Module):
         if kv_dtype == "fp8" and kv_layout != "natural":
             raise ValueError("QuantLlamaAttentionFused: kv_dtype 'fp8' needs kv_layout 'natural' (the FT decode kernel reads a cache of the "
                              "activations' dtype)")
+        if qk_norm is not None and kv_layout != "natural":
+            raise NotImplementedError("QuantLlamaAttentionFused: qk_norm is not implemented on the FT cache (kv_layout 'ft': its decode kernel "
+                                      "rotates q and k itself); use kv_layout 'natural'")
         self.kv_layout = kv_layout
         self.kv_dtype = kv_dtype
         self.args = args
@@ -94,6 +102,8 @@ class QuantLlamaAttentionFused(nn.Module):
         self.hidden_size = args.hidden_size
         self.num_heads = args.num_attention_heads
         self.head_dim = self.hidden_size // self.num_heads
+        if getattr(args, "head_dim", None) is not None:  # declared independently of hidden_size / num_heads (Qwen3, Gemma-3)
+            self.head_dim = int(args.head_dim)
         self.num_key_value_heads = args.num_key_value_heads
         self.num_key_value_groups = self.num_heads // self.num_key_value_heads
         self.max_position_embeddings = getattr(args, "max_position_embeddings", None)
@@ -105,6 +115,17 @@ class QuantLlamaAttentionFused(nn.Module):
             self.rope_scaling = self.rope_scaling.get("factor", 1.0)
         if self.head_dim not in (64, 128):
             raise ValueError(f"QuantLlamaAttentionFused: head dim {self.head_dim} is not supported (supported head dims: 64, 128)")
+        self.qk_norm_eps = None
+        if qk_norm is not None:
+            q_weight, k_weight, eps = qk_norm
+            for name, w in (("q_weight", q_weight), ("k_weight", k_weight)):
+                if tuple(w.shape) != (self.head_dim,):
+                    raise ValueError(f"QuantLlamaAttentionFused: qk_norm {name} must be [head_dim] = [{self.head_dim}], got {tuple(w.shape)}")
+            self.qk_norm_eps = float(eps)
+            if not (self.qk_norm_eps >= 0.0 and self.qk_norm_eps != float("inf")):
+                raise ValueError(f"QuantLlamaAttentionFused: qk_norm eps must be finite and >= 0, got {eps!r}")
+            self.register_buffer("q_norm_weight", q_weight.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
+            self.register_buffer("k_norm_weight", k_weight.detach().to(device=dev, dtype=torch.float32).contiguous().clone())
         self.qkv_proj = qkv_layer
         self.o_proj = o_proj
         self.kv_max_seq_len = kv_max_seq_len
@@ -124,6 +145,15 @@ class QuantLlamaAttentionFused(nn.Module):
         self.cache_v = torch.zeros((max_batch_size, self.num_key_value_heads, kv_max_seq_len, self.head_dim), dtype=torch.float16, device=dev)
         self.cache_k = torch.zeros((max_batch_size, self.num_key_value_heads, self.head_dim // 8, kv_max_seq_len, 8), dtype=torch.float16,
                                    device=dev)
+
+    def _store(self, eng, entry, xqkv, *args):
+        """eng.<entry>(xqkv, *args) -- or with `qk_norm` its `_qknorm` sibling, which takes the gammas and eps behind the same arguments."""
+        if self.qk_norm_eps is None:
+            return getattr(eng, entry)(xqkv, *args)
+        if self.q_norm_weight.device != xqkv.device:
+            self.q_norm_weight = self.q_norm_weight.to(xqkv.device)
+            self.k_norm_weight = self.k_norm_weight.to(xqkv.device)
+        return getattr(eng, entry + "_qknorm")(xqkv, *args, self.q_norm_weight, self.k_norm_weight, self.qk_norm_eps)
 
     @torch.no_grad()
     def forward(self, x, start_pos, freqs, mask=None, chunk_prefilling=False, decode_max_seqlen=None, block_table=None, page_size=None):
@@ -168,8 +198,8 @@ class QuantLlamaAttentionFused(nn.Module):
             if self.cache_k.device != xqkv.device:
                 for name in ("cache_k", "cache_v", "cache_k_scale", "cache_v_scale"):
                     setattr(self, name, getattr(self, name).to(xqkv.device))
-            xq = eng.rope_kv_store_natural_fp8(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, self.cache_k_scale,
-                                               self.cache_v_scale, start_pos, self.n_local_heads, self.num_key_value_heads)
+            xq = self._store(eng, "rope_kv_store_natural_fp8", xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v,
+                             self.cache_k_scale, self.cache_v_scale, start_pos, self.n_local_heads, self.num_key_value_heads)
             end = start_pos + seqlen
             output = ops.attn_kv8(xq, self.cache_k[:bsz, :end], self.cache_v[:bsz, :end], self.cache_k_scale[:bsz, :end],
                                   self.cache_v_scale[:bsz, :end], causal=True)
@@ -180,8 +210,8 @@ class QuantLlamaAttentionFused(nn.Module):
         if self.kv_layout == "natural":  # long_forward (fused_attn.py:505-546); `chunk_prefilling` changes nothing there: the history is attended
             from .flash_attn_compat import flash_attn_func
 
-            xq = eng.rope_kv_store_natural(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
-                                           self.num_key_value_heads)
+            xq = self._store(eng, "rope_kv_store_natural", xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos,
+                             self.n_local_heads, self.num_key_value_heads)
             output = flash_attn_func(xq, self.cache_k[:bsz, :start_pos + seqlen], self.cache_v[:bsz, :start_pos + seqlen], causal=True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if seqlen > 1:
@@ -316,9 +346,9 @@ class QuantLlamaAttentionFused(nn.Module):
             kv = tuple(t.view(pool if t.dim() == 4 else pool[:3]) for t in kv)
             table = (block_table,)
         where = ("paged" if table else "natural", "_paged" if table else "")
-        store = getattr(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""))
         attn = getattr(eng, "attn_prefill" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
-        xq = store(xqkv, freqs, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
+        xq = self._store(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""), xqkv, freqs, *kv, *table, cu_seqlens_q,
+                         max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
         if self.sliding_window is not None:
             from .ops import ATTN_SPLIT_MIN_KEYS
 
@@ -377,22 +407,25 @@ class QuantLlamaAttentionFused(nn.Module):
                 shared = (g.group_members, g.group_prefix, g.seq_prefix[:bsz], min(g.max_prefix, bound // 64 * 64))
             if self.kv_dtype == "fp8":
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool), self.cache_k_scale.view(pool[:3]), self.cache_v_scale.view(pool[:3]))
-                xq = eng.rope_kv_store_paged_pos_fp8(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
+                xq = self._store(eng, "rope_kv_store_paged_pos_fp8", xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads,
+                                 self.num_key_value_heads)
                 attn = eng.attn_prefill_paged_kv8 if prompt else eng.attn_kvcache_paged_shared_kv8 if shared else eng.attn_kvcache_paged_kv8
                 output = attn(xq, *pools, block_table, start_pos, bound, *shared, seqlen, scale, True)
             else:
                 pools = (self.cache_k.view(pool), self.cache_v.view(pool))
-                xq = eng.rope_kv_store_paged_pos(xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads, self.num_key_value_heads)
+                xq = self._store(eng, "rope_kv_store_paged_pos", xqkv, freqs, *pools, block_table, start_pos, self.n_local_heads,
+                                 self.num_key_value_heads)
                 attn = eng.attn_prefill_paged if prompt else eng.attn_kvcache_paged_shared if shared else eng.attn_kvcache_paged
                 output = attn(xq, *pools, block_table, start_pos, bound, *shared, seqlen, scale, True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if self.kv_dtype == "fp8":
-            xq = eng.rope_kv_store_natural_pos_fp8(xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos,
-                                                   self.n_local_heads, self.num_key_value_heads)
+            xq = self._store(eng, "rope_kv_store_natural_pos_fp8", xqkv, freqs, self.cache_k, self.cache_v, self.cache_k_scale,
+                             self.cache_v_scale, start_pos, self.n_local_heads, self.num_key_value_heads)
             attn = eng.attn_prefill_kvcache_kv8 if prompt else eng.attn_kvcache_kv8
             output = attn(xq, self.cache_k, self.cache_v, self.cache_k_scale, self.cache_v_scale, start_pos, bound, seqlen, scale, True)
         else:
-            xq = eng.rope_kv_store_natural_pos(xqkv, freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads, self.num_key_value_heads)
+            xq = self._store(eng, "rope_kv_store_natural_pos", xqkv, freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
+                             self.num_key_value_heads)
             attn = eng.attn_prefill_kvcache if prompt else eng.attn_kvcache
             output = attn(xq, self.cache_k, self.cache_v, start_pos, bound, seqlen, scale, True)
         return self.o_proj(output.view(bsz, seqlen, -1))
@@ -434,7 +467,8 @@ def make_quant_attn(model, dev, max_batch_size=1, kv_layout="ft", kv_dtype=None)
     """tinychat/modules/fused_attn.py:549-634: replace every module that carries q_proj, k_proj, v_proj, o_proj, `args` and
     `kv_max_seq_len` (the reference's LlamaAttentionFused / Qwen2AttentionFused) by a QuantLlamaAttentionFused over one fused
     qkv WQLinear, then move the model to `dev`.  `kv_layout="natural"` builds the long-context mode, `kv_dtype="fp8"` its FP8 cache.
-    `make_quant_attn_window` is the same with a sliding window."""
+    `make_quant_attn_window` is the same with a sliding window.  A module that carries `q_norm` or `k_norm` (Qwen3, Gemma-3) is refused:
+    `make_quant_attn_qknorm` builds those."""
     return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, None)
 
 
@@ -447,15 +481,45 @@ def make_quant_attn_window(model, dev, sliding_window, max_batch_size=1, kv_layo
     return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window)
 
 
-def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window):
+def make_quant_attn_qknorm(model, dev, max_batch_size=1, kv_layout="natural", kv_dtype=None, sliding_window=None, norm_offset=0.0):
+    """`make_quant_attn` for a model whose attention blocks put a per-head RMSNorm on q and k between the projection and RoPE (Qwen3, dense
+    and MoE; Gemma-3): a module's `q_norm` / `k_norm` submodules supply the weights (`.weight`, [head_dim]) and the eps (`variance_epsilon`
+    or `eps`), and every module is built with `qk_norm=(norm_offset + q_norm.weight.float(), norm_offset + k_norm.weight.float(), eps)`.
+    `norm_offset=1.0` is Gemma-3's (1 + w), formed in float32; `sliding_window` as in `make_quant_attn_window` (None: full attention).  A
+    module without both norms is refused.  A function of its own: `make_quant_attn` keeps its parameter list."""
+    return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, norm_offset=float(norm_offset))
+
+
+def _norm_eps(norm, name):
+    for attr in ("variance_epsilon", "eps"):
+        if getattr(norm, attr, None) is not None:
+            return float(getattr(norm, attr))
+    raise ValueError(f"make_quant_attn_qknorm: {name} carries neither variance_epsilon nor eps")
+
+
+def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, norm_offset=None):
     want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
     for name, m in list(model.named_modules()):
         if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
             continue
+        has_norm = [hasattr(m, a) and getattr(m, a) is not None for a in ("q_norm", "k_norm")]
+        qk_norm = None
+        if norm_offset is None:
+            if any(has_norm):  # dropping the norm silently gives wrong logits
+                raise ValueError(f"make_quant_attn: module {name!r} carries a per-head q_norm / k_norm (Qwen3, Gemma-3); build it with "
+                                 "make_quant_attn_qknorm, which fuses the norm into the rope + KV-store launch")
+        else:
+            if not all(has_norm):
+                raise ValueError(f"make_quant_attn_qknorm: module {name!r} must carry both q_norm and k_norm (`make_quant_attn` builds the "
+                                 "modules without a norm)")
+            eps_q, eps_k = _norm_eps(m.q_norm, name + ".q_norm"), _norm_eps(m.k_norm, name + ".k_norm")
+            if eps_q != eps_k:
+                raise ValueError(f"make_quant_attn_qknorm: q_norm and k_norm of module {name!r} have different eps ({eps_q}, {eps_k})")
+            qk_norm = (norm_offset + m.q_norm.weight.detach().float(), norm_offset + m.k_norm.weight.detach().float(), eps_q)
         qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
         attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
                                         max_batch_size=max_batch_size, kv_layout=kv_layout, kv_dtype=kv_dtype,
-                                        sliding_window=sliding_window)
+                                        sliding_window=sliding_window, **({} if qk_norm is None else {"qk_norm": qk_norm}))
         if "." in name:
             parent_name, child_name = name.rsplit(".", 1)
             parent = model.get_submodule(parent_name)

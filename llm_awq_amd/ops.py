@@ -1391,8 +1391,34 @@ def _caches(who, qkv, k_cache, v_cache, k_scale, v_scale):
     return _Kv(k_cache, v_cache, k_scale, v_scale)
 
 
-def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_seqlens=None, packed=None):
-    """The ten store entries of the C ABI over a described cache.  cache_seqlens None: the host position start_pos and the call's angles;
+def _norm_pair(who, q_norm, k_norm):
+    """Whether the call brings the per-head q/k norm; one gamma without the other is refused (before anything else is looked at)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError(f"{who}: q_norm and k_norm come together")
+    return q_norm is not None
+
+
+def _qk_norm(who, qkv, Dh, q_norm, k_norm, norm_eps):
+    """The per-head q/k RMSNorm of a store call: None without one, else (q_gamma, k_gamma, eps) with the gammas as float32 [Dh] on the GPU
+    of qkv.  A gamma of T becomes float32 exactly; a float32 one (Gemma-3's 1 + w) is taken as it is."""
+    if not _norm_pair(who, q_norm, k_norm):
+        return None
+    _on_gpu(q_norm, k_norm)
+    gammas = []
+    for name, g in (("q_norm", q_norm), ("k_norm", k_norm)):
+        if g.device != qkv.device or g.dtype not in (torch.float32, qkv.dtype) or tuple(g.shape) != (Dh,):
+            raise ValueError(f"{who}: {name} must be a [Dh] = [{Dh}] tensor of float32 or of the input's dtype on the GPU of qkv")
+        g = g.float().contiguous()
+        gammas.append(g if g.data_ptr() % 16 == 0 else g.clone())
+    eps = float(norm_eps)
+    if not (eps >= 0.0 and eps != float("inf")):
+        raise ValueError(f"{who}: norm_eps must be finite and >= 0, got {norm_eps!r}")
+    return gammas[0], gammas[1], eps
+
+
+def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_seqlens=None, packed=None, norm=None):
+    """The ten store entries of the C ABI over a described cache; with norm = (q_gamma, k_gamma, eps) of _qk_norm, their _qknorm
+    siblings.  cache_seqlens None: the host position start_pos and the call's angles;
     otherwise the positions are read on the device and freqs is the model's whole angle table [P, rot_dim].  packed = (cu_seqlens_q,
     max_seqlen_q, q_out or None), checked by the caller: qkv is the packed tokens [total_q, ..] of a step (device positions only)."""
     devlen = cache_seqlens is not None
@@ -1416,7 +1442,8 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
         raise ValueError(f"{who}: freqs holds fewer than B * S * rot_dim angles")
     q_out = _packed_out(who, "q_out", q_out, qkv, int(nheads), kv.Dh) if packed else \
         torch.empty(B, S, nheads, kv.Dh, dtype=qkv.dtype, device=qkv.device)
-    head = (qkv.data_ptr(), freqs.data_ptr(), q_out.data_ptr(), *kv.ptrs())
+    gammas = () if norm is None else (norm[0].data_ptr(), norm[1].data_ptr(), norm[2])  # directly after the angles
+    head = (qkv.data_ptr(), freqs.data_ptr(), *gammas, q_out.data_ptr(), *kv.ptrs())
     shape = (*tokens, int(nheads), int(nheads_kv), kv.Dh, rot)
     tail = (*qkv.stride()[:-1], _dt(qkv), _stream(qkv))  # the batch stride (a rectangle's only) and the row stride
     form = "_varq" if packed else "_pos"
@@ -1428,7 +1455,7 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
     else:
         entry, args = "natural", (*head, B, kv.outer, *shape, kv.rows, int(start_pos), *tail)
     with torch.cuda.device(qkv.device):
-        _capi.check(getattr(_capi.lib(), "awq_rope_kv_store_" + entry + ("_fp8" if kv.fp8 else ""))(*args))
+        _capi.check(getattr(_capi.lib(), "awq_rope_kv_store_" + entry + ("_fp8" if kv.fp8 else "") + ("" if norm is None else "_qknorm"))(*args))
     return q_out
 
 
@@ -1481,9 +1508,19 @@ def rope_kv_store_natural_fp8(qkv, freqs, k_cache, v_cache, k_scale, v_scale, st
     """C-ABI awq_rope_kv_store_natural_fp8: rope_kv_store_natural with k and v quantised on their way into the FP8 caches (kv8_quant's
     format).  k_cache / v_cache [Bc, Lmax, Hkv, Dh] float8_e4m3fn or uint8, k_scale / v_scale [Bc, Lmax, Hkv] float32.  Writes codes and
     scales at [b, start_pos + s]; returns the rotated q [B, S, H, Dh], rope_kv_store_natural's bits."""
+    return rope_kv_store_natural_fp8_qknorm(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos, nheads, nheads_kv)
+
+
+def rope_kv_store_natural_fp8_qknorm(qkv, freqs, k_cache, v_cache, k_scale, v_scale, start_pos: int, nheads: int, nheads_kv: int, *, q_norm=None,
+                                     k_norm=None, norm_eps: float = 1e-6):
+    """`rope_kv_store_natural_fp8` with the per-head q/k RMSNorm of `rope_kv_store_natural` (C-ABI awq_rope_kv_store_natural_fp8_qknorm): the
+    same arguments and, keyword-only, q_norm / k_norm ([Dh], float32 or the input's dtype; both or neither) and norm_eps.  The quantiser
+    sees the normalised, rotated k; v is untouched.  A function of its own: `rope_kv_store_natural_fp8` keeps its parameter list."""
     who = "rope_kv_store_natural_fp8"
+    _norm_pair(who, q_norm, k_norm)
     _on_gpu(qkv, freqs, k_cache, v_cache, k_scale, v_scale)
-    return _rope_store(who, qkv, freqs, _caches(who, qkv, k_cache, v_cache, k_scale, v_scale), nheads, nheads_kv, start_pos=start_pos)
+    kv = _caches(who, qkv, k_cache, v_cache, k_scale, v_scale)
+    return _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=start_pos, norm=_qk_norm(who, qkv, kv.Dh, q_norm, k_norm, norm_eps))
 
 
 def _check_kv8(who, q, k, v, k_scale, v_scale):
@@ -1622,16 +1659,23 @@ def attn_prefill_kvcache(q, k_cache, v_cache, seqlens_k, max_seqlen_k: int, seql
                        v_scale)
 
 
-def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None):
+def rope_kv_store_natural_pos(qkv, freqs_table, k_cache, v_cache, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None, v_scale=None, *,
+                              q_norm=None, k_norm=None, norm_eps: float = 1e-6):
     """C-ABI awq_rope_kv_store_natural_pos[_fp8]: rope_kv_store_natural[_fp8] with each sequence's position read on the device.
     cache_seqlens int32 [B] holds the tokens already in each sequence's cache; token s of sequence b is rotated by row
     cache_seqlens[b] + s of freqs_table [P, rot_dim] (float32, the model's whole angle table) and stored at that cache position.  A
     sequence with cache_seqlens[b] < 0 or cache_seqlens[b] + S > min(Lmax, P) is inactive: nothing of it is stored and its q rows are
-    zeros.  With k_scale / v_scale the caches are FP8 (rope_kv_store_natural_fp8's arguments).  Returns the rotated q [B, S, H, Dh]."""
+    zeros.  With k_scale / v_scale the caches are FP8 (rope_kv_store_natural_fp8's arguments).  Returns the rotated q [B, S, H, Dh].
+
+    q_norm / k_norm (keyword-only, both or neither; [Dh], float32 or the input's dtype) and norm_eps: every q head and every k head is
+    RMS-normalised over Dh before the rotation, in the same launch (C-ABI `_qknorm` sibling; Qwen3, Gemma-3) -- y = T((x * rsqrt(mean(x^2)
+    + norm_eps)) * gamma), `rmsnorm`'s arithmetic on the head as a row.  v is untouched."""
     who = "rope_kv_store_natural_pos"
+    _norm_pair(who, q_norm, k_norm)
     _on_gpu(qkv, freqs_table, cache_seqlens)
-    return _rope_store(who, qkv, freqs_table, _caches(who, qkv, k_cache, v_cache, k_scale, v_scale), nheads, nheads_kv,
-                       cache_seqlens=cache_seqlens)
+    kv = _caches(who, qkv, k_cache, v_cache, k_scale, v_scale)
+    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens,
+                       norm=_qk_norm(who, qkv, kv.Dh, q_norm, k_norm, norm_eps))
 
 
 # ---- the paged KV cache: the two calls above over a pool of pages and a per-sequence block table ------------------------------------
@@ -1795,12 +1839,22 @@ def rope_kv_store_paged(qkv, freqs_table, k_pool, v_pool, block_table, cache_seq
     [num_pages, page_size, Hkv, Dh] (the page is looked up per token: a chunk may cross page edges).  A sequence with cache_seqlens[b] < 0
     or cache_seqlens[b] + S > min(pages_per_seq * page_size, P) is inactive: nothing of it is stored and its q rows are zeros.  With
     k_scale / v_scale [num_pages, page_size, Hkv] the pools are FP8.  Returns the rotated q [B, S, H, Dh]."""
+    return rope_kv_store_paged_qknorm(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads, nheads_kv, k_scale, v_scale)
+
+
+def rope_kv_store_paged_qknorm(qkv, freqs_table, k_pool, v_pool, block_table, cache_seqlens, nheads: int, nheads_kv: int, k_scale=None,
+                               v_scale=None, *, q_norm=None, k_norm=None, norm_eps: float = 1e-6):
+    """`rope_kv_store_paged` with the per-head q/k RMSNorm of `rope_kv_store_natural_pos` (C-ABI awq_rope_kv_store_paged_pos[_fp8]_qknorm): the
+    same arguments and, keyword-only, q_norm / k_norm ([Dh], float32 or the input's dtype; both or neither) and norm_eps.  A function of
+    its own: `rope_kv_store_paged` keeps its parameter list."""
     who = "rope_kv_store_paged"
+    _norm_pair(who, q_norm, k_norm)
     _on_gpu(qkv, freqs_table, cache_seqlens)
     if qkv.dim() != 3 or qkv.stride(2) != 1:
         raise ValueError(f"{who}: qkv must be [B, S, (H + 2 Hkv) * Dh] with a unit last stride")
     kv = _check_pools(who, qkv, k_pool, v_pool, block_table, k_scale, v_scale, qkv.shape[0])
-    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens)
+    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens,
+                       norm=_qk_norm(who, qkv, kv.Dh, q_norm, k_norm, norm_eps))
 
 
 # ---- packed steps (continuous batching): per-sequence numbers of new tokens, read on the device ---------------------------------------
@@ -1837,7 +1891,7 @@ def _packed_out(who, name, given, ref, H, Dh):
 
 
 def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, nheads: int, nheads_kv: int, block_table=None,
-                       k_scale=None, v_scale=None, q_out=None):
+                       k_scale=None, v_scale=None, q_out=None, *, q_norm=None, k_norm=None, norm_eps: float = 1e-6):
     """C-ABI awq_rope_kv_store_natural_varq[_fp8] / awq_rope_kv_store_paged_varq[_fp8]: `rope_kv_store_natural_pos` / `rope_kv_store_paged`
     over PACKED tokens.  qkv [total_q, (H + 2 Hkv) * Dh] with a unit last stride; sequence b owns rows cu_seqlens_q[b] ..
     cu_seqlens_q[b + 1] - 1 (int32 [B + 1] on the GPU, non-decreasing, cu[0] = 0; the host never reads it).  Token s = t - cu[b] of
@@ -1846,8 +1900,13 @@ def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, 
     v_scale the FP8 format.  Sq_b = 0 is a slot with nothing to do.  A sequence with cache_seqlens[b] < 0, Sq_b > max_seqlen_q or
     cache_seqlens[b] + Sq_b > min(capacity, P) is inactive: nothing of it is stored and its q rows are zeros.  Rows >= cu[B] (the padding
     of a fixed token budget) are neither read nor written: hand q_out in to keep what they hold.  For every active sequence the rows,
-    the cache bytes and the scales are those of the rectangular call on that sequence alone.  Returns the rotated q [total_q, H, Dh]."""
+    the cache bytes and the scales are those of the rectangular call on that sequence alone.  Returns the rotated q [total_q, H, Dh].
+
+    q_norm / k_norm (keyword-only, both or neither; [Dh], float32 or the input's dtype) and norm_eps: every q head and every k head is
+    RMS-normalised over Dh before the rotation, in the same launch (C-ABI `_qknorm` sibling; Qwen3, Gemma-3) -- y = T((x * rsqrt(mean(x^2)
+    + norm_eps)) * gamma), `rmsnorm`'s arithmetic on the head as a row.  v is untouched."""
     who = "rope_kv_store_varq"
+    _norm_pair(who, q_norm, k_norm)
     _on_gpu(qkv, freqs_table, cache_seqlens)
     if qkv.dim() != 2 or qkv.stride(1) != 1:
         raise ValueError(f"{who}: qkv must be the packed tokens [total_q, (H + 2 Hkv) * Dh] with a unit last stride")
@@ -1858,7 +1917,8 @@ def rope_kv_store_varq(qkv, freqs_table, k, v, cu_seqlens_q, max_seqlen_q: int, 
         kv = _caches(who, qkv, k, v, k_scale, v_scale)
         if kv.outer < B:
             raise ValueError(f"{who}: batch {B} exceeds the cache batch {kv.outer}")
-    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens, packed=(cu_seqlens_q, max_seqlen_q, q_out))
+    return _rope_store(who, qkv, freqs_table, kv, nheads, nheads_kv, cache_seqlens=cache_seqlens, packed=(cu_seqlens_q, max_seqlen_q, q_out),
+                       norm=_qk_norm(who, qkv, kv.Dh, q_norm, k_norm, norm_eps))
 
 
 def attn_prefill_varq(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, lens_before_step: bool = True, block_table=None,
@@ -2019,16 +2079,23 @@ def rope_kv_store(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nhe
     return q_out
 
 
-def rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nheads_kv: int):
+def rope_kv_store_natural(qkv, freqs, k_cache, v_cache, start_pos: int, nheads: int, nheads_kv: int, *, q_norm=None, k_norm=None,
+                          norm_eps: float = 1e-6):
     """C-ABI awq_rope_kv_store_natural: rope_kv_store for natural-layout caches k_cache / v_cache [Bc, Lmax, Hkv, Dh] (tinychat's
     long-context path).  Writes the rotated k into k_cache[b, start_pos + s] and v into v_cache[b, start_pos + s]; returns the rotated
-    q [B, S, H, Dh]."""
+    q [B, S, H, Dh].
+
+    q_norm / k_norm (keyword-only, both or neither; [Dh], float32 or the input's dtype) and norm_eps: every q head and every k head is
+    RMS-normalised over Dh before the rotation, in the same launch (C-ABI `_qknorm` sibling; Qwen3, Gemma-3) -- y = T((x * rsqrt(mean(x^2)
+    + norm_eps)) * gamma), `rmsnorm`'s arithmetic on the head as a row.  v is untouched."""
+    _norm_pair("rope_kv_store_natural", q_norm, k_norm)
     _on_gpu(qkv, freqs, k_cache, v_cache)
     if k_cache.device != qkv.device or v_cache.device != qkv.device or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
         raise ValueError("rope_kv_store_natural: the caches must have the device and dtype of the input")
     if v_cache.dim() != 4 or k_cache.shape != v_cache.shape or not v_cache.is_contiguous() or not k_cache.is_contiguous():
         raise ValueError("rope_kv_store_natural: contiguous k_cache / v_cache [Bc, Lmax, Hkv, Dh] of one shape are expected")
-    return _rope_store("rope_kv_store_natural", qkv, freqs, _Kv(k_cache, v_cache), nheads, nheads_kv, start_pos=start_pos)
+    return _rope_store("rope_kv_store_natural", qkv, freqs, _Kv(k_cache, v_cache), nheads, nheads_kv, start_pos=start_pos,
+                       norm=_qk_norm("rope_kv_store_natural", qkv, v_cache.shape[3], q_norm, k_norm, norm_eps))
 
 
 def attn_prefill_ftcache(q, k_cache, v_cache, kv_start: int, seqlen_k: int, softmax_scale=None, causal: bool = True):
