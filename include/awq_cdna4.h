@@ -131,8 +131,8 @@ int awq_w4a16_mlp_gate_up_cdna4(const void* x, const void* qweight_gate_up, cons
 /* QuantLlamaMLP.our_llama_mlp for ANY row count (tinychat/modules/fused_mlp.py:36-83: decode = two gemv_forward_cuda_new + F.silu +
  * multiply, prefill = two gemm_forward_cuda_new + F.silu + multiply) on the pair as llm_awq_amd.fused_mlp stacks it: gate and up
  * rows interleaved 8 + 8 inside every 16-row slab (n2 = 2 * intermediate rows).  out[m, n2/2] = T(T(silu(x.Wg^T)) * (x.Wu^T)).
- * m <= 8: one streaming launch (sz_half if given, else sz_packed); m > 8: the prefill tile kernels with the SiLU * mul tail fused
- * into their epilogue -- the [m, n2] intermediate is never written.  sz_half may be NULL. */
+ * The [m, n2] intermediate is never written, whichever kernel serves the row count: linear_route (csrc/awq_linear_route.hpp) holds
+ * the rule, awq_w4a16_linear_route_cdna4 (entry 4) answers it for a call.  sz_half may be NULL. */
 int awq_w4a16_mlp_gate_up_forward_cdna4(const void* x, const void* qweight_interleaved, const void* sz_packed, const void* sz_half,
                                         void* out, int m, int n2, int k, int group_size, int dtype, void* stream);
 /* the same with an optional scratch buffer (awq_w4a16_mlp_gate_up_forward_cdna4_workspace_bytes, 64-byte aligned; NULL / too small: ignored): with it
@@ -141,7 +141,8 @@ size_t awq_w4a16_mlp_gate_up_forward_cdna4_workspace_bytes(int m, int n2, int k)
 int awq_w4a16_mlp_gate_up_forward_cdna4_ws(const void* x, const void* qweight_interleaved, const void* sz_packed, const void* sz_half, void* out, int m,
                                            int n2, int k, int group_size, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
-/* gemm / WQLinear.forward dispatch on cdna4-interleaved weights (any m >= 1; m <= 16 runs the GEMV) */
+/* gemm / WQLinear.forward dispatch on cdna4-interleaved weights (any m >= 1): which kernel serves a call is linear_route's answer
+ * (csrc/awq_linear_route.hpp; query: awq_w4a16_linear_route_cdna4) */
 /* RMSNorm fused in front of the quantised linear: replaces the FTLlamaRMSNorm launch
  * (tinychat/modules/fused_norm.py:7-21 -> awq/kernels/csrc/layernorm/layernorm.cu:39-61, layernorm_forward_cuda) followed by
  * WQLinear.forward / QuantLlamaMLP's gate/up pair.  x is the UN-normalised activation [m, k], gamma the norm weight [k]:
@@ -215,6 +216,16 @@ int awq_w4a16_decode_cdna4_plan(int m, int n, int k, int epilogue, int* kernel);
  * chunk: 0, 0, 0, 0, 0, block shape x 8 + x pieces staged per step (shape 0 = 8 waves x 1 slab, 1 = 16 x 1, 2 = 8 x 2, 3 = 8 x 7; pieces 1 - 4) }.
  * out may be NULL. */
 int awq_w4a16_decode_cdna4_plan_detail(int m, int n, int k, int epilogue, int chunk, int out[8]);
+/* Which launcher serves a call of one of the six dense W4 cdna4 entries below -- the route the entry itself switches on (linear_route,
+ * csrc/awq_linear_route.hpp: the one place where the rules are written; tests/linear_route_cases.py pins it).  entry: 0 awq_w4a16_forward_cdna4,
+ * 1 ..._forward_cdna4_szh, 2 awq_w4a16_gemm_cdna4, 3 awq_w4a16_gemv_cdna4, 4 awq_w4a16_mlp_gate_up_forward_cdna4_ws (n = n2), 5 awq_w4a16_partial_cdna4.
+ * flags, the facts about the call's pointers: 1 sz_packed given, 2 sz_half given and 16-byte aligned, 4 bias given, 8 workspace given, 16 the
+ * workspace is 64-byte aligned and at least the entry's ..._workspace_bytes (read by entry 4).  Returns the leaf: 1 streaming decode kernel,
+ * 2 register-ring GEMV, 3 mid-M kernel, 4 skinny kernel's 16-row form, 5 skinny kernel, 6 skinny gate/up form, 7 tile kernels, 8 the generic
+ * launch (launch_gemm / the entry-3 GEMV); 0 = the entry refuses these arguments (out untouched).  out = { leaf, scale format (0 sz_packed,
+ * 1 sz_half), epilogue (0 plain / bias, 1 SiLU * mul pair, 2 fp32 partial), bias (0 none, 1 fused, 2 a separate bias-add launch), workspace
+ * handed on, bias must be 16-byte aligned, deciding row of the entry's table, 0 }.  out may be NULL.  Host only. */
+int awq_w4a16_linear_route_cdna4(int entry, int m, int n, int k, int flags, int out[8]);
 int awq_w4a16_gemm_cdna4(const void* x, const void* qweight_cdna4, const void* scales, const void* scaled_zeros,
                          const void* sz_packed, void* out, int m, int n, int k, int group_size, int dtype,
                          void* workspace, size_t workspace_bytes, void* stream);

@@ -53,6 +53,7 @@ SIGNATURES = {
     "awq_w4a16_gemm_cdna4_narrow_kernel": (_i, [_i, _i, _i, _i, _i, _i]),
     "awq_w4a16_decode_cdna4_plan": (_i, [_i, _i, _i, _i, _vp]),
     "awq_w4a16_decode_cdna4_plan_detail": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "awq_w4a16_linear_route_cdna4": (_i, [_i, _i, _i, _i, _i, _vp]),
     "awq_w4a16_gemm_cdna4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awq_w4a16_forward_cdna4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awq_w4a16_forward_cdna4_szh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

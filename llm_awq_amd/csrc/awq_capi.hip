@@ -35,7 +35,42 @@ int check_common(const void* x, const void* qweight, const void* scales, const v
     return AWQ_ERR_ALIGN;
   return AWQ_OK;
 }
+
+// Steps 2 - 5 of a dense W4 cdna4 entry, behind its own argument checks: the route (awq_linear_route.hpp), the ONE launcher of its leaf, the separate bias
+// launch where the route says so.  No fall-through: a launcher cannot refuse a call its own predicate routed to it (tests/linear_route_check.cpp).
+int launch_routed(int entry, const void* x, const void* qw, const void* scales, const void* zeros, const void* szp, const void* szh, const void* bias, void* out, int m,
+                  int n, int k, int dtype, void* ws, size_t ws_bytes, int flags, hipStream_t st) {
+  using namespace awq;
+  const LinearRoute r = linear_route(entry, m, n, k, flags, device_cu_count(), g_linear);
+  if (r.bias_align16 && bias && !aligned16(bias)) return AWQ_ERR_ALIGN;
+  const void *sz = r.szfmt ? szh : szp, *b = r.bias == kBiasFused ? bias : nullptr;
+  const int pair = r.epilogue == kEpiPair ? 2 : 0, f32 = r.epilogue == kEpiPartial ? 1 : 0;
+  if (!r.ws) ws = nullptr, ws_bytes = 0;
+  int rc = -1;
+  switch (r.leaf) {
+    case kLeafDecode: rc = launch_gemv_dma(x, qw, sz, b, out, m, n, k, pair, dtype, r.szfmt, st, f32); break;
+    case kLeafGemvRing: rc = launch_gemv_cdna4(x, qw, szp, b, out, m, n, k, 0, 4, dtype, st); break;
+    case kLeafMidm: rc = launch_midm_cdna4(x, qw, sz, b, out, m, n, k, pair, dtype, r.szfmt, 4, f32, ws, ws_bytes, st); break;
+    case kLeafSkinny16: rc = launch_skinny_decode(x, qw, sz, b, out, m, n, k, pair, dtype, r.szfmt, st, f32); break;
+    case kLeafSkinny: rc = launch_skinny_cdna4(x, qw, szp, b, out, m, n, k, dtype, st, f32, ws, ws_bytes); break;
+    case kLeafSkinnyGateUp: rc = launch_skinny_gate_up(x, qw, szp, out, m, n, k, dtype, st); break;
+    case kLeafTiles: rc = launch_gemm_cdna4_v3(x, qw, szp, b, out, m, n, k, 0, dtype, ws, ws_bytes, st, 4, pair ? 2 : (f32 ? 3 : 0), r.szfmt ? szh : nullptr); break;
+    case kLeafGeneric:
+      rc = entry == kEntryGemv ? launch_gemv(x, qw, scales, zeros, szp, out, m, n, k, dtype, 1, st) : launch_gemm(x, qw, scales, zeros, szp, out, m, n, k, dtype, 1, ws, ws_bytes, st);
+      break;
+  }
+  if (rc != 0) return AWQ_ERR_SHAPE;
+  if (r.bias == kBiasAdd) launch_bias_add(out, bias, m, n, dtype, st);
+  return finish_launch();
+}
+inline int route_flags(const void* szp, const void* szh, const void* bias, const void* ws) {
+  return (szp ? awq::kHasSzPacked : 0) | (szh ? awq::kHasSzHalf : 0) | (bias ? awq::kHasBias : 0) | (ws ? awq::kHasWs : 0);
+}
 }  // namespace
+
+namespace awq {
+LinearKnobs g_linear;
+}
 
 extern "C" {
 
@@ -89,7 +124,7 @@ int awq_w4a16_forward(const void* x, const void* qweight, const void* scales, co
       check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype) == AWQ_OK && awq::gemv_v2fast_enabled() &&
       awq::launch_gemv_v2fast(x, qweight, scales, scaled_zeros, bias, out, m, n, k, k / 128, dtype, (hipStream_t)stream) == 0)
     return finish_launch();  // bias fused into the decode kernel's epilogue
-  if (m > 8 && m <= 255 && bias && group_size == 128 && awq::gemm_variant_get() == 0 &&
+  if (m > 8 && m <= 255 && bias && group_size == 128 && awq::g_linear.gemm_variant == 0 &&
       check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype) == AWQ_OK &&
       awq::launch_skinny_v2(x, qweight, scales, scaled_zeros, bias, out, m, n, k, k / 128, dtype, (hipStream_t)stream) == 0)
     return finish_launch();  // bias fused into the skinny kernel's epilogue
@@ -208,9 +243,8 @@ int awq_w4a16_gemv_cdna4(const void* x, const void* qweight, const void* scales,
   int st = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
   if (st != AWQ_OK) return st;
   if ((n % 16) != 0) return AWQ_ERR_SHAPE;
-  if (!(sz_packed && m <= 8 && awq::launch_gemv_cdna4(x, qweight, sz_packed, nullptr, out, m, n, k, 0, 4, dtype, (hipStream_t)stream) == 0))
-    awq::launch_gemv(x, qweight, scales, scaled_zeros, sz_packed, out, m, n, k, dtype, 1, (hipStream_t)stream);
-  return finish_launch();
+  return launch_routed(awq::kEntryGemv, x, qweight, scales, scaled_zeros, sz_packed, nullptr, nullptr, out, m, n, k, dtype, nullptr, 0, route_flags(sz_packed, nullptr, nullptr, nullptr),
+                       (hipStream_t)stream);
 }
 
 int awq_w4a16_mlp_gate_up_cdna4(const void* x, const void* qweight_gate_up, const void* sz_packed, void* out, int m,
@@ -226,8 +260,6 @@ int awq_w4a16_mlp_gate_up_cdna4(const void* x, const void* qweight_gate_up, cons
   return finish_launch();
 }
 
-static int g_skinny16_szh = 1;     // knob skinny16_szh: 0 = 9 .. 16 rows on the T-typed sz_packed form as in rounds 1 - 5
-static int g_mlp_skinny_max = 64;  // knob mlp_skinny_max: row counts up to this go to the skinny kernel's fused epilogue (8 = never)
 int awq_w4a16_mlp_gate_up_forward_cdna4(const void* x, const void* qweight_interleaved, const void* sz_packed, const void* sz_half,
                                         void* out, int m, int n2, int k, int group_size, int dtype, void* stream) {
   return awq_w4a16_mlp_gate_up_forward_cdna4_ws(x, qweight_interleaved, sz_packed, sz_half, out, m, n2, k, group_size, dtype, nullptr, 0, stream);
@@ -249,36 +281,10 @@ int awq_w4a16_mlp_gate_up_forward_cdna4_ws(const void* x, const void* qweight_in
   if (n2 < 16 || (n2 % 16) != 0 || k < 128 || (k % 128) != 0 || (size_t)m * (size_t)k >= (1ull << 31)) return AWQ_ERR_SHAPE;
   if (!aligned16(x) || !aligned16(qweight_interleaved) || !aligned16(out) || !aligned16(sz_packed) || (sz_half && !aligned16(sz_half)))
     return AWQ_ERR_ALIGN;
-  if (m <= 8) {  // decode: one streaming launch, rows r and r + 8 of a slab paired in the epilogue
-    if (awq::launch_gemv_dma(x, qweight_interleaved, sz_half ? sz_half : sz_packed, nullptr, out, m, n2, k, 2, dtype, sz_half ? 1 : 0,
-                             (hipStream_t)stream) != 0)
-      return AWQ_ERR_SHAPE;
-    return finish_launch();
-  }
-  // 9 .. 255 rows: the mid-M kernel (x tile shared by the block, waves split N, K split across blocks), rows r and r + 8 of a slab paired in its epilogue
-  if (awq::midm_takes(m, n2, k) &&
-      awq::launch_midm_cdna4(x, qweight_interleaved, sz_half ? sz_half : sz_packed, nullptr, out, m, n2, k, 2, dtype, sz_half ? 1 : 0, 4, 0, workspace, workspace_bytes,
-                             (hipStream_t)stream) == 0)
-    return finish_launch();
-  // 9 .. 16 rows with the layer's sz_half side buffer: the skinny kernel's one-column-block shapes in the f16-mantissa dequant form (the batched-decode instantiations:
-  // the same block shapes as launch_skinny_gate_up picks at <= 16 rows, ~10 VALU fewer per tile -- round 6, third session)
-  if (m <= 16 && sz_half && g_skinny16_szh &&
-      awq::launch_skinny_decode(x, qweight_interleaved, sz_half, nullptr, out, m, n2, k, 2, dtype, 1, (hipStream_t)stream, 0) == 0)
-    return finish_launch();
-  // (knob midm = 0) 9 .. 64 rows: one weight pass on the skinny kernel, rows r and r + 8 of a slab paired in its epilogue (a 256-row tile masked down to m rows costs
-  // the same for every m: 46 vs 31 us at 64 rows on Llama-3-8B's pair, profiles/r05_skinny_splitk.txt)
-  if (m <= g_mlp_skinny_max && awq::launch_skinny_gate_up(x, qweight_interleaved, sz_packed, out, m, n2, k, dtype, (hipStream_t)stream) == 0)
-    return finish_launch();
-  // prefill / batched decode: the tile kernels with the SiLU * mul tail fused into their epilogue (out is [m, n2 / 2]: the
-  // [m, n2] intermediate of the reference's two GEMMs + F.silu + multiply never exists)
-  if (workspace && ((reinterpret_cast<uintptr_t>(workspace) & 63) != 0 || workspace_bytes < awq::gemm_cdna4_v3_workspace_bytes(m, n2, k))) {
-    workspace = nullptr;  // (optional scratch: without it the columns behind the full rounds run as 256 x 128 blocks)
-    workspace_bytes = 0;
-  }
-  if (awq::launch_gemm_cdna4_v3(x, qweight_interleaved, sz_packed, nullptr, out, m, n2, k, 0, dtype, workspace, workspace_bytes, (hipStream_t)stream, 4, 2,
-                                sz_half) != 0)
-    return AWQ_ERR_SHAPE;
-  return finish_launch();
+  // (a workspace that is misaligned or below the tile kernels' size is dropped by their row only: the mid-M row before it is offered the workspace as it came)
+  const bool ws_tiles = workspace && m > 8 && (reinterpret_cast<uintptr_t>(workspace) & 63) == 0 && workspace_bytes >= awq::gemm_cdna4_v3_workspace_bytes(m, n2, k);
+  return launch_routed(awq::kEntryGateUp, x, qweight_interleaved, nullptr, nullptr, sz_packed, sz_half, nullptr, out, m, n2, k, dtype, workspace, workspace_bytes,
+                       route_flags(sz_packed, sz_half, nullptr, workspace) | (ws_tiles ? awq::kWsTiles : 0), (hipStream_t)stream);
 }
 
 int awq_w4a16_rmsnorm_forward_cdna4(const void* x, const void* gamma, float eps, const void* qweight, const void* sz_packed,
@@ -1412,10 +1418,23 @@ int awq_layernorm_quant(const void* x, const void* gamma, const void* beta, floa
   return finish_launch();
 }
 
+// The scratch a caller of the forward entries should bring: the largest any leaf of its row class can use -- NOT always what the routed leaf uses: the first row
+// speaks for the mid-M kernel whenever midm_takes accepts the shape, also where a forward row in front of it decides (no sz_packed: the generic kernels;
+// gemm_variant != 0), and the third for the tile kernels on calls launch_gemm keeps on its generic kernels.  Pinned by tests/linear_route_cases.py.
 size_t awq_w4a16_forward_cdna4_workspace_bytes(int m, int n, int k) {
   if (awq::midm_takes(m, n, k)) return awq::midm_workspace_bytes(m, n, k);  // 9 .. 255 rows: the fp32 parts of the mid-M kernel's K split
   if (m > 8 && m < 256 && !awq::gemm_cdna4_v3_takes(m, k)) return awq::skinny_splitk_workspace_bytes(m, n, k);  // (knob midm = 0) the skinny launch's K split
   return awq::gemm_cdna4_v3_workspace_bytes(m, n, k);
+}
+// The route of a call of entry `entry` (LinearEntry) with pointer facts `flags` (LinearFlags): returns the leaf (LinearLeaf; 0 = the entry refuses the arguments or
+// no launcher serves them) and writes leaf, scale format, epilogue, bias handling, workspace handed on, bias read as 16-byte vectors, deciding row, 0
+int awq_w4a16_linear_route_cdna4(int entry, int m, int n, int k, int flags, int out[8]) {
+  if (entry < awq::kEntryForward || entry > awq::kEntryPartial || flags < 0 || flags > 31 || m < 1 || n < 16 || (n % 16) != 0 || k < 128 || (k % 128) != 0) return 0;
+  if ((entry == awq::kEntryGemv && m > 16) || (entry == awq::kEntryGateUp && (size_t)m * (size_t)k >= (1ull << 31))) return 0;
+  const awq::LinearRoute r = awq::linear_route(entry, m, n, k, flags, awq::device_cu_count(), awq::g_linear);
+  const int w[8] = {r.leaf, r.szfmt, r.epilogue, r.bias, r.ws ? 1 : 0, r.bias_align16 ? 1 : 0, r.row, 0};
+  for (int i = 0; out != nullptr && r.leaf != awq::kLeafNone && i < 8; ++i) out[i] = w[i];
+  return r.leaf;
 }
 int awq_midm_init(void) { return awq::midm_init() == 0 ? AWQ_OK : AWQ_ERR_LAUNCH; }
 int awq_w4a16_gemm_cdna4_pair_plan(int m, int n, int k) { return awq::gemm_cdna4_v3_pair_plan(m, n, k); }
@@ -1433,77 +1452,28 @@ int awq_w4a16_gemm_cdna4(const void* x, const void* qweight, const void* scales,
   int st = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
   if (st != AWQ_OK) return st;
   if ((n % 16) != 0) return AWQ_ERR_SHAPE;
-  const bool skinny = sz_packed && m > 8 && m < 256 && awq::gemm_variant_get() == 0 && !awq::gemm_cdna4_v3_takes(m, k) &&
-                      awq::launch_skinny_cdna4(x, qweight, sz_packed, nullptr, out, m, n, k, dtype, (hipStream_t)stream, 0, workspace, workspace_bytes) == 0;
-  if (!skinny && !(sz_packed && m <= 8 && awq::launch_gemv_cdna4(x, qweight, sz_packed, nullptr, out, m, n, k, 0, 4, dtype, (hipStream_t)stream) == 0))
-    awq::launch_gemm(x, qweight, scales, scaled_zeros, sz_packed, out, m, n, k, dtype, 1, workspace, workspace_bytes, (hipStream_t)stream);
-  return finish_launch();
+  return launch_routed(awq::kEntryGemm, x, qweight, scales, scaled_zeros, sz_packed, nullptr, nullptr, out, m, n, k, dtype, workspace, workspace_bytes,
+                       route_flags(sz_packed, nullptr, nullptr, workspace), (hipStream_t)stream);
 }
 
 int awq_w4a16_forward_cdna4_szh(const void* x, const void* qweight, const void* scales, const void* scaled_zeros, const void* sz_packed,
                                 const void* sz_half, const void* bias, void* out, int m, int n, int k, int group_size, int dtype, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-  if (sz_half && sz_packed && group_size == 128 && aligned16(sz_half) && awq::midm_takes(m, n, k)) {
-    // 9 .. 255 rows with the layer's sz_half side buffer: the mid-M kernel in the f16-mantissa dequant form
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if (bias && !aligned16(bias)) return AWQ_ERR_ALIGN;
-    if (awq::launch_midm_cdna4(x, qweight, sz_half, bias, out, m, n, k, 0, dtype, 1, 4, 0, workspace, workspace_bytes, (hipStream_t)stream) == 0) return finish_launch();
-  }
-  if (sz_half && sz_packed && m >= 9 && m <= 16 && group_size == 128 && g_skinny16_szh && awq::gemm_variant_get() == 0 && aligned16(sz_half) && (n % 16) == 0) {
-    // 9 .. 16 rows with the layer's sz_half side buffer: the skinny kernel's one-column-block shapes in the f16-mantissa dequant form
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if (bias && !aligned16(bias)) return AWQ_ERR_ALIGN;
-    if (awq::launch_skinny_decode(x, qweight, sz_half, bias, out, m, n, k, 0, dtype, 1, (hipStream_t)stream, 0) == 0) return finish_launch();
-  }
-  if (sz_half && sz_packed && m >= 256 && group_size == 128 && awq::gemm_variant_get() == 0 && aligned16(sz_half)) {
-    // prefill with the layer's sz_half side buffer: the tile kernels dequantise in the f16-mantissa form (every block width, the block pairs included)
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if ((n % 16) != 0 || (bias && !aligned16(bias))) return (n % 16) ? AWQ_ERR_SHAPE : AWQ_ERR_ALIGN;
-    if (awq::launch_gemm_cdna4_v3(x, qweight, sz_packed, bias, out, m, n, k, 0, dtype, workspace, workspace_bytes, (hipStream_t)stream, 4, 0, sz_half) == 0)
-      return finish_launch();
-  }
-  return awq_w4a16_forward_cdna4(x, qweight, scales, scaled_zeros, sz_packed, bias, out, m, n, k, group_size, dtype, workspace, workspace_bytes, stream);
+  int st = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
+  if (st != AWQ_OK) return st;
+  if ((n % 16) != 0) return AWQ_ERR_SHAPE;
+  return launch_routed(awq::kEntryForwardSzh, x, qweight, scales, scaled_zeros, sz_packed, sz_half, bias, out, m, n, k, dtype, workspace, workspace_bytes,
+                       route_flags(sz_packed, aligned16(sz_half) ? sz_half : nullptr, bias, workspace), (hipStream_t)stream);  // (a misaligned sz_half: the sz_packed path)
 }
 
 int awq_w4a16_forward_cdna4(const void* x, const void* qweight, const void* scales, const void* scaled_zeros,
                             const void* sz_packed, const void* bias, void* out, int m, int n, int k, int group_size,
                             int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (m <= 8 && sz_packed && group_size == 128) {  // decode: bias fused into the GEMV epilogue
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if ((n % 16) != 0) return AWQ_ERR_SHAPE;
-    if (awq::launch_gemv_cdna4(x, qweight, sz_packed, bias, out, m, n, k, 0, 4, dtype, (hipStream_t)stream) == 0) return finish_launch();
-  }
-  if (sz_packed && group_size == 128 && awq::gemm_variant_get() == 0 && awq::midm_takes(m, n, k)) {
-    // 9 .. 255 rows: the mid-M kernel, bias fused
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if (bias && !aligned16(bias)) return AWQ_ERR_ALIGN;
-    if (awq::launch_midm_cdna4(x, qweight, sz_packed, bias, out, m, n, k, 0, dtype, 0, 4, 0, workspace, workspace_bytes, (hipStream_t)stream) == 0) return finish_launch();
-  }
-  if (m > 8 && m < 256 && sz_packed && group_size == 128 && awq::gemm_variant_get() == 0 && !awq::gemm_cdna4_v3_takes(m, k)) {
-    // (knob midm = 0) short prompts / batched decode: skinny kernel, bias fused
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if ((n % 16) != 0) return AWQ_ERR_SHAPE;
-    if (awq::launch_skinny_cdna4(x, qweight, sz_packed, bias, out, m, n, k, dtype, (hipStream_t)stream, 0, workspace, workspace_bytes) == 0) return finish_launch();
-  }
-  if (bias && awq::gemm_cdna4_v3_takes(m, k) && sz_packed && group_size == 128 && awq::gemm_variant_get() == 0) {
-    // prefill: bias fused into the prefill GEMM epilogue (awq_gemm_v4.hip / awq_gemm_v4n.hip) (no second kernel)
-    int st0 = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
-    if (st0 != AWQ_OK) return st0;
-    if ((n % 16) != 0 || !aligned16(bias)) return (n % 16) ? AWQ_ERR_SHAPE : AWQ_ERR_ALIGN;
-    if (awq::launch_gemm_cdna4_v3(x, qweight, sz_packed, bias, out, m, n, k, 0, dtype, workspace, workspace_bytes, (hipStream_t)stream) == 0)
-      return finish_launch();
-  }
-  int st = awq_w4a16_gemm_cdna4(x, qweight, scales, scaled_zeros, sz_packed, out, m, n, k, group_size, dtype, workspace,
-                                workspace_bytes, stream);  // m <= 16 is routed to the GEMV inside
-  if (st != AWQ_OK || !bias) return st;
-  awq::launch_bias_add(out, bias, m, n, dtype, (hipStream_t)stream);
-  return finish_launch();
+  int st = check_common(x, qweight, scales, scaled_zeros, out, m, n, k, group_size, dtype);
+  if (st != AWQ_OK) return st;
+  if ((n % 16) != 0) return AWQ_ERR_SHAPE;
+  return launch_routed(awq::kEntryForward, x, qweight, scales, scaled_zeros, sz_packed, nullptr, bias, out, m, n, k, dtype, workspace, workspace_bytes,
+                       route_flags(sz_packed, nullptr, bias, workspace), (hipStream_t)stream);
 }
 
 // ---- tensor-parallel row split: the K shard's fp32 partial + the single rounding after the sum ----
@@ -1514,20 +1484,8 @@ int awq_w4a16_partial_cdna4(const void* x, const void* qweight, const void* sz_p
   if (group_size != 128) return AWQ_ERR_GROUP;
   if (m < 1 || n < 16 || k < 128 || (n % 16) != 0 || (k % 128) != 0) return AWQ_ERR_SHAPE;
   if (!aligned16(x) || !aligned16(qweight) || !aligned16(out_f32) || !aligned16(sz_packed) || !aligned16(sz_half)) return AWQ_ERR_ALIGN;
-  const hipStream_t st = (hipStream_t)stream;
-  if (m <= 8) {  // decode: the streaming kernel (or the skinny kernel where it takes the row count), f16-mantissa dequant when the layer allows it
-    if (awq::launch_gemv_dma(x, qweight, sz_half ? sz_half : sz_packed, nullptr, out_f32, m, n, k, 0, dtype, sz_half ? 1 : 0, st, 1) == 0) return finish_launch();
-    if (awq::launch_skinny_decode(x, qweight, sz_packed, nullptr, out_f32, m, n, k, 0, dtype, 0, st, 1) == 0) return finish_launch();
-    return AWQ_ERR_SHAPE;
-  }
-  if (awq::midm_takes(m, n, k) &&
-      awq::launch_midm_cdna4(x, qweight, sz_half ? sz_half : sz_packed, nullptr, out_f32, m, n, k, 0, dtype, sz_half ? 1 : 0, 4, 1, nullptr, 0, st) == 0)
-    return finish_launch();
-  if (m < 256 && !awq::gemm_cdna4_v3_takes(m, k)) {
-    if (awq::launch_skinny_cdna4(x, qweight, sz_packed, nullptr, out_f32, m, n, k, dtype, st, 1) == 0) return finish_launch();
-  }
-  if (awq::launch_gemm_cdna4_v3(x, qweight, sz_packed, nullptr, out_f32, m, n, k, 0, dtype, nullptr, 0, st, 4, 3) != 0) return AWQ_ERR_SHAPE;
-  return finish_launch();
+  return launch_routed(awq::kEntryPartial, x, qweight, nullptr, nullptr, sz_packed, sz_half, nullptr, out_f32, m, n, k, dtype, nullptr, 0, route_flags(sz_packed, sz_half, nullptr, nullptr),
+                       (hipStream_t)stream);
 }
 
 int awq_round_bias_f32(const float* in_f32, const void* bias, void* out, int m, int n, int dtype, void* stream) {
@@ -2048,8 +2006,19 @@ int awq_tune_set(const char* key, int value) {
   // can change the summation order of results, so a default process cannot reach them: AWQ_TUNING=1 in the environment opts in
   const char* gate = getenv("AWQ_TUNING");
   if (!gate || gate[0] != '1') return AWQ_ERR_SHAPE;
+  using K = awq::LinearKnobs;
+  static const struct {
+    const char* key;
+    int K::*knob;
+  } kLinear[] = {{"gemm_variant", &K::gemm_variant}, {"midm", &K::midm}, {"midm_min", &K::midm_min}, {"midm_max", &K::midm_max}, {"midm_waves", &K::midm_waves},
+                 {"midm_ns", &K::midm_ns}, {"midm_ks", &K::midm_ks}, {"gemm_small_m", &K::gemm_small_m}, {"gemm_v4", &K::gemm_v4}, {"gemv_dma", &K::gemv_dma},
+                 {"mlp_skinny_max", &K::mlp_skinny_max}, {"skinny16_szh", &K::skinny16_szh}};
+  for (const auto& e : kLinear)
+    if (!strcmp(key, e.key)) {
+      awq::g_linear.*e.knob = value;
+      return AWQ_OK;
+    }
   if (awq::gemv_tune_set(key, value) == 0) return AWQ_OK;
-  if (awq::gemm_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::gemv_cdna4_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::skinny_tune_set(key, value) == 0) return AWQ_OK;
   if (awq::midm_tune_set(key, value) == 0) return AWQ_OK;
@@ -2060,14 +2029,6 @@ int awq_tune_set(const char* key, int value) {
   if (awq::w8a8_tune_set(key, value) == 0) return AWQ_OK;
   if (!strcmp(key, "w3_skinny_max")) {
     g_w3_skinny_max = value;
-    return AWQ_OK;
-  }
-  if (!strcmp(key, "mlp_skinny_max")) {
-    g_mlp_skinny_max = value;
-    return AWQ_OK;
-  }
-  if (!strcmp(key, "skinny16_szh")) {
-    g_skinny16_szh = value;
     return AWQ_OK;
   }
   return AWQ_ERR_SHAPE;

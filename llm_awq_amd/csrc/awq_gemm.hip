@@ -382,22 +382,11 @@ int launch_moe_gemm(const void* x, const void* qw, const void* s, const void* z,
   return 0;
 }
 
-namespace {
-int g_gemm_variant = 0;  // 0 = auto, 1 = force 128x128, 2 = force 256x256, 3 = force 256x256 v3 (cdna4 layout)
-}
-int gemm_variant_get() { return g_gemm_variant; }
-int gemm_tune_set(const char* key, int value) {
-  if (!strcmp(key, "gemm_variant")) {
-    g_gemm_variant = value;
-    return 0;
-  }
-  return -1;
-}
-
+// (knob gemm_variant, g_linear: 0 = auto, 1 = force 128x128, 2 = force 256x256, 3 = force 256x256 v3 (cdna4 layout))
 template <typename DT, int LAYOUT>
 static int launch_gemm_t(const void* x, const void* qw, const void* s, const void* z, void* out, int m, int n, int k,
                          hipStream_t st) {
-  const bool big = g_gemm_variant == 2 || (g_gemm_variant == 0 && m > 128);
+  const bool big = g_linear.gemm_variant == 2 || (g_linear.gemm_variant == 0 && m > 128);
   if (big) {
     const int tiles_m = (m + TM - 1) / TM, tiles_n = (n + TN - 1) / TN;
     auto kern = gemm_w4a16_256x256_kernel<DT, LAYOUT>;
@@ -416,14 +405,14 @@ static int launch_gemm_t(const void* x, const void* qw, const void* s, const voi
 
 int launch_gemm(const void* x, const void* qw, const void* s, const void* z, const void* szp, void* out, int m, int n,
                 int k, int dtype, int layout, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (layout == 0 && g_gemm_variant == 0 && m > 8 && m <= 255 &&
+  if (layout == 0 && g_linear.gemm_variant == 0 && m > 8 && m <= 255 &&
       launch_skinny_v2(x, qw, s, z, nullptr, out, m, n, k, k / kGroup, dtype, st) == 0)
     return 0;  // short prompts / batched decode on un-repacked (fp16) checkpoints
   if (m <= 16) return launch_gemv(x, qw, s, z, szp, out, m, n, k, dtype, layout, st);
   if (layout == 1) {
     // variant 3 / auto: v3 kernel with the tile width picked by chip fill; 4 = force 256 x 256; 5 = force 256 x 128
-    if ((g_gemm_variant >= 3 || (g_gemm_variant == 0 && gemm_cdna4_v3_takes(m, k))) &&
-        launch_gemm_cdna4_v3(x, qw, szp, nullptr, out, m, n, k, g_gemm_variant == 4 ? 256 : (g_gemm_variant == 5 ? 128 : 0), dtype, ws, ws_bytes, st) == 0)
+    if ((g_linear.gemm_variant >= 3 || (g_linear.gemm_variant == 0 && tiles_take(m, k, g_linear))) &&
+        launch_gemm_cdna4_v3(x, qw, szp, nullptr, out, m, n, k, g_linear.gemm_variant == 4 ? 256 : (g_linear.gemm_variant == 5 ? 128 : 0), dtype, ws, ws_bytes, st) == 0)
       return 0;
     return dtype == 0 ? launch_gemm_t<F16, 1>(x, qw, s, z, out, m, n, k, st) : launch_gemm_t<BF16, 1>(x, qw, s, z, out, m, n, k, st);
   }

@@ -15,14 +15,12 @@ namespace awq {
 namespace {
 constexpr int TM = 256;
 constexpr double kNarrowRate = 0.80;  // 256 x 128 tiles (awq_gemm_v4n.hip) vs 256 x 256 (awq_gemm_v6.hip) at equal chip fill (0.83 against awq_gemm_v4.hip, profiles/r01_gemm_v4.txt)
-int g_small_m = 1;  // knob gemm_small_m: 0 = the prefill GEMM only takes m >= 256 (see gemm_cdna4_v3_takes)
 int g_splitk = 1;  // narrow tiles: split K over blocks when the tiles fill less than half of the chip and a workspace is given
 int g_v6 = 1;  // 1 (default): 256-wide tiles of m >= 256 run awq_gemm_v6.hip (one software-pipelined wave per SIMD); 0 (tests): awq_gemm_v4n.hip's 128-wide tiles
 int g_tile_n = 0;  // knob gemm_tile_n: 128 / 256 force one tile width for callers that pass tile_n = 0 (tests of a specific kernel)
 int g_v6_192 = 1;  // knob gemm_v6_192: 0 = no 192-wide blocks in the tile plan
 int g_v6_pair = 1;  // knob gemm_v6_pair: K split over pairs of 256 x 256 blocks where the 256-wide tiles fill at most half the chip (needs the workspace)
 int g_v6_szh = 1;  // knob gemm_v6_szh: 1 = v6 dequantises in the f16-mantissa form when the caller hands its sz_half buffer (QuantLlamaMLP's gate/up launch): -40 VALU per K tile; neutral in round 2, +0.1-0.3 % at M = 2048 / +0.5-1.2 % at M = 4096 on the power-limited round-4 loop (profiles/r04_v6_szh_ab.txt)
-int g_v4 = 1;  // knob gemm_v4: 0 = the tile kernels take no m below 256 (the skinny kernel serves 9 .. 255 rows); the loop it once selected is gone
 void launch_wide(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int n_begin,
                  int n_end, int dtype, hipStream_t st, int bits, int epi, const void* szh = nullptr, int tile_n = 256) {
   if (g_v6 && m >= 256) {  // (szh: the caller's sz_half side buffer, reported exact for this layer -> the f16-mantissa dequant form, every block width)
@@ -72,7 +70,6 @@ bool moe_v6_enabled() { return g_moe_v6 != 0; }
 int gemm_v3_tune_set(const char* key, int value) {
   if (!strcmp(key, "moe_v6")) g_moe_v6 = value;
   else if (!strcmp(key, "moe_tail")) moe_v6_set_tail(value);
-  else if (!strcmp(key, "gemm_v4")) g_v4 = value;
   else if (!strcmp(key, "gemm_v6")) {  // units: 0 off, 1 = the 256-wide tiles, 2 = every tile; tens (probe builds): timing-only probe of the kernel
     g_v6 = value % 10;
     gemm_v6_set_probe(value / 10);
@@ -85,7 +82,6 @@ int gemm_v3_tune_set(const char* key, int value) {
   else if (!strcmp(key, "gemm_v6_192")) g_v6_192 = value;
   else if (!strcmp(key, "gemm_v6_128")) g_v6_128 = value;
   else if (!strcmp(key, "moe_v4")) g_moe_v4 = value;
-  else if (!strcmp(key, "gemm_small_m")) g_small_m = value;
   else if (!strcmp(key, "gemm_splitk_cap")) g_v4n_ksplit_cap = value;
   else if (!strcmp(key, "gemm_splitk")) {  // 0 = off, 1 = auto, n > 1 = force n K ranges
     g_splitk = value;
@@ -128,19 +124,12 @@ Plan plan_tiles(int m, int n, int tile_n, bool allow192 = false) {
 }
 }  // namespace
 
-// Which m the prefill GEMM takes.  m >= 256 always; below that the narrow-tile kernel runs ONE row tile whose missing rows are
-// not stored, at the cost of a 256-row tile whatever m is, while the skinny kernel (awq_skinny_cdna4.hip) re-streams and
-// re-dequantises the weights once per 64 rows: the crossover measured on the Llama shapes (profiles/r01_small_m_sweep.txt) sits
-// at m ~ 75 for K >= 8192 and ~150 for K = 4096, which m * K >= 0.6 M approximates; at m = 255 the GEMM is 1.6 - 3.1x faster.
-bool gemm_cdna4_v3_takes(int m, int k) {
-  if (m >= TM) return true;
-  if (g_small_m == 2) return g_v4 && m > 8;  // experiments: every m the skinny kernel would take
-  return g_small_m && g_v4 && m >= 72 && (long)m * k >= 600000;
-}
+// Which m the prefill GEMM takes: tiles_take (awq_linear_route.hpp), at the knobs of this process
+bool gemm_cdna4_v3_takes(int m, int k) { return tiles_take(m, k, g_linear); }
 
 // fp32 workspace the call below can use to split K when its tiles under-fill the chip (0 = none needed)
 size_t gemm_cdna4_v3_workspace_bytes(int m, int n, int k) {
-  if (!gemm_cdna4_v3_takes(m, k) || (n % 16) != 0 || (k % 128) != 0 || !g_v4 || !g_splitk) return 0;
+  if (!gemm_cdna4_v3_takes(m, k) || (n % 16) != 0 || (k % 128) != 0 || !g_linear.gemm_v4 || !g_splitk) return 0;
   if (gemm_cdna4_v3_pair_plan(m, n, k)) return gemm_v6_pair_workspace_bytes(m, n, k);
   if (m < TM) return gemm_v4n_workspace_bytes(m, n, k);
   const Plan p = plan_tiles(m, n, 0);
@@ -190,8 +179,7 @@ int gemm_cdna4_v3_narrow_kernel(int m, int n_cols, int k, int bits, int has_work
 
 int launch_gemm_cdna4_v3(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
                          int tile_n, int dtype, void* ws, size_t ws_bytes, hipStream_t st, int bits, int epi, const void* szh) {
-  // (w3c tiles have no skinny kernel: the masked single-row-tile path of the narrow kernel serves every m > 8)
-  if (!szp || !(gemm_cdna4_v3_takes(m, k) || ((bits == 3 || epi) && m > 8)) || (n % 16) != 0 || (k % 128) != 0 || (size_t)m * (size_t)k >= (1ull << 31)) return -1;
+  if (!tiles_serve(m, n, k, bits, epi, szp != nullptr, g_linear)) return -1;
   // tiles that fill at most half the chip and a long K: pairs of 256 x 256 blocks, each half of K, combined inside the launch (needs the workspace)
   const bool use_szh = szh != nullptr && bits == 4 && g_v6_szh;
   if (g_v6 && g_v6_pair && g_splitk && (bits == 4 || bits == 3) && (epi == 0 || epi == 2) && !tile_n && !g_tile_n && ws != nullptr &&

@@ -407,7 +407,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv_dma_kernel_m1(const uint16_t*
 }
 
 namespace {
-DecodeKnobs g_knobs;  // awq_tune_set (tests, tools); the rules that read them: awq_decode_plan.hpp
+DecodeKnobs& g_knobs = g_linear.decode;  // awq_tune_set (tests, tools); the rules that read them: awq_decode_plan.hpp
 }  // namespace
 
 int gemv_dma_tune_set(const char* key, int value) {
@@ -507,10 +507,7 @@ int gemv_dma_plan_detail(int m, int n, int k, int epi, int chunk, int out[8]) {
 // epi as in the kernel header; returns -1 if the shape is not served.  One launch per chunk of the plan, each a pass over the weights.
 int launch_gemv_dma(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi,
                     int dtype, int szfmt, hipStream_t st, int f32out) {
-  if (f32out && (epi != 0 || bias != nullptr)) return -1;
-  DecodeKnobs knobs = g_knobs;
-  if (!szp || (epi == 2 && bias)) knobs.skinny_from = 9;  // (what launch_skinny_decode does not serve stays on the streaming kernel)
-  const DecodePlan p = decode_plan(m, n, k, epi, device_cu_count(), knobs);
+  const DecodePlan p = decode_leaf_plan(m, n, k, epi, szp != nullptr, bias != nullptr, f32out != 0, device_cu_count(), g_linear);  // (decode_serves: its .served)
   if (!p.served) return -1;
   const size_t ncols = epi ? (size_t)n / 2 : (size_t)n;
   for (int i = 0, r = 0; i < p.nchunks; r += p.chunk[i].rows, ++i) {  // r: the chunk's first row

@@ -6,7 +6,11 @@
 
 #include <atomic>
 
+#include "awq_linear_route.hpp"
+
 namespace awq {
+// every knob the routes of the dense W4 cdna4 entries read (awq_linear_route.hpp); awq_tune_set writes it, the launchers and the entries read it (awq_capi.hip)
+extern LinearKnobs g_linear;
 // Kernels that use more than 64 KiB of dynamic LDS must be opted in with hipFuncSetAttribute, and the attribute belongs to the
 // (kernel, DEVICE) pair: a single-process multi-GPU caller (the reference's accelerate layer placement, awq/entry.py:167-186)
 // launches the same kernel on several devices.  One LdsOptIn per kernel instantiation remembers, per device ordinal, that the
@@ -94,7 +98,6 @@ int launch_gemm_cdna4_v3(const void* x, const void* qw, const void* szp, const v
                          int tile_n, int dtype, void* ws, size_t ws_bytes, hipStream_t st, int bits = 4, int epi = 0, const void* szh = nullptr);
 // epi 2: qw holds QuantLlamaMLP's 8 + 8 row-interleaved gate / up pair, out[m, n/2] = silu(gate) * up fused into the tile epilogue
 // epi 3: out is float [m, n]: the fp32 accumulators unrounded, no bias (K-shard partial of a tensor-parallel row split)
-int gemm_variant_get();
 // skinny GEMM, 9 <= m <= 255 (row chunks of <= 64), cdna4 layout + packed sz (awq_skinny_cdna4.hip); bias may be nullptr; -1 if unsupported
 int launch_skinny_cdna4(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
                         int dtype, hipStream_t st, int f32out = 0, void* ws = nullptr, size_t ws_bytes = 0);
@@ -123,7 +126,6 @@ int launch_skinny_decode(const void* x, const void* qw, const void* szp, const v
 int launch_moe_gemm(const void* x, const void* qw, const void* s, const void* z, const void* offsets, void* out, int total_m,
                     int experts, int n, int k, int gpad, int dtype, int layout, hipStream_t st);
 int gemv_tune_set(const char* key, int value);
-int gemm_tune_set(const char* key, int value);
 int gemm_v3_tune_set(const char* key, int value);  // tile-plan / dispatch knobs (awq_gemm_plan.hip)
 // 256 x 128 tiles with the same hand-scheduled K loop (awq_gemm_v4n.hip)
 void launch_gemm_cdna4_v4n(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,

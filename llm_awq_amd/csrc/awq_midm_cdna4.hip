@@ -463,22 +463,12 @@ unsigned* splitk_ticket_words(hipStream_t st, int groups) {
 }
 
 namespace {
-
-int g_midm = 1;                                     // knob midm: 0 = off (the skinny / masked-tile kernels of rounds 1-5 serve 9 .. 255 rows)
-int g_midm_min = 65, g_midm_max = 128;              // knobs midm_min / midm_max: the row counts the forward entries hand to this kernel (tests: 9 .. 255); the defaults = the by-shape rules of midm_takes
-int g_midm_waves = 0, g_midm_ns = 0, g_midm_ks = 0;  // knobs midm_waves / midm_ns / midm_ks: force a block shape / part count (experiments, tests)
-int g_midm_probe = 0;                               // knob midm_probe: timing probes of AWQ_PROBES builds (see the kernel)
+int g_midm_probe = 0;  // knob midm_probe: timing probes of AWQ_PROBES builds (see the kernel); the other midm knobs: g_linear (awq_linear_route.hpp)
 }  // namespace
 
 int midm_tune_set(const char* key, int value) {
-  if (!strcmp(key, "midm")) g_midm = value;
-  else if (!strcmp(key, "midm_min")) g_midm_min = value;
-  else if (!strcmp(key, "midm_max")) g_midm_max = value;
-  else if (!strcmp(key, "midm_waves")) g_midm_waves = value;
-  else if (!strcmp(key, "midm_ns")) g_midm_ns = value;
-  else if (!strcmp(key, "midm_ks")) g_midm_ks = value;
-  else if (!strcmp(key, "midm_probe")) g_midm_probe = value;
-  else return -1;
+  if (strcmp(key, "midm_probe")) return -1;
+  g_midm_probe = value;
   return 0;
 }
 
@@ -486,83 +476,22 @@ namespace {
 struct MidmCfg {
   int waves, ns, cb, ks;
 };
-// LDS of a block: DX x stages of 16 cb rows (padded to whole rounds of pieces), per wave a ring of DX + 1 slots of ns (tile + scale piece)
-constexpr int midm_xstage(int cb, int waves) { return (4 * cb + waves - 1) / waves * waves * 1024; }
-constexpr int midm_lds(int cb, int waves, int ns, int dx) { return dx * midm_xstage(cb, waves) + waves * ns * (dx + 1) * 1280; }
-// ring depth: the DX - 1 groups in flight are what the CU has outstanding -- as deep as ~150 KiB of LDS allows, 3 .. 8 stages
-constexpr int midm_dx(int cb, int waves, int ns) {
-  int dx = 8;
-  while (dx > 3 && midm_lds(cb, waves, ns, dx) > 150 * 1024) --dx;
-  return dx;
-}
-int ks_for(int groups, int nit, int cus) {
-  int ks = 1;
-  while (groups * ks * 2 <= cus && nit / (ks * 2) >= 2) ks *= 2;
-  return ks;
-}
-// Block shape and K parts for a pass of m <= 128 rows (profiles/r06_midm_sweep.txt).  One slab per wave; eight waves (two per SIMD) unless the K split
-// that fills the chip would then leave a block fewer than eight k-steps (o_proj: 4096 x 4096) -- four waves halve the slab group instead; ks fills the
+// Block shape (midm_shape, awq_linear_route.hpp: with the LDS rule and the rows a call is handed over for) and K parts for a pass of m <= 128 rows: ks fills the
 // chip with blocks, every part keeps at least two k-steps.
 bool midm_pick(int m, int n, int k, bool may_split, MidmCfg& c) {
   const int nslab = n / 16, nit = k / 128, cus = device_cu_count();
-  c.cb = (m + 15) / 16;
-  c.ns = g_midm_ns ? g_midm_ns : 1;
-  if (g_midm_waves) c.waves = g_midm_waves;
-  else {
-    const int g8 = (nslab + 8 * c.ns - 1) / (8 * c.ns);
-    c.waves = nit / ks_for(g8, nit, cus) >= 8 ? 8 : 4;
-  }
+  const bool fits = midm_shape(m, n, k, cus, g_linear, c.waves, c.ns, c.cb);
   const int groups = (nslab + c.waves * c.ns - 1) / (c.waves * c.ns);
-  int ks = g_midm_ks > 0 ? g_midm_ks : ks_for(groups, nit, cus);
+  int ks = g_linear.midm_ks > 0 ? g_linear.midm_ks : midm_ks_for(groups, nit, cus);
   if (ks > nit / 2) ks = nit / 2 > 0 ? nit / 2 : 1;
   if (!may_split || ks < 1) ks = 1;
   c.ks = ks;
-  return c.cb >= 1 && c.cb <= 8 && ((c.waves == 8 && c.ns == 1) || (c.waves == 4 && (c.ns == 1 || c.ns == 2))) &&
-         midm_lds(c.cb, c.waves, c.ns, midm_dx(c.cb, c.waves, c.ns)) <= 160 * 1024;
-}
-// the rows of a call are served in passes of at most 128 (129 .. 255: two equal passes, each re-streaming the weights)
-void midm_passes(int m, int& chunks, int& rows) {
-  chunks = (m + 127) / 128;
-  rows = (m + chunks - 1) / chunks;
+  return fits;
 }
 }  // namespace
 
-// Which calls the forward entries hand to this kernel.  Measured against the round-5 kernels on the Llama-3-8B shapes (profiles/r06_midm_sweep.txt) and, third session,
-// on the Llama-3-70B / Llama-2-7B shapes and with the true round-5 baseline above 128 rows (profiles/r06_midm_routing.txt):
-//   * 65 .. 128 rows always (one pass: 0.60 - 0.94 x the time of the skinny kernel's two chunks / the masked 256-row tile on every shape measured);
-//   * 129 .. 192 rows NOT any more: two passes, each re-streaming the weights, lose to the masked tile + split-K wherever K is long (down_proj 14336 -> 4096: 1.22 - 1.32 x,
-//     Llama-3-70B qkv / o: 1.2 - 1.36 x) and tie on the K = 4096 projections (0.96 - 1.13 x) -- the second session's figure for down_proj came from a baseline run with a
-//     scratch sized for another plan;
-//   * below 65 rows the skinny kernel (x through registers, up to seven slabs per block, no barrier) is as fast or faster on the Llama-3-8B shapes, but its block shapes leave
-//     other shapes under-filled -- this kernel's K split across blocks takes: 17 .. 32 rows against n >= 16384 (0.81 - 0.88 x); every row count against a very long K and a
-//     narrow n (Llama-3-70B down_proj, 28672 -> 8192: 0.57 - 0.87 x at 16 .. 64 rows); 33 .. 64 rows against n = 8192-class matrices (the skinny kernel's four-slab blocks fill
-//     half the chip: Llama-3-70B o_proj 0.76 x); 49 .. 64 rows against wide pairs whose slab count is not one round of seven-slab blocks (gate/up of Llama-3-70B / Llama-2-7B: 0.84 - 0.89 x).
-namespace {
-bool midm_small_takes(int m, int n, int k) {
-  const int nslab = n / 16, nit = k / 128, cus = device_cu_count();
-  const int g7 = (nslab + 6) / 7;
-  const bool seven_round = g7 <= cus + 16 && g7 >= cus * 9 / 10;  // (awq_skinny_cdna4.hip: seven slabs per block = one round of one block per CU)
-  if (m >= 17 && m <= 32 && n >= 16384) return true;
-  if (nit >= 192 && nslab <= 512) return true;
-  if (m >= 33 && nslab >= 512 && nslab < 640) return true;
-  if (m >= 49 && n >= 16384 && !seven_round) return true;
-  return false;
-}
-}  // namespace
-bool midm_takes(int m, int n, int k) {
-  if (!g_midm || m < 9 || m > 255 || (n % 16) != 0 || (k % 128) != 0 || k < 256) return false;
-  if (g_midm_min == 65 && g_midm_max == 128) {  // the product's rules
-    if (m > 128 || (m < 65 && !midm_small_takes(m, n, k))) return false;
-  } else {  // knobs (tests, sweeps): a plain row range; 129 .. 192 rows against a wide n stay on the tiles as in the first two sessions
-    if (m < g_midm_min || m > g_midm_max) return false;
-    if (m > 128 && n >= 16384 && g_midm_max <= 192) return false;
-  }
-  if ((size_t)n * (size_t)k / 2 >= (1ull << 31) || (size_t)m * (size_t)k * 2 >= (1ull << 31)) return false;
-  int chunks, rows;
-  midm_passes(m, chunks, rows);
-  MidmCfg c;
-  return midm_pick(rows, n, k, true, c);
-}
+// Which calls the forward entries hand to this kernel: midm_takes (awq_linear_route.hpp), at the knobs of this process and the CUs of this device
+bool midm_takes(int m, int n, int k) { return midm_takes(m, n, k, device_cu_count(), g_linear); }
 // K parts of a pass of m rows (1 = unsplit) and the fp32 scratch of a call: [parts][rows of a pass][n] (the passes share it: they run one after the other)
 int midm_parts(int m, int n, int k) {
   MidmCfg c;
@@ -634,7 +563,7 @@ static int launch_midm_pass(const void* x, const void* qw, const void* szp, cons
 // unrounded, no bias) or 2 (out [m, n / 2] = silu(gate) * up).  ws: optional fp32 scratch of the K split (midm_workspace_bytes).  -1 if not served.
 int launch_midm_cdna4(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi, int dtype, int szfmt,
                       int bits, int f32out, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (!szp || bits != 4 || !midm_takes(m, n, k) || (epi != 0 && epi != 2) || (epi == 2 && ((n % 32) != 0 || bias || f32out)) || (f32out && bias)) return -1;
+  if (!szp || !midm_serves(m, n, k, epi, bias != nullptr, f32out != 0, bits, device_cu_count(), g_linear)) return -1;
   int chunks, rows;
   midm_passes(m, chunks, rows);
   const size_t ocols = epi == 2 ? (size_t)n / 2 : (size_t)n;

@@ -366,8 +366,7 @@ static int launch_skinny_64(const void* x, const void* qw, const void* szp, cons
 // kernel's long serial K loop on one wave of tiles (measured: profiles/r01_skinny_sweep.txt) except for very wide N.
 int launch_skinny_cdna4(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k,
                         int dtype, hipStream_t st, int f32out, void* ws, size_t ws_bytes) {
-  if (!szp || m < 1 || m > 255 || (n % 16) != 0 || (k % 128) != 0 || (size_t)m * (size_t)k >= (1ull << 31) || (f32out && bias)) return -1;
-  if (m > 128 && n >= 16384) return -1;
+  if (!szp || !skinny_serves(m, n, k, bias != nullptr, f32out != 0)) return -1;
   const int chunks = (m + 63) / 64, rows = (m + chunks - 1) / chunks;
   for (int r0 = 0; r0 < m; r0 += rows) {
     const int mr = m - r0 < rows ? m - r0 : rows;
@@ -425,7 +424,7 @@ static int launch_skinny_64(const void* x, const void* qw, const void* szp, cons
 // QuantLlamaMLP's interleaved gate / up stack (EPI 2: out [m, n2 / 2] = silu(gate) * up) for 9 <= m <= 64 rows: ONE weight pass with the x slices in
 // registers, instead of a 256-row tile of the prefill GEMM masked down to m rows (awq_w4a16_mlp_gate_up_forward_cdna4).  Returns -1 if unsupported.
 int launch_skinny_gate_up(const void* x, const void* qw, const void* szp, void* out, int m, int n2, int k, int dtype, hipStream_t st) {
-  if (!szp || m < 9 || m > 64 || (n2 % 32) != 0 || (k % 128) != 0 || (size_t)m * (size_t)k >= (1ull << 31)) return -1;
+  if (!szp || !skinny_gate_up_serves(m, n2, k)) return -1;
   if (dtype == 0) return launch_skinny_64<F16, 2>(x, qw, szp, nullptr, out, m, n2, k, st, 0, nullptr, 0);
   return launch_skinny_64<BF16, 2>(x, qw, szp, nullptr, out, m, n2, k, st, 0, nullptr, 0);
 }
@@ -486,7 +485,7 @@ static void launch_skinny_pieces(const DecodeChunk& c, const void* x, const void
 // epi 0 (bias fused) or 2 (8 + 8 interleaved gate / up pair -> silu(gate) * up, out [m, n / 2]).  Returns -1 if unsupported.
 int launch_skinny_decode(const void* x, const void* qw, const void* szp, const void* bias, void* out, int m, int n, int k, int epi,
                          int dtype, int szfmt, hipStream_t st, int f32out) {
-  if (!szp || m < 1 || m > 16 || (n % 16) != 0 || (k % 128) != 0 || (epi != 0 && epi != 2) || (epi == 2 && bias) || (f32out && (epi || bias))) return -1;
+  if (!szp || !skinny16_serves(m, n, k, epi, bias != nullptr, f32out != 0)) return -1;
   const DecodeChunk c = skinny_decode_chunk(m, n / 16, k / 128, device_cu_count());  // block shape and x pieces: awq_decode_plan.hpp
 #define AWQ_SD(DT_, DQ_)                                                                             \
   if (epi == 2) launch_skinny_pieces<DT_, DQ_, 2>(c, x, qw, szp, bias, out, m, n, k, st, f32out);    \
