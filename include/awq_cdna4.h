@@ -402,6 +402,26 @@ int awq_lm_head_logprobs_plan(int t, int v, int k, int out[4]);
 int awq_token_logprobs(const void* logits, int logits_dtype, long ld, const int* targets, float* logprob, float* lse, int* argmax, int b, int v,
                        void* stream);
 
+/* ---- FINAL-LOGIT SOFT-CAPPING (Gemma-2: final_logit_softcapping = 30): every logit z becomes softcap * tanh(z / softcap), evaluated in fp32 with
+ * the device function of the attention cap (absolute error of tanh <= 10 * 2^-24).  DESIGN.md "Soft-capping" states the results by values.
+ *   awq_lm_head_softcap           awq_lm_head's arguments with softcap in front of max_blocks.  The cap is applied to the fp32 sum behind the bias,
+ *                                 before the one rounding to out_dtype: with out_dtype AWQ_F32 the result carries the bits of awq_logit_softcap on
+ *                                 awq_lm_head's fp32 output.
+ *   awq_lm_head_logprobs_softcap  awq_lm_head_logprobs' arguments with softcap behind round_logits.  Every z is capped before it enters the max / sum-exp,
+ *                                 the target pick and the argmax.  With round_logits != 0: z is rounded to T, capped in fp32 and rounded to T once more.
+ *   awq_logit_softcap             logits that already exist, in place: logits [b, v] of logits_dtype (AWQ_F32 / AWQ_F16 / AWQ_BF16), row stride ld
+ *                                 elements (ld >= v), element-size aligned; computed in fp32 and rounded once.  seqlens int32 [b] or NULL: a row with
+ *                                 seqlens[row] < 0 is neither read nor written.  One elementwise launch, no workspace.  1 <= b <= 65535 * 1024,
+ *                                 1 <= v <= 2^30 (AWQ_ERR_SHAPE).
+ * softcap == 0 is "no cap": the first two ARE awq_lm_head / awq_lm_head_logprobs and return their bits, the third launches nothing.  softcap < 0,
+ * infinite or NaN: AWQ_ERR_SHAPE.  Otherwise the codes of the uncapped entries; all checked before anything is launched. ---- */
+int awq_lm_head_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                        int out_dtype, int m, int v, int k, int dtype, float softcap, int max_blocks, void* stream);
+int awq_lm_head_logprobs_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                                 float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                                 float softcap, void* workspace, size_t workspace_bytes, int max_blocks, void* stream);
+int awq_logit_softcap(void* logits, int logits_dtype, long ld, const int* seqlens, int b, int v, float softcap, void* stream);
+
 /* ---- Multi-LoRA on packed steps: y[t, :] += scaling[a] (x[t, :] A_a^T) B_a^T with a = adapter_ids[owner of row t], in TWO launches per adapted
  * linear whatever the mix of adapters, decodes and prompt chunks (shrink, then expand).  DESIGN.md "Multi-LoRA" states the result by values:
  *   x             T [total_q, k], row stride ldx elements (ldx % 8 == 0, ldx >= k): the packed rows of the step
@@ -1108,6 +1128,46 @@ int awq_attn_paged_varq_window_kv8(const void* q, const void* k_pool, const void
                                    long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
                                    long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
                                    int split_seqlen_q, int split_min_keys, int window_left, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* ---- SOFT-CAPPED logits on a windowed mixed step (Gemma-2: cap 50, Grok-1: cap 30): awq_attn_varq_softcap[_kv8] /
+ *      awq_attn_paged_varq_softcap[_kv8] take the arguments of awq_attn_varq_window[_kv8] / awq_attn_paged_varq_window[_kv8] with softcap
+ *      directly behind window_left.  The logits of row s of sequence b become
+ *          z_j = softcap * tanh(softmax_scale * (q . k_j) / softcap),   then the causal / window mask, then softmax.
+ *      The mask is applied behind the cap, by selection: a masked logit is -inf (not -softcap) and a dead key's score, a NaN included,
+ *      contributes nothing.  softmax_scale is free (Gemma-2-27B: 144^-0.5).  Everything else is the contract of the *_window entries:
+ *      positions and rows with p < 0, activity and padding rows, the rule on keys_b, the anchor, and "no key, scale or table entry below
+ *      the first tile is read".  A layer without a window passes window_left = max_seqlen_k - 1 (larger values are clamped to it).
+ *      tanh is evaluated in fp32 from the hardware exp2 and rcp, absolute error <= 10 * 2^-24.
+ * softcap == 0: no cap -- the call IS the *_window entry and returns its bits.
+ * Plan and workspace: awq_attn_varq_window_plan / awq_attn_varq_window_workspace_bytes, unchanged.
+ * Returns the codes of the *_window entries, and: softcap < 0, infinite or NaN AWQ_ERR_SHAPE.  Every check precedes the first launch. */
+int awq_attn_varq_softcap(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q,
+                         int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                         long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                         int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_varq_softcap_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                             int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                             int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_row_stride,
+                             long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                             long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                             long long v_scale_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                             int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq_softcap(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                               const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                               int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                               int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q,
+                               int split_min_keys, int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream);
+int awq_attn_paged_varq_softcap_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                   const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                   const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                   int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                   long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                   long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                   long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                   int split_seqlen_q, int split_min_keys, int window_left, float softcap, void* workspace, size_t workspace_bytes,
                                    void* stream);
 
 /* ---- Encoder-tower attention over packed sequences (flash_attn_varlen_qkvpacked_func's forward: tinychat/models/internvl/internvit.py:45-90).

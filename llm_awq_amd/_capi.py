@@ -78,6 +78,10 @@ SIGNATURES = {
     "awq_lm_head_logprobs_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awq_lm_head_logprobs_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_token_logprobs": (_i, [_vp, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    # final-logit soft-capping: softcap in front of max_blocks / behind round_logits, and logits capped in place
+    "awq_lm_head_softcap": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _i, _vp]),
+    "awq_lm_head_logprobs_softcap": (_i, [_vp, ctypes.c_long, _vp, ctypes.c_float] + [_vp] * 7 + [_i] * 5 + [ctypes.c_float, _vp, _sz, _i, _vp]),
+    "awq_logit_softcap": (_i, [_vp, _i, ctypes.c_long, _vp, _i, _i, ctypes.c_float, _vp]),
     "awq_lora_plan": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int)]),
     "awq_lora_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awq_lora_shrink": (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _sz] + [_i] * 8 + [_vp]),
@@ -191,6 +195,15 @@ SIGNATURES = {
                                    [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i] + [_i, _i, _i, _vp, _sz, _vp]),
     "awq_attn_paged_varq_window_kv8": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
                                        [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i] + [_i, _i, _i, _vp, _sz, _vp]),
+    # capped logits on a windowed mixed step: the *_window entries' arguments with softcap behind window_left
+    "awq_attn_varq_softcap": (_i, [_vp] * 4 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i] +
+                              [_i, _i, _i, ctypes.c_float, _vp, _sz, _vp]),
+    "awq_attn_varq_softcap_kv8": (_i, [_vp] * 6 + [_i, _vp, _i, _i, _vp] + [_i] * 6 + [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i] +
+                                  [_i, _i, _i, ctypes.c_float, _vp, _sz, _vp]),
+    "awq_attn_paged_varq_softcap": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                    [ctypes.c_longlong] * 5 + [ctypes.c_float, _i, _i] + [_i, _i, _i, ctypes.c_float, _vp, _sz, _vp]),
+    "awq_attn_paged_varq_softcap_kv8": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp] + [_i] * 5 + [ctypes.c_longlong] + [_i] * 3 +
+                                        [ctypes.c_longlong] * 9 + [ctypes.c_float, _i, _i] + [_i, _i, _i, ctypes.c_float, _vp, _sz, _vp]),
     "awq_rope_kv_store_natural_varq": (_i, [_vp] * 6 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
     "awq_rope_kv_store_natural_varq_fp8": (_i, [_vp] * 8 + [_i, _i, _vp] + [_i] * 8 + [ctypes.c_longlong, _i, _vp]),
     "awq_rope_kv_store_paged_varq": (_i, [_vp] * 7 + [_i, _vp] + [_i] * 10 + [ctypes.c_longlong] * 6 + [_i, _vp]),

@@ -28,7 +28,7 @@ ARCH = "gfx950"
 HIP_SOURCES = ["awq_gemv.hip", "awq_gemv_cdna4.hip", "awq_gemv_dma.hip", "awq_v2_kernels.hip", "awq_gemm.hip", "awq_gemm_plan.hip", "awq_gemm_v4n.hip", "awq_gemm_v6.hip", "awq_skinny_cdna4.hip", "awq_midm_cdna4.hip", "awq_util.hip", "awq_oneshot.hip", "awq_attn_cdna4.hip", "awq_attn_prefill_cdna4.hip", "awq_attn_chunk_cdna4.hip", "awq_attn_splitkv_cdna4.hip", "awq_attn_kv8_cdna4.hip", "awq_attn_tower_cdna4.hip", "awq_w8a8_cdna4.hip", "awq_moe_route_cdna4.hip", "awq_sample_cdna4.hip", "awq_spec_cdna4.hip", "awq_lm_head_cdna4.hip", "awq_lm_logprobs_cdna4.hip", "awq_lora_cdna4.hip", "awq_quant_cdna4.hip", "awq_capi.hip"]
 # (round 4: the experiment kernels that AWQ_PROBES=1 builds once compiled -- v5, v6w -- are history: tools/EXPERIMENTS.md names the commits)
 PROBE_SOURCES = []
-HIP_DEPS = ["awq_decode_plan.hpp", "awq_linear_route.hpp", "awq_device.hpp", "awq_devlen.hpp", "awq_dma.hpp", "awq_kernels.hpp", "awq_kv8.hpp", "awq_kvcache.hpp", "awq_kvstore.hpp", "awq_paged.hpp", "awq_quant_grid.hpp", "awq_rope.hpp", "awq_sample_row.hpp", "awq_shared.hpp", "awq_varq.hpp", "awq_window.hpp", os.path.join(ROOT, "include", "awq_cdna4.h")]
+HIP_DEPS = ["awq_decode_plan.hpp", "awq_linear_route.hpp", "awq_device.hpp", "awq_devlen.hpp", "awq_dma.hpp", "awq_kernels.hpp", "awq_kv8.hpp", "awq_kvcache.hpp", "awq_kvstore.hpp", "awq_paged.hpp", "awq_quant_grid.hpp", "awq_rope.hpp", "awq_sample_row.hpp", "awq_shared.hpp", "awq_softcap.hpp", "awq_varq.hpp", "awq_window.hpp", os.path.join(ROOT, "include", "awq_cdna4.h")]
 
 
 def _newer(target: str, deps) -> bool:

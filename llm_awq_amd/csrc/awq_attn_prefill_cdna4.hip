@@ -31,6 +31,7 @@
 #include "awq_paged.hpp"
 #include "awq_rope.hpp"
 #include "awq_varq.hpp"
+#include "awq_softcap.hpp"
 #include "awq_window.hpp"
 
 #include <math.h>
@@ -87,12 +88,20 @@ struct PrefillWinArgs : PrefillMixArgs {
   WindowArgs w;
 };
 
+// Softcap<Window<VarQMix<..>>> only (awq_softcap.hpp): the cap behind the window.  A struct of its own again: the windowed kernels keep their
+// PrefillWinArgs block
+struct PrefillCapArgs : PrefillWinArgs {
+  SoftcapArgs cap;
+};
+
 struct NoLenArgs {};
 template <typename DT>
 using LenArgsOf = typename std::conditional<
-    IsWindow<DT>::value, PrefillWinArgs,
-    typename std::conditional<IsVarQMix<DT>::value, PrefillMixArgs,
-                              typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type>::type>::type;
+    IsSoftcap<DT>::value, PrefillCapArgs,
+    typename std::conditional<
+        IsWindow<DT>::value, PrefillWinArgs,
+        typename std::conditional<IsVarQMix<DT>::value, PrefillMixArgs,
+                                  typename std::conditional<IsDevLen<DT>::value, PrefillLenArgs, NoLenArgs>::type>::type>::type>::type;
 __device__ __forceinline__ PrefillLenArgs len_args(const NoLenArgs&) { return PrefillLenArgs{nullptr, 0, 0, PageArgs{nullptr, 0, 0, 0}, VarQArgs{nullptr, 0, 0, 0}}; }
 __device__ __forceinline__ PrefillLenArgs len_args(const PrefillLenArgs& x) { return x; }
 __device__ __forceinline__ VarQSplitArgs split_args(const NoLenArgs&) { return VarQSplitArgs{0, 0}; }
@@ -101,6 +110,9 @@ __device__ __forceinline__ VarQSplitArgs split_args(const PrefillMixArgs& x) { r
 __device__ __forceinline__ WindowArgs window_args(const NoLenArgs&) { return WindowArgs{0}; }
 __device__ __forceinline__ WindowArgs window_args(const PrefillLenArgs&) { return WindowArgs{0}; }
 __device__ __forceinline__ WindowArgs window_args(const PrefillWinArgs& x) { return x.w; }
+__device__ __forceinline__ SoftcapArgs cap_args(const NoLenArgs&) { return SoftcapArgs{0.f, 0.f}; }
+__device__ __forceinline__ SoftcapArgs cap_args(const PrefillLenArgs&) { return SoftcapArgs{0.f, 0.f}; }
+__device__ __forceinline__ SoftcapArgs cap_args(const PrefillCapArgs& x) { return x.cap; }
 
 // LDS images: rows of DH elements, the 16-byte chunks of a row permuted by an XOR that depends on the row.
 //   K (read by rows, ds_read_b128, 16 consecutive lanes = 16 consecutive rows, one chunk): the 16 rows land on 16 different 16-byte slots
@@ -177,6 +189,10 @@ struct IsFtCache<FtCache<DT>> {
 // start.  A row may meet its first attended key tiles after its wave's first one: the running max is still -inf then, the DevLen guards'
 // case.  With left >= Sk_b - 1 every one of these is the VarQMix expression: t_lo = 0, no tile skipped, no key masked -- same bits.
 //
+// Softcap<Window<VarQMix<..>>> (awq_softcap.hpp, awq_attn_varq_softcap[_kv8], awq_attn_paged_varq_softcap[_kv8]): the windowed form with the
+// logit x = cap_log2e * softcap_tanh(s * scale_over_cap) in the place of x = s * scale_log2e.  The mask selects behind it, so a masked logit
+// is -inf and a dead key's score, a NaN included, is never looked at; nothing else differs.
+//
 // The device-length forms take their PrefillLenArgs as a SECOND kernel argument.  For the host-length forms that argument is the empty
 // NoLenArgs -- one padded byte behind PrefillArgs that no instruction reads: their PrefillArgs, their registers and their instruction
 // stream are those of the one-argument kernel.
@@ -189,6 +205,8 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
   constexpr bool WINDOW = IsWindow<DT>::value;
+  constexpr bool SOFTCAP = IsSoftcap<DT>::value;
+  static_assert(!SOFTCAP || WINDOW, "a cap exists on the windowed form only");
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!FT || !DEVLEN, "the FT caches take a host length");
   static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
@@ -443,6 +461,7 @@ __global__ __launch_bounds__(NW * 64) void attn_prefill_kernel(PrefillArgs a, Le
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           float x = s[kb2][e] * a.scale_log2e;
+          if constexpr (SOFTCAP) x = cap_args(xs).cap_log2e * softcap_tanh(s[kb2][e] * cap_args(xs).scale_over_cap);
           if constexpr (WINDOW) {
             if (need_mask || need_lo) {  // both ends in one unsigned compare: lo <= key <= lim  <=>  key - lo <= lim - lo
               const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
@@ -823,16 +842,28 @@ int launch_kv_prefill(const KvAttnCall& c, hipStream_t st) {
     a.ntiles = (c.Sq + rows - 1) / rows;
     const int nw = rows / kMfmaRows;
     if (c.window_left >= 0) {  // a windowed step (awq_window.hpp): the mixed form for every split_seqlen_q, 0 hands nothing to the split pair
-      PrefillWinArgs m;
+      PrefillCapArgs m;
       static_cast<PrefillLenArgs&>(m) = x;
       m.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
       m.w = WindowArgs{c.window_left};
+      if (c.softcap > 0.f) {  // a capped step (awq_softcap.hpp): the windowed form with the cap behind it
+        m.cap = softcap_args(c.scale, c.softcap);
+        if (kv.block_table) {
+          if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, SoftcapWindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+          else launch_kv_prefill_varq_as<TCache, SoftcapWindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        } else {
+          if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, SoftcapWindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+          else launch_kv_prefill_varq_as<TCache, SoftcapWindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        }
+        return 0;
+      }
+      const PrefillWinArgs& w = m;
       if (kv.block_table) {
-        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
-        else launch_kv_prefill_varq_as<TCache, WindowVarQMixPagedDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixPagedDevLen>(a, w, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, WindowVarQMixPagedDevLen>(a, w, c.Dh, c.dtype, nw, blocks, st);
       } else {
-        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
-        else launch_kv_prefill_varq_as<TCache, WindowVarQMixDevLen>(a, m, c.Dh, c.dtype, nw, blocks, st);
+        if (kv.k_scale) launch_kv_prefill_varq_as<Kv8, WindowVarQMixDevLen>(a, w, c.Dh, c.dtype, nw, blocks, st);
+        else launch_kv_prefill_varq_as<TCache, WindowVarQMixDevLen>(a, w, c.Dh, c.dtype, nw, blocks, st);
       }
       return 0;
     }

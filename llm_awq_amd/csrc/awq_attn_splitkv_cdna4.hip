@@ -54,6 +54,7 @@
 #include "awq_paged.hpp"
 #include "awq_shared.hpp"
 #include "awq_varq.hpp"
+#include "awq_softcap.hpp"
 #include "awq_window.hpp"
 
 #include <math.h>
@@ -113,6 +114,10 @@ struct VarQSplitKArgs : PagedSplitArgs {
 struct WindowSplitKArgs : VarQSplitKArgs {
   WindowArgs w;
 };
+// Softcap<Window<VarQ<..>>> only (awq_softcap.hpp): the cap behind the window, for the split kernel alone -- the combine is the windowed one
+struct SoftcapSplitKArgs : WindowSplitKArgs {
+  SoftcapArgs cap;
+};
 // Shared<..> only (awq_shared.hpp): the group arrays behind the paged arguments, for all three launches of the call
 struct SharedSplitArgs : PagedSplitArgs {
   SharedArgs sh;
@@ -121,9 +126,11 @@ template <typename DT>
 using SplitArgsOf = typename std::conditional<
     IsShared<DT>::value, SharedSplitArgs,
     typename std::conditional<
-        IsWindow<DT>::value, WindowSplitKArgs,
-        typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
-                                  typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type>::type>::type;
+        IsSoftcap<DT>::value, SoftcapSplitKArgs,
+        typename std::conditional<
+            IsWindow<DT>::value, WindowSplitKArgs,
+            typename std::conditional<IsVarQ<DT>::value, VarQSplitKArgs,
+                                      typename std::conditional<IsPaged<DT>::value, PagedSplitArgs, SplitArgs>::type>::type>::type>::type>::type;
 template <typename DT>
 using CombineArgsOf = typename std::conditional<
     IsShared<DT>::value, SharedSplitArgs,
@@ -137,6 +144,8 @@ __device__ __forceinline__ VarQSplitArgs split_args(const SplitArgs&) { return V
 __device__ __forceinline__ VarQSplitArgs split_args(const VarQSplitKArgs& a) { return a.sp; }
 __device__ __forceinline__ WindowArgs window_args(const SplitArgs&) { return WindowArgs{0}; }
 __device__ __forceinline__ WindowArgs window_args(const WindowSplitKArgs& a) { return a.w; }
+__device__ __forceinline__ SoftcapArgs cap_args(const SplitArgs&) { return SoftcapArgs{0.f, 0.f}; }
+__device__ __forceinline__ SoftcapArgs cap_args(const SoftcapSplitKArgs& a) { return a.cap; }
 __device__ __forceinline__ PageArgs page_args(const SplitArgs&) { return PageArgs{nullptr, 0, 0, 0}; }
 __device__ __forceinline__ PageArgs page_args(const PagedSplitArgs& a) { return a.pg; }
 
@@ -183,6 +192,9 @@ __device__ __forceinline__ int v_off(int row, int ch) {
 // a wave-uniform test, the low mask runs only in tiles below the wave's last window start, and a row whose window starts behind the
 // split's last key leaves m = -inf, l = 0 for that split, which the combine skips.  Every row attends its own key, so some split's m is finite.
 //
+// Softcap<Window<VarQ<..>>> (awq_softcap.hpp, a capped windowed step): the windowed block with the logit
+// x = cap_log2e * softcap_tanh(s * scale_over_cap) in the place of x = s * scale_log2e; the mask selects behind it, as without a cap.
+//
 // SharedSuffix<Paged<DevLen<..>>> (awq_shared.hpp, awq_attn_kvcache_paged_shared): the Paged block with k_begin = P_b + split * chunk,
 // P_b = pfx(seq_prefix[b], Sk_b) one scalar expression behind the length load, and its partial in entry ws_first + split of the
 // workspace's ws_splits entries per row.  No key, scale or table entry below P_b is read (the page walk begins at k_begin).
@@ -200,6 +212,8 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
   constexpr bool PAGED = IsPaged<DT>::value;
   constexpr bool VARQ = IsVarQ<DT>::value;
   constexpr bool WINDOW = IsWindow<DT>::value;
+  constexpr bool SOFTCAP = IsSoftcap<DT>::value;
+  static_assert(!SOFTCAP || WINDOW, "a cap exists on the windowed form only");
   static_assert(!PAGED || DEVLEN, "the paged form reads its lengths on the device");
   static_assert(!VARQ || DEVLEN, "packed queries read their lengths on the device");
   static_assert(!WINDOW || VARQ, "a window exists on the packed form only");
@@ -477,6 +491,7 @@ __global__ __launch_bounds__(kNW * 64) void attn_splitkv_kernel(SplitArgsOf<DT> 
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           float x = s[kb2][e] * a.scale_log2e;
+          if constexpr (SOFTCAP) x = cap_args(a).cap_log2e * softcap_tanh(s[kb2][e] * cap_args(a).scale_over_cap);
           if constexpr (WINDOW) {
             if (need_mask || need_lo) {  // both ends in one unsigned compare: lo <= key <= lim  <=>  key - lo <= lim - lo
               const int key = t0 + 32 * kb2 + (e & 3) + 8 * (e >> 2) + 4 * hh;
@@ -772,7 +787,7 @@ void launch_for_cache(const A& a, int Dh, int dtype, hipStream_t st) {
 int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, hipStream_t st) {
   const KvView& kv = c.kv;
   const bool mixed = c.cu_seqlens_q && c.split_seqlen_q > 0;  // the packed pair: c.Sq is max_seqlen_q, c.seqlen_offset the flag
-  WindowSplitKArgs a;
+  SoftcapSplitKArgs a;
   a.q = (const uint16_t*)c.q;
   a.k = (const uint16_t*)kv.k;
   a.v = (const uint16_t*)kv.v;
@@ -803,12 +818,17 @@ int launch_kv_attn(const KvAttnCall& c, int splits, int chunk, void* workspace, 
   a.vq = VarQArgs{c.cu_seqlens_q, c.total_q, c.max_seqlen_q, c.seqlen_offset ? 1 : 0};
   a.sp = VarQSplitArgs{c.split_seqlen_q, c.split_min_keys};
   a.w = WindowArgs{c.window_left >= 0 ? c.window_left : 0};
+  a.cap = softcap_args(c.scale, c.softcap > 0.f ? c.softcap : 1.f);
+  const WindowSplitKArgs& win = a;
   const VarQSplitKArgs& varq = a;
   const PagedSplitArgs& paged = a;
   const SplitArgs& dense = a;
-  if (mixed && c.window_left >= 0) {  // a windowed step (awq_window.hpp): the caller's plan is awq_attn_varq_window_plan's
-    if (kv.block_table) launch_for_cache<WindowVarQPagedDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
-    else launch_for_cache<WindowVarQDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
+  if (mixed && c.window_left >= 0 && c.softcap > 0.f) {  // a capped windowed step (awq_softcap.hpp): the window's plan and combine
+    if (kv.block_table) launch_for_cache<SoftcapWindowVarQPagedDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
+    else launch_for_cache<SoftcapWindowVarQDevLen, WindowVarQDevLen>(a, c.Dh, c.dtype, st);
+  } else if (mixed && c.window_left >= 0) {  // a windowed step (awq_window.hpp): the caller's plan is awq_attn_varq_window_plan's
+    if (kv.block_table) launch_for_cache<WindowVarQPagedDevLen, WindowVarQDevLen>(win, c.Dh, c.dtype, st);
+    else launch_for_cache<WindowVarQDevLen, WindowVarQDevLen>(win, c.Dh, c.dtype, st);
   } else if (mixed) {
     if (kv.block_table) launch_for_cache<VarQPagedDevLen, VarQDevLen>(varq, c.Dh, c.dtype, st);
     else launch_for_cache<VarQDevLen, VarQDevLen>(varq, c.Dh, c.dtype, st);

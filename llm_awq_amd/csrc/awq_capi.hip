@@ -557,6 +557,8 @@ static int kv_attn_check(const KvAttnCall& c, int fmt) {
                          (c.H >= 1 && c.Hkv >= 1 && (c.H % c.Hkv) == 0 && (long long)c.split_seqlen_q * (c.H / c.Hkv) > 128)))
     return AWQ_ERR_SHAPE;
   if ((fmt & KV_WINDOW) && (c.window_left < 0 || !c.causal)) return AWQ_ERR_SHAPE;
+  // (a cap, awq_softcap.hpp: 0 is none, anything else finite and positive; the comparison refuses a NaN)
+  if (!(c.softcap >= 0.f && c.softcap <= 3.4028234663852886e38f)) return AWQ_ERR_SHAPE;
   // (host lengths: the T entry keeps the one-pass kernel's head dim 72 for the calls the plan hands to it; the FP8 kernels have 64 / 128)
   if (!(devlen ? kvcache_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.max_seqlen_k, fmt & KV_ONEPASS)
                : ((!(fmt & KV_FP8) || c.Dh == 64 || c.Dh == 128) && prefill_shape_ok(c.B, c.H, c.Hkv, c.Dh, c.Sq, c.Sk, c.causal))) ||
@@ -1082,10 +1084,11 @@ static int window_clamped(int window_left, int max_seqlen_k) { return window_lef
 
 // windowed (awq_window.hpp, the *_window entries): window_left >= 0 and causal join the shape phase, the window is clamped to
 // max_seqlen_k - 1 (beyond that it hides no key), and the plan and the workspace are the window's.
+// softcap (awq_softcap.hpp, the *_softcap entries): a windowed call whose logits are capped; 0 is the windowed call itself, bit for bit.
 static int kv_varq_attn(KvAttnCall c, int fmt, int split_seqlen_q, int split_min_keys, void* workspace, size_t workspace_bytes, void* stream,
-                        bool windowed = false, int window_left = 0) {
+                        bool windowed = false, int window_left = 0, float softcap = 0.f) {
   c.split_seqlen_q = split_seqlen_q, c.split_min_keys = split_min_keys;
-  if (windowed) c.window_left = window_left;
+  if (windowed) c.window_left = window_left, c.softcap = softcap;
   const int rc = kv_attn_check(c, fmt | KV_ONEPASS | KV_MIX | (windowed ? KV_WINDOW : 0));
   if (rc != AWQ_OK) return rc;
   if (c.max_seqlen_k > c.kv.capacity() || c.seqlen_offset < 0) return AWQ_ERR_SHAPE;
@@ -1227,6 +1230,64 @@ int awq_attn_paged_varq_window_kv8(const void* q, const void* k_pool, const void
   return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
                                      nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
                       KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left);
+}
+
+// ---- a cap on the logits of a windowed mixed step (awq_softcap.hpp): the four entries above with softcap behind window_left.  The plan
+//      and the workspace are awq_attn_varq_window_plan / awq_attn_varq_window_workspace_bytes; softcap = 0 is the *_window entry
+
+int awq_attn_varq_softcap(const void* q, const void* k_cache, const void* v_cache, void* out, int batch, const int* cu_seqlens_q, int max_seqlen_q,
+                         int total_q, const int* seqlens_k, int lens_before_step, int max_seqlen_k, int lmax, int nheads, int nheads_kv,
+                         int head_dim, long long q_row_stride, long long k_batch_stride, long long k_row_stride, long long v_batch_stride,
+                         long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                         int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left, softcap);
+}
+
+int awq_attn_varq_softcap_kv8(const void* q, const void* k_cache, const void* v_cache, const float* k_scale, const float* v_scale, void* out,
+                             int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                             int max_seqlen_k, int lmax, int nheads, int nheads_kv, int head_dim, long long q_row_stride,
+                             long long k_batch_stride, long long k_row_stride, long long v_batch_stride, long long v_row_stride,
+                             long long k_scale_batch_stride, long long k_scale_row_stride, long long v_scale_batch_stride,
+                             long long v_scale_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q, int split_min_keys,
+                             int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_scales(kv_view(k_cache, v_cache, batch, lmax, k_batch_stride, k_row_stride, v_batch_stride, v_row_stride), k_scale,
+                                v_scale, k_scale_batch_stride, k_scale_row_stride, v_scale_batch_stride, v_scale_row_stride);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_FP8 | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left, softcap);
+}
+
+int awq_attn_paged_varq_softcap(const void* q, const void* k_pool, const void* v_pool, void* out, const int* block_table, int batch,
+                               const int* cu_seqlens_q, int max_seqlen_q, int total_q, const int* seqlens_k, int lens_before_step,
+                               int max_seqlen_k, int num_pages, int page_size, int pages_per_seq, long long table_row_stride, int nheads,
+                               int nheads_kv, int head_dim, long long q_row_stride, long long k_page_stride, long long k_row_stride,
+                               long long v_page_stride, long long v_row_stride, float softmax_scale, int causal, int dtype, int split_seqlen_q,
+                               int split_min_keys, int window_left, float softcap, void* workspace, size_t workspace_bytes, void* stream) {
+  const KvView kv = with_table(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left, softcap);
+}
+
+int awq_attn_paged_varq_softcap_kv8(const void* q, const void* k_pool, const void* v_pool, const float* k_scale, const float* v_scale, void* out,
+                                   const int* block_table, int batch, const int* cu_seqlens_q, int max_seqlen_q, int total_q,
+                                   const int* seqlens_k, int lens_before_step, int max_seqlen_k, int num_pages, int page_size,
+                                   int pages_per_seq, long long table_row_stride, int nheads, int nheads_kv, int head_dim,
+                                   long long q_row_stride, long long k_page_stride, long long k_row_stride, long long v_page_stride,
+                                   long long v_row_stride, long long k_scale_page_stride, long long k_scale_row_stride,
+                                   long long v_scale_page_stride, long long v_scale_row_stride, float softmax_scale, int causal, int dtype,
+                                   int split_seqlen_q, int split_min_keys, int window_left, float softcap, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  const KvView kv = with_table(with_scales(kv_view(k_pool, v_pool, num_pages, page_size, k_page_stride, k_row_stride, v_page_stride, v_row_stride),
+                                           k_scale, v_scale, k_scale_page_stride, k_scale_row_stride, v_scale_page_stride, v_scale_row_stride),
+                               block_table, table_row_stride, pages_per_seq);
+  return kv_varq_attn(varq_attn_call(q, out, kv, batch, cu_seqlens_q, max_seqlen_q, total_q, seqlens_k, lens_before_step, max_seqlen_k, nheads,
+                                     nheads_kv, head_dim, q_row_stride, softmax_scale, causal, dtype),
+                      KV_FP8 | KV_PAGED | KV_DEVLEN | KV_VARQ, split_seqlen_q, split_min_keys, workspace, workspace_bytes, stream, true, window_left, softcap);
 }
 
 int awq_rope_kv_store_natural_varq(const void* qkv, const float* freqs_table, void* q_out, void* k_cache, void* v_cache, const int* cache_seqlens,
@@ -1709,17 +1770,26 @@ int awq_spec_accept(const void* row_tokens, const void* input_ids, const void* c
   return finish_launch();
 }
 
+// a cap (awq_softcap.hpp): 0 is none, anything else finite and positive; the comparison refuses a NaN
+static bool softcap_ok(float cap) { return cap >= 0.f && cap <= 3.4028234663852886e38f; }
+
 // ---- LM head for decode and the token embedding gather (awq_lm_head_cdna4.hip) ----
 int awq_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                 int out_dtype, int m, int v, int k, int dtype, int max_blocks, void* stream) {
+  return awq_lm_head_softcap(x, ldx, gamma, eps, weight, bias, seqlens, out, out_dtype, m, v, k, dtype, 0.f, max_blocks, stream);
+}
+
+// softcap = 0 is awq_lm_head: the same checks, the same kernels
+int awq_lm_head_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                        int out_dtype, int m, int v, int k, int dtype, float softcap, int max_blocks, void* stream) {
   if (!x || !weight || !out) return AWQ_ERR_NULL;
   if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
   if (out_dtype != AWQ_F32 && out_dtype != dtype) return AWQ_ERR_DTYPE;
   if (m < 1 || m > 64) return AWQ_ERR_BATCH;
-  if (v < 1 || k < 8 || (k % 8) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0) return AWQ_ERR_SHAPE;
+  if (v < 1 || k < 8 || (k % 8) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0 || !softcap_ok(softcap)) return AWQ_ERR_SHAPE;
   if (!aligned16(x) || !aligned16(weight) || !aligned16(out) || !aligned16(gamma) || !aligned16(bias) || !aligned_to(seqlens, 4)) return AWQ_ERR_ALIGN;
-  if (awq::launch_lm_head(x, ldx, gamma, eps, weight, bias, seqlens, out, out_dtype == AWQ_F32 ? 1 : 0, m, v, k, dtype, max_blocks,
-                          (hipStream_t)stream) != 0)
+  if (awq::launch_lm_head_softcap(x, ldx, gamma, eps, weight, bias, seqlens, out, out_dtype == AWQ_F32 ? 1 : 0, m, v, k, dtype, softcap, max_blocks,
+                                  (hipStream_t)stream) != 0)
     return AWQ_ERR_SHAPE;
   return finish_launch();
 }
@@ -1750,18 +1820,27 @@ size_t awq_lm_head_logprobs_workspace_bytes(int t, int v, int k, int with_gamma)
 int awq_lm_head_logprobs(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
                          float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
                          void* workspace, size_t workspace_bytes, int max_blocks, void* stream) {
+  return awq_lm_head_logprobs_softcap(x, ldx, gamma, eps, weight, bias, targets, logprob, lse, target_logit, argmax, t, v, k, dtype, round_logits, 0.f,
+                                      workspace, workspace_bytes, max_blocks, stream);
+}
+
+// softcap = 0 is awq_lm_head_logprobs: the same checks, the same kernels
+int awq_lm_head_logprobs_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                                 float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                                 float softcap, void* workspace, size_t workspace_bytes, int max_blocks, void* stream) {
   if (!x || !weight) return AWQ_ERR_NULL;
   if (!targets && (logprob || target_logit)) return AWQ_ERR_NULL;  // without targets there is no target logit to report
   if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
   int plan[4];
-  if (awq::lm_logprobs_plan(t, v, k, plan) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0 || (gamma && ldx != k)) return AWQ_ERR_SHAPE;
+  if (awq::lm_logprobs_plan(t, v, k, plan) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0 || (gamma && ldx != k) || !softcap_ok(softcap))
+    return AWQ_ERR_SHAPE;
   if (!aligned16(x) || !aligned16(weight) || !aligned16(gamma) || !aligned16(bias) || !aligned16(workspace)) return AWQ_ERR_ALIGN;
   const void* words[] = {targets, logprob, lse, target_logit, argmax};
   for (const void* w : words)
     if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
   if (!workspace || workspace_bytes < awq::lm_logprobs_workspace_bytes(t, v, k, gamma != nullptr)) return AWQ_ERR_WORKSPACE;
-  if (awq::launch_lm_logprobs(x, ldx, gamma, eps, weight, bias, targets, logprob, lse, target_logit, argmax, t, v, k, dtype, round_logits, workspace,
-                              max_blocks, (hipStream_t)stream) != 0)
+  if (awq::launch_lm_logprobs_softcap(x, ldx, gamma, eps, weight, bias, targets, logprob, lse, target_logit, argmax, t, v, k, dtype, round_logits,
+                                      softcap, workspace, max_blocks, (hipStream_t)stream) != 0)
     return AWQ_ERR_SHAPE;
   return finish_launch();
 }
@@ -1777,6 +1856,17 @@ int awq_token_logprobs(const void* logits, int logits_dtype, long ld, const int*
   for (const void* w : words)
     if (!aligned_to(w, 4)) return AWQ_ERR_ALIGN;
   if (awq::launch_token_logprobs(logits, logits_dtype, ld, targets, logprob, lse, argmax, b, v, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
+// logits that already exist, capped in place (awq_util.hip).  softcap = 0 is "no cap": nothing is launched and the logits keep their bits
+int awq_logit_softcap(void* logits, int logits_dtype, long ld, const int* seqlens, int b, int v, float softcap, void* stream) {
+  if (!logits) return AWQ_ERR_NULL;
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (b < 1 || b > 65535 * 1024 || v < 1 || v > (1 << 30) || ld < v || !softcap_ok(softcap)) return AWQ_ERR_SHAPE;
+  if (!aligned_to(logits, logits_dtype == AWQ_F32 ? 4 : 2) || !aligned_to(seqlens, 4)) return AWQ_ERR_ALIGN;
+  if (softcap == 0.f) return AWQ_OK;
+  if (awq::launch_logit_softcap(logits, logits_dtype, ld, seqlens, b, v, softcap, (hipStream_t)stream) != 0) return AWQ_ERR_SHAPE;
   return finish_launch();
 }
 

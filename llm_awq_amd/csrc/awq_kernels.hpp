@@ -179,6 +179,9 @@ int launch_spec_accept(const void* row_tokens, const void* input_ids, const void
 int lm_head_plan(int m, int v, int k, int out[4]);
 int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                    int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st);
+// the same launch with the logits capped behind the bias (awq_softcap.hpp): y <- softcap * tanh(y / softcap) in fp32; softcap = 0: launch_lm_head
+int launch_lm_head_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                           int out_f32, int m, int v, int k, int dtype, float softcap, int max_blocks, hipStream_t st);
 int launch_embed_tokens(const int* tokens, const void* table, void* out, int n, int v, int k, hipStream_t st);  // zeros for an id outside [0, v)
 // Token log-probabilities (awq_lm_logprobs_cdna4.hip): the LM head fused with log-sum-exp (tile launch + combine launch; with gamma the rmsnorm launch
 // runs first into the head of the workspace), and the companion for logits that already exist.  The plan is {row tile, vocabulary tile, blocks, k step};
@@ -190,6 +193,13 @@ int launch_lm_logprobs(const void* x, long ldx, const void* gamma, float eps, co
                        hipStream_t st);
 int launch_token_logprobs(const void* logits, int logits_dtype, long ld, const int* targets, float* logprob, float* lse, int* argmax, int b, int v,
                           hipStream_t st);
+// every logit capped in the tile epilogue before the max / sum-exp, the target pick and the argmax (awq_softcap.hpp); softcap = 0: launch_lm_logprobs
+int launch_lm_logprobs_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                               float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                               float softcap, void* workspace, int max_blocks, hipStream_t st);
+// logits that already exist, capped in place (awq_util.hip): z <- softcap * tanh(z / softcap) in fp32, one elementwise launch; rows with
+// seqlens[b] < 0 untouched (seqlens may be null); logits_dtype 0 fp16, 1 bf16, 2 fp32
+int launch_logit_softcap(void* logits, int logits_dtype, long ld, const int* seqlens, int b, int v, float softcap, hipStream_t st);
 // Multi-LoRA on packed steps (awq_lora_cdna4.hip): shrink (x A_a^T into the fp32 K-split workspace) and expand (scale, round, B_a^T, add into y in
 // place), the adapter of a row read on the device; the plan is {KS, k per split, expand column tile, waves}; -1 if the sizes are outside the documented
 // limits, pointers / alignment / workspace size validated by the caller

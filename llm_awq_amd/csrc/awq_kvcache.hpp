@@ -75,6 +75,9 @@ struct KvAttnCall {
   // a sliding window on a packed step (awq_window.hpp, awq_attn_varq_window and its siblings): a row attends its own key and the
   // window_left keys before it, clamped by the entry to max_seqlen_k - 1.  -1: no window, the kernels above
   int window_left = -1;
+  // a cap on the logits of a windowed step (awq_softcap.hpp, awq_attn_varq_softcap and its siblings): cap * tanh(scale * q.k / cap) in
+  // front of the mask.  Finite and > 0; 0: no cap, the kernels above
+  float softcap = 0.f;
 };
 
 // what awq_attn_kvcache_paged_shared[_kv8] takes beside attn_kvcache_paged's KvAttnCall (awq_shared.hpp)

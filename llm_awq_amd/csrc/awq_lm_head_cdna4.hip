@@ -20,8 +20,11 @@
 // The order of every sum depends on K alone: not on M, not on gamma, not on the grid.  No workspace, no atomics.
 // An MFMA row is a dot product of its own A row: a NaN in row b of x stays in row b of the result, so inactive rows (seqlens[b] < 0) need no
 // masking on the way in; they are skipped on the way out.  A launch whose rows are all inactive returns before its first weight load.
+//   cap      awq_lm_head_softcap (awq_softcap.hpp; Gemma-2's final_logit_softcapping): y <- cap * tanh(y / cap) behind the bias, in fp32, before the
+//            one rounding to out_dtype.  A compile-time form: lm_head_softcap_kernel is lm_head_body<.., true>, lm_head_kernel stays <.., false>.
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
+#include "awq_softcap.hpp"
 
 namespace awq {
 namespace {
@@ -66,8 +69,9 @@ __device__ __forceinline__ u32x4 lm_norm8(const u32x4& xv, const u32x4& gv, floa
   return u32x4{o4[0], o4[1], o4[2], o4[3]};
 }
 
-template <typename DT, int MT, bool NORM, int PF>
-__global__ __launch_bounds__(kLmThreads) void lm_head_kernel(const LmHeadArgs a) {
+template <typename DT, int MT, bool NORM, int PF, bool CAP>
+__device__ __forceinline__ void lm_head_body(const LmHeadArgs& a, float cap) {
+  (void)cap;
   constexpr int NR = MT * kLmVT * 4;  // accumulator registers of a lane
   __shared__ float part[kLmWaves * NR * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
@@ -214,6 +218,7 @@ __global__ __launch_bounds__(kLmThreads) void lm_head_kernel(const LmHeadArgs a)
       if (mrow < M && ((active >> mrow) & 1ull) && n < V) {
         float y = (part[idx] + part[NR * 64 + idx]) + (part[2 * NR * 64 + idx] + part[3 * NR * 64 + idx]);
         if (a.bias) y += DT::to_float(a.bias[n]);
+        if constexpr (CAP) y = softcap_logit(y, cap);
         const size_t o = (size_t)mrow * (size_t)V + (size_t)n;
         if (a.out_f32) reinterpret_cast<float*>(a.out)[o] = y;
         else reinterpret_cast<uint16_t*>(a.out)[o] = DT::from_float(y);
@@ -267,6 +272,16 @@ __global__ __launch_bounds__(kLmThreads) void lm_head_kernel(const LmHeadArgs a)
   }
 }
 
+template <typename DT, int MT, bool NORM, int PF>
+__global__ __launch_bounds__(kLmThreads) void lm_head_kernel(const LmHeadArgs a) {
+  lm_head_body<DT, MT, NORM, PF, false>(a, 0.f);
+}
+// the cap rides BEHIND LmHeadArgs: lm_head_kernel keeps its argument block
+template <typename DT, int MT, bool NORM, int PF>
+__global__ __launch_bounds__(kLmThreads) void lm_head_softcap_kernel(const LmHeadArgs a, float cap) {
+  lm_head_body<DT, MT, NORM, PF, true>(a, cap);
+}
+
 // out[i, :] = table[tokens[i], :] for 0 <= tokens[i] < v, zeros otherwise; one 16-byte granule per thread and turn
 __global__ __launch_bounds__(256) void embed_tokens_kernel(const int* __restrict__ tokens, const u32x4* __restrict__ table, u32x4* __restrict__ out,
                                                            size_t total, int v, int kg) {
@@ -280,18 +295,21 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int* __restrict
 }
 
 template <typename DT, int MT, int PF>
-void lm_head_launch_mt(const LmHeadArgs& a, int blocks, hipStream_t st) {
-  if (a.gamma) hipLaunchKernelGGL((lm_head_kernel<DT, MT, true, PF>), dim3(blocks), dim3(kLmThreads), 0, st, a);
+void lm_head_launch_mt(const LmHeadArgs& a, float cap, int blocks, hipStream_t st) {
+  if (cap > 0.f) {
+    if (a.gamma) hipLaunchKernelGGL((lm_head_softcap_kernel<DT, MT, true, PF>), dim3(blocks), dim3(kLmThreads), 0, st, a, cap);
+    else hipLaunchKernelGGL((lm_head_softcap_kernel<DT, MT, false, PF>), dim3(blocks), dim3(kLmThreads), 0, st, a, cap);
+  } else if (a.gamma) hipLaunchKernelGGL((lm_head_kernel<DT, MT, true, PF>), dim3(blocks), dim3(kLmThreads), 0, st, a);
   else hipLaunchKernelGGL((lm_head_kernel<DT, MT, false, PF>), dim3(blocks), dim3(kLmThreads), 0, st, a);
 }
 
 template <typename DT>
-void lm_head_launch(const LmHeadArgs& a, int blocks, hipStream_t st) {
+void lm_head_launch(const LmHeadArgs& a, float cap, int blocks, hipStream_t st) {
   switch ((a.m + 15) / 16) {
-    case 1: lm_head_launch_mt<DT, 1, 4>(a, blocks, st); break;
-    case 2: lm_head_launch_mt<DT, 2, 2>(a, blocks, st); break;
-    case 3: lm_head_launch_mt<DT, 3, 2>(a, blocks, st); break;
-    default: lm_head_launch_mt<DT, 4, 2>(a, blocks, st); break;
+    case 1: lm_head_launch_mt<DT, 1, 4>(a, cap, blocks, st); break;
+    case 2: lm_head_launch_mt<DT, 2, 2>(a, cap, blocks, st); break;
+    case 3: lm_head_launch_mt<DT, 3, 2>(a, cap, blocks, st); break;
+    default: lm_head_launch_mt<DT, 4, 2>(a, cap, blocks, st); break;
   }
 }
 
@@ -310,13 +328,19 @@ int lm_head_plan(int m, int v, int k, int out[4]) {
 
 int launch_lm_head(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
                    int out_f32, int m, int v, int k, int dtype, int max_blocks, hipStream_t st) {
+  return launch_lm_head_softcap(x, ldx, gamma, eps, weight, bias, seqlens, out, out_f32, m, v, k, dtype, 0.f, max_blocks, st);
+}
+
+// softcap > 0: the capped epilogue; 0: launch_lm_head, the same kernels
+int launch_lm_head_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* seqlens, void* out,
+                           int out_f32, int m, int v, int k, int dtype, float softcap, int max_blocks, hipStream_t st) {
   int plan[4];
   if (lm_head_plan(m, v, k, plan) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0) return -1;
   const int blocks = max_blocks > 0 && max_blocks < plan[0] ? max_blocks : plan[0];
   const LmHeadArgs a = {(const uint16_t*)x, (const uint16_t*)gamma, (const uint16_t*)weight, (const uint16_t*)bias, seqlens, out, ldx, eps, m, v, k,
                         out_f32};
-  if (dtype == 0) lm_head_launch<F16>(a, blocks, st);
-  else lm_head_launch<BF16>(a, blocks, st);
+  if (dtype == 0) lm_head_launch<F16>(a, softcap, blocks, st);
+  else lm_head_launch<BF16>(a, softcap, blocks, st);
   return 0;
 }
 

@@ -20,8 +20,13 @@
 // bits wherever it is served.  A token is a COLUMN of the matrix product: whatever an ignored row of x holds (NaN included) stays in its own column.
 //
 // token_logprobs_kernel is the companion for logits that already exist ([B, V] fp32 / T with a row stride): one block per row, two passes, fixed order.
+//
+//   cap      awq_lm_head_logprobs_softcap (awq_softcap.hpp): every logit is capped in the tile epilogue, z <- cap * tanh(z / cap) in fp32 behind the
+//            bias, BEFORE it enters the max / sum-exp, the target pick and the argmax.  With round_logits z is rounded to T, capped in fp32 and
+//            rounded to T once more.  A compile-time form: lp_tile_softcap_kernel is lp_tile_body<.., true>, lp_tile_kernel stays <.., false>.
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
+#include "awq_softcap.hpp"
 
 namespace awq {
 namespace {
@@ -65,8 +70,9 @@ __device__ __forceinline__ LpPart lp_merge(const LpPart& a, const LpPart& b) {
   return r;
 }
 
-template <typename DT>
-__global__ __launch_bounds__(kLpThreads) void lp_tile_kernel(const LpArgs a) {
+template <typename DT, bool CAP>
+__device__ __forceinline__ void lp_tile_body(const LpArgs& a, float cap) {
+  (void)cap;
   using vec8 = typename DT::vec8;
   __shared__ __attribute__((aligned(16))) char smem[2 * kLpBufBytes];  // ALL of the block's LDS: the two staging buffers; the epilogue's meeting reuses it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1, r32 = lane & 31, h = lane >> 5;
@@ -189,6 +195,10 @@ __global__ __launch_bounds__(kLpThreads) void lp_tile_kernel(const LpArgs a) {
           const int v = v0 + wr * 64 + vi * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
           float zz = acc[vi][ti][e] + bz[vi * 16 + e];  // (+ 0.f without a bias: exact)
           if (a.round_logits) zz = DT::to_float(DT::from_float(zz));
+          if constexpr (CAP) {
+            zz = softcap_logit(zz, cap);
+            if (a.round_logits) zz = DT::to_float(DT::from_float(zz));
+          }
           if (v >= V) zz = kNegInf;
           z[vi * 16 + e] = zz;
           if (zz > p.m) {
@@ -245,6 +255,16 @@ __global__ __launch_bounds__(kLpThreads) void lp_tile_kernel(const LpArgs a) {
     }
     __syncthreads();  // the next tile stages into the meeting's bytes
   }
+}
+
+template <typename DT>
+__global__ __launch_bounds__(kLpThreads) void lp_tile_kernel(const LpArgs a) {
+  lp_tile_body<DT, false>(a, 0.f);
+}
+// the cap rides BEHIND LpArgs: lp_tile_kernel keeps its argument block
+template <typename DT>
+__global__ __launch_bounds__(kLpThreads) void lp_tile_softcap_kernel(const LpArgs a, float cap) {
+  lp_tile_body<DT, true>(a, cap);
 }
 
 struct LpOut {
@@ -411,6 +431,14 @@ size_t lm_logprobs_workspace_bytes(int t, int v, int k, int with_gamma) {
 int launch_lm_logprobs(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets, float* logprob,
                        float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits, void* workspace, int max_blocks,
                        hipStream_t st) {
+  return launch_lm_logprobs_softcap(x, ldx, gamma, eps, weight, bias, targets, logprob, lse, target_logit, argmax, t, v, k, dtype, round_logits, 0.f,
+                                    workspace, max_blocks, st);
+}
+
+// softcap > 0: the capped tile epilogue; 0: launch_lm_logprobs, the same kernels
+int launch_lm_logprobs_softcap(const void* x, long ldx, const void* gamma, float eps, const void* weight, const void* bias, const int* targets,
+                               float* logprob, float* lse, float* target_logit, int* argmax, int t, int v, int k, int dtype, int round_logits,
+                               float softcap, void* workspace, int max_blocks, hipStream_t st) {
   int plan[4];
   if (lm_logprobs_plan(t, v, k, plan) != 0 || ldx < k || (ldx % 8) != 0 || max_blocks < 0 || (gamma && ldx != k)) return -1;
   char* ws = reinterpret_cast<char*>(workspace);
@@ -424,7 +452,10 @@ int launch_lm_logprobs(const void* x, long ldx, const void* gamma, float eps, co
   const LpArgs a = {(const uint16_t*)x, (const uint16_t*)weight, (const uint16_t*)bias, targets, (float*)ws, (float*)(ws + part), (int*)(ws + 2 * part),
                     (float*)(ws + 3 * part), ldx, t, v, k, round_logits != 0, ntr, ntv};
   const int blocks = max_blocks > 0 && max_blocks < plan[2] ? max_blocks : plan[2];
-  if (dtype == 0) hipLaunchKernelGGL((lp_tile_kernel<F16>), dim3(blocks), dim3(kLpThreads), 0, st, a);
+  if (softcap > 0.f) {
+    if (dtype == 0) hipLaunchKernelGGL((lp_tile_softcap_kernel<F16>), dim3(blocks), dim3(kLpThreads), 0, st, a, softcap);
+    else hipLaunchKernelGGL((lp_tile_softcap_kernel<BF16>), dim3(blocks), dim3(kLpThreads), 0, st, a, softcap);
+  } else if (dtype == 0) hipLaunchKernelGGL((lp_tile_kernel<F16>), dim3(blocks), dim3(kLpThreads), 0, st, a);
   else hipLaunchKernelGGL((lp_tile_kernel<BF16>), dim3(blocks), dim3(kLpThreads), 0, st, a);
   const LpOut o = {targets, logprob, lse, target_logit, argmax};
   hipLaunchKernelGGL(lp_combine_kernel, dim3((t + 3) / 4), dim3(256), 0, st, a.pm, a.ps, a.pi, a.ptl, o, t, v, ntv);

@@ -7,6 +7,7 @@
 // tinychat/offline-weight-repacker.py:8-19,64-73,111-152 (v1 -> v2).
 #include "awq_device.hpp"
 #include "awq_kernels.hpp"
+#include "awq_softcap.hpp"
 
 namespace awq {
 
@@ -424,6 +425,38 @@ int launch_round_bias_f32(const void* in_f32, const void* bias, void* out, int m
   const unsigned blocks = (unsigned)(octets + 255) / 256 > 4096u ? 4096u : (unsigned)((octets + 255) / 256);
   if (dtype == 0) hipLaunchKernelGGL((round_bias_f32_kernel<F16>), dim3(blocks), dim3(256), 0, st, (const float*)in_f32, (const uint16_t*)bias, (uint16_t*)out, octets, n);
   else hipLaunchKernelGGL((round_bias_f32_kernel<BF16>), dim3(blocks), dim3(256), 0, st, (const float*)in_f32, (const uint16_t*)bias, (uint16_t*)out, octets, n);
+  return 0;
+}
+
+// logits [b, v] with row stride ld, capped in place (awq_softcap.hpp; Gemma-2's final_logit_softcapping on logits that already exist):
+// z <- T(cap * tanh(f32(z) / cap)), one rounding.  One thread per element and turn; a row with seqlens[row] < 0 is neither read nor written.
+// DTYPE 0 fp16, 1 bf16, 2 fp32.
+template <int DTYPE>
+__global__ __launch_bounds__(256) void logit_softcap_kernel(void* __restrict__ logits, long ld, const int* __restrict__ seqlens, size_t total, int v,
+                                                            float cap) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t row = i / (size_t)v, at = row * (size_t)ld + (i - row * (size_t)v);
+    if (seqlens != nullptr && seqlens[row] < 0) continue;
+    if constexpr (DTYPE == 2) {
+      float* z = reinterpret_cast<float*>(logits) + at;
+      *z = softcap_logit(*z, cap);
+    } else if constexpr (DTYPE == 0) {
+      uint16_t* z = reinterpret_cast<uint16_t*>(logits) + at;
+      *z = F16::from_float(softcap_logit(F16::to_float(*z), cap));
+    } else {
+      uint16_t* z = reinterpret_cast<uint16_t*>(logits) + at;
+      *z = BF16::from_float(softcap_logit(BF16::to_float(*z), cap));
+    }
+  }
+}
+
+int launch_logit_softcap(void* logits, int logits_dtype, long ld, const int* seqlens, int b, int v, float softcap, hipStream_t st) {
+  if (b < 1 || v < 1 || ld < v || !(softcap > 0.f)) return -1;
+  const size_t total = (size_t)b * (size_t)v;
+  const unsigned blocks = (total + 255) / 256 > 65536u ? 65536u : (unsigned)((total + 255) / 256);
+  if (logits_dtype == 2) hipLaunchKernelGGL((logit_softcap_kernel<2>), dim3(blocks), dim3(256), 0, st, logits, ld, seqlens, total, v, softcap);
+  else if (logits_dtype == 0) hipLaunchKernelGGL((logit_softcap_kernel<0>), dim3(blocks), dim3(256), 0, st, logits, ld, seqlens, total, v, softcap);
+  else hipLaunchKernelGGL((logit_softcap_kernel<1>), dim3(blocks), dim3(256), 0, st, logits, ld, seqlens, total, v, softcap);
   return 0;
 }
 

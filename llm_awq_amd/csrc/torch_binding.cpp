@@ -714,8 +714,16 @@ std::vector<torch::Tensor> spec_accept(torch::Tensor row_tokens, torch::Tensor i
 }
 
 // ---- LM head for decode (final RMSNorm + vocabulary GEMV, one launch) and the token embedding gather that takes the sampler's -1 ----
-torch::Tensor lm_head(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
-                      c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out, at::ScalarType out_dtype, int64_t max_blocks) {
+// a cap as the C ABI takes it: finite and not negative, 0 = no cap
+static float checked_softcap(const char* who, double softcap) {
+  const float cap = (float)softcap;
+  TORCH_CHECK(softcap >= 0.0 && cap <= 3.4028234663852886e38f, who, ": softcap ", softcap, " must be finite and not negative (0: no cap)");
+  return cap;
+}
+
+static torch::Tensor lm_head_impl(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> gamma, double eps,
+                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out,
+                                  at::ScalarType out_dtype, int64_t max_blocks, float softcap) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && (x.stride(1) == 1 || x.size(1) <= 1), "awq_inference_engine: lm_head: x must be a [M, K] GPU tensor with a contiguous last dimension");
   TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() && weight.dim() == 2 && weight.size(1) == x.size(1) && weight.scalar_type() == x.scalar_type(),
               "lm_head: weight must be a contiguous [V, K] GPU tensor of x's dtype");
@@ -739,11 +747,42 @@ torch::Tensor lm_head(torch::Tensor x, torch::Tensor weight, c10::optional<torch
     o = seqlens.has_value() ? torch::zeros({m, v}, x.options().dtype(out_dtype)) : torch::empty({m, v}, x.options().dtype(out_dtype));
   }
   const int64_t ldx = m > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), k) / 8 * 8;
-  raise_on(awq_lm_head(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
-                       vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(seqlens, at::kInt, m, "seqlens"), o.data_ptr(),
-                       out_dtype == at::kFloat ? AWQ_F32 : code, (int)m, (int)v, (int)k, code, (int)max_blocks,
-                       (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  raise_on(awq_lm_head_softcap(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
+                               vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(seqlens, at::kInt, m, "seqlens"), o.data_ptr(),
+                               out_dtype == at::kFloat ? AWQ_F32 : code, (int)m, (int)v, (int)k, code, softcap, (int)max_blocks,
+                               (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
   return o;
+}
+
+torch::Tensor lm_head(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
+                      c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out, at::ScalarType out_dtype, int64_t max_blocks) {
+  return lm_head_impl(x, weight, gamma, eps, bias, seqlens, out, out_dtype, max_blocks, 0.f);  // softcap 0: awq_lm_head itself
+}
+
+// lm_head with every logit capped in the epilogue: softcap * tanh(y / softcap) on the fp32 sum behind the bias, before the one rounding
+torch::Tensor lm_head_softcap(torch::Tensor x, torch::Tensor weight, double softcap, c10::optional<torch::Tensor> gamma, double eps,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> seqlens, c10::optional<torch::Tensor> out,
+                              at::ScalarType out_dtype, int64_t max_blocks) {
+  return lm_head_impl(x, weight, gamma, eps, bias, seqlens, out, out_dtype, max_blocks, checked_softcap("lm_head_softcap", softcap));
+}
+
+// logits [B, V] that already exist, capped in place; rows with seqlens < 0 untouched.  Returns logits
+torch::Tensor logit_softcap_(torch::Tensor logits, double softcap, c10::optional<torch::Tensor> seqlens) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && (logits.stride(1) == 1 || logits.size(1) <= 1),
+              "awq_inference_engine: logit_softcap_: logits must be a [B, V] GPU tensor with a contiguous last dimension");
+  const auto st = logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, "logit_softcap_: logits must be float32, bfloat16 or float16");
+  const int64_t b = logits.size(0), v = logits.size(1);
+  TORCH_CHECK(!seqlens.has_value() || (seqlens->is_cuda() && seqlens->is_contiguous() && seqlens->scalar_type() == at::kInt && seqlens->numel() == b &&
+                                       seqlens->device() == logits.device()),
+              "logit_softcap_: seqlens must be a contiguous int32 [B] tensor on the logits' device");
+  const float cap = checked_softcap("logit_softcap_", softcap);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  const int64_t ld = b > 1 ? logits.stride(0) : std::max<int64_t>(logits.stride(0), v);
+  raise_on(awq_logit_softcap(logits.data_ptr(), st == at::kFloat ? AWQ_F32 : (st == at::kHalf ? AWQ_F16 : AWQ_BF16), (long)ld,
+                             seqlens.has_value() ? (const int*)seqlens->data_ptr() : nullptr, (int)b, (int)v, cap,
+                             (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return logits;
 }
 
 torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
@@ -762,9 +801,9 @@ torch::Tensor embed_tokens(torch::Tensor tokens, torch::Tensor table) {
 
 // ---- Token log-probabilities: LM head fused with log-sum-exp; returns (logprob, lse, target_logit, argmax), zero-filled where a row is ignored (and
 //      logprob / target_logit all zeros without targets) ----
-std::vector<torch::Tensor> lm_head_logprobs(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> targets,
-                                            c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias, bool round_logits,
-                                            int64_t max_blocks) {
+static std::vector<torch::Tensor> lm_head_logprobs_impl(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> targets,
+                                                       c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
+                                                       bool round_logits, int64_t max_blocks, float softcap) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && (x.stride(1) == 1 || x.size(1) <= 1),
               "awq_inference_engine: lm_head_logprobs: x must be a [T, K] GPU tensor with a contiguous last dimension");
   TORCH_CHECK(weight.is_cuda() && weight.is_contiguous() && weight.dim() == 2 && weight.size(1) == x.size(1) && weight.scalar_type() == x.scalar_type(),
@@ -786,12 +825,25 @@ std::vector<torch::Tensor> lm_head_logprobs(torch::Tensor x, torch::Tensor weigh
   at::Tensor ws = torch::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
   const int64_t ldx = gamma.has_value() ? k : (t > 1 ? x.stride(0) : std::max<int64_t>(x.stride(0), k) / 8 * 8);
   const bool tg = targets.has_value();
-  raise_on(awq_lm_head_logprobs(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
-                                vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(targets, at::kInt, t, "targets"),
-                                tg ? (float*)logprob.data_ptr() : nullptr, (float*)lse.data_ptr(), tg ? (float*)tl.data_ptr() : nullptr,
-                                (int*)argmax.data_ptr(), (int)t, (int)v, (int)k, code, round_logits ? 1 : 0, ws.data_ptr(), bytes, (int)max_blocks,
-                                (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  raise_on(awq_lm_head_logprobs_softcap(x.data_ptr(), (long)ldx, vec(gamma, x.scalar_type(), k, "gamma"), (float)eps, weight.data_ptr(),
+                                        vec(bias, x.scalar_type(), v, "bias"), (const int*)vec(targets, at::kInt, t, "targets"),
+                                        tg ? (float*)logprob.data_ptr() : nullptr, (float*)lse.data_ptr(), tg ? (float*)tl.data_ptr() : nullptr,
+                                        (int*)argmax.data_ptr(), (int)t, (int)v, (int)k, code, round_logits ? 1 : 0, softcap, ws.data_ptr(), bytes,
+                                        (int)max_blocks, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
   return {logprob, lse, tl, argmax};
+}
+
+std::vector<torch::Tensor> lm_head_logprobs(torch::Tensor x, torch::Tensor weight, c10::optional<torch::Tensor> targets,
+                                            c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias, bool round_logits,
+                                            int64_t max_blocks) {
+  return lm_head_logprobs_impl(x, weight, targets, gamma, eps, bias, round_logits, max_blocks, 0.f);  // softcap 0: awq_lm_head_logprobs itself
+}
+
+// lm_head_logprobs with every logit capped before the max / sum-exp, the target pick and the argmax
+std::vector<torch::Tensor> lm_head_logprobs_softcap(torch::Tensor x, torch::Tensor weight, double softcap, c10::optional<torch::Tensor> targets,
+                                                    c10::optional<torch::Tensor> gamma, double eps, c10::optional<torch::Tensor> bias,
+                                                    bool round_logits, int64_t max_blocks) {
+  return lm_head_logprobs_impl(x, weight, targets, gamma, eps, bias, round_logits, max_blocks, checked_softcap("lm_head_logprobs_softcap", softcap));
 }
 
 // (logprob, lse, argmax) of logits [B, V] that already exist
@@ -1333,6 +1385,10 @@ struct PackedStep {
   // a mixed step with a sliding window (attn_varq_window and its siblings): a row attends its own key and the window_left keys before it.
   // window_left < 0: no window
   int64_t window_left = -1;
+  // a windowed step whose logits are capped (attn_varq_softcap and its siblings): cap * tanh(scale * q.k / cap) in front of the mask.
+  // capped: the call goes to the *_softcap entries, which hand softcap = 0 to the *_window ones
+  bool capped = false;
+  double softcap = 0.0;
 };
 
 static void check_cu_seqlens(const char* who, const torch::Tensor& cu, const torch::Tensor& ref, int64_t max_seqlen_q) {
@@ -1556,6 +1612,11 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   const bool windowed = mixed && step.window_left >= 0;
   const int wl = (int)std::min<int64_t>(step.window_left, 0x7FFFFFFF);
   if (windowed) TORCH_CHECK(causal, who, ": a sliding window needs causal = true");
+  const bool capped = windowed && step.capped;
+  const float scap = (float)step.softcap;
+  if (step.capped)
+    TORCH_CHECK(windowed && step.softcap >= 0.0 && scap <= 3.4028234663852886e38f, who, ": softcap ", step.softcap,
+                " must be finite and not negative (0: no cap)");
   check_seqlens(who, "seqlens_k", seqlens_k, q, batch);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   at::Tensor out = packed ? packed_out(who, "out", *step.out, q, total, nheads, headdim)
@@ -1584,7 +1645,19 @@ static torch::Tensor attn_kvcache_impl(const char* who, const torch::Tensor& q, 
   if (mixed) {
     const int ssq = (int)step.split_seqlen_q, smk = (int)std::min<int64_t>(step.split_min_keys, 0x7FFFFFFF);
     void* wp = wsb ? ws.data_ptr() : nullptr;
-    if (windowed && paged && fp8)
+    if (capped && paged && fp8)
+      raise_on(awq_attn_paged_varq_softcap_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs,
+                                               kbs, krs, vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ssq, smk, wl, scap, wp, wsb, st));
+    else if (capped && paged)
+      raise_on(awq_attn_paged_varq_softcap(qp, kp, vp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs, kbs, krs, vbs,
+                                           vrs, scale, cz, dt, ssq, smk, wl, scap, wp, wsb, st));
+    else if (capped && fp8)
+      raise_on(awq_attn_varq_softcap_kv8(qp, kp, vp, ksp, vsp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, ksbs, ksrs,
+                                         vsbs, vsrs, scale, cz, dt, ssq, smk, wl, scap, wp, wsb, st));
+    else if (capped)
+      raise_on(awq_attn_varq_softcap(qp, kp, vp, op, B, cup, Sq, T, lens, off, bound, L, H, Hkv, Dh, qrs, kbs, krs, vbs, vrs, scale, cz, dt, ssq, smk,
+                                     wl, scap, wp, wsb, st));
+    else if (windowed && paged && fp8)
       raise_on(awq_attn_paged_varq_window_kv8(qp, kp, vp, ksp, vsp, op, btp, B, cup, Sq, T, lens, off, bound, pages, page, pps, btrs, H, Hkv, Dh, qrs,
                                               kbs, krs, vbs, vrs, ksbs, ksrs, vsbs, vsrs, scale, cz, dt, ssq, smk, wl, wp, wsb, st));
     else if (windowed && paged)
@@ -2023,6 +2096,47 @@ torch::Tensor attn_paged_varq_window_kv8(const torch::Tensor q, const torch::Ten
   return attn_kvcache_impl("attn_paged_varq_window_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0,
                            softmax_scale, causal, true,
                            {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left});
+}
+
+// attn_varq_softcap[_kv8] / attn_paged_varq_softcap[_kv8]: the four entries above with softcap behind window_left -- the logits become
+// softcap * tanh(softmax_scale * q.k / softcap) in front of the causal / window mask (Gemma-2, Grok-1).  softcap = 0: the *_window entry.
+torch::Tensor attn_varq_softcap(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor cu_seqlens_q,
+                               int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q,
+                               int64_t split_min_keys, int64_t window_left, double softcap, bool lens_before_step, double softmax_scale, bool causal,
+                               c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_varq_softcap: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_varq_softcap", q, {k_cache, v_cache, nullptr, nullptr, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale, causal,
+                           true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left, true, softcap});
+}
+
+torch::Tensor attn_varq_softcap_kv8(const torch::Tensor q, const torch::Tensor k_cache, const torch::Tensor v_cache, const torch::Tensor k_scale,
+                                   const torch::Tensor v_scale, const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q,
+                                   const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q, int64_t split_min_keys,
+                                   int64_t window_left, double softcap, bool lens_before_step, double softmax_scale, bool causal,
+                                   c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_varq_softcap_kv8: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_varq_softcap_kv8", q, {k_cache, v_cache, &k_scale, &v_scale, nullptr}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left, true, softcap});
+}
+
+torch::Tensor attn_paged_varq_softcap(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor block_table,
+                                     const torch::Tensor cu_seqlens_q, int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k,
+                                     int64_t split_seqlen_q, int64_t split_min_keys, int64_t window_left, double softcap, bool lens_before_step,
+                                     double softmax_scale, bool causal, c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_paged_varq_softcap: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_paged_varq_softcap", q, {k_pool, v_pool, nullptr, nullptr, &block_table}, seqlens_k, max_seqlen_k, 0, softmax_scale,
+                           causal, true, {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left, true, softcap});
+}
+
+torch::Tensor attn_paged_varq_softcap_kv8(const torch::Tensor q, const torch::Tensor k_pool, const torch::Tensor v_pool, const torch::Tensor k_scale,
+                                         const torch::Tensor v_scale, const torch::Tensor block_table, const torch::Tensor cu_seqlens_q,
+                                         int64_t max_seqlen_q, const torch::Tensor seqlens_k, int64_t max_seqlen_k, int64_t split_seqlen_q,
+                                         int64_t split_min_keys, int64_t window_left, double softcap, bool lens_before_step, double softmax_scale, bool causal,
+                                         c10::optional<torch::Tensor> out) {
+  TORCH_CHECK(split_seqlen_q >= 0 && window_left >= 0, "attn_paged_varq_softcap_kv8: split_seqlen_q and window_left must not be negative");
+  return attn_kvcache_impl("attn_paged_varq_softcap_kv8", q, {k_pool, v_pool, &k_scale, &v_scale, &block_table}, seqlens_k, max_seqlen_k, 0,
+                           softmax_scale, causal, true,
+                           {&cu_seqlens_q, max_seqlen_q, &out, lens_before_step, split_seqlen_q, split_min_keys, window_left, true, softcap});
 }
 
 // (splits, chunk) of awq_attn_varq_window_plan: attn_kvcache_plan's for min(max_seqlen_k, window_left + split_seqlen_q + 63).  Host only.
@@ -2573,6 +2687,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
         py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"),
         py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_softcap", &attn_varq_softcap, "attn_varq_window with the logits capped: softcap * tanh(scale * q.k / softcap) in front of the mask",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"),
+        py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("softcap"), py::arg("lens_before_step"),
+        py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_varq_softcap_kv8", &attn_varq_softcap_kv8, "attn_varq_softcap on the FP8 cache", py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("softcap"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_paged_varq_softcap", &attn_paged_varq_softcap, "attn_varq_softcap over a paged KV cache", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"), py::arg("seqlens_k"), py::arg("max_seqlen_k"),
+        py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("softcap"), py::arg("lens_before_step"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("out") = py::none());
+  m.def("attn_paged_varq_softcap_kv8", &attn_paged_varq_softcap_kv8, "attn_paged_varq_softcap on FP8 pools", py::arg("q"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("k_scale"), py::arg("v_scale"), py::arg("block_table"), py::arg("cu_seqlens_q"), py::arg("max_seqlen_q"),
+        py::arg("seqlens_k"), py::arg("max_seqlen_k"), py::arg("split_seqlen_q"), py::arg("split_min_keys"), py::arg("window_left"), py::arg("softcap"),
+        py::arg("lens_before_step"), py::arg("softmax_scale"), py::arg("causal"), py::arg("out") = py::none());
   m.def("attn_varq_window_plan", &attn_varq_window_plan,
         "(splits, chunk) of the split pair of a windowed mixed step: attn_kvcache_plan's for min(max_seqlen_k, window_left + split_seqlen_q + 63)",
         py::arg("batch"), py::arg("nheads"), py::arg("nheads_kv"), py::arg("head_dim"), py::arg("split_seqlen_q"), py::arg("max_seqlen_k"),
@@ -2670,12 +2800,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lm_head", &lm_head, "logits [M, V] = rmsnorm(x) @ weight^T (+ bias): final RMSNorm and vocabulary GEMV in one launch, inactive rows (seqlens < 0) untouched",
         py::arg("x"), py::arg("weight"), py::arg("gamma") = py::none(), py::arg("eps") = 0.0, py::arg("bias") = py::none(),
         py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
+  m.def("lm_head_softcap", &lm_head_softcap, "lm_head with the logits capped in the epilogue: softcap * tanh(y / softcap) in fp32 behind the bias",
+        py::arg("x"), py::arg("weight"), py::arg("softcap"), py::arg("gamma") = py::none(), py::arg("eps") = 0.0, py::arg("bias") = py::none(),
+        py::arg("seqlens") = py::none(), py::arg("out") = py::none(), py::arg("out_dtype") = at::kFloat, py::arg("max_blocks") = 0);
+  m.def("logit_softcap_", &logit_softcap_, "existing logits [B, V] (fp32 / bf16 / fp16) capped in place; rows with seqlens < 0 untouched",
+        py::arg("logits"), py::arg("softcap"), py::arg("seqlens") = py::none());
   m.def("embed_tokens", &embed_tokens, "out[i] = table[tokens[i]], zeros for an id outside the table (-1 = a finished slot)", py::arg("tokens"),
         py::arg("table"));
   m.def("lm_head_logprobs", &lm_head_logprobs,
         "(logprob, lse, target_logit, argmax) per row of x against weight [V, K]: the LM head fused with log-sum-exp, no logits written; rows whose target "
         "is outside [0, V) are ignored",
         py::arg("x"), py::arg("weight"), py::arg("targets") = py::none(), py::arg("gamma") = py::none(), py::arg("eps") = 0.0,
+        py::arg("bias") = py::none(), py::arg("round_logits") = false, py::arg("max_blocks") = 0);
+  m.def("lm_head_logprobs_softcap", &lm_head_logprobs_softcap,
+        "lm_head_logprobs with every logit capped, softcap * tanh(z / softcap), before the max / sum-exp, the target pick and the argmax",
+        py::arg("x"), py::arg("weight"), py::arg("softcap"), py::arg("targets") = py::none(), py::arg("gamma") = py::none(), py::arg("eps") = 0.0,
         py::arg("bias") = py::none(), py::arg("round_logits") = false, py::arg("max_blocks") = 0);
   m.def("token_logprobs", &token_logprobs, "(logprob, lse, argmax) per row of existing logits [B, V] (fp32 / bf16 / fp16)", py::arg("logits"),
         py::arg("targets") = py::none());

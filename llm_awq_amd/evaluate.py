@@ -32,8 +32,14 @@ def _hidden(hidden_fn, batch):
     return h.reshape(-1, h.shape[-1])
 
 
-def perplexity(hidden_fn, head, input_ids, seqlen: int = 2048, round_logits: bool = True) -> float:
-    """entry.py:304-326 over the head's log-probabilities.  The windows' NLLs are added on the device in fp32, in window order; one host read at the end."""
+def _cap_kw(final_softcap):
+    """`final_softcap` for head.logprobs, handed over only when one is given: a head without the keyword is called as before."""
+    return {} if final_softcap is None else {"final_softcap": final_softcap}
+
+
+def perplexity(hidden_fn, head, input_ids, seqlen: int = 2048, round_logits: bool = True, final_softcap=None) -> float:
+    """entry.py:304-326 over the head's log-probabilities.  The windows' NLLs are added on the device in fp32, in window order; one host read at the end.
+    `final_softcap` (None: the head's own, if any) caps the logits as c * tanh(z / c) before the log-sum-exp (Gemma-2: 30)."""
     ids = _ids_1d(input_ids)
     nsamples = ids.numel() // seqlen
     if seqlen < 2 or nsamples < 1:
@@ -43,14 +49,15 @@ def perplexity(hidden_fn, head, input_ids, seqlen: int = 2048, round_logits: boo
         batch = ids[i * seqlen:(i + 1) * seqlen]
         with torch.no_grad():
             h = _hidden(hidden_fn, batch)
-            lp = head.logprobs(h[:-1], batch[1:].to(device=h.device, dtype=torch.int32), round_logits=round_logits)["logprob"]
+            lp = head.logprobs(h[:-1], batch[1:].to(device=h.device, dtype=torch.int32), round_logits=round_logits, **_cap_kw(final_softcap))["logprob"]
             nll = (-(lp.float().sum()) / (seqlen - 1)).float() * seqlen   # CrossEntropyLoss's mean, then `loss.float() * model.seqlen`
         total = nll if total is None else total + nll
     return float(torch.exp(total / (nsamples * seqlen)).item())
 
 
-def loglikelihood(hidden_fn, head, context_ids, continuation_ids, round_logits: bool = True):
-    """lm-eval's pair for one request: (sum of log p(continuation token | everything before it), whether each of them was the argmax)."""
+def loglikelihood(hidden_fn, head, context_ids, continuation_ids, round_logits: bool = True, final_softcap=None):
+    """lm-eval's pair for one request: (sum of log p(continuation token | everything before it), whether each of them was the argmax).
+    `final_softcap` as in `perplexity`."""
     ctx, cont = _ids_1d(context_ids), _ids_1d(continuation_ids)
     if ctx.numel() < 1 or cont.numel() < 1:
         raise ValueError("loglikelihood: context and continuation must hold at least one token each")
@@ -58,13 +65,14 @@ def loglikelihood(hidden_fn, head, context_ids, continuation_ids, round_logits: 
     with torch.no_grad():
         h = _hidden(hidden_fn, inp)[-cont.numel():]
         tg = cont.to(device=h.device, dtype=torch.int32)
-        res = head.logprobs(h, tg, round_logits=round_logits, want=("logprob", "argmax"))
+        res = head.logprobs(h, tg, round_logits=round_logits, want=("logprob", "argmax"), **_cap_kw(final_softcap))
         both = torch.stack([res["logprob"].double().sum(), (res["argmax"] == tg).all().double()]).cpu()   # one host read
     return float(both[0]), bool(both[1] != 0)
 
 
-def perplexity_hf(model, input_ids, seqlen: int = 2048, round_logits: bool = True) -> float:
-    """`perplexity` for a Hugging Face style causal LM: `model.model(ids)[0]` are the hidden states behind the final norm, `model.lm_head` the head."""
+def perplexity_hf(model, input_ids, seqlen: int = 2048, round_logits: bool = True, final_softcap=None) -> float:
+    """`perplexity` for a Hugging Face style causal LM: `model.model(ids)[0]` are the hidden states behind the final norm, `model.lm_head` the head.
+    `final_softcap` is the model's final_logit_softcapping (Gemma-2: 30); it is passed through, the config is not read."""
     from .lm_head import LMHead
-    head = LMHead.from_modules(None, model.lm_head)
+    head = LMHead.from_modules(None, model.lm_head, final_softcap=final_softcap)
     return perplexity(lambda b: model.model(b.to(head.weight.device))[0], head, input_ids, seqlen, round_logits)

@@ -76,11 +76,22 @@ class QuantLlamaAttentionFused(nn.Module):
     head is normalised over head_dim between the qkv projection and the rotation, inside the store launch of every natural-layout route
     (the `rope_kv_store_*_qknorm` entries).  The weights [head_dim] are held as the float32 buffers `q_norm_weight` / `k_norm_weight`
     (Gemma-3 hands in 1 + w, formed in float32); `kv_layout="ft"` with `qk_norm` raises NotImplementedError.  `head_dim` is
-    `args.head_dim` where the config declares one (Qwen3: hidden 1024, 16 heads, head_dim 128), else hidden_size // num_heads."""
+    `args.head_dim` where the config declares one (Qwen3: hidden 1024, 16 heads, head_dim 128), else hidden_size // num_heads.
+    `softmax_scale=s` (None: head_dim ** -0.5, nothing changes) replaces head_dim ** -0.5 on every path that takes a scale (Gemma-2-27B:
+    144 ** -0.5, its query_pre_attn_scalar); the FT decode kernel (int `start_pos`, one token, `kv_layout="ft"`) forms its own scale and
+    raises NotImplementedError with one.  `attn_softcap=c` (None: no cap, nothing changes; Gemma-2 50, Grok-1 30) caps the attention logits
+    as c * tanh(s * q.k / c) in front of the mask.  It is served where the window is -- `forward_packed`, `forward_packed_split` and `forward`
+    with a tensor `start_pos`, on the attn_*_varq_softcap entries, a layer without `sliding_window` with a window that hides nothing; an int
+    `start_pos`, `kv_layout="ft"`, `forward_shared` and FT `chunk_prefilling` raise NotImplementedError before any work."""
 
     def __init__(self, hidden_size, num_heads, kv_max_seq_len, qkv_layer, o_proj, dev, args, max_batch_size=1, kv_layout="ft", kv_dtype=None,
-                 sliding_window=None, qk_norm=None):
+                 sliding_window=None, qk_norm=None, attn_softcap=None, softmax_scale=None):
         super().__init__()
+        for name, val in (("attn_softcap", attn_softcap), ("softmax_scale", softmax_scale)):
+            if val is not None and (isinstance(val, bool) or not isinstance(val, (int, float)) or not (0.0 < float(val) < float("inf"))):
+                raise ValueError(f"QuantLlamaAttentionFused: {name} {val!r} must be None or a finite float > 0")
+        self.attn_softcap = None if attn_softcap is None else float(attn_softcap)
+        self._scale_given = softmax_scale is not None
         if sliding_window is not None and (isinstance(sliding_window, bool) or int(sliding_window) != sliding_window or int(sliding_window) < 1):
             raise ValueError(f"QuantLlamaAttentionFused: sliding_window {sliding_window!r} must be None or an int >= 1 (the keys a row attends, "
                              "itself included)")
@@ -115,6 +126,7 @@ class QuantLlamaAttentionFused(nn.Module):
             self.rope_scaling = self.rope_scaling.get("factor", 1.0)
         if self.head_dim not in (64, 128):
             raise ValueError(f"QuantLlamaAttentionFused: head dim {self.head_dim} is not supported (supported head dims: 64, 128)")
+        self.softmax_scale = self.head_dim ** -0.5 if softmax_scale is None else float(softmax_scale)
         self.qk_norm_eps = None
         if qk_norm is not None:
             q_weight, k_weight, eps = qk_norm
@@ -172,16 +184,18 @@ class QuantLlamaAttentionFused(nn.Module):
 
         A PACKED step of continuous batching (per-sequence numbers of new tokens) is `forward_packed`.
 
-        With `sliding_window` the call needs a tensor `start_pos`: it builds the uniform cu_seqlens_q = [0, seqlen, 2 seqlen, ..] on the
+        With `sliding_window` or `attn_softcap` the call needs a tensor `start_pos`: it builds the uniform cu_seqlens_q = [0, seqlen, 2 seqlen, ..] on the
         device and is `forward_packed_split` on the batch as one packed step (split_seqlen_q = seqlen while seqlen * (H / Hkv) <= 128,
         else 0)."""
         if self.sliding_window is not None:
             self._check_window(start_pos, chunk_prefilling)
+        if self.attn_softcap is not None:
+            self._check_window(start_pos, chunk_prefilling, "attn_softcap")
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
         eng = load_engine()
         bsz, seqlen, _ = x.shape
-        if self.sliding_window is not None:
+        if self.sliding_window is not None or self.attn_softcap is not None:
             from .ops import ATTN_SPLIT_MIN_KEYS
 
             cu = torch.arange(0, (bsz + 1) * seqlen, seqlen, dtype=torch.int32, device=x.device)
@@ -202,7 +216,7 @@ class QuantLlamaAttentionFused(nn.Module):
                              self.cache_k_scale, self.cache_v_scale, start_pos, self.n_local_heads, self.num_key_value_heads)
             end = start_pos + seqlen
             output = ops.attn_kv8(xq, self.cache_k[:bsz, :end], self.cache_v[:bsz, :end], self.cache_k_scale[:bsz, :end],
-                                  self.cache_v_scale[:bsz, :end], causal=True)
+                                  self.cache_v_scale[:bsz, :end], **self._scale_kw(), causal=True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if self.cache_k.dtype != xqkv.dtype or self.cache_k.device != xqkv.device:  # the reference's .to(xq) (:256-257)
             self.cache_k = self.cache_k.to(xqkv)
@@ -212,15 +226,19 @@ class QuantLlamaAttentionFused(nn.Module):
 
             xq = self._store(eng, "rope_kv_store_natural", xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos,
                              self.n_local_heads, self.num_key_value_heads)
-            output = flash_attn_func(xq, self.cache_k[:bsz, :start_pos + seqlen], self.cache_v[:bsz, :start_pos + seqlen], causal=True)
+            output = flash_attn_func(xq, self.cache_k[:bsz, :start_pos + seqlen], self.cache_v[:bsz, :start_pos + seqlen], **self._scale_kw(),
+                                     causal=True)
             return self.o_proj(output.view(bsz, seqlen, -1))
         if seqlen > 1:
             xq = eng.rope_kv_store(xqkv.reshape(bsz, seqlen, -1), freqs, self.cache_k, self.cache_v, start_pos, self.n_local_heads,
                                    self.num_key_value_heads)
             kv_start, seqlen_k = (0, start_pos + seqlen) if chunk_prefilling else (start_pos, seqlen)
-            output = eng.attn_prefill_ftcache(xq, self.cache_k, self.cache_v, kv_start, seqlen_k, self.head_dim ** -0.5, True)
+            output = eng.attn_prefill_ftcache(xq, self.cache_k, self.cache_v, kv_start, seqlen_k, self.softmax_scale, True)
             output = output.view(bsz, seqlen, -1)
         else:
+            if self._scale_given:
+                raise NotImplementedError("QuantLlamaAttentionFused: softmax_scale is not implemented for the FT decode kernel (int start_pos, one "
+                                          "token, kv_layout 'ft': it forms head_dim ** -0.5 itself); use kv_layout 'natural'")
             xqkv = xqkv.view(bsz, self.n_local_heads + self.num_key_value_heads * 2, self.head_dim)
             xq = xqkv[:, :self.n_local_heads]
             xk = xqkv[:, self.n_local_heads:self.n_local_heads + self.num_key_value_heads]
@@ -230,16 +248,20 @@ class QuantLlamaAttentionFused(nn.Module):
             output = output.reshape(bsz, 1, -1)
         return self.o_proj(output)
 
-    def _check_window(self, start_pos, chunk_prefilling=False):
-        """What `sliding_window` is not built for, refused before any work."""
+    def _scale_kw(self):
+        """softmax_scale for the calls that default to head_dim ** -0.5 themselves: handed over only when the module was given one."""
+        return {"softmax_scale": self.softmax_scale} if self._scale_given else {}
+
+    def _check_window(self, start_pos, chunk_prefilling=False, what="sliding_window"):
+        """What `sliding_window` (and `attn_softcap`, which rides the windowed entries) is not built for, refused before any work."""
         who = "QuantLlamaAttentionFused"
         if self.kv_layout != "natural":
             if chunk_prefilling:
-                raise NotImplementedError(f"{who}: sliding_window is not implemented for chunk_prefilling on the FT cache (kv_layout 'ft'); "
+                raise NotImplementedError(f"{who}: {what} is not implemented for chunk_prefilling on the FT cache (kv_layout 'ft'); "
                                           "use kv_layout 'natural' with start_pos as a tensor")
-            raise NotImplementedError(f"{who}: sliding_window is not implemented on the FT cache (kv_layout 'ft'); use kv_layout 'natural'")
+            raise NotImplementedError(f"{who}: {what} is not implemented on the FT cache (kv_layout 'ft'); use kv_layout 'natural'")
         if not isinstance(start_pos, torch.Tensor):
-            raise NotImplementedError(f"{who}: sliding_window is not implemented for an int start_pos (the host-length path); pass start_pos "
+            raise NotImplementedError(f"{who}: {what} is not implemented for an int start_pos (the host-length path); pass start_pos "
                                       "as an int32 tensor [bsz] on the GPU")
 
     def _check_paged(self, start_pos, block_table, page_size):
@@ -315,9 +337,12 @@ class QuantLlamaAttentionFused(nn.Module):
 
     def _forward_packed(self, x, start_pos, freqs, cu_seqlens_q, max_seqlen_q, decode_max_seqlen, block_table, page_size, split):
         """The packed step; split = (split_seqlen_q, split_min_keys) routes its attention to the mixed entries.  With `sliding_window` the
-        windowed mixed entries serve every call; no split is then split_seqlen_q = 0."""
+        windowed mixed entries serve every call; no split is then split_seqlen_q = 0.  With `attn_softcap` their *_softcap siblings do, a
+        layer without `sliding_window` under window_left = bound - 1, which hides nothing."""
         if self.sliding_window is not None:
             self._check_window(start_pos)
+        if self.attn_softcap is not None:
+            self._check_window(start_pos, what="attn_softcap")
         self._check_packed(x, start_pos, cu_seqlens_q, max_seqlen_q)
         if block_table is not None or page_size is not None:
             self._check_paged(start_pos, block_table, page_size)
@@ -326,7 +351,7 @@ class QuantLlamaAttentionFused(nn.Module):
         total = x.shape[1]
         bound = self.kv_max_seq_len if decode_max_seqlen is None else int(decode_max_seqlen)
         xqkv = self.qkv_proj(x).reshape(total, -1)
-        scale = self.head_dim ** -0.5
+        scale = self.softmax_scale
         fp8 = self.kv_dtype == "fp8"
         names = ("cache_k", "cache_v") + (("cache_k_scale", "cache_v_scale") if fp8 else ())
         if fp8:
@@ -349,7 +374,14 @@ class QuantLlamaAttentionFused(nn.Module):
         attn = getattr(eng, "attn_prefill" + where[1] + "_varq" + ("_kv8" if fp8 else ""))
         xq = self._store(eng, "rope_kv_store_" + where[0] + "_varq" + ("_fp8" if fp8 else ""), xqkv, freqs, *kv, *table, cu_seqlens_q,
                          max_seqlen_q, start_pos, self.n_local_heads, self.num_key_value_heads)
-        if self.sliding_window is not None:
+        if self.attn_softcap is not None:
+            from .ops import ATTN_SPLIT_MIN_KEYS
+
+            ssq, smk = split if split is not None else (0, ATTN_SPLIT_MIN_KEYS)
+            left = bound - 1 if self.sliding_window is None else self.sliding_window - 1
+            attn = getattr(eng, "attn" + where[1] + "_varq_softcap" + ("_kv8" if fp8 else ""))
+            output = attn(xq, *kv, *table, cu_seqlens_q, max_seqlen_q, start_pos, bound, ssq, smk, left, self.attn_softcap, True, scale, True)
+        elif self.sliding_window is not None:
             from .ops import ATTN_SPLIT_MIN_KEYS
 
             ssq, smk = split if split is not None else (0, ATTN_SPLIT_MIN_KEYS)
@@ -372,6 +404,8 @@ class QuantLlamaAttentionFused(nn.Module):
         self._check_paged(start_pos, block_table, page_size)
         if self.sliding_window is not None:
             raise NotImplementedError("QuantLlamaAttentionFused: forward_shared is not implemented with sliding_window")
+        if self.attn_softcap is not None:
+            raise NotImplementedError("QuantLlamaAttentionFused: forward_shared is not implemented with attn_softcap")
         if prefix_groups is not None and prefix_groups.seq_prefix.shape[0] < x.shape[0]:
             raise ValueError(f"QuantLlamaAttentionFused: prefix_groups covers {prefix_groups.seq_prefix.shape[0]} slots, the batch has {x.shape[0]}")
         return self._forward_device_pos(load_engine(), x, start_pos, freqs, decode_max_seqlen, block_table, page_size, prefix_groups)
@@ -387,7 +421,7 @@ class QuantLlamaAttentionFused(nn.Module):
         bsz, seqlen, _ = x.shape
         bound = self.kv_max_seq_len if decode_max_seqlen is None else int(decode_max_seqlen)
         xqkv = self.qkv_proj(x).reshape(bsz, seqlen, -1)
-        scale = self.head_dim ** -0.5
+        scale = self.softmax_scale
         prompt = seqlen * self.num_key_value_groups > 128  # more query rows per KV head than the split pair serves
         if self.kv_dtype == "fp8":
             if self.cache_k.device != xqkv.device:
@@ -490,6 +524,23 @@ def make_quant_attn_qknorm(model, dev, max_batch_size=1, kv_layout="natural", kv
     return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, norm_offset=float(norm_offset))
 
 
+def make_quant_attn_softcap(model, dev, attn_softcap, softmax_scale=None, sliding_window=None, max_batch_size=1, kv_layout="natural",
+                            kv_dtype=None):
+    """`make_quant_attn` for a model that soft-caps its attention logits (Gemma-2: attn_softcap 50 with softmax_scale 144 ** -0.5 on the
+    27B; Grok-1: 30): every module is built with `attn_softcap` and `softmax_scale` (None: head_dim ** -0.5).  `sliding_window` is None
+    (every layer global), an int (every layer), or a sequence with one entry per replaced module in the order they are met, a None entry a
+    global layer -- Gemma-2 alternates, `[4096, None] * 23`.  Values are passed through; the model's config is not read.  A function of its
+    own: `make_quant_attn` keeps its parameter list."""
+    if attn_softcap is None:
+        raise ValueError("make_quant_attn_softcap: attn_softcap must be a finite float > 0 (`make_quant_attn` builds the modules without a cap)")
+    per_layer = None
+    if sliding_window is not None and not isinstance(sliding_window, int):
+        per_layer = list(sliding_window)
+        sliding_window = None
+    return _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, per_layer_window=per_layer,
+                            extra={"attn_softcap": attn_softcap, "softmax_scale": softmax_scale})
+
+
 def _norm_eps(norm, name):
     for attr in ("variance_epsilon", "eps"):
         if getattr(norm, attr, None) is not None:
@@ -497,11 +548,17 @@ def _norm_eps(norm, name):
     raise ValueError(f"make_quant_attn_qknorm: {name} carries neither variance_epsilon nor eps")
 
 
-def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, norm_offset=None):
+def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_window, norm_offset=None, per_layer_window=None, extra=None):
+    """per_layer_window: one `sliding_window` per replaced module, in the order they are met (None: `sliding_window` for all); extra:
+    further keywords of every module (`make_quant_attn_softcap`)."""
     want = ("q_proj", "k_proj", "v_proj", "o_proj", "args", "kv_max_seq_len")
-    for name, m in list(model.named_modules()):
-        if name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want):
-            continue
+    todo = [(name, m) for name, m in model.named_modules()
+            if not (name == "" or isinstance(m, QuantLlamaAttentionFused) or not all(hasattr(m, a) for a in want))]
+    if per_layer_window is not None and len(per_layer_window) != len(todo):
+        raise ValueError(f"make_quant_attn_softcap: sliding_window has {len(per_layer_window)} entries for {len(todo)} attention modules")
+    for index, (name, m) in enumerate(todo):
+        if per_layer_window is not None:
+            sliding_window = per_layer_window[index]
         has_norm = [hasattr(m, a) and getattr(m, a) is not None for a in ("q_norm", "k_norm")]
         qk_norm = None
         if norm_offset is None:
@@ -519,7 +576,7 @@ def _make_quant_attn(model, dev, max_batch_size, kv_layout, kv_dtype, sliding_wi
         qkv = fuse_qkv(m.q_proj, m.k_proj, m.v_proj)
         attn = QuantLlamaAttentionFused(m.args.hidden_size, m.args.num_attention_heads, m.kv_max_seq_len, qkv, m.o_proj, dev, m.args,
                                         max_batch_size=max_batch_size, kv_layout=kv_layout, kv_dtype=kv_dtype,
-                                        sliding_window=sliding_window, **({} if qk_norm is None else {"qk_norm": qk_norm}))
+                                        sliding_window=sliding_window, **({} if qk_norm is None else {"qk_norm": qk_norm}), **(extra or {}))
         if "." in name:
             parent_name, child_name = name.rsplit(".", 1)
             parent = model.get_submodule(parent_name)

@@ -749,6 +749,41 @@ def lm_head(x, weight, gamma=None, eps=0.0, bias=None, seqlens=None, out=None, o
     x: [M, K] or a strided view with a contiguous last dimension (h[:, -1, :]): the row stride is passed on, nothing is copied.  gamma [K] (None:
     no norm), bias [V], weight as nn.Linear holds it.  seqlens int32 [M]: rows with a negative entry are left untouched in `out` (a fresh `out`
     is then allocated zeroed).  out_dtype: torch.float32 (what sample_logits should be fed) or x.dtype."""
+    return _lm_head(x, weight, gamma, eps, bias, seqlens, out, out_dtype, max_blocks, None)
+
+
+def lm_head_softcap(x, weight, softcap, gamma=None, eps=0.0, bias=None, seqlens=None, out=None, out_dtype=torch.float32, max_blocks=0):
+    """C-ABI awq_lm_head_softcap: `lm_head` with every logit capped in the launch's epilogue, y <- softcap * tanh(y / softcap) on the fp32 sum behind
+    the bias and before the one rounding to out_dtype (Gemma-2's final_logit_softcapping = 30).  With out_dtype float32 the result carries the bits of
+    `logit_softcap_(lm_head(...), softcap)`.  softcap: a finite float >= 0; 0 is "no cap" and returns the bits of `lm_head`.  A function of its own:
+    `lm_head` keeps its parameter list."""
+    return _lm_head(x, weight, gamma, eps, bias, seqlens, out, out_dtype, max_blocks, _check_softcap("lm_head_softcap", softcap))
+
+
+def logit_softcap_(logits, softcap, seqlens=None):
+    """C-ABI awq_logit_softcap: logits [B, V] that already exist (fp32 / bf16 / fp16, any row stride, contiguous last dimension) capped IN PLACE,
+    z <- softcap * tanh(z / softcap), computed in fp32 and rounded once.  seqlens int32 [B]: rows with a negative entry are left untouched.
+    softcap: a finite float >= 0; 0 changes nothing.  Returns `logits`."""
+    if logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("logit_softcap_: logits must be a [B, V] GPU tensor")
+    codes = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}
+    if logits.dtype not in codes:
+        raise TypeError(f"logit_softcap_: logits must be float32, bfloat16 or float16, got {logits.dtype}")
+    cap = _check_softcap("logit_softcap_", softcap)
+    b, v = logits.shape
+    if logits.stride(1) != 1 and v > 1:
+        raise ValueError("logit_softcap_: the last dimension of logits must be contiguous")
+    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.numel() != b or seqlens.device != logits.device or not seqlens.is_contiguous()):
+        raise ValueError("logit_softcap_: seqlens must be contiguous int32 [B] on the logits' device")
+    ld = logits.stride(0) if b > 1 else max(logits.stride(0), v)
+    with torch.cuda.device(logits.device):
+        _capi.check(_capi.lib().awq_logit_softcap(logits.data_ptr(), codes[logits.dtype], ld, None if seqlens is None else seqlens.data_ptr(), b, v,
+                                                  cap, _stream(logits)))
+    return logits
+
+
+def _lm_head(x, weight, gamma, eps, bias, seqlens, out, out_dtype, max_blocks, softcap):
+    """The body of `lm_head` (softcap None) and `lm_head_softcap` (softcap a checked float)."""
     if x.dim() != 2 or weight.dim() != 2:
         raise ValueError("lm_head: x must be [M, K] and weight [V, K]")
     for t in (x, weight, gamma, bias, seqlens, out):
@@ -774,10 +809,13 @@ def lm_head(x, weight, gamma=None, eps=0.0, bias=None, seqlens=None, out=None, o
         raise ValueError("lm_head: out must be a contiguous [M, V] tensor of out_dtype on x's device")
     ldx = x.stride(0) if m > 1 else max(x.stride(0), k) // 8 * 8  # (a single row's stride is never used)
     ptr = lambda t: None if t is None else t.data_ptr()
+    head = (x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(seqlens), out.data_ptr(),
+            _capi.AWQ_F32 if out_dtype == torch.float32 else _dt(x), m, v, k, _dt(x))
     with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().awq_lm_head(x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(seqlens), out.data_ptr(),
-                                            _capi.AWQ_F32 if out_dtype == torch.float32 else _dt(x), m, v, k, _dt(x), int(max_blocks),
-                                            _stream(x)))
+        if softcap is None:
+            _capi.check(_capi.lib().awq_lm_head(*head, int(max_blocks), _stream(x)))
+        else:
+            _capi.check(_capi.lib().awq_lm_head_softcap(*head, softcap, int(max_blocks), _stream(x)))
     return out
 
 
@@ -835,13 +873,18 @@ def _logprob_outputs(who, n, device, targets, want, out):
 
 
 def lm_head_logprobs(x, weight, targets=None, gamma=None, eps=0.0, bias=None, round_logits=False, ws=None, want=("logprob", "lse"), out=None,
-                     max_blocks=0):
+                     max_blocks=0, *, softcap=0.0):
     """C-ABI awq_lm_head_logprobs: per row of x [T, K], against weight [V, K] (nn.Linear.weight as loaded): lse = log sum_v exp(z), target_logit =
     z[targets], logprob = target_logit - lse and argmax (lowest index among the maxima) of z = rmsnorm(x) @ weight^T (+ bias), without the logits ever
     being written to memory.  round_logits: every z is rounded once to x's dtype first, as an nn.Linear would store it.  targets int32 [T]: a row
     whose target is outside [0, V) (-1, -100) is ignored -- its outputs keep what they held (zeros in fresh ones).  x may be a strided view with a
     contiguous last dimension when gamma is None.  ws: a uint8 workspace of at least lm_head_logprobs_workspace_bytes (allocated when None; pass
-    one, and `out`, to capture the call).  Returns a dict with the outputs named in `want`: fp32 [T], argmax int32 [T]."""
+    one, and `out`, to capture the call).  Returns a dict with the outputs named in `want`: fp32 [T], argmax int32 [T].
+
+    softcap (keyword-only; C-ABI awq_lm_head_logprobs_softcap): every z is capped, z <- softcap * tanh(z / softcap) in fp32, before it enters the
+    max / sum-exp, the target pick and the argmax (Gemma-2's final_logit_softcapping = 30); with round_logits z is rounded to x's dtype, capped in
+    fp32 and rounded once more.  A finite float >= 0; 0 (the default) is no cap, the uncapped entry."""
+    softcap = _check_softcap("lm_head_logprobs", softcap)
     if x.dim() != 2 or weight.dim() != 2:
         raise ValueError("lm_head_logprobs: x must be [T, K] and weight [V, K]")
     for t in (x, weight, gamma, bias, targets, ws):
@@ -870,11 +913,14 @@ def lm_head_logprobs(x, weight, targets=None, gamma=None, eps=0.0, bias=None, ro
     if gamma is not None:
         ldx = k
     ptr = lambda t: None if t is None else t.data_ptr()
+    head = (x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(targets), ptr(res.get("logprob")), ptr(res.get("lse")),
+            ptr(res.get("target_logit")), ptr(res.get("argmax")), n, v, k, _dt(x), int(bool(round_logits)))
+    tail = (ws.data_ptr(), ws.numel(), int(max_blocks), _stream(x))
     with torch.cuda.device(x.device):
-        _capi.check(_capi.lib().awq_lm_head_logprobs(x.data_ptr(), ldx, ptr(gamma), float(eps), weight.data_ptr(), ptr(bias), ptr(targets),
-                                                     ptr(res.get("logprob")), ptr(res.get("lse")), ptr(res.get("target_logit")),
-                                                     ptr(res.get("argmax")), n, v, k, _dt(x), int(bool(round_logits)), ws.data_ptr(), ws.numel(),
-                                                     int(max_blocks), _stream(x)))
+        if softcap == 0.0:
+            _capi.check(_capi.lib().awq_lm_head_logprobs(*head, *tail))
+        else:
+            _capi.check(_capi.lib().awq_lm_head_logprobs_softcap(*head, softcap, *tail))
     return res
 
 
@@ -1460,12 +1506,13 @@ def _rope_store(who, qkv, freqs, kv, nheads, nheads_kv, start_pos=None, cache_se
 
 
 def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_scale, causal, one_pass=False, packed=None, split=None,
-                  window=None):
+                  window=None, softcap=None):
     """The device-length attention entries of the C ABI over a described cache (q and kv checked by the caller): the four of the split
     pair, or with one_pass the four of the one-pass prefill kernel (any Sq, no workspace).  packed = (cu_seqlens_q, max_seqlen_q, out or
     None), checked by the caller (one_pass only): q is the packed rows [total_q, H, Dh] of a step, the four varq entries serve and
     seqlen_offset carries the flag lens_before_step.  split = (split_seqlen_q, split_min_keys), with packed: a mixed step, the four
-    awq_attn_[paged_]varq entries and the split pair's workspace.  window = window_left, with split: the four *_window entries and their plan."""
+    awq_attn_[paged_]varq entries and the split pair's workspace.  window = window_left, with split: the four *_window entries and their plan.
+    softcap (a float, with window): the four *_softcap entries, which take the window's plan and workspace."""
     if packed:
         cu, Sq, out = packed
         (T, H, Dh), B = q.shape, cu.shape[0] - 1
@@ -1487,9 +1534,11 @@ def _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, seqlen_offset, softmax_sc
         else:
             wsb = L.awq_attn_varq_window_workspace_bytes(B, H, kv.Hkv, Dh, split[0], int(max_seqlen_k), window)
         ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=q.device)
-        entry = getattr(L, "awq_attn_" + ("paged_" if kv.paged else "") + "varq" + ("" if window is None else "_window") + ("_kv8" if kv.fp8 else ""))
+        form = "" if window is None else ("_window" if softcap is None else "_softcap")
+        entry = getattr(L, "awq_attn_" + ("paged_" if kv.paged else "") + "varq" + form + ("_kv8" if kv.fp8 else ""))
+        tail = () if window is None else ((window,) if softcap is None else (window, softcap))
         with torch.cuda.device(q.device):
-            _capi.check(entry(*head, split[0], split[1], *(() if window is None else (window,)), ws.data_ptr(), wsb, _stream(q)))
+            _capi.check(entry(*head, split[0], split[1], *tail, ws.data_ptr(), wsb, _stream(q)))
         return out
     if one_pass:
         entry = getattr(L, "awq_attn_prefill_" + ("paged" if kv.paged else "kvcache") + ("_varq" if packed else "") + ("_kv8" if kv.fp8 else ""))
@@ -2008,9 +2057,41 @@ def attn_varq_window(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_se
                       lens_before_step, block_table, softmax_scale, causal, k_scale, v_scale, out, window_left)
 
 
+def attn_varq_softcap(q, k, v, cu_seqlens_q, max_seqlen_q: int, seqlens_k, max_seqlen_k: int, softcap: float, window_left=None,
+                      split_seqlen_q: int = 1, split_min_keys=None, lens_before_step: bool = True, block_table=None, softmax_scale=None,
+                      causal: bool = True, k_scale=None, v_scale=None, out=None):
+    """C-ABI awq_attn_varq_softcap[_kv8] / awq_attn_paged_varq_softcap[_kv8]: `attn_varq_window`'s arguments and contract with the
+    attention logits soft-capped (Gemma-2: softcap 50 with softmax_scale 144 ** -0.5; Grok-1: softcap 30):
+
+        z_j = softcap * tanh(softmax_scale * (q . k_j) / softcap),   then the causal / window mask, then softmax.
+
+    The mask is applied behind the cap, by selection: a masked logit is -inf, not -softcap, and a dead key's score contributes nothing.
+    window_left None is a layer without a window, max_seqlen_k - 1.  softcap must be a finite float >= 0; 0 is "no cap" and returns the
+    bits of `attn_varq_window`.  A negative, infinite or NaN softcap and causal = False are refused before any work.  The plan is
+    `attn_varq_window_plan`.  A function of its own: `attn_varq` and `attn_varq_window` keep their parameter lists."""
+    softcap = _check_softcap("attn_varq_softcap", softcap)
+    if window_left is None:
+        window_left = max(int(max_seqlen_k) - 1, 0)
+    return _attn_varq("attn_varq_softcap", q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k, split_seqlen_q, split_min_keys,
+                      lens_before_step, block_table, softmax_scale, causal, k_scale, v_scale, out, window_left, softcap)
+
+
+def _check_softcap(who, softcap):
+    """A cap as a float: finite and >= 0 (0: no cap), as it fits fp32."""
+    import math
+
+    try:
+        cap = float(softcap)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: softcap must be a float, got {softcap!r}") from None
+    if not (math.isfinite(cap) and 0.0 <= cap <= 3.4028234663852886e38):
+        raise ValueError(f"{who}: softcap {cap} must be finite and not negative (0: no cap)")
+    return cap
+
+
 def _attn_varq(who, q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k, split_seqlen_q, split_min_keys, lens_before_step, block_table,
-               softmax_scale, causal, k_scale, v_scale, out, window_left):
-    """The body of `attn_varq` (window_left None) and `attn_varq_window`."""
+               softmax_scale, causal, k_scale, v_scale, out, window_left, softcap=None):
+    """The body of `attn_varq` (window_left None), `attn_varq_window` and `attn_varq_softcap` (softcap a checked float)."""
     if window_left is not None:
         window_left = int(window_left)
         if window_left < 0:
@@ -2037,7 +2118,8 @@ def _attn_varq(who, q, k, v, cu_seqlens_q, max_seqlen_q, seqlens_k, max_seqlen_k
     if kv.Hkv >= 1 and q.shape[1] % kv.Hkv == 0 and split_seqlen_q * (q.shape[1] // kv.Hkv) > 128:
         raise ValueError(f"{who}: split_seqlen_q * (H / Hkv) = {split_seqlen_q * (q.shape[1] // kv.Hkv)} exceeds 128")
     return _attn_kvcache(who, q, kv, seqlens_k, max_seqlen_k, bool(lens_before_step), softmax_scale, causal, one_pass=True,
-                         packed=(cu_seqlens_q, max_seqlen_q, out), split=(split_seqlen_q, min(split_min_keys, 0x7FFFFFFF)), window=window_left)
+                         packed=(cu_seqlens_q, max_seqlen_q, out), split=(split_seqlen_q, min(split_min_keys, 0x7FFFFFFF)), window=window_left,
+                         softcap=softcap)
 
 
 def _ft_caches(who, ref, k_cache, v_cache):
