@@ -300,6 +300,35 @@ int awq_moe_gather(const void* x, const void* order, void* xs, int tokens, int t
  * every element of out T [tokens, hidden] (no zero-fill, no scatter).  ys T [tokens top_k, hidden], hidden % 8 == 0. */
 int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, void* stream);
 
+/* ---- MoE routing for many-expert models (Qwen3-MoE, gpt-oss, DeepSeek-V2 / V3 / R1, Kimi-K2): awq_moe_route's five outputs -- so awq_moe_gather, the
+ * grouped launches and awq_moe_combine follow unchanged -- for 1 <= num_experts <= 512 with the scoring and selection rules of those routers.
+ * With l the row's logits as fp32:
+ *   scores     score AWQ_MOE_SOFTMAX: s_e = exp(l_e - max l) / sum_E exp(l - max l);  AWQ_MOE_SIGMOID: s_e = 1 / (1 + exp(-l_e))
+ *   key        bias == NULL: l_e (monotone in s_e for both scorings);  bias fp32 [num_experts] (sigmoid only): s_e + bias_e in fp32.  Keys are
+ *              compared through awq_moe_route's monotone float -> unsigned key, a total order whatever the bits
+ *   groups     n_group divides num_experts, a group is num_experts / n_group consecutive experts; a group's score is the fp32 sum of its group_top
+ *              (1 or 2; softmax: 1) largest keys; the topk_group groups with the largest scores are kept (equal scores: the lower group) and the
+ *              experts of the other groups are never selected
+ *   topk_ids   the top_k largest keys among the kept experts in descending order; equal keys: the lower index
+ *   topk_w     the unbiased scores s of the picked, divided by (their sum + 1e-20) if renormalize != 0, then times scale, all in fp32 (softmax with
+ *              renormalize: exp(l_j - l_0) / sum_{i < top_k} exp(l_i - l_0), as awq_moe_route)
+ *   order / inv / offsets: awq_moe_route's stable sort of the flat slots t top_k + j by expert
+ * Limits (AWQ_ERR_SHAPE otherwise, before anything is launched): 1 <= num_experts <= 512, 1 <= top_k <= min(num_experts, 8), tokens >= 1,
+ * tokens * top_k <= 2^20, score one of the two, a bias with sigmoid only, 1 <= n_group <= 16 dividing num_experts, 1 <= topk_group <= n_group,
+ * topk_group * num_experts / n_group >= top_k, 1 <= group_top <= min(2, num_experts / n_group), group_top == 1 with softmax.  Pointers:
+ * AWQ_ERR_NULL / AWQ_ERR_ALIGN as awq_moe_route (bias and workspace 4 bytes).  Up to 64 tokens the call is ONE launch and needs no workspace;
+ * above, three launches (select, scan, place) over `workspace` of at least awq_moe_route_scored_workspace(tokens, num_experts, top_k) bytes
+ * (at most 2 MiB; AWQ_ERR_WORKSPACE otherwise; its contents before and after the call mean nothing).  Which form runs and every grid size depend
+ * on (tokens, num_experts, top_k) only.  No global atomics, no host read, no flags to reset: a call is a pure function of its inputs, bit-stable
+ * from run to run, capturable.  A row that holds a NaN or an infinite logit has unspecified weights; its ids are still top_k distinct experts of
+ * the kept groups and the three index arrays a valid sort. ---- */
+#define AWQ_MOE_SOFTMAX 0
+#define AWQ_MOE_SIGMOID 1
+size_t awq_moe_route_scored_workspace(int tokens, int num_experts, int top_k);
+int awq_moe_route_scored(const void* router_logits, int logits_dtype, int tokens, int num_experts, int top_k, int score, int renormalize,
+                         const void* bias, int n_group, int topk_group, int group_top, float scale, void* topk_ids, void* topk_w, void* order,
+                         void* inv, void* offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Next-token sampling on the device: what tinychat/stream_generators/stream_gen.py:19-32,120-134 does between two decode steps
  * (temperature -> repetition penalty -> top-p -> top-k -> softmax -> multinomial -> int()), as ONE launch without a host read.  logits
  * [batch, vocab] (AWQ_F16 / AWQ_BF16 / AWQ_F32, contiguous, aligned to its element) -> tokens int32 [batch].  Every parameter is a per-row device array

@@ -66,6 +66,9 @@ SIGNATURES = {
     "awq_moe_route": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "awq_moe_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_moe_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # (logits, dtype, tokens, experts, top_k, score, renormalize, bias, n_group, topk_group, group_top, scale, five outputs, workspace, bytes, stream)
+    "awq_moe_route_scored": (_i, [_vp] + [_i] * 6 + [_vp] + [_i] * 3 + [ctypes.c_float] + [_vp] * 6 + [_sz, _vp]),
+    "awq_moe_route_scored_workspace": (_sz, [_i, _i, _i]),
     "awq_sample_logits": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "awq_spec_draft_ngram": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
     "awq_spec_pack": (_i, [_vp] * 6 + [_i] * 3 + [_vp]),

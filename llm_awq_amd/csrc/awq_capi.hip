@@ -1686,6 +1686,27 @@ int awq_moe_combine(const void* ys, const void* inv, const void* topk_w, void* o
   return finish_launch();
 }
 
+// ---- MoE routing for many-expert models (awq_moe_route_scored_cdna4.hip) ----
+size_t awq_moe_route_scored_workspace(int tokens, int num_experts, int top_k) {
+  return awq::moe_route_scored_workspace_bytes(tokens, num_experts, top_k);
+}
+
+int awq_moe_route_scored(const void* router_logits, int logits_dtype, int tokens, int num_experts, int top_k, int score, int renormalize,
+                         const void* bias, int n_group, int topk_group, int group_top, float scale, void* topk_ids, void* topk_w, void* order,
+                         void* inv, void* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!router_logits || !topk_ids || !topk_w || !order || !inv || !offsets) return AWQ_ERR_NULL;
+  if (logits_dtype != AWQ_F16 && logits_dtype != AWQ_BF16 && logits_dtype != AWQ_F32) return AWQ_ERR_DTYPE;
+  if (!awq::moe_route_scored_sizes_ok(tokens, num_experts, top_k, score, bias != nullptr, n_group, topk_group, group_top)) return AWQ_ERR_SHAPE;
+  if (!aligned_to(router_logits, logits_dtype == AWQ_F32 ? 4 : 2) || !aligned_to(bias, 4) || !aligned_to(topk_ids, 4) || !aligned_to(topk_w, 4) ||
+      !aligned_to(order, 4) || !aligned_to(inv, 4) || !aligned_to(offsets, 4) || !aligned_to(workspace, 4))
+    return AWQ_ERR_ALIGN;
+  const int rc = awq::launch_moe_route_scored(router_logits, logits_dtype, tokens, num_experts, top_k, score, renormalize, bias, n_group, topk_group,
+                                              group_top, scale, topk_ids, topk_w, order, inv, offsets, workspace, workspace_bytes,
+                                              (hipStream_t)stream);
+  if (rc != 0) return rc == -2 ? AWQ_ERR_WORKSPACE : AWQ_ERR_SHAPE;
+  return finish_launch();
+}
+
 // ---- next-token sampling on the device (awq_sample_cdna4.hip) ----
 int awq_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,
                       const void* top_p, const void* repetition_penalty, void* history, void* hist_len, int max_history, void* seqlens,

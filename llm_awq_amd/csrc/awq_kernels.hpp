@@ -156,6 +156,14 @@ int launch_moe_route(const void* logits, int logits_dtype, int tokens, int exper
                      void* order, void* inv, void* offsets, hipStream_t st);
 int launch_moe_gather(const void* x, const void* order, void* xs, int tokens, int top_k, int hidden, hipStream_t st);  // xs[r] = x[order[r] / top_k]
 int launch_moe_combine(const void* ys, const void* inv, const void* topk_w, void* out, int tokens, int top_k, int hidden, int dtype, hipStream_t st);
+// MoE routing for many-expert models (awq_moe_route_scored_cdna4.hip): experts <= 512, score 0 softmax / 1 sigmoid, bias fp32 [experts] or null,
+// group-limited selection; one launch up to 64 tokens, else select / scan / place over `workspace` (int32 [chunks, experts]).  -1: sizes or
+// options outside the documented rules, -2: workspace missing or too small; pointers validated by the caller
+bool moe_route_scored_sizes_ok(int tokens, int experts, int top_k, int score, int has_bias, int n_group, int topk_group, int group_top);
+size_t moe_route_scored_workspace_bytes(int tokens, int experts, int top_k);
+int launch_moe_route_scored(const void* logits, int logits_dtype, int tokens, int experts, int top_k, int score, int renormalize, const void* bias,
+                            int n_group, int topk_group, int group_top, float scale, void* topk_ids, void* topk_w, void* order, void* inv,
+                            void* offsets, void* workspace, size_t workspace_bytes, hipStream_t st);
 // next-token sampling on the device (awq_sample_cdna4.hip): one block per row of logits [batch, vocab]; -1 if the sizes are outside the documented
 // limits, pointers validated by the caller (every pointer but logits / u / tokens may be null = that step is off); flags: 1 append, 2 advance
 int launch_sample_logits(const void* logits, int logits_dtype, int batch, int vocab, const void* u, const void* temperature, const void* top_k,

@@ -531,6 +531,38 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Te
   return {ids, w, order, inv, offsets};
 }
 
+// the same five outputs for up to 512 experts: softmax / sigmoid scores, selection bias, group-limited top-k, renormalised and scaled weights
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> moe_route_scored(
+    torch::Tensor router_logits, int64_t top_k, const std::string& score, bool renormalize, c10::optional<torch::Tensor> bias, int64_t n_group,
+    int64_t topk_group, int64_t group_top, double scale) {
+  TORCH_CHECK(router_logits.is_cuda() && router_logits.is_contiguous() && router_logits.dim() == 2,
+              "awq_inference_engine: router_logits must be a contiguous [T, E] GPU tensor");
+  const auto st = router_logits.scalar_type();
+  TORCH_CHECK(st == at::kFloat || st == at::kBFloat16 || st == at::kHalf, "moe_route_scored: float32 / bfloat16 / float16 logits");
+  TORCH_CHECK(score == "softmax" || score == "sigmoid", "moe_route_scored: score must be 'softmax' or 'sigmoid'");
+  const int code = st == at::kFloat ? AWQ_F32 : dtype_code(router_logits);
+  const int64_t t = router_logits.size(0), e = router_logits.size(1);
+  TORCH_CHECK(top_k >= 1 && top_k <= 8 && t >= 1 && t * top_k <= (1 << 20) && e >= 1 && e <= 512,
+              "moe_route_scored: 1 <= E <= 512, 1 <= top_k <= 8, 1 <= T, T * top_k <= 2^20");
+  TORCH_CHECK(n_group >= 1 && n_group <= 16 && topk_group >= 1 && topk_group <= 16 && group_top >= 1 && group_top <= 2,
+              "moe_route_scored: 1 <= topk_group <= n_group <= 16, group_top 1 or 2");
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() && bias->scalar_type() == at::kFloat && bias->numel() == e &&
+                    bias->device() == router_logits.device(),
+                "moe_route_scored: bias must be a contiguous float32 [E] tensor on the logits' device");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(router_logits.device());
+  const auto iopt = router_logits.options().dtype(at::kInt);
+  at::Tensor ids = torch::empty({t, top_k}, iopt), w = torch::empty({t, top_k}, router_logits.options().dtype(at::kFloat));
+  at::Tensor order = torch::empty({t * top_k}, iopt), inv = torch::empty({t * top_k}, iopt), offsets = torch::empty({e + 1}, iopt);
+  const size_t ws_bytes = awq_moe_route_scored_workspace((int)t, (int)e, (int)top_k);
+  at::Tensor ws = torch::empty({(int64_t)(ws_bytes / 4)}, iopt);
+  raise_on(awq_moe_route_scored(router_logits.data_ptr(), code, (int)t, (int)e, (int)top_k, score == "sigmoid" ? AWQ_MOE_SIGMOID : AWQ_MOE_SOFTMAX,
+                                renormalize ? 1 : 0, bias.has_value() ? bias->data_ptr() : nullptr, (int)n_group, (int)topk_group, (int)group_top,
+                                (float)scale, ids.data_ptr(), w.data_ptr(), order.data_ptr(), inv.data_ptr(), offsets.data_ptr(),
+                                ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()));
+  return {ids, w, order, inv, offsets};
+}
+
 torch::Tensor moe_gather(torch::Tensor x, torch::Tensor order, int64_t top_k) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 && order.is_cuda() && order.is_contiguous() && order.scalar_type() == at::kInt,
               "awq_inference_engine: x must be a contiguous [T, H] GPU tensor and order int32 on the GPU");
@@ -2776,6 +2808,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_forward_cdna4", &moe_forward_cdna4, "grouped per-expert forward on cdna4 buffers (GEMV for <= 8 rows, GEMM otherwise)");
   m.def("moe_route", &moe_route, "router logits [T, E] -> (topk_ids, topk_w, order, inv, offsets): top-k gate + stable sort by expert, one launch",
         py::arg("router_logits"), py::arg("top_k"), py::arg("renormalize") = true);
+  m.def("moe_route_scored", &moe_route_scored,
+        "moe_route's outputs for up to 512 experts: softmax / sigmoid scores, selection bias, group-limited top-k, renormalised and scaled weights",
+        py::arg("router_logits"), py::arg("top_k"), py::kw_only(), py::arg("score") = "softmax", py::arg("renormalize") = true,
+        py::arg("bias") = py::none(), py::arg("n_group") = 1, py::arg("topk_group") = 1, py::arg("group_top") = 1, py::arg("scale") = 1.0);
   m.def("moe_gather", &moe_gather, "xs[r] = x[order[r] / top_k]", py::arg("x"), py::arg("order"), py::arg("top_k"));
   m.def("moe_combine", &moe_combine, "out[t] = sum_j ys[inv[t k + j]] * w[t, j] (fp32 sum of T-rounded products, one final rounding)", py::arg("ys"),
         py::arg("inv"), py::arg("topk_w"));

@@ -10,6 +10,7 @@ launches (`routing="device"`: `ops.moe_route` / `moe_gather` / `moe_combine`, no
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
@@ -148,23 +149,63 @@ class GroupedGateUp(_LayoutMarker, nn.Module):
                                          sz_half=getattr(self, "szh_cdna4", None))
 
 
+@dataclass(frozen=True)
+class MoeRouter:
+    """The router of a many-expert model: the keyword arguments of `ops.moe_route_scored` (DESIGN.md "MoE routing, scored").
+    Qwen3-MoE: MoeRouter();  DeepSeek-V3: MoeRouter("sigmoid", True, bias, n_group=8, topk_group=4, group_top=2, scale=2.5)."""
+    score: str = "softmax"
+    renormalize: bool = True
+    bias: Optional[torch.Tensor] = None  # float32 [E], sigmoid only: added to the scores for the choice, not for the weights
+    n_group: int = 1
+    topk_group: int = 1
+    group_top: int = 1
+    scale: float = 1.0
+
+    def kwargs(self):
+        return dict(score=self.score, renormalize=self.renormalize, bias=self.bias, n_group=self.n_group, topk_group=self.topk_group,
+                    group_top=self.group_top, scale=self.scale)
+
+    def route_torch(self, router_logits: torch.Tensor, top_k: int):
+        """the same contract in torch glue, on any device -> (ids int64 [T, k], w float32 [T, k]); the reference composition of the device entry
+        (`torch.topk` does not promise the lower index among equal keys)"""
+        from .ops import check_moe_router
+        l = router_logits.float()
+        T, E = l.shape
+        check_moe_router(T, E, int(top_k), self.score, self.bias, self.n_group, self.topk_group, self.group_top)
+        s = torch.softmax(l, dim=-1) if self.score == "softmax" else torch.sigmoid(l)
+        key = l if self.bias is None else s + self.bias.to(l.device)
+        if self.n_group > 1:
+            gscore = key.view(T, self.n_group, -1).topk(self.group_top, dim=-1)[0].sum(-1)
+            keep = torch.zeros_like(gscore, dtype=torch.bool).scatter_(1, gscore.topk(self.topk_group, dim=-1)[1], True)
+            key = key.masked_fill(~keep.repeat_interleave(E // self.n_group, dim=1), float("-inf"))
+        ids = key.topk(int(top_k), dim=-1)[1]
+        w = s.gather(1, ids)
+        if self.renormalize:
+            w = w / (w.sum(-1, keepdim=True) + 1e-20)
+        return ids, w * self.scale
+
+
 class SparseMoeMLP(nn.Module):
     """Mixtral-style block: y = sum_k p_k * w2_e( silu(w1_e x) * w3_e x ) over each token's top-k experts."""
 
-    def __init__(self, w1, w3, w2: GroupedWQLinear, top_k: int = 2, gate_up: Optional[GroupedGateUp] = None, routing: str = "torch"):
+    def __init__(self, w1, w3, w2: GroupedWQLinear, top_k: int = 2, gate_up: Optional[GroupedGateUp] = None, routing: str = "torch",
+                 router: Optional[MoeRouter] = None):
         """w1 / w3: GroupedWQLinear modules (two grouped launches + the SiLU * mul tail as a third), or None with `gate_up` = a
         GroupedGateUp built from the same experts (ONE grouped launch for h: `SparseMoeMLP.fused(w1_experts, w3_experts, w2, top_k)`).
         routing: "torch" = the torch glue of `forward` (the default; `torch.bincount` reads back to the host, so it cannot be captured), "device" =
-        `ops.moe_route` -> `ops.moe_gather` -> the grouped launches -> `ops.moe_combine`: nothing but HIP launches, no host read, GPU tensors only."""
+        `ops.moe_route` -> `ops.moe_gather` -> the grouped launches -> `ops.moe_combine`: nothing but HIP launches, no host read, GPU tensors only.
+        router: None = the Mixtral gate above (softmax, top-k, renormalised; up to 64 experts on the device); a MoeRouter = that router's rules,
+        through `ops.moe_route_scored` (routing="device", up to 512 experts) or `MoeRouter.route_torch` (routing="torch")."""
         super().__init__()
         if routing not in ("torch", "device"):
             raise ValueError(f"SparseMoeMLP: routing must be 'torch' or 'device', got {routing!r}")
-        self.w1, self.w3, self.w2, self.top_k, self.gate_up, self.routing = w1, w3, w2, top_k, gate_up, routing
+        self.w1, self.w3, self.w2, self.top_k, self.gate_up, self.routing, self.router = w1, w3, w2, top_k, gate_up, routing, router
         assert gate_up is not None or (w1 is not None and w3 is not None)
 
     @classmethod
-    def fused(cls, w1_experts: Sequence[WQLinear], w3_experts: Sequence[WQLinear], w2: GroupedWQLinear, top_k: int = 2, routing: str = "torch"):
-        return cls(None, None, w2, top_k, GroupedGateUp(w1_experts, w3_experts), routing)
+    def fused(cls, w1_experts: Sequence[WQLinear], w3_experts: Sequence[WQLinear], w2: GroupedWQLinear, top_k: int = 2, routing: str = "torch",
+              router: Optional[MoeRouter] = None):
+        return cls(None, None, w2, top_k, GroupedGateUp(w1_experts, w3_experts), routing, router)
 
     def _h(self, xs, offsets):
         if self.gate_up is not None:
@@ -181,13 +222,20 @@ class SparseMoeMLP(nn.Module):
     def forward(self, x: torch.Tensor, router_logits: torch.Tensor) -> torch.Tensor:
         if self.routing == "device":
             from . import ops
-            _ids, w, order, inv, offsets = ops.moe_route(router_logits.contiguous(), self.top_k, renormalize=True)
+            if self.router is None:
+                _ids, w, order, inv, offsets = ops.moe_route(router_logits.contiguous(), self.top_k, renormalize=True)
+            else:
+                _ids, w, order, inv, offsets = ops.moe_route_scored(router_logits.contiguous(), self.top_k, **self.router.kwargs())
             xs = ops.moe_gather(x.contiguous(), order, self.top_k)
             return ops.moe_combine(self.w2(self._h(xs, offsets), offsets), inv, w)
         T = x.shape[0]
-        probs = torch.softmax(router_logits.float(), dim=-1)
-        w, ids = torch.topk(probs, self.top_k, dim=-1)
-        w = (w / w.sum(-1, keepdim=True)).to(x.dtype)
+        if self.router is None:
+            probs = torch.softmax(router_logits.float(), dim=-1)
+            w, ids = torch.topk(probs, self.top_k, dim=-1)
+            w = (w / w.sum(-1, keepdim=True)).to(x.dtype)
+        else:
+            ids, w = self.router.route_torch(router_logits, self.top_k)
+            w = w.to(x.dtype)
         order, offsets = sort_by_expert(ids, self.w2.num_experts)
         xs = x[order // self.top_k]
         h = self._h(xs, offsets)

@@ -510,6 +510,56 @@ def moe_route(router_logits, top_k: int, renormalize: bool = True):
     return ids, w, order, inv, offsets
 
 
+def moe_route_scored(router_logits, top_k: int, *, score: str = "softmax", renormalize: bool = True, bias=None, n_group: int = 1,
+                     topk_group: int = 1, group_top: int = 1, scale: float = 1.0):
+    """C-ABI awq_moe_route_scored: moe_route's five outputs for 1 <= E <= 512 experts with the routers of Qwen3-MoE / gpt-oss / DeepSeek-V2 / V3 /
+    Kimi-K2 (DESIGN.md "MoE routing, scored").  score "softmax" | "sigmoid"; bias float32 [E] (sigmoid only) is added to the scores for the choice
+    alone; n_group groups of E / n_group consecutive experts, of which the topk_group with the largest score (the sum of a group's group_top
+    largest keys) stay selectable; weights = the picked experts' scores, renormalised over the picked if asked, times scale.  One launch up to 64
+    tokens, three above (over a workspace allocated here); rules outside the contract raise ValueError before anything is launched."""
+    _need_gpu(router_logits, bias)
+    if router_logits.dim() != 2:
+        raise ValueError("moe_route_scored: router_logits must be [T, E]")
+    code = {torch.float16: _capi.AWQ_F16, torch.bfloat16: _capi.AWQ_BF16, torch.float32: _capi.AWQ_F32}.get(router_logits.dtype)
+    if code is None:
+        raise TypeError(f"moe_route_scored: expected float32/bfloat16/float16 logits, got {router_logits.dtype}")
+    t, e = router_logits.shape
+    k, dev = int(top_k), router_logits.device
+    check_moe_router(t, e, k, score, bias, n_group, topk_group, group_top)
+    ids = torch.empty(t, k, dtype=torch.int32, device=dev)
+    w = torch.empty(t, k, dtype=torch.float32, device=dev)
+    order = torch.empty(t * k, dtype=torch.int32, device=dev)
+    inv = torch.empty_like(order)
+    offsets = torch.empty(e + 1, dtype=torch.int32, device=dev)
+    L = _capi.lib()
+    ws_bytes = L.awq_moe_route_scored_workspace(t, e, k)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        _capi.check(L.awq_moe_route_scored(router_logits.data_ptr(), code, t, e, k, MOE_SCORES[score], 1 if renormalize else 0,
+                                           bias.data_ptr() if bias is not None else None, int(n_group), int(topk_group), int(group_top), float(scale),
+                                           ids.data_ptr(), w.data_ptr(), order.data_ptr(), inv.data_ptr(), offsets.data_ptr(),
+                                           ws.data_ptr() if ws is not None else None, ws_bytes, _stream(router_logits)))
+    return ids, w, order, inv, offsets
+
+
+MOE_SCORES = {"softmax": 0, "sigmoid": 1}  # AWQ_MOE_SOFTMAX / AWQ_MOE_SIGMOID
+
+
+def check_moe_router(t, e, k, score, bias, n_group, topk_group, group_top):
+    """the refusals of awq_moe_route_scored as ValueErrors (include/awq_cdna4.h lists them)"""
+    if score not in MOE_SCORES:
+        raise ValueError(f"moe_route_scored: score must be 'softmax' or 'sigmoid', got {score!r}")
+    if not (1 <= e <= 512 and 1 <= k <= min(8, e) and t >= 1 and t * k <= 1 << 20):
+        raise ValueError("moe_route_scored: 1 <= E <= 512, 1 <= top_k <= min(8, E), 1 <= T, T * top_k <= 2^20")
+    if bias is not None and (score != "sigmoid" or bias.dtype != torch.float32 or bias.numel() != e):
+        raise ValueError("moe_route_scored: bias must be float32 [E] and comes with score='sigmoid' only")
+    n_group, topk_group, group_top = int(n_group), int(topk_group), int(group_top)
+    if not (1 <= n_group <= 16 and e % n_group == 0 and 1 <= topk_group <= n_group and topk_group * (e // n_group) >= k):
+        raise ValueError("moe_route_scored: n_group <= 16 must divide E, 1 <= topk_group <= n_group, and the kept groups must hold top_k experts")
+    if not (1 <= group_top <= min(2, e // n_group)) or (score == "softmax" and group_top != 1):
+        raise ValueError("moe_route_scored: group_top is 1 or 2 (1 with softmax) and at most the group's size")
+
+
 def moe_gather(x, order, top_k: int):
     """C-ABI awq_moe_gather: xs[r] = x[order[r] // top_k]; x [T, H] bf16 / fp16 with H % 8 == 0, order int32 [T top_k] -> xs [T top_k, H]."""
     _need_gpu(x, order)
