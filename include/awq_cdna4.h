@@ -1340,6 +1340,29 @@ int awq_rope_kv_store_paged_varq_fp8_qknorm(const void* qkv, const float* freqs_
                                             long long v_scale_page_stride, long long v_scale_row_stride, long long qkv_row_stride, int dtype,
                                             void* stream);
 
+/* ---- The LATENT KV cache of multi-head latent attention (DeepSeek-V2 / V3 / R1, Kimi-K2; csrc/awq_mla.hpp, csrc/awq_attn_mla_cdna4.hip).
+ *      A cache row is 576 T per token whatever the head count: columns 0..511 the normalised latent, 512..575 the rotated shared key.
+ *      The cache is dense [cache_outer >= batch, cache_rows = Lmax, 576] (block_table NULL) or a pool [cache_outer = num_pages,
+ *      cache_rows = page_size, 576] behind block_table int32 [>= batch, pages_per_seq] (page_size % 64 == 0), with an outer and a row
+ *      stride of its own (elements, multiples of 8, row stride >= 576).  The step is packed: cu_seqlens_q int32 [batch + 1],
+ *      cache_seqlens int32 [batch] = the tokens already cached, both read on the device only.  Latent width 512 and rope width 64 are
+ *      compile-time constants; T is fp16 or bf16.
+ * awq_mla_kv_store, one launch: kv_a T [total_q, 576] (row stride kv_a_row_stride) is kv_a_proj_with_mqa's output, q_pe T [total_q, H, 64]
+ *     (token and head strides) a view of q_b_proj's.  Token s of sequence b, at position p = cache_seqlens[b] + s: cache row p columns
+ *     0..511 <- awq_rmsnorm's arithmetic on the 512 raw columns with gamma fp32 [512] (the same bits for a gamma T holds); columns
+ *     512..575 <- awq_rope_with_pos's rotation by row p of freqs_table fp32 [table_rows, 64]; q_abs[t, h, 512..575] <- the rotated q_pe
+ *     (q_abs T [total_q, H, 576] contiguous; its columns 0..511 are the caller's).  rope_interleaved = 1: the input pairs are (2 i, 2 i + 1)
+ *     and the result is the plain rotation of the input permuted to [0, 2, .., 62, 1, 3, .., 63].  A sequence with cache_seqlens[b] < 0,
+ *     Sq_b > max_seqlen_q or cache_seqlens[b] + Sq_b > min(capacity, table_rows) stores nothing and gets zero q_pe columns; rows >= cu[batch]
+ *     are neither read nor written.
+ * Returns AWQ_ERR_NULL, AWQ_ERR_DTYPE, AWQ_ERR_SHAPE, AWQ_ERR_ALIGN (16 bytes for tensors, 4 for the int arrays, 8 elements for strides),
+ *     AWQ_ERR_LAUNCH -- all but the last without a GPU call. */
+int awq_mla_kv_store(const void* kv_a, const void* q_pe, void* q_abs, void* cache, const int* block_table, const int* cu_seqlens_q,
+                     const int* cache_seqlens, const float* freqs_table, const float* gamma, float eps, int batch, int nheads, int total_q,
+                     int max_seqlen_q, int table_rows, int rope_interleaved, int cache_outer, int cache_rows, int pages_per_seq,
+                     long long table_row_stride, long long kv_a_row_stride, long long q_pe_token_stride, long long q_pe_head_stride,
+                     long long cache_outer_stride, long long cache_row_stride, int dtype, void* stream);
+
 /* Tuning hook for tests, experiments and benchmarks (not part of the reference surface): integer knobs that force one of the
  * shipped code paths ("gemm_variant", "gemm_splitk", "gemv_dma", "gemvd_waves", "attn_prefill_rows", "attn_splitkv_chunk", "tower_rows", "w8a8_tile", ...) so that tests can cover each of them; 0
  * restores the default heuristic.  A default process cannot reach it: unless AWQ_TUNING=1 is set in the environment every

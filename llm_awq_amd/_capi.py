@@ -223,6 +223,7 @@ SIGNATURES = {
     "awq_gelu_quant_per_token": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "awq_layernorm_quant": (_i, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i, _i, _i, _i, _vp]),
     "awq_tune_set": (_i, [ctypes.c_char_p, _i]),
+    "awq_mla_kv_store": (_i, [_vp] * 9 + [ctypes.c_float] + [_i] * 9 + [ctypes.c_longlong] * 6 + [_i, _vp]),
 }
 # the _qknorm sibling of every natural-layout store: its arguments with q_gamma, k_gamma and norm_eps directly after the angles
 for _n in ("natural", "natural_pos", "paged_pos", "natural_varq", "paged_varq"):

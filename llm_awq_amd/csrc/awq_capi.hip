@@ -9,6 +9,7 @@
 
 #include "awq_kernels.hpp"
 #include "awq_kvcache.hpp"
+#include "awq_mla.hpp"
 
 namespace {
 thread_local char g_last_hip_error[256] = "";
@@ -2143,6 +2144,46 @@ int awq_tune_set(const char* key, int value) {
     return AWQ_OK;
   }
   return AWQ_ERR_SHAPE;
+}
+
+// ---- The latent KV cache of multi-head latent attention (awq_mla.hpp): the packed store ----
+static awq::MlaCache mla_cache(const void* cache, const int* block_table, int outer, int rows, int pages_per_seq, long long bt_rs, long long c_os,
+                               long long c_rs) {
+  return awq::MlaCache{cache, c_os, c_rs, outer, rows, block_table, bt_rs, pages_per_seq};
+}
+// the shape and alignment terms of the cache; need = the positions the call may touch (0: no bound of its own)
+static bool mla_cache_shape_ok(const awq::MlaCache& k, int batch, long long need) {
+  if (k.c_os < 0 || k.c_rs < awq::kMlaRow || k.c_rs > (1ll << 20)) return false;
+  if (k.block_table)
+    return k.rows >= 64 && (k.rows % 64) == 0 && k.outer >= 1 && k.pages_per_seq >= 1 && k.bt_rs >= k.pages_per_seq &&
+           need <= (long long)k.pages_per_seq * k.rows;
+  return k.outer >= batch && k.rows >= 1 && need <= k.rows;
+}
+static bool mla_cache_aligned(const awq::MlaCache& k) {
+  return aligned16(k.c) && (k.c_os % 8) == 0 && (k.c_rs % 8) == 0 && (!k.block_table || aligned4(k.block_table));
+}
+static bool mla_step_ok(int batch, int nheads, int total_q, int max_seqlen_q) {
+  return batch >= 1 && nheads >= 1 && nheads <= awq::kMlaMaxHeads && varq_shape_ok(batch, max_seqlen_q, total_q);
+}
+int awq_mla_kv_store(const void* kv_a, const void* q_pe, void* q_abs, void* cache, const int* block_table, const int* cu_seqlens_q,
+                     const int* cache_seqlens, const float* freqs_table, const float* gamma, float eps, int batch, int nheads, int total_q,
+                     int max_seqlen_q, int table_rows, int rope_interleaved, int cache_outer, int cache_rows, int pages_per_seq,
+                     long long table_row_stride, long long kv_a_row_stride, long long q_pe_token_stride, long long q_pe_head_stride,
+                     long long cache_outer_stride, long long cache_row_stride, int dtype, void* stream) {
+  if (!kv_a || !q_pe || !q_abs || !cache || !cu_seqlens_q || !cache_seqlens || !freqs_table || !gamma) return AWQ_ERR_NULL;
+  if (dtype != AWQ_F16 && dtype != AWQ_BF16) return AWQ_ERR_DTYPE;
+  const awq::MlaCache k = mla_cache(cache, block_table, cache_outer, cache_rows, pages_per_seq, table_row_stride, cache_outer_stride, cache_row_stride);
+  if (!mla_step_ok(batch, nheads, total_q, max_seqlen_q) || !mla_cache_shape_ok(k, batch, 0) || table_rows < 1 ||
+      (rope_interleaved != 0 && rope_interleaved != 1) || kv_a_row_stride < awq::kMlaRow || q_pe_head_stride < awq::kMlaRope ||
+      q_pe_token_stride < 0 || !(eps >= 0.f && eps <= 3.402823466e38f))
+    return AWQ_ERR_SHAPE;
+  if (!aligned16(kv_a) || !aligned16(q_pe) || !aligned16(q_abs) || !mla_cache_aligned(k) || !aligned4(cu_seqlens_q) || !aligned4(cache_seqlens) ||
+      !aligned16(freqs_table) || !aligned16(gamma) || (kv_a_row_stride % 8) != 0 || (q_pe_token_stride % 8) != 0 || (q_pe_head_stride % 8) != 0)
+    return AWQ_ERR_ALIGN;
+  awq::launch_mla_kv_store({kv_a, q_pe, q_abs, k, cu_seqlens_q, cache_seqlens, freqs_table, gamma, eps, kv_a_row_stride, q_pe_token_stride,
+                            q_pe_head_stride, batch, nheads, total_q, max_seqlen_q, table_rows, rope_interleaved, dtype},
+                           (hipStream_t)stream);
+  return finish_launch();
 }
 
 }  // extern "C"

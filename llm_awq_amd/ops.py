@@ -2392,3 +2392,62 @@ def layernorm_quant(x, gamma, beta, scale, out_i8, eps: float, per_token: bool =
     with torch.cuda.device(x.device):
         _capi.check(_capi.lib().awq_layernorm_quant(x.data_ptr(), gamma.data_ptr(), None if beta is None else beta.data_ptr(), float(eps),
                                                      out_i8.data_ptr(), scale.data_ptr(), m, k, int(bool(per_token)), _dt(x), _stream(x)))
+
+
+# ---- the latent KV cache of multi-head latent attention (csrc/awq_mla.hpp): DeepSeek-V2 / V3 / R1, Kimi-K2 ---------------------------
+MLA_LATENT, MLA_ROPE, MLA_ROW = 512, 64, 576
+
+
+def _mla_cache(who, ref, cache, block_table, batch):
+    """The latent cache [Bc >= B, Lmax, 576] or pool [num_pages, page_size, 576] (+ table) of one call: the entry's cache arguments."""
+    _on_gpu(cache)
+    if cache.dtype != ref.dtype or cache.device != ref.device or cache.dim() != 3 or cache.shape[2] != MLA_ROW or cache.stride(2) != 1:
+        raise ValueError(f"{who}: the cache must be [outer, rows, 576] of the input's dtype with a unit last stride on its GPU")
+    if block_table is None:
+        if cache.shape[0] < batch:
+            raise ValueError(f"{who}: batch {batch} exceeds the cache batch {cache.shape[0]}")
+        return (None, cache.shape[0], cache.shape[1], 0, 0, cache.stride(0), cache.stride(1)), cache.shape[1]
+    _on_gpu(block_table)
+    if cache.shape[1] < 64 or cache.shape[1] % 64:
+        raise ValueError(f"{who}: a pool [num_pages, page_size, 576] with page_size a multiple of 64 is expected, got {tuple(cache.shape)}")
+    if block_table.device != ref.device or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] < batch or \
+            block_table.shape[1] < 1 or block_table.stride(1) != 1 or block_table.stride(0) < block_table.shape[1]:
+        raise ValueError(f"{who}: block_table must be an int32 [>= B, pages_per_seq] tensor with a unit last stride on the GPU of the input")
+    return (block_table.data_ptr(), cache.shape[0], cache.shape[1], block_table.shape[1], block_table.stride(0), cache.stride(0),
+            cache.stride(1)), block_table.shape[1] * cache.shape[1]
+
+
+def mla_kv_store(kv_a, q_pe, q_abs, cache, cu_seqlens_q, max_seqlen_q: int, cache_seqlens, freqs_table, gamma, eps: float,
+                 block_table=None, rope_interleaved: bool = False):
+    """C-ABI awq_mla_kv_store, one launch of a packed step.  kv_a [total_q, 576] (kv_a_proj_with_mqa's output: the raw latent | the raw
+    k_pe) and q_pe [total_q, H, 64] (a view of q_b_proj's output) may be strided views with a unit last stride.  Token s of sequence b
+    goes to position cache_seqlens[b] + s of `cache` -- dense [Bc >= B, Lmax, 576], or with block_table a pool [num_pages, page_size,
+    576]: columns 0..511 get `rmsnorm`'s bits for gamma (float32 [512]) and eps, columns 512..575 `fused_rope_with_pos`'s rotation by
+    that row of freqs_table [P, 64] (float32).  The rotated q_pe goes to q_abs[:, :, 512:] (q_abs [total_q, H, 576] contiguous; its
+    first 512 columns are the caller's).  rope_interleaved: the inputs hold the pairs as (2 i, 2 i + 1) (DeepSeek checkpoints); the
+    outputs are in half-split order either way.  A sequence with cache_seqlens[b] < 0, more than max_seqlen_q tokens, or a chunk that
+    does not fit the cache or the table stores nothing and gets zero q_pe columns; rows >= cu[B] are neither read nor written."""
+    who = "mla_kv_store"
+    _on_gpu(kv_a, q_pe, q_abs, cache_seqlens, freqs_table, gamma)
+    if kv_a.dim() != 2 or kv_a.shape[1] != MLA_ROW or kv_a.stride(1) != 1:
+        raise ValueError(f"{who}: kv_a must be [total_q, 576] with a unit last stride")
+    B = _check_packed(who, "kv_a", kv_a, cu_seqlens_q, max_seqlen_q)
+    T = kv_a.shape[0]
+    if q_pe.dim() != 3 or q_pe.shape[0] != T or q_pe.shape[2] != MLA_ROPE or q_pe.stride(2) != 1 or q_pe.dtype != kv_a.dtype or q_pe.device != kv_a.device:
+        raise ValueError(f"{who}: q_pe must be [total_q, H, 64] of kv_a's dtype with a unit last stride on its GPU")
+    H = q_pe.shape[1]
+    if q_abs.dtype != kv_a.dtype or q_abs.device != kv_a.device or tuple(q_abs.shape) != (T, H, MLA_ROW) or not q_abs.is_contiguous():
+        raise ValueError(f"{who}: q_abs must be a contiguous [total_q, H, 576] tensor of kv_a's dtype on its GPU")
+    _check_seqlens(who, "cache_seqlens", cache_seqlens, kv_a, B)
+    if freqs_table.device != kv_a.device or freqs_table.dtype != torch.float32 or freqs_table.dim() != 2 or freqs_table.shape[1] != MLA_ROPE or \
+            not freqs_table.is_contiguous():
+        raise ValueError(f"{who}: freqs_table must be a contiguous float32 [P, 64] tensor on the GPU of kv_a")
+    if gamma.device != kv_a.device or gamma.dtype != torch.float32 or tuple(gamma.shape) != (MLA_LATENT,) or not gamma.is_contiguous():
+        raise ValueError(f"{who}: gamma must be a contiguous float32 [512] tensor on the GPU of kv_a")
+    (bt, outer, rows, pps, bt_rs, c_os, c_rs), _ = _mla_cache(who, kv_a, cache, block_table, B)
+    with torch.cuda.device(kv_a.device):
+        _capi.check(_capi.lib().awq_mla_kv_store(kv_a.data_ptr(), q_pe.data_ptr(), q_abs.data_ptr(), cache.data_ptr(), bt, cu_seqlens_q.data_ptr(),
+                                                 cache_seqlens.data_ptr(), freqs_table.data_ptr(), gamma.data_ptr(), float(eps), B, H, T,
+                                                 int(max_seqlen_q), freqs_table.shape[0], int(bool(rope_interleaved)), outer, rows, pps, bt_rs,
+                                                 kv_a.stride(0), q_pe.stride(0), q_pe.stride(1), c_os, c_rs, _dt(kv_a), _stream(kv_a)))
+    return q_abs
